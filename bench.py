@@ -7,12 +7,23 @@ power_to_db(ref=max, top_db=80) -> DCT-II ortho, 13 coefficients.  Inputs are re
 when the timed region starts.  One step = one pass of the hot path over the batch: ONE kernel launch
 (samples in, MFCCs out) on every GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c4] [--prewarm P]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c4] [--dump-outputs DIR] [--full [--prewarm P]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the outputs of the last
+timed step under DIR when `--dump-outputs DIR` is given, and the JSON line.  Everything else this file measures -- the CPU
+baseline, the `steady_clock` re-timing, the dominant kernel's roofline figures and, for N > 1, `compute_only_ms`,
+`ranks_seen` and the `--reserve-cus auto` re-timing -- runs only with `--full`; without it those fields are null.
+
+`--dump-outputs DIR` writes what the timed path handed its caller in the last timed step (rank 0's gathered block for
+N > 1) as DIR/<name>.npy in float32: `mfcc` [clips, 13, 94] for c2, `features` [clips, 22, 94] for c4.  A block above
+64 MB is cut to a fixed, seeded sample of whole clips, whose indices go to DIR/<name>_clip_index.npy (float64).  The inputs are seeded,
+so two builds given the same arguments can be compared output for output.
+
 Both shapes work for N > 1: started plainly (no WORLD_SIZE in the environment), the parent -- which never touches the
-GPU -- times the CPU baseline, then starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a fresh
-child process, hands it the baseline through the environment, relays rank 0's JSON line and the child's return code.
+GPU -- times the CPU baseline (`--full` only), then starts `python -m torch.distributed.run --nproc-per-node N bench.py ...`
+as a fresh child process, hands it the baseline through the environment, relays rank 0's JSON line and the child's
+return code.
 
 `--config c4` (BASELINE.json configs[3]): per GPU 2048 clips, MFCC + spectral centroid + rolloff + contrast packed
 to one [2048, 22, 94] block per step, gathered to rank 0.
@@ -25,13 +36,13 @@ point-to-point channels to fit them.
 
 `value` / `ms_per_step` are the driver's protocol and nothing else: W warm-up steps, then exactly K timed steps between
 two barrier + synchronize pairs.  On a GPU coming from idle the first ~150 launches (30 ms) run below the steady clock,
-so a short run (K = 20) reads lower than a long one; the same K steps timed again behind `--prewarm` further launches
-are reported BESIDE the value as `steady_clock` (never as `value`).  Rank 0 prints ONE JSON line.
+so a short run (K = 20) reads lower than a long one; with `--full` the same K steps timed again behind `--prewarm` further
+launches are reported BESIDE the value as `steady_clock` (never as `value`).  Rank 0 prints ONE JSON line.
 
-N > 1 adds what the first hardware run needs to diagnose itself: `compute_only_ms` (the same K steps with the gather
-off, timed first), `gather_wait_ms` (host time spent inside the waits for the gathers of the timed steps, per step),
-`ranks_seen` (world size and every rank's device), and -- `--reserve-cus auto` -- one re-timing with 32 CUs set aside
-for the collective when a step costs more than 1.15 x its compute.
+N > 1 reports `gather_wait_ms` (host time spent inside the waits for the gathers of the timed steps, per step); `--full`
+adds what the first hardware run needs to diagnose itself: `compute_only_ms` (the same K steps with the gather off, timed
+first), `ranks_seen` (world size and every rank's device), and -- `--reserve-cus auto` -- one re-timing with 32 CUs set
+aside for the collective when a step costs more than 1.15 x its compute.
 """
 import argparse
 import json
@@ -157,6 +168,22 @@ def cpu_baseline(target_seconds=10.0, all_cores_seconds=4.0):
 
 
 CPU_ENV = "SYG_BENCH_CPU_BASELINE"
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20250523
+
+
+def dump_outputs(out_dir, name, block):
+    """`block` (the [clips, rows, frames] result of the last timed step, on the host) as out_dir/<name>.npy in float32;
+    above DUMP_MAX_BYTES a fixed, seeded sample of whole clips, in clip order, with their indices beside it."""
+    os.makedirs(out_dir, exist_ok=True)
+    block = np.ascontiguousarray(block, dtype=np.float32)
+    n = block.shape[0]
+    per_clip = max(1, block[0].nbytes) if n else 1
+    if block.nbytes > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_MAX_BYTES // per_clip, replace=False))
+        block = block[keep]
+        np.save(os.path.join(out_dir, f"{name}_clip_index.npy"), keep.astype(np.float64))
+    np.save(os.path.join(out_dir, f"{name}.npy"), block)
 
 
 def launch_ranks(a):
@@ -168,7 +195,7 @@ def launch_ranks(a):
     import socket
     import subprocess
     env = dict(os.environ)
-    if not a.no_cpu_baseline and not env.get(CPU_ENV):
+    if a.full and not a.no_cpu_baseline and not env.get(CPU_ENV):
         env[CPU_ENV] = json.dumps(cpu_baseline())
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     rc = 1
@@ -203,15 +230,22 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, the `steady_clock` re-timing, "
+                         "the dominant kernel's roofline figures and, for N > 1, compute_only_ms / ranks_seen / the "
+                         "--reserve-cus auto re-timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step to DIR/<name>.npy (float32, at most 64 MB)")
     ap.add_argument("--prewarm", type=int, default=300,
-                    help="launches between the driver-protocol measurement (`value`) and the `steady_clock` re-timing; 0: skip it")
+                    help="--full: launches between the driver-protocol measurement (`value`) and the `steady_clock` re-timing; "
+                         "0: skip it")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--clips", type=int, default=0, help="clips per GPU (default: the configuration's)")
     ap.add_argument("--reserve-cus", default="auto",
                     help="N > 1: leave this many CUs to RCCL (two-launch form, capped p2p channels); `auto` (default): time the "
-                         "plain form -- that is `value` -- and, when a step costs more than 1.15 x its compute, once more with 32 CUs "
-                         "set aside, reported beside it as `reserve_cus_retry`")
+                         "plain form -- that is `value` -- and, with --full, when a step costs more than 1.15 x its compute, once "
+                         "more with 32 CUs set aside, reported beside it as `reserve_cus_retry`")
     a = ap.parse_args()
     reserve_auto = a.reserve_cus == "auto"
     a.reserve_cus = 0 if reserve_auto else int(a.reserve_cus)
@@ -224,9 +258,9 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     a.gpus = world
 
-    # CPU baseline: on rank 0, before any GPU initialisation (forks workers); a launching parent has already timed it
+    # CPU baseline (--full): on rank 0, before any GPU initialisation (forks workers); a launching parent has already timed it
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         if os.environ.get(CPU_ENV):
             cpu = json.loads(os.environ[CPU_ENV])
         else:
@@ -290,17 +324,22 @@ def main():
     gat = RootGather(n_total, (B, rows, T_FRAMES), torch.float32, "cpu" if same_gpu else torch.device("cuda", dev_index))
     backend = "gloo (same-GPU / dry rehearsal, through the host)" if same_gpu else "RCCL"
     wait_acc = [0.0]
+    last = [None]                                      # what the caller of the path holds after the latest step
 
     def finish_gather():
         t0 = time.perf_counter()
-        gat.finish()                                   # (the previous step's gather; a stream-side wait under RCCL)
+        got = gat.finish()                             # (the previous step's gather; a stream-side wait under RCCL)
         wait_acc[0] += time.perf_counter() - t0
+        if got is not None:
+            last[0] = got                              # rank 0: the gathered [n_total, ...] block
 
     def step(gather=True):
         out = compute()
         if world > 1 and gather:
             finish_gather()
             gat.start(out.cpu() if same_gpu else out)
+        else:
+            last[0] = out
         return out
 
     def dev_sync():
@@ -335,13 +374,19 @@ def main():
     for _ in range(a.warmup):
         step()
     compute_only = None
-    if world > 1:
+    if world > 1 and a.full:
         compute_only, _ = timed(a.steps, gather=False)
+    last[0] = None
     elapsed, gather_wait = timed(a.steps)
-    # once more behind `--prewarm` further launches (a GPU coming from idle needs ~150 launches to reach its steady clock):
-    # reported beside the value, never as the value
+    # the result of the last timed step, as its caller receives it (rank 0 holds the gathered block when N > 1)
+    dump_name = "mfcc" if a.config == "c2" else "features"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dump_name, last[0].cpu().numpy())
+    last[0] = None
+    # --full: once more behind `--prewarm` further launches (a GPU coming from idle needs ~150 launches to reach its steady
+    # clock): reported beside the value, never as the value
     steady = None
-    if a.prewarm > 0:
+    if a.full and a.prewarm > 0:
         for _ in range(a.prewarm):
             compute()
         for _ in range(a.warmup):
@@ -350,7 +395,7 @@ def main():
     # --reserve-cus auto: a step that costs more than 1.15 x its compute is waiting for the collective (or the collective
     # for CUs: the persistent kernels fill every CU); one re-timing with 32 CUs left to RCCL, both printed
     retry = None
-    if world > 1 and reserve_auto and not dry:
+    if world > 1 and a.full and reserve_auto and not dry:
         ref_el = steady if steady is not None else elapsed
         if ref_el > 1.15 * compute_only:
             ops.set_reserved_cus(32)
@@ -362,7 +407,7 @@ def main():
                      "gather_wait_ms": round(r_wait / a.steps * 1e3, 4),
                      "value": round(n_total * L * a.steps / r_el / 1e6, 1)}
     ranks_seen = None
-    if world > 1:
+    if world > 1 and a.full:
         names = [None] * world
         dist.all_gather_object(names, "cpu (dry run)" if dry else f"cuda:{dev_index} {torch.cuda.get_device_name(dev_index)}")
         ranks_seen = {"world_size": dist.get_world_size(), "backend": backend, "devices": names}
@@ -370,7 +415,7 @@ def main():
     # dominant kernel: HIP events on the stream it is launched on, back-to-back launches (steady clock: the timed
     # steps above have just run); the average includes the ~2 us dispatch gap, rocprofv3's per-dispatch average does not
     roof = None
-    if rank == 0 and not dry:
+    if rank == 0 and a.full and not dry:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         reps = 200                                         # (>= 30 ms of back-to-back launches: the steady clock)
         if a.config == "c2" and one_launch:

@@ -3,8 +3,10 @@
 CPU (float64 NumPy/SciPy) restatement of the sygnals windowed-transform /
 feature-extraction hot path.  It exists to *check* the HIP product path.
 
-Only ``tests/``, ``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of
-``bench.py`` may import anything from here.  ``sygnals_amd`` (the product)
+Only ``tests/``, ``__graft_entry__.smoke()``, the ``cpu_baseline`` leg of
+``bench.py`` and ``__graft_entry__.build()`` (``build_ref``: the reference,
+byte-compiled into ``oracle/_ref/`` for the CPU tests) may import anything
+from here.  ``sygnals_amd`` (the product)
 never imports it and has no CPU fallback: it raises when the HIP library or
 a GPU is missing.
 

@@ -7,6 +7,14 @@ import pytest
 from click.testing import CliRunner
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the reference's `sygnals` package, byte-compiled by build() (oracle/build_ref.py); absent where build() found no reference
+REF = os.path.join(ROOT, "oracle", "_ref")
+
+
+def _reference_or_skip():
+    if not os.path.isdir(os.path.join(REF, "sygnals", "plugins")):
+        pytest.skip("reference not built into oracle/_ref (build() found no reference checkout)")
+    return REF
 
 
 class FakeRegistry:
@@ -48,9 +56,7 @@ def test_plugin_registers_into_fake_registry():
 
 
 def test_plugin_against_the_reference_registry_when_present():
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "sygnals", "plugins")):
-        pytest.skip("reference checkout not present on this box")
+    ref = _reference_or_skip()
     sys.path.insert(0, ref)
     try:
         from sygnals.plugins.api import PluginRegistry, SygnalsPluginBase
@@ -177,12 +183,10 @@ def test_reference_plugin_loader_discovers_and_loads_the_backend(tmp_path):
     """Drives the reference's own PluginLoader.discover_and_load() (sygnals/plugins/loader.py:291-384): a local plugin
     directory holding this package's plugin.toml -> manifest parse (:63-83), PEP 440 compatibility check against the
     core version (:85-103), entry-point import (:105-158), setup() and the nine registration hooks in loader order
-    (:266-274).  Build container only (the reference does not exist on the GPU box).  The reference imports the
+    (:266-274).  Runs wherever build() compiled the reference into oracle/_ref.  The reference imports the
     `toml` package, which this image lacks: a tomli-backed module with the three names the loader uses stands in
     for it for the duration of the test."""
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "sygnals", "plugins")):
-        pytest.skip("reference checkout not present on this box")
+    ref = _reference_or_skip()
     import importlib
     import shutil
     import types

@@ -7,10 +7,10 @@ cd "$(dirname "$0")/.."
 OUT=${1:-gpurun_out/prof_r02}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-CMD="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+CMD="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --full"
 # the trace pass runs the default step counts (300 pre-warm + 50 warm-up + 500 timed + 100 for the roofline block): its
 # per-dispatch average is then dominated by steady-clock launches, like the figure bench.py prints
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --no-cpu-baseline > "$OUT/trace.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 bench.py --no-cpu-baseline --full > "$OUT/trace.log" 2>&1
 echo "trace rc=$?"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_ANY --output-format csv -d "$OUT/pmc1" -- $CMD > "$OUT/pmc1.log" 2>&1
 echo "pmc1 rc=$?"
