@@ -7,8 +7,9 @@
 //            processed; each wave takes its (overlapped) frame from there, applies the analysis window (LDS copy)
 //            and runs a 1024-point complex FFT held 16 points per lane (radix 16 x 16 x 4).  The two exchanges go
 //            through a 4.1 KiB per-wave scratch that aliases the wave's own power row, in two half-rounds each:
-//            full-wave ds_write_b64 / ds_read_b64, conflict-free under the per-instruction LDS banking, the lane
-//            pair (L, L + 32) completing each other's rows with v_permlane32_swap.  Real-FFT split on mirror
+//            lane-indexed planar stores (ds_write_addtid_b32) and full-wave ds_read_b64 of writer-lane pairs,
+//            conflict-free under the per-instruction LDS banking, the lane pair (L, L + 32) completing each
+//            other's rows with v_permlane32_swap.  Real-FFT split on mirror
 //            pairs, |X|^2 stored as one skewed 1025-bin row.
 //   barrier A
 //   project  the W power rows are the B operand of v_mfma_f32_16x16x4_f32: the mel filterbank is stored
@@ -25,7 +26,7 @@
 // Reference behaviour reproduced: librosa.stft (center zero padding, periodic window, rfft) -> np.abs ->
 // **2 -> melspectrogram -> power_to_db(ref=np.max) -> mfcc, as called from sygnals/core/features/manager.py:184-187,
 // 198, 219-223 and cepstral.py:106-115; per-frame statistics follow sygnals/core/features/frequency_domain.py:24-386.
-// Index maps and LDS bank behaviour are validated by tools/wave_fft_model_v4.py.
+// Index maps and LDS bank behaviour are validated by tools/wave_fft_model_v5.py.
 #include "common.h"
 #include <stdlib.h>
 #include <string.h>
@@ -46,8 +47,7 @@ constexpr int MC = 1024;         // complex points per frame
 constexpr int NBIN = 1025;
 constexpr int MAXW = 16;         // waves per workgroup (8 or 16)
 constexpr int P_STRIDE = 1090;   // == 2 (mod 32): conflict-free MFMA B-operand reads; rows are skewed, see ppos()
-constexpr int PL2 = 132;         // exchange-2 plane stride (complex): 128 group slots + 4 skew
-constexpr int SC_COMPLEX = 4 * PL2;   // per-wave exchange scratch: 528 complex = 4224 B
+constexpr int SC_COMPLEX = 528;  // per-wave exchange scratch: 528 complex = 4224 B (16 rows of 256 B + skew)
 constexpr int TW2_STRIDE = 18;   // complex entries per lane class (16 + 2 pad: distinct banks)
 constexpr int TW2_FLOATS = 4 * TW2_STRIDE * 2;
 constexpr int TW1_FLOATS = 15 * 64 * 2;
@@ -94,8 +94,55 @@ struct MfccArgs {
   int rows_per_clip;     // rows between two clips of `out` (n_mfcc, or more when the MFCCs are the head of a wider block)
 };
 
-// exchange 2 (half buffer by c' & 7, planar in b'): slot of group (c, c') inside a plane
-__device__ __forceinline__ int x2g(int c, int cp) { return (cp & 7) * 16 + ((c + 4 * ((cp & 7) >> 1)) & 15); }
+// The two exchanges are lane-indexed (ds_write_addtid_b32: a store writes one 64-float ROW, float L from lane L, at
+// M0 + an immediate offset -- no address VGPR and 2 LDS cycles for 256 B, against 6 for a ds_write_b64).  A complex
+// register goes out as two planar rows (re, im); a ds_read_b64 then fetches one component of the writer lanes
+// (2m, 2m + 1).  The lanes' roles are chosen so that the operands a reader needs together sit in such lane pairs, and
+// the rows are spaced so that every read is conflict-free (tools/wave_fft_model_v5.py):
+//   pass 1   lane l holds column b = p1col(l) = 4 a + b' with a = l & 15, b' = (l >> 4) ^ ((l >> 2) & 2)
+//   exch. 1  row r, plane p at float X1_ROW r + 64 p (one 8-byte bank slot of skew per row)
+//   pass 2   lane L holds (c = 8 (L >> 5) + c7, b'): rho = (L >> 1) & 7 = ((c7 & 3) << 1) | (c7 >> 2),
+//            b' = 2 ((L >> 4) & 1) + (L & 1) -- the b' = 0, 1 and b' = 2, 3 of one c are lane pairs
+//   exch. 2  row c' & 7, plane p at float X2_ROW (c' & 7) + 64 p (two slots of skew per row)
+//   units    u = lane + 64 j: c = UNIT_C[u >> 3], c' = u & 7; each 32-lane group holds four c closed under the
+//            mirror c -> 16 - c and under c -> c + 8, which is what makes exchange 2's reads conflict-free
+constexpr int X1_ROW = 130;      // floats; 8 rows x 2 planes end at float 1038 <= 2 * SC_COMPLEX
+constexpr int X2_ROW = 132;      // floats; ... at float 1052
+static_assert(7 * X1_ROW + 128 <= 2 * SC_COMPLEX && 7 * X2_ROW + 128 <= 2 * SC_COMPLEX, "exchange rows must fit the scratch");
+constexpr unsigned long long UNIT_C = 0xdb53ea62f971c840ull;   // nibble i: c of units 8 i .. 8 i + 7
+__device__ __forceinline__ int p1col(int l) { return 4 * (l & 15) + ((l >> 4) ^ ((l >> 2) & 2)); }
+__device__ __forceinline__ int x2rho(int c7) { return ((c7 & 3) << 1) | (c7 >> 2); }
+// exchange-2 read position (float, plane 0, b' = 0) of group (c, c')
+__device__ __forceinline__ int x2g(int c, int cp) { return X2_ROW * (cp & 7) + 32 * (c >> 3) + 2 * x2rho(c & 7); }
+
+// The eight complex registers x[0..7] as 16 lane-indexed rows: x[r].x at byte ROW * 4 r, x[r].y 256 bytes behind it,
+// from M0 = m0 (the LDS byte address of the scratch).  M0 is set here and clobbered: the compiler re-loads it for its
+// own users (the stage buffer's LDS-DMA).
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"     // (M0 is a reserved register: the clobber is what makes the
+template <int ROW>                                  //  compiler set it again before its own M0 users)
+__device__ __forceinline__ void addtid_rows(uint32_t m0, const float2* x) {
+#define SYG_ADDTID(d, o) "ds_write_addtid_b32 %" #d " offset:%" #o "\n\t"
+  asm volatile("s_mov_b32 m0, %0\n\t"
+               "s_nop 0\n\t"             // (an M0 write needs one wait state before an LDS add-TID instruction reads it)
+               SYG_ADDTID(1, 17) SYG_ADDTID(2, 25)
+               SYG_ADDTID(3, 18) SYG_ADDTID(4, 26)
+               SYG_ADDTID(5, 19) SYG_ADDTID(6, 27)
+               SYG_ADDTID(7, 20) SYG_ADDTID(8, 28)
+               SYG_ADDTID(9, 21) SYG_ADDTID(10, 29)
+               SYG_ADDTID(11, 22) SYG_ADDTID(12, 30)
+               SYG_ADDTID(13, 23) SYG_ADDTID(14, 31)
+               SYG_ADDTID(15, 24) SYG_ADDTID(16, 32)
+               :: "s"(m0), "v"(x[0].x), "v"(x[0].y), "v"(x[1].x), "v"(x[1].y), "v"(x[2].x), "v"(x[2].y),
+                  "v"(x[3].x), "v"(x[3].y), "v"(x[4].x), "v"(x[4].y), "v"(x[5].x), "v"(x[5].y), "v"(x[6].x),
+                  "v"(x[6].y), "v"(x[7].x), "v"(x[7].y),
+                  "n"(0), "n"(4 * ROW), "n"(8 * ROW), "n"(12 * ROW), "n"(16 * ROW), "n"(20 * ROW), "n"(24 * ROW),
+                  "n"(28 * ROW), "n"(256), "n"(4 * ROW + 256), "n"(8 * ROW + 256), "n"(12 * ROW + 256),
+                  "n"(16 * ROW + 256), "n"(20 * ROW + 256), "n"(24 * ROW + 256), "n"(28 * ROW + 256)
+               : "memory", "m0");
+#undef SYG_ADDTID
+}
+#pragma clang diagnostic pop
 
 struct LaneConst {
   float2 twb[2];     // W_2048^kb of each unit (kb = c + 16 c'); pair d uses twb * W_8^d
@@ -104,10 +151,10 @@ struct LaneConst {
   int pmb[2];        // ppos(1024 - kb)
   int dA2, dA3;      // unit-0 position offsets for d = 2, 3 (544, 816 -- except lane 0)
   int kb[2];         // kb (complex-output mode)
-  int g0[2], g1[2];  // exchange-2 slot of the primary (c' < 8) / mirror (c' >= 8) group
+  int g0[2], g1[2];  // exchange-2 read position of the primary (c' < 8) / mirror (c' >= 8) group
 };
 
-// unit u = lane + 64 j: primary group (c = u >> 3, c' = u & 7), bins k = kb + 256 d; mirror group
+// unit u = lane + 64 j: primary group (c = UNIT_C[u >> 3], c' = u & 7), bins k = kb + 256 d; mirror group
 // (16 - c, 15 - c') holds bins 1024 - k, with the c = 0 exceptions (0, 16 - c') and, for u = 0 (lane 0), the
 // self-mirrored pair of groups (0,0) / (0,8) whose four pairs are the bins {0, 256, 128, 384} (+ bin 512).
 // TWB: also fetch twb from the twiddle table (false: the caller keeps twb and re-makes the rest -- lane arithmetic only)
@@ -116,7 +163,7 @@ __device__ __forceinline__ void init_lane_const(LaneConst& lc, int lane, const f
   constexpr float C1 = 0.92387953251128673848f, S1 = 0.38268343236508977173f, R = 0.70710678118654752440f;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int u = lane + 64 * j, c = u >> 3, cp = u & 7;
+    const int c = (int)((uint32_t)(UNIT_C >> (32 * j)) >> (4 * (lane >> 3))) & 15, cp = lane & 7;
     int cm = 16 - c, cmp = 15 - cp;
     if (c == 0) { cm = 0; cmp = (cp == 0) ? 8 : 16 - cp; }
     lc.g0[j] = x2g(c, cp);
@@ -134,7 +181,7 @@ __device__ __forceinline__ void init_lane_const(LaneConst& lc, int lane, const f
   lc.dA3 = sp ? ppos(384) : 816;
 }
 
-// 1024-point complex forward FFT of the windowed frame + real split.  v[a] holds z[64a + lane] on entry.
+// 1024-point complex forward FFT of the windowed frame + real split.  v[a] holds z[64a + p1col(lane)] on entry.
 // On exit pair (j, d) holds X[k] in xs[j][d] and X[1024 - k] in xm[j][d] (k = kb_j + 256 d; lane 0 / unit 0:
 // k = 0, 256, 128, 384); lane 0 also returns X[512].
 // PD: priority drop (MODE 1 keeps the top level for its row functions, the transform then runs one level lower)
@@ -144,30 +191,41 @@ template <int PD = 0, bool X2 = false>
 __device__ __forceinline__ void wave_rfft2048(float2 (&v)[16], const LaneConst& lc, float2* __restrict__ sc,
                                              const float2* __restrict__ tw1l, const float2* __restrict__ tw2l,
                                              int lane, float2 (&xs)[2][4], float2 (&xm)[2][4], float2& x512 TARGS) {
-  const int cl = lane >> 2, bp = lane & 3;
+  // this lane's roles (see the maps above X1_ROW): pass-1 column, pass-2 (c7 = c & 7, b', upper half-wave)
+  const int col = p1col(lane);
+  const int hi = lane >> 5, rho = (lane >> 1) & 7, bp = ((lane >> 3) & 2) | (lane & 1);
+  const int c7 = (rho >> 1) | ((rho & 1) << 2);
+  const float* scf = reinterpret_cast<const float*>(sc);
+  typedef __attribute__((address_space(3))) const float* lds_cfptr;
+  const uint32_t m0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_cfptr)scf);
   // ---- pass 1: radix-16 over a (stride 64), twiddle W_1024^(b*c)
   dft16(v);
 #pragma unroll
-  for (int c = 1; c < 16; ++c) v[c] = cmul(v[c], tw1l[(c - 1) * 64 + lane]);
-  // ---- exchange 1 in two half-rounds through a 512-complex buffer.  Round h moves the 8 ROWS c = 8h..8h+7:
-  // all 64 lanes store (row r = c & 7 at r*64 + (b ^ 4r)) -- an LDS store costs its 6 cycles whatever the EXEC
-  // mask, so half-wave stores would pay twice.  A pass-2 lane (c = lane>>2, b' = lane&3) needs the 16 operands
-  // y[c][4a + b'] of ONE row, which only one of the rounds holds: in round h the lane pair (L, L + 32) shares
-  // the reading of row (L>>2) + 8h -- L takes a = 0..7, L + 32 takes a = 8..15 -- and v_permlane32_swap then
-  // hands each lane the half it is missing (L's round-1 operands <-> (L+32)'s round-0 operands): full-wave
-  // stores AND full-wave loads for 16 extra VALU instructions.
+  for (int c = 1; c < 16; ++c) v[c] = cmul(v[c], tw1l[(c - 1) * 64 + col]);
+  // ---- exchange 1 in two half-rounds.  Round h moves the 8 ROWS c = 8h..8h+7 (lane-indexed, 16 stores).  A pass-2
+  // lane (c, b') needs the 16 operands y[c][4a + b'] of ONE row, which only one of the rounds holds: in round h the
+  // lane pair (L, L + 32) shares the reading of row c7 + 8h -- L takes a = 0..7, L + 32 takes a = 8..15, four
+  // ds_read_b64 per plane, each the operands a = 2i, 2i + 1 of its half (writer lanes 16 (b' ^ 2 hi) + 8 hi + 2i,
+  // + 1) -- and v_permlane32_swap then hands each lane the half it is missing (L's round-1 operands <-> (L+32)'s
+  // round-0 operands): full-wave stores AND full-wave loads for 16 extra VALU instructions.
   TICK(1, v[1].x);
   float2 t[16];
   {
-    const int r7 = cl & 7;
-    const int rbase = r7 * 64 + bp + 8 * (cl & 8) / 2;      // + 32 for the upper half-wave (a = 8..15)
+    const float* rd = scf + X1_ROW * c7 + 8 * hi + 16 * (bp ^ (2 * hi));
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) sc[r * 64 + (lane ^ (4 * r))] = v[8 * h + r];
+      addtid_rows<X1_ROW>(m0, v + 8 * h);
       wave_lds_sync();
 #pragma unroll
-      for (int i = 0; i < 8; ++i) t[8 * h + i] = sc[rbase + 4 * (i ^ r7)];
+      for (int i = 0; i < 4; ++i) {
+        // (the empty asm keeps the IR load-store vectorizer from fusing the contiguous 8-byte reads of consecutive i
+        // into ds_read2_b64, which runs at half the rate of ds_read_b64 and banks on 32 dwords)
+        if (i > 0) asm volatile("" ::: "memory");
+        const float2 re = *reinterpret_cast<const float2*>(rd + 2 * i);
+        const float2 im = *reinterpret_cast<const float2*>(rd + 64 + 2 * i);
+        t[8 * h + 2 * i] = make_float2(re.x, im.x);
+        t[8 * h + 2 * i + 1] = make_float2(re.y, im.y);
+      }
       wave_lds_sync();
     }
 #pragma unroll
@@ -179,7 +237,7 @@ __device__ __forceinline__ void wave_rfft2048(float2 (&v)[16], const LaneConst& 
     }
   }
   TICK(2, t[0].x);
-  // ---- pass 2: lane = (c = lane>>2, b' = lane&3); radix-16 over a'
+  // ---- pass 2: lane = (c, b'); radix-16 over a'
   SETPRIO(2 - PD > 0 ? 2 - PD : 0);
   dft16(t);
   {
@@ -196,21 +254,24 @@ __device__ __forceinline__ void wave_rfft2048(float2 (&v)[16], const LaneConst& 
     }
   }
   // ---- exchange 2 in two half-rounds (c' < 8, then c' >= 8); every unit's primary group has c' < 8 and its
-  // mirror c' >= 8, so round 0 delivers all primaries and round 1 all mirrors.  Pass 3 = radix-4 over b'.
+  // mirror c' >= 8, so round 0 delivers all primaries and round 1 all mirrors.  A group's four b' are the lane
+  // pairs (b' 0, 1) and (2, 3): four ds_read_b64 (two per plane).  Pass 3 = radix-4 over b'.
   TICK(3, t[1].x);
   float2 G[2][4], H[2][4];
   {
-    const int wbase = bp * PL2;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) sc[wbase + r * 16 + ((cl + 4 * (r >> 1)) & 15)] = t[8 * h + r];
+      addtid_rows<X2_ROW>(m0, t + 8 * h);
       wave_lds_sync();
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const float2* p = sc + (h == 0 ? lc.g0[j] : lc.g1[j]);
-        if (h == 0) bfly4(p[0], p[PL2], p[2 * PL2], p[3 * PL2], G[j][0], G[j][1], G[j][2], G[j][3]);
-        else bfly4(p[0], p[PL2], p[2 * PL2], p[3 * PL2], H[j][0], H[j][1], H[j][2], H[j][3]);
+        const float* p = scf + (h == 0 ? lc.g0[j] : lc.g1[j]);
+        const float2 r01 = *reinterpret_cast<const float2*>(p), i01 = *reinterpret_cast<const float2*>(p + 64);
+        const float2 r23 = *reinterpret_cast<const float2*>(p + 16), i23 = *reinterpret_cast<const float2*>(p + 80);
+        const float2 z0 = make_float2(r01.x, i01.x), z1 = make_float2(r01.y, i01.y);
+        const float2 z2 = make_float2(r23.x, i23.x), z3 = make_float2(r23.y, i23.y);
+        if (h == 0) bfly4(z0, z1, z2, z3, G[j][0], G[j][1], G[j][2], G[j][3]);
+        else bfly4(z0, z1, z2, z3, H[j][0], H[j][1], H[j][2], H[j][3]);
       }
       wave_lds_sync();
     }
@@ -259,7 +320,7 @@ __device__ __forceinline__ void wave_rfft2048(float2 (&v)[16], const LaneConst& 
   }
 }
 
-// Raw samples of one frame: element n = 64a + lane of the packed complex frame covers samples s0 + 2n,
+// Raw samples of one frame: element n = 64a + p1col(lane) of the packed complex frame covers samples s0 + 2n,
 // s0 + 2n + 1; samples outside [0, L) are the zero padding of center=True.  The loads are only issued here;
 // the analysis window (LDS copy) is applied by apply_window() when the frame is consumed.
 //   LOAD 0 / 1: straight from global memory (scalar / 8-byte loads)
@@ -267,24 +328,25 @@ __device__ __forceinline__ void wave_rfft2048(float2 (&v)[16], const LaneConst& 
 template <int LOAD>
 __device__ __forceinline__ void fetch_frame(float2 (&v)[16], const float* __restrict__ yb, int64_t L, int64_t s0,
                                             const float* __restrict__ stage_frame, int lane) {
+  const int col = p1col(lane);
   if (LOAD == 2) {
     const float2* sf = reinterpret_cast<const float2*>(stage_frame);
 #pragma unroll
-    for (int a = 0; a < 16; ++a) v[a] = sf[64 * a + lane];
+    for (int a = 0; a < 16; ++a) v[a] = sf[64 * a + col];
     return;
   }
   const bool interior = (s0 >= 0) && (s0 + NFFT <= L);
   if (interior) {
 #pragma unroll
     for (int a = 0; a < 16; ++a) {
-      const int n = 64 * a + lane;
+      const int n = 64 * a + col;
       if (LOAD == 1) v[a] = *reinterpret_cast<const float2*>(yb + s0 + 2 * n);
       else v[a] = make_float2(yb[s0 + 2 * n], yb[s0 + 2 * n + 1]);
     }
   } else {
 #pragma unroll
     for (int a = 0; a < 16; ++a) {
-      const int64_t s = s0 + 2 * (64 * a + lane);
+      const int64_t s = s0 + 2 * (64 * a + col);
       v[a].x = (s >= 0 && s < L) ? yb[s] : 0.f;
       v[a].y = (s + 1 >= 0 && s + 1 < L) ? yb[s + 1] : 0.f;
     }
@@ -292,9 +354,10 @@ __device__ __forceinline__ void fetch_frame(float2 (&v)[16], const float* __rest
 }
 
 __device__ __forceinline__ void apply_window(float2 (&v)[16], const float2* __restrict__ winl, int lane) {
+  const int col = p1col(lane);
 #pragma unroll
   for (int a = 0; a < 16; ++a) {
-    const float2 wv = winl[64 * a + lane];
+    const float2 wv = winl[64 * a + col];
     v[a] = make_float2(v[a].x * wv.x, v[a].y * wv.y);
   }
 }
