@@ -444,6 +444,38 @@ int syg_frame_stats_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int f
 int syg_rms_from_spec_f32(const float* S, int64_t rows, int F, int frame_length, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Pitch: librosa 0.10 yin / pyin as called by fundamental_frequency, sygnals/core/audio/features.py:135-220 (jitter
+ * :319 and shimmer :412 call it when no f0 / voiced_flag is given).  Parity is unpinned (librosa is not a dependency):
+ * the float64 restatement of tests/pitch_ref.py is the contract; the host constants come from sygnals_amd/_pitch.py.
+ * syg_pitch_frames_f32: one wave per frame, frame_length = 2048 only (SYG_E_UNSUPPORTED otherwise), any
+ *   1 <= win_length < 2048, any hop; center pads frame_length / 2 zeros on each side.  Lags min_period .. max_period
+ *   (n_lag = max_period - min_period + 1), 1 <= min_period < max_period <= frame_length - win_length - 1.
+ *   twiddle      [2048] complex W_2048^k
+ *   mode 0 (yin) f0_out [B, T]: sr / (min_period + idx + parabolic shift), idx = first trough under trough_threshold,
+ *                else the first global minimum
+ *   mode 1 (pyin) per frame a candidate list of stride K >= ceil(n_lag / 2) + 1: cand_bin int32 / cand_prob float32
+ *                [B, T, K], cand_count [B, T] (bins distinct and < n_bins, in lag order), voiced_prob [B, T];
+ *                ptab: float64 table of sygnals_amd/_pitch.py (thresholds, beta probabilities, no-trough masses,
+ *                Boltzmann factors); fmin / n_bins define the 10-cent pitch grid
+ *   cmndf_out    [B, T, n_lag] float32 or NULL: the cumulative mean normalised difference the decisions are taken on
+ * syg_pyin_viterbi_f32: one workgroup per clip over the 2 n_bins pYIN states.  Consumes candidate lists as above
+ *   (bins must be distinct within a frame) and voiced_prob; ltab: [2, n_rows, 2 half_width + 1] float64
+ *   log(p T + tiny) of the stay (p = 0.99) and switch blocks, rows as _pitch.transition_tables(); lconst_host: HOST
+ *   float64 {log(tiny), log p_init voiced, log p_init unvoiced}.  Writes f0_out (NaN where unvoiced), voiced_out
+ *   (0 / 1) and state_out (may be NULL) [B, T]; backpointers in work (syg_pyin_work_bytes(B, T, n_bins) bytes).
+ * ------------------------------------------------------------------------------- */
+int syg_pitch_frames_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int frame_length, int win_length, int hop,
+                         int center, int64_t T, double sr, int min_period, int max_period, int mode,
+                         double trough_threshold, double fmin, int n_bins, const double* ptab, int K,
+                         const float* twiddle, float* f0_out, int* cand_bin, float* cand_prob, int* cand_count,
+                         float* voiced_prob, float* cmndf_out, void* stream);
+int64_t syg_pyin_work_bytes(int64_t B, int64_t T, int n_bins);
+int syg_pyin_viterbi_f32(const int* cand_bin, const float* cand_prob, const int* cand_count, const float* voiced_prob,
+                         int64_t B, int64_t T, int K, int n_bins, int half_width, const double* ltab, int n_rows,
+                         const double* lconst_host, double fmin, void* work, int64_t work_bytes, float* f0_out,
+                         uint8_t* voiced_out, int* state_out, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Constant-Q transform building blocks: librosa.cqt as called by compute_cqt,
  * sygnals/core/dsp.py:276-284 (recursive per-octave algorithm; the host composes the octaves).
  *   syg_decimate2_f32   y[b, n] = scale * sum_j taps[j] * x[b, 2n + (ntaps-1)/2 - j], n < ceil(L/2)

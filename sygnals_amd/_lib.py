@@ -85,6 +85,10 @@ SIGNATURES = {
     "syg_col_quantiles_f32": (_i, [_p, _l, _l, _p, _i, _p, _p]),
     "syg_zoom_f32": (_i, [_p, _i, _i, _i, _i, _i, _p, _p]),
     "syg_pcm_to_f32": (_i, [_p, _i, _l, _l, _i, _l, _p, _l, _p]),
+    "syg_pitch_frames_f32": (_i, [_p, _l, _l, _l, _i, _i, _i, _i, _l, _d, _i, _i, _i, _d, _d, _i, _p, _i, _p, _p, _p, _p, _p,
+                                  _p, _p, _p]),
+    "syg_pyin_work_bytes": (_l, [_l, _l, _i]),
+    "syg_pyin_viterbi_f32": (_i, [_p, _p, _p, _p, _l, _l, _i, _i, _i, _p, _i, _p, _d, _p, _l, _p, _p, _p, _p]),
 }
 
 _lib = None

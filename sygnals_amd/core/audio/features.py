@@ -3,11 +3,15 @@
 The reference forwards both to librosa (`librosa.feature.zero_crossing_rate`: EDGE padding, threshold 1e-10,
 first sample of a frame never counts; `librosa.feature.rms`: zero padding, or from a magnitude spectrogram with DC /
 Nyquist halved).  Here one wave per frame computes them (`syg_frame_stats_f32`, `syg_rms_from_spec_f32`).
-The pitch-based placeholders of that file (hnr, jitter, shimmer) are not offloaded.
+fundamental_frequency (:135-220; librosa 0.10 yin / pyin, parity unpinned: the float64 restatement of
+tests/pitch_ref.py is the contract) runs the frame stage and the Viterbi decode on the device (`syg_pitch_frames_f32`,
+`syg_pyin_viterbi_f32`); jitter (:319) and shimmer (:412) are host arithmetic on its f0 / voicing and on the device
+rms_energy.  harmonic_to_noise_ratio is not offloaded.
 """
 from __future__ import annotations
 
 import logging
+import warnings
 from typing import Any, Optional
 
 import numpy as np
@@ -52,3 +56,129 @@ def rms_energy(y=None, *, S=None, frame_length: int = 2048, hop_length: int = 51
         raise ValueError("rms_energy: only pad_mode='constant' is offloaded")
     st = ops.frame_stats(ops.to_device_f32(np.asarray(y)[None, :]), frame_length, hop_length, center, mask=1 << _ROW_RMS)
     return st[0, _ROW_RMS].cpu().numpy().astype(np.float64)
+
+
+_EPSILON = 1e-10
+
+
+def _pitch_defaults(fmin, fmax, hop_length):
+    from ... import _pitch as P
+    return (P.C2 if fmin is None else float(fmin)), (P.C7 if fmax is None else float(fmax)), hop_length
+
+
+def fundamental_frequency_batch(y, sr: int, fmin: Optional[float] = None, fmax: Optional[float] = None,
+                                method: str = "pyin", hop_length: Optional[int] = None, frame_length: int = 2048,
+                                win_length: Optional[int] = None, center: bool = True):
+    """Batched fundamental_frequency of clips y [B, L] (a float32 device tensor or an array): device tensors
+    (times [T] float64 on the host, f0 [B, T] with NaN unvoiced, voiced_flag [B, T] float32 0 / 1, voiced_probs [B, T])."""
+    fmin, fmax, hop = _pitch_defaults(fmin, fmax, hop_length)
+    y = y if hasattr(y, "is_cuda") else ops.to_device_f32(np.atleast_2d(np.asarray(y)))
+    if y.dim() != 2:
+        raise ValueError("Input audio batch must be a 2D array [B, L].")
+    if method == "pyin":
+        f0, vf, vp = ops.pitch_pyin(y, sr, fmin, fmax, frame_length, win_length, hop, center)
+        vf = vf.float()
+    elif method == "yin":
+        f0 = ops.pitch_yin(y, sr, fmin, fmax, frame_length, win_length, hop, center)
+        vf = _finite01(f0)
+        vp = vf
+    else:
+        raise ValueError(f"Unsupported pitch estimation method: {method}. Choose 'pyin' or 'yin'.")
+    hop_calc = hop if hop is not None else 512
+    times = np.arange(f0.shape[1], dtype=np.float64) * hop_calc / sr
+    return times, f0, vf, vp
+
+
+def _finite01(t):
+    return t.isfinite().float()
+
+
+def fundamental_frequency(y, sr: int, fmin: Optional[float] = None, fmax: Optional[float] = None,
+                          method: str = "pyin", hop_length: Optional[int] = None, **kwargs: Any):
+    y = np.asarray(y)
+    if y.ndim != 1:
+        raise ValueError("Input audio data must be a 1D array.")
+    logger.debug(f"Estimating Fundamental Frequency (Pitch) using {method}: fmin={fmin}, fmax={fmax}, hop={hop_length}")
+    allowed = {"frame_length", "win_length", "center"}
+    if set(kwargs) - allowed:
+        raise TypeError(f"fundamental_frequency: unsupported librosa arguments on the device backend: "
+                        f"{sorted(set(kwargs) - allowed)}")
+    if method not in ("pyin", "yin"):
+        raise ValueError(f"Unsupported pitch estimation method: {method}. Choose 'pyin' or 'yin'.")
+    times, f0, vf, vp = fundamental_frequency_batch(y[None, :], sr, fmin, fmax, method, hop_length, **kwargs)
+    return (times, f0[0].cpu().numpy().astype(np.float64), vf[0].cpu().numpy().astype(np.float64),
+            vp[0].cpu().numpy().astype(np.float64))
+
+
+def jitter(y, sr: int, f0=None, voiced_flag=None, method: str = "local_abs", f0_min: float = 75.0,
+           f0_max: float = 600.0, hop_length: Optional[int] = None):
+    warnings.warn("Jitter feature is an approximation based on frame-level F0 period differences.", UserWarning,
+                  stacklevel=2)
+    logger.warning("Jitter feature is an approximation based on frame-level F0 period differences.")
+    if method != "local_abs":
+        raise NotImplementedError(f"Jitter method '{method}' not implemented. Only 'local_abs' is available.")
+    if f0 is None or voiced_flag is None:
+        logger.warning("F0 or voiced_flag not provided. Calculating F0 internally using pyin.")
+        hop_calc = hop_length if hop_length is not None else 512
+        try:
+            _, f0, voiced_flag, _ = fundamental_frequency(y, sr, fmin=f0_min, fmax=f0_max, method="pyin",
+                                                          hop_length=hop_calc)
+        except Exception as e:
+            logger.error(f"Internal F0 calculation failed for Jitter: {e}")
+            n = 1 + len(y) // hop_calc if hop_calc > 0 else 0
+            return np.full(n, np.nan, dtype=np.float64)
+    f0 = np.asarray(f0, dtype=np.float64)
+    voiced_flag = np.asarray(voiced_flag, dtype=np.float64)
+    if len(f0) != len(voiced_flag):
+        raise ValueError("Length of f0 and voiced_flag must match.")
+    n = len(f0)
+    out = np.full(n, np.nan, dtype=np.float64)
+    periods = np.full(n, np.nan, dtype=np.float64)
+    ok = (voiced_flag > 0.5) & np.isfinite(f0) & (f0 >= f0_min) & (f0 <= f0_max)
+    periods[ok] = 1.0 / f0[ok]
+    diffs = np.abs(np.diff(periods))
+    out[1:] = diffs
+    out[1:][~np.isfinite(diffs)] = np.nan
+    if n:
+        out[0] = np.nan
+    out[voiced_flag <= 0.5] = np.nan
+    return out
+
+
+def shimmer(y, sr: int, voiced_flag=None, method: str = "local_rms_rel", frame_length: int = 2048,
+            hop_length: Optional[int] = None, center: bool = True):
+    warnings.warn("Shimmer feature is an approximation based on frame-level relative RMS differences.", UserWarning,
+                  stacklevel=2)
+    logger.warning("Shimmer feature is an approximation based on frame-level relative RMS differences.")
+    y = np.asarray(y)
+    if y.ndim != 1:
+        raise ValueError("Input audio 'y' must be 1D for shimmer calculation.")
+    if method != "local_rms_rel":
+        raise NotImplementedError(f"Shimmer method '{method}' not implemented. Only 'local_rms_rel' is available.")
+    hop_calc = hop_length if hop_length is not None else frame_length // 4
+    if hop_calc <= 0:
+        raise ValueError("Hop length must be positive.")
+    try:
+        rms = rms_energy(y=y, frame_length=frame_length, hop_length=hop_calc, center=center)
+    except Exception as e:
+        logger.error(f"Internal RMS calculation failed for Shimmer: {e}")
+        return np.full(1 + len(y) // hop_calc, np.nan, dtype=np.float64)
+    if voiced_flag is None:
+        logger.warning("voiced_flag not provided for Shimmer. Calculating F0 internally using pyin.")
+        try:
+            _, _, voiced_flag, _ = fundamental_frequency(y, sr, fmin=75.0, fmax=600.0, method="pyin", hop_length=hop_calc)
+        except Exception as e:
+            logger.error(f"Internal F0/voicing calculation failed for Shimmer: {e}")
+            return np.full(len(rms), np.nan, dtype=np.float64)
+    voiced_flag = np.asarray(voiced_flag, dtype=np.float64)
+    n = min(len(rms), len(voiced_flag))
+    if n == 0:
+        return np.array([], dtype=np.float64)
+    rms = rms[:n]
+    vf = voiced_flag[:n]
+    out = np.full(n, np.nan, dtype=np.float64)
+    both = (vf[1:] > 0.5) & (vf[:-1] > 0.5)
+    s = rms[1:] + rms[:-1]
+    val = np.where(s > _EPSILON, 2.0 * np.abs(rms[1:] - rms[:-1]) / np.where(s > _EPSILON, s, 1.0), 0.0)
+    out[1:][both] = val[both]
+    return out

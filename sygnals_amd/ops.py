@@ -1795,3 +1795,100 @@ def cqt(y: torch.Tensor, sr: float, hop_length: int = 512, fmin=None, n_bins: in
     if two:
         main.wait_stream(side)
     return out
+
+
+# ------------------------------------------------------------------ pitch (yin / pyin)
+def _pitch_setup(y, sr, fmin, fmax, frame_length, win_length, hop, center):
+    from . import _pitch as P
+    require_gpu()
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
+        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
+    if y.stride(1) != 1:
+        y = y.contiguous()
+    win_length = int(win_length) if win_length is not None else frame_length // 2
+    hop = int(hop) if hop is not None else frame_length // 4
+    if not (0 < fmin < fmax <= sr / 2):
+        raise ValueError(f"pitch: need 0 < fmin < fmax <= sr / 2 (got fmin={fmin}, fmax={fmax}, sr={sr})")
+    if not (0 < win_length < frame_length):
+        raise ValueError(f"win_length={win_length} must be a positive integer less than frame_length={frame_length}")
+    min_p, max_p = P.periods(sr, fmin, fmax, frame_length, win_length)
+    B, L = y.shape
+    Tn = P.num_frames(L, frame_length, hop, center)
+    if Tn <= 0:
+        raise ValueError("signal too short for one frame")
+    return P, y, win_length, hop, min_p, max_p, B, L, Tn
+
+
+def pitch_frames(y: torch.Tensor, sr: float, fmin: float, fmax: float, frame_length: int = 2048,
+                 win_length: Optional[int] = None, hop: Optional[int] = None, center: bool = True, mode: str = "pyin",
+                 trough_threshold: float = 0.1, want_cmndf: bool = False) -> dict:
+    """Frame stage of yin / pyin on clips y [B, L] (syg_pitch_frames_f32): f0 (yin) or the pYIN candidate lists,
+    plus the CMNDF [B, T, n_lag] when want_cmndf."""
+    P, y, win_length, hop, min_p, max_p, B, L, Tn = _pitch_setup(y, sr, fmin, fmax, frame_length, win_length, hop, center)
+    dev = y.device
+    n_lag = max_p - min_p + 1
+    n_bins = P.n_pitch_bins(fmin, fmax)
+    K = P.cand_stride(n_lag)
+    out = dict(T=Tn, n_bins=n_bins, K=K, min_p=min_p, max_p=max_p, hop=hop)
+    cm = torch.empty((B, Tn, max(n_lag, 1)), dtype=torch.float32, device=dev) if want_cmndf else None
+    f0 = cb = cp = cc = vp = ptab = None
+    if mode == "yin":
+        f0 = torch.empty((B, Tn), dtype=torch.float32, device=dev)
+    elif mode == "pyin":
+        cb = torch.empty((B, Tn, K), dtype=torch.int32, device=dev)
+        cp = torch.empty((B, Tn, K), dtype=torch.float32, device=dev)
+        cc = torch.empty((B, Tn), dtype=torch.int32, device=dev)
+        vp = torch.empty((B, Tn), dtype=torch.float32, device=dev)
+        ptab = _cached(("pyin_tab", K), lambda: _dev(P.pyin_device_table(K)))
+    else:
+        raise ValueError(f"Unsupported pitch estimation method: {mode}. Choose 'pyin' or 'yin'.")
+    rc = lib().syg_pitch_frames_f32(_ptr(y), B, L, _ld(y), int(frame_length), win_length, hop, int(center), Tn, float(sr),
+                                    min_p, max_p, 0 if mode == "yin" else 1, float(trough_threshold), float(fmin), n_bins,
+                                    _ptr(ptab), K, _ptr(twiddle_dev(2048)), _ptr(f0), _ptr(cb), _ptr(cp), _ptr(cc),
+                                    _ptr(vp), _ptr(cm), C.c_void_p(_stream_ptr()))
+    check(rc, "syg_pitch_frames_f32")
+    out.update(f0=f0, cand_bin=cb, cand_prob=cp, cand_count=cc, voiced_prob=vp, cmndf=cm)
+    return out
+
+
+def pyin_viterbi(cand_bin: torch.Tensor, cand_prob: torch.Tensor, cand_count: torch.Tensor, voiced_prob: torch.Tensor,
+                 n_bins: int, width: int, fmin: float):
+    """Viterbi decode of pYIN candidate lists (syg_pyin_viterbi_f32) -> f0 [B, T] (NaN unvoiced), voiced (bool),
+    state (int32)."""
+    from . import _pitch as P
+    B, Tn, K = cand_bin.shape
+    dev = cand_bin.device
+    tabs, R, h = P.transition_tables(int(n_bins), int(width))
+    ltab = _cached(("pyin_ltab", int(n_bins), int(width)), lambda: _dev(tabs))
+    lconst = np.ascontiguousarray(P.log_consts(int(n_bins)))
+    wb = lib().syg_pyin_work_bytes(B, Tn, int(n_bins))
+    if wb < 0:
+        raise ValueError(f"pyin_viterbi: bad shape B={B} T={Tn} n_bins={n_bins}")
+    work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+    f0 = torch.empty((B, Tn), dtype=torch.float32, device=dev)
+    voiced = torch.empty((B, Tn), dtype=torch.uint8, device=dev)
+    state = torch.empty((B, Tn), dtype=torch.int32, device=dev)
+    rc = lib().syg_pyin_viterbi_f32(_ptr(cand_bin.contiguous()), _ptr(cand_prob.contiguous()), _ptr(cand_count.contiguous()),
+                                    _ptr(voiced_prob.contiguous()), B, Tn, K, int(n_bins), h, _ptr(ltab), R,
+                                    lconst.ctypes.data_as(C.c_void_p), float(fmin), _ptr(work), wb, _ptr(f0), _ptr(voiced),
+                                    _ptr(state), C.c_void_p(_stream_ptr()))
+    check(rc, "syg_pyin_viterbi_f32")
+    return f0, voiced.bool(), state
+
+
+def pitch_yin(y: torch.Tensor, sr: float, fmin: float, fmax: float, frame_length: int = 2048,
+              win_length: Optional[int] = None, hop: Optional[int] = None, center: bool = True,
+              trough_threshold: float = 0.1) -> torch.Tensor:
+    """librosa.yin on clips y [B, L] -> f0 [B, T] float32 device tensor."""
+    return pitch_frames(y, sr, fmin, fmax, frame_length, win_length, hop, center, "yin", trough_threshold)["f0"]
+
+
+def pitch_pyin(y: torch.Tensor, sr: float, fmin: float, fmax: float, frame_length: int = 2048,
+               win_length: Optional[int] = None, hop: Optional[int] = None, center: bool = True):
+    """librosa.pyin on clips y [B, L] -> (f0 [B, T] float32 with NaN unvoiced, voiced_flag [B, T] bool,
+    voiced_prob [B, T] float32), device tensors."""
+    from . import _pitch as P
+    fr = pitch_frames(y, sr, fmin, fmax, frame_length, win_length, hop, center, "pyin")
+    f0, voiced, _ = pyin_viterbi(fr["cand_bin"], fr["cand_prob"], fr["cand_count"], fr["voiced_prob"], fr["n_bins"],
+                                 P.transition_width(sr, fr["hop"]), fmin)
+    return f0, voiced, fr["voiced_prob"]
