@@ -107,8 +107,8 @@ def transition_local(n: int, width: int) -> np.ndarray:
         row = np.zeros(n, dtype=np.float64)
         if width <= n:
             row[lpad:lpad + width] = win
-        else:                                    # librosa.util.pad_center cannot pad: the window is cut to n centred
-            c0 = (width - n) // 2
+        else:                                    # librosa.util.pad_center cannot pad: the window is cut to n, its centre
+            c0 = width // 2 - (n - 1) // 2       # at (n - 1) // 2 where pad_center puts it, so the roll lands it on i
             row[:] = win[c0:c0 + n]
         row = np.roll(row, n // 2 + i + 1)
         row[min(n, i + width // 2 + 1):] = 0

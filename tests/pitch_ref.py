@@ -16,16 +16,23 @@ def frames(y, frame_length=2048, hop=512, center=True):
     return y[idx]                                                     # [T, N]
 
 
-def cmndf(fr, win_length, min_p, max_p):
-    """[T, N] frames -> [T, n_lag] cumulative mean normalised difference (librosa's FFT form)."""
+def acf_energy(fr, win_length):
+    """[T, N] frames -> (acf, e) [T, N - W] before librosa's |.| < 1e-6 clamps: acf(tau) = sum_{j=1..W} x_j x_{j+tau},
+    e(tau) = sum_{j=tau+1..tau+W} x_j^2."""
     N = fr.shape[1]
     W = win_length
     a = np.fft.rfft(fr, N, axis=1)
     b = np.fft.rfft(fr[:, W:0:-1], N, axis=1)
     acf = np.fft.irfft(a * b, N, axis=1)[:, W:]
-    acf[np.abs(acf) < 1e-6] = 0
     en = np.cumsum(fr ** 2, axis=1)
     en = en[:, W:] - en[:, :-W]
+    return acf, en
+
+
+def cmndf(fr, win_length, min_p, max_p):
+    """[T, N] frames -> [T, n_lag] cumulative mean normalised difference (librosa's FFT form)."""
+    acf, en = acf_energy(fr, win_length)
+    acf[np.abs(acf) < 1e-6] = 0
     en[np.abs(en) < 1e-6] = 0
     d = en[:, :1] + en - 2 * acf
     num = d[:, min_p:max_p + 1]

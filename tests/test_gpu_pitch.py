@@ -96,29 +96,39 @@ def _device_candidates(fr, b, t):
     return fr["cand_bin"][b, t, :n], fr["cand_prob"][b, t, :n]
 
 
+def check_emission_frame(h, b, t, sr, fmin):
+    """pYIN emission of the device frame (b, t) against R.pyin_frame fed the device CMNDF: bins exact, probabilities and
+    voiced_prob within 1e-6.  h: pitch_frames output on the host.  Returns False (nothing checked) when a trough's
+    120 log2 argument sits within 1e-6 of a rounding point, where the bins may differ."""
+    sr = float(sr)
+    c = h["cmndf"][b, t].astype(np.float64)
+    tr = np.nonzero(R.troughs(c))[0]
+    sh = R.parabolic_shifts(c)
+    x = 120 * np.log2(sr / (h["min_p"] + tr + sh[tr]) / fmin)
+    if np.any(np.abs(np.abs(x - np.floor(x)) - 0.5) < 1e-6):
+        return False
+    rb, rp, rvp = R.pyin_frame(c, sr, h["min_p"], fmin, h["n_bins"])
+    db, dp = _device_candidates(h, b, t)
+    where = f"clip {b} frame {t}"
+    assert sorted(db.tolist()) == sorted(rb.tolist()), where
+    np.testing.assert_allclose(dp[np.argsort(db)], rp[np.argsort(rb)], rtol=0, atol=1e-6, err_msg=where)
+    assert abs(h["voiced_prob"][b, t] - rvp) <= 1e-6, where
+    return True
+
+
+def host_frames(fr):
+    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in fr.items()}
+
+
 @pytest.mark.parametrize("sr", [48000, 22050])
 def test_emission_exact_on_device_cmndf(sr):
     ops = _ops()
     Y = np.concatenate([_mixed_clips(sr, sr), _vibrato_clips(8, sr, 1.0, seed=5)])
     fr = ops.pitch_frames(ops.to_device_f32(Y), sr, P.C2, P.C7, mode="pyin", want_cmndf=True)
-    h = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in fr.items()}
-    n = h["n_bins"]
+    h = host_frames(fr)
     for b in range(len(Y)):
         for t in range(h["T"]):
-            c = h["cmndf"][b, t].astype(np.float64)
-            rb, rp, rvp = R.pyin_frame(c, sr, h["min_p"], P.C2, n)
-            db, dp = _device_candidates(h, b, t)
-            # bins whose 120 log2 argument sits within 1e-6 of a rounding point may differ
-            tr = np.nonzero(R.troughs(c))[0]
-            sh = R.parabolic_shifts(c)
-            x = 120 * np.log2(sr / (h["min_p"] + tr + sh[tr]) / P.C2)
-            if np.any(np.abs(np.abs(x - np.floor(x)) - 0.5) < 1e-6):
-                continue
-            assert sorted(db.tolist()) == sorted(rb.tolist()), f"clip {b} frame {t}"
-            order = np.argsort(rb)
-            np.testing.assert_allclose(dp[np.argsort(db)],
-                                       rp[order], rtol=0, atol=1e-6)
-            assert abs(h["voiced_prob"][b, t] - rvp) <= 1e-6
+            check_emission_frame(h, b, t, sr, P.C2)
 
 
 def _ref_lists(Y, sr):

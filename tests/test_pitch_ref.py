@@ -29,6 +29,27 @@ def test_transition_rows(n, width):
         assert Rr == 2 * h + 1 and tabs.shape == (2, Rr, 2 * h + 1)
 
 
+@pytest.mark.parametrize("n,width", [(39, 141), (361, 551), (4, 5), (608, 611), (2, 31)])
+def test_transition_wider_than_states(n, width):
+    """width > n (a chosen behaviour, not pinned against librosa, which may reject it): the n centre entries of the
+    triangle window are rolled onto each row and masked to |j - i| <= width // 2, so inside the band the row reads the
+    window at the CIRCULAR offset (j - i) mod n; with width // 2 >= n - 1 nothing is masked."""
+    from scipy.signal import get_window
+    T = P.transition_local(n, width)
+    h = width // 2
+    m = (n - 1) // 2                                                    # the centre, as librosa's pad_center
+    w = get_window("triangle", width, fftbins=False)[h - m:h - m + n]     # offsets -m .. n - 1 - m
+    for i in range(n):
+        j = np.arange(n)
+        raw = np.where(np.abs(j - i) <= h, w[(j - i + m) % n], 0.0)
+        np.testing.assert_allclose(T[i], raw / math.fsum(raw), rtol=1e-15, atol=0, err_msg=f"row {i}")
+        assert np.argmax(T[i]) == i, f"row {i}: the peak is off the diagonal"
+    if h >= n - 1:
+        assert T[0, n - 1] == T[0, 1] > 0
+    tabs, Rr, hh = P.transition_tables(n, width)
+    assert Rr == n and hh == h
+
+
 def test_beta_and_boltzmann():
     assert math.isclose(P.beta_probs().sum(), beta.cdf(1, 2, 18), rel_tol=0, abs_tol=1e-15)
     for n in (1, 2, 7, 50):
@@ -80,7 +101,10 @@ def test_duplicate_bin_and_top_bin_traps():
     assert n not in b2 and len(b2) == 0 and vp2 == 0.0
 
 
-@pytest.mark.parametrize("n,width", [(40, 11), (61, 21), (25, 31)])
+# besides the edge-rows + interior-pattern tables: R == n with width > n (39, 141), width == n, jitter's 75-600 Hz range at
+# hop 2048 / 16 kHz (361, 551), h = 0 (601, 1: hop 32 / 48 kHz), a single pitch bin and an even n below the width
+@pytest.mark.parametrize("n,width", [(40, 11), (61, 21), (25, 31), (39, 141), (51, 51), (1, 1), (1, 51), (361, 551),
+                                     (601, 1), (40, 51)])
 def test_band_viterbi_equals_dense(n, width):
     rng = np.random.default_rng(n + width)
     for _ in range(3):
@@ -89,8 +113,8 @@ def test_band_viterbi_equals_dense(n, width):
         vps = rng.uniform(0, 1, Tn)
         for t in range(Tn):
             k = rng.integers(0, 4)
-            bins = rng.choice(n, size=k, replace=False)
-            obs[bins, t] = rng.uniform(0, 0.5, k)
+            bins = rng.choice(n, size=min(k, n), replace=False)
+            obs[bins, t] = rng.uniform(0, 0.5, len(bins))
         obs[n:, :] = (1 - vps[None, :]) / n
         p_init = np.zeros(2 * n)
         p_init[n:] = 1 / n
