@@ -476,6 +476,41 @@ int syg_pyin_viterbi_f32(const int* cand_bin, const float* cand_prob, const int*
                          uint8_t* voiced_out, int* state_out, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * HPSS: librosa 0.10 effects.hpss (kernel_size 31, margins, power) as called by harmonic_to_noise_ratio,
+ * sygnals/core/audio/features.py:225-316, after the complex STFT of syg_stft2048_c2c_f32 (D [B, T, 1025] complex,
+ * frame-major).  Parity is unpinned (librosa is not a dependency): the float64 restatement of tests/hpss_ref.py is the
+ * contract.
+ * syg_hpss_masks_f32: S = |D| computed as __fsqrt_rn(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im))) with IEEE
+ *   round-to-nearest at every step, no FMA (a host test rebuilds it bit for bit).  H = median over time (window win_harm) per bin, P = median over bins (window win_perc)
+ *   per frame, scipy.ndimage.median_filter semantics: window [i - k/2, i - k/2 + k - 1], element of rank k/2 (the upper
+ *   median for even k), indices folded by half-sample symmetric reflection as often as needed.  1 <= win <= 63 each.
+ *   mask_harm = softmask(H, P margin_harm), mask_perc = softmask(P, H margin_perc) [B, T, 1025] float32 (util.softmask:
+ *   Z = max(X, X_ref), Z < FLT_MIN -> 0.5 when both margins are 1, else 0; power = +inf -> X > X_ref).
+ *   power > 0 (finite or +inf), margins >= 1.  harm_out / perc_out [B, T, 1025] or NULL: the medians H / P.
+ * syg_istft2048_f32: librosa.istft(D masked, n_fft 2048, hop 512, center, length) -> y [B, length] (row stride ldy).
+ *   window: [2048] float64, a periodic window (w[s] = w[2048 - s]: only w[0 .. 1024] is read; hann for every
+ *   reference call path), twiddle: [2048] complex W_2048^k.  Frames
+ *   min(T, ceil((length + 2048) / 512)); each is window * irfft (Im of bins 0 and 1024 ignored), overlap-added in frame
+ *   order, the first 1024 samples trimmed, divided by the float64 window sum-square (rounded once) where it exceeds
+ *   FLT_MIN.  mask_a / mask_b [B, T, 1025] float32 multiply D on load (mask_a NULL: the plain istft into y_a); a second
+ *   component (mask_b, y_b) runs in the same launch, its waves beside the first's so that the reads of D meet in
+ *   cache.  No atomics: the result is bit-identical from run to run.  hop != 512 or center != 1: SYG_E_UNSUPPORTED.
+ * syg_hnr_rows_f32: frames of frame_length at hop (center pads frame_length / 2 zeros on each side; T frames, the
+ *   framing rule of librosa.feature.rms) of y_harm / y_perc [B, L] (row stride ldy).  Frame powers P = rms^2, rms =
+ *   sqrt(mean x^2) in float64; hnr_out [B, T] = 10 log10(P_h / P_p) where both exceed 1e-10, +80 / -80 where only
+ *   P_h / P_p does, NaN otherwise.  rms_harm_out / rms_perc_out [B, T] or NULL.
+ * ------------------------------------------------------------------------------- */
+int syg_hpss_masks_f32(const float* D, int64_t B, int64_t T, int win_harm, int win_perc, double power,
+                       double margin_harm, double margin_perc, float* mask_harm, float* mask_perc, float* harm_out,
+                       float* perc_out, void* stream);
+int syg_istft2048_f32(const float* D, int64_t B, int64_t T, int hop, int center, int64_t length, const double* window,
+                      const float* twiddle, const float* mask_a, float* y_a, const float* mask_b, float* y_b,
+                      int64_t ldy, void* stream);
+int syg_hnr_rows_f32(const float* y_harm, const float* y_perc, int64_t B, int64_t L, int64_t ldy, int frame_length,
+                     int hop, int center, int64_t T, float* hnr_out, float* rms_harm_out, float* rms_perc_out,
+                     void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Constant-Q transform building blocks: librosa.cqt as called by compute_cqt,
  * sygnals/core/dsp.py:276-284 (recursive per-octave algorithm; the host composes the octaves).
  *   syg_decimate2_f32   y[b, n] = scale * sum_j taps[j] * x[b, 2n + (ntaps-1)/2 - j], n < ceil(L/2)

@@ -89,6 +89,9 @@ SIGNATURES = {
                                   _p, _p, _p]),
     "syg_pyin_work_bytes": (_l, [_l, _l, _i]),
     "syg_pyin_viterbi_f32": (_i, [_p, _p, _p, _p, _l, _l, _i, _i, _i, _p, _i, _p, _d, _p, _l, _p, _p, _p, _p]),
+    "syg_hpss_masks_f32": (_i, [_p, _l, _l, _i, _i, _d, _d, _d, _p, _p, _p, _p, _p]),
+    "syg_istft2048_f32": (_i, [_p, _l, _l, _i, _i, _l, _p, _p, _p, _p, _p, _p, _l, _p]),
+    "syg_hnr_rows_f32": (_i, [_p, _p, _l, _l, _l, _i, _i, _i, _l, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -6,7 +6,9 @@ Nyquist halved).  Here one wave per frame computes them (`syg_frame_stats_f32`, 
 fundamental_frequency (:135-220; librosa 0.10 yin / pyin, parity unpinned: the float64 restatement of
 tests/pitch_ref.py is the contract) runs the frame stage and the Viterbi decode on the device (`syg_pitch_frames_f32`,
 `syg_pyin_viterbi_f32`); jitter (:319) and shimmer (:412) are host arithmetic on its f0 / voicing and on the device
-rms_energy.  harmonic_to_noise_ratio is not offloaded.
+rms_energy.  harmonic_to_noise_ratio (:225-316; librosa 0.10 effects.hpss, parity unpinned: the float64 restatement
+of tests/hpss_ref.py is the contract) runs the STFT, the median-filter soft masks, both inverse STFTs and the per-frame
+energy ratio on the device (`syg_stft2048_c2c_f32`, `syg_hpss_masks_f32`, `syg_istft2048_f32`, `syg_hnr_rows_f32`).
 """
 from __future__ import annotations
 
@@ -182,3 +184,58 @@ def shimmer(y, sr: int, voiced_flag=None, method: str = "local_rms_rel", frame_l
     val = np.where(s > _EPSILON, 2.0 * np.abs(rms[1:] - rms[:-1]) / np.where(s > _EPSILON, s, 1.0), 0.0)
     out[1:][both] = val[both]
     return out
+
+
+_HPSS_KWARGS = {"power", "n_fft", "win_length", "window", "center"}
+
+
+def _hpss_kwargs(kwargs):
+    if set(kwargs) - _HPSS_KWARGS:
+        raise TypeError(f"harmonic_to_noise_ratio: unsupported librosa arguments on the device backend: "
+                        f"{sorted(set(kwargs) - _HPSS_KWARGS)}")
+    hk = dict(kwargs)
+    # the STFT settings the device path supports are checked here, outside the reference's NaN path
+    ops._hpss_stft_args(hk.get("n_fft", 2048), None, hk.get("win_length"), hk.get("window", "hann"),
+                        hk.get("center", True))
+    return hk
+
+
+def harmonic_to_noise_ratio_batch(y, sr: int, frame_length: int = 2048, hop_length: Optional[int] = None,
+                                  harmonic_margin=1.0, percussive_margin=1.0, **kwargs: Any):
+    """Batched harmonic_to_noise_ratio of clips y [B, L] (a float32 device tensor or an array) -> float32 [B, T]
+    device tensor with the reference's NaN / +-80 rules.  Errors raise (no NaN path)."""
+    hk = _hpss_kwargs(kwargs)
+    if hasattr(y, "is_cuda"):                # a torch tensor: moved to the device as float32 unless it is already
+        y = y if (y.is_cuda and y.dtype == ops.torch.float32) else ops.to_device_f32(y)
+    else:
+        y = ops.to_device_f32(np.atleast_2d(np.asarray(y)))
+    if y.dim() != 2:
+        raise ValueError("Input audio batch must be a 2D array [B, L].")
+    hop_calc = hop_length if hop_length is not None else frame_length // 4
+    yh, yp = ops.hpss(y, kernel_size=31, power=hk.get("power", 2.0), margin=(harmonic_margin, percussive_margin),
+                      win_length=hk.get("win_length"), window=hk.get("window", "hann"), center=hk.get("center", True),
+                      n_fft=hk.get("n_fft", 2048))
+    return ops.hnr_rows(yh, yp, frame_length, hop_calc, center=True)
+
+
+def harmonic_to_noise_ratio(y, sr: int, frame_length: int = 2048, hop_length: Optional[int] = None,
+                            harmonic_margin=1.0, percussive_margin=1.0, **kwargs: Any):
+    warnings.warn("harmonic_to_noise_ratio feature is an approximation based on HPSS energy ratio.", UserWarning,
+                  stacklevel=2)
+    logger.warning("harmonic_to_noise_ratio feature is an approximation based on HPSS energy ratio.")
+    y = np.asarray(y)
+    if y.ndim != 1:
+        raise ValueError("Input audio 'y' must be 1D for HPSS-based HNR.")
+    _hpss_kwargs(kwargs)
+    ops.require_gpu()
+    hop_length_calc = hop_length if hop_length is not None else frame_length // 4
+    try:
+        out = harmonic_to_noise_ratio_batch(y[None, :], sr, frame_length, hop_length, harmonic_margin,
+                                            percussive_margin, **kwargs)
+        hnr_db = out[0].cpu().numpy().astype(np.float64)
+        logger.debug(f"Calculated approximate HNR for {len(hnr_db)} frames.")
+        return hnr_db
+    except Exception as e:
+        logger.error(f"Error calculating approximate HNR using HPSS: {e}")
+        num_frames = 1 + len(y) // hop_length_calc if hop_length_calc > 0 else 0
+        return np.full(num_frames, np.nan, dtype=np.float64)

@@ -1892,3 +1892,124 @@ def pitch_pyin(y: torch.Tensor, sr: float, fmin: float, fmax: float, frame_lengt
     f0, voiced, _ = pyin_viterbi(fr["cand_bin"], fr["cand_prob"], fr["cand_count"], fr["voiced_prob"], fr["n_bins"],
                                  P.transition_width(sr, fr["hop"]), fmin)
     return f0, voiced, fr["voiced_prob"]
+
+
+# ------------------------------------------------------------------ HPSS (harmonic / percussive separation)
+def _pair(v, what):
+    if np.isscalar(v):
+        return v, v
+    v = tuple(v)
+    if len(v) != 2:
+        raise ValueError(f"{what} must be a scalar or a pair")
+    return v[0], v[1]
+
+
+def _hpss_stft_args(n_fft, hop_length, win_length, window, center):
+    if n_fft != 2048:
+        raise ValueError(f"hpss: n_fft={n_fft} is not offloaded (only 2048)")
+    win_length = 2048 if win_length is None else int(win_length)
+    hop = win_length // 4 if hop_length is None else int(hop_length)
+    if win_length != 2048 or hop != 512 or not isinstance(window, str) or window != "hann" or not center:
+        raise ValueError("hpss: only window='hann', win_length=2048, hop 512 and center=True are offloaded "
+                         f"(got window={window!r}, win_length={win_length}, hop={hop}, center={center})")
+    return hop
+
+
+def window64_dev() -> torch.Tensor:
+    """Periodic Hann window of 2048 points as float64 (the synthesis window of istft2048)."""
+    return _cached(("win64", "hann", 2048), lambda: _dev(T.analysis_window("hann", 2048, 2048)))
+
+
+def istft2048(D: torch.Tensor, hop: int = 512, length: Optional[int] = None, center: bool = True, window="hann",
+              win_length: Optional[int] = None, mask=None, ldy: Optional[int] = None) -> torch.Tensor:
+    """librosa.istft(n_fft=2048) of the frame-major complex STFT D [B, T, 1025, 2] (syg_istft2048_f32) -> y [B, length].
+    mask: None, one real mask [B, T, 1025] applied to D on load, or a pair of masks -> a pair of outputs (one read of D).
+    length defaults to 512 (T - 1), librosa's center=True length.  ldy: row stride of the output (>= length)."""
+    require_gpu()
+    _hpss_stft_args(2048, hop, win_length, window, center)
+    if D.dim() != 4 or D.shape[2] != 1025 or D.shape[3] != 2 or D.dtype != torch.float32 or not D.is_cuda:
+        raise ValueError("D must be a float32 CUDA tensor [B, T, 1025, 2]")
+    D = D.contiguous()
+    B, Tn = D.shape[0], D.shape[1]
+    length = 512 * (Tn - 1) if length is None else int(length)
+    if length < 1:
+        raise ValueError("istft2048: length must be >= 1")
+    ld = length if ldy is None else int(ldy)
+    two = isinstance(mask, (tuple, list))
+    masks = [m.contiguous() if m is not None else None for m in (mask if two else (mask,))]
+    for m in masks:
+        if m is not None and (m.shape != (B, Tn, 1025) or m.dtype != torch.float32):
+            raise ValueError("mask must be float32 [B, T, 1025]")
+    outs = [torch.zeros((B, ld), dtype=torch.float32, device=D.device) for _ in masks]
+    rc = lib().syg_istft2048_f32(_ptr(D), B, Tn, int(hop), int(bool(center)), length, _ptr(window64_dev()),
+                                 _ptr(twiddle_dev(2048)), _ptr(masks[0]), _ptr(outs[0]),
+                                 _ptr(masks[1]) if two else None, _ptr(outs[1]) if two else None, ld,
+                                 C.c_void_p(_stream_ptr()))
+    check(rc, "syg_istft2048_f32")
+    outs = [o[:, :length] for o in outs]
+    return tuple(outs) if two else outs[0]
+
+
+def hpss_masks(D: torch.Tensor, kernel_size=31, power: float = 2.0, margin=1.0, medians: bool = False):
+    """decompose.hpss(mask=True) on the complex STFT D [B, T, 1025, 2] (syg_hpss_masks_f32) -> (mask_harm, mask_perc)
+    [B, T, 1025] float32, plus the medians (H, P) when `medians`."""
+    require_gpu()
+    kh, kp = _pair(kernel_size, "kernel_size")
+    mh, mp = _pair(margin, "margin")
+    if mh < 1 or mp < 1:
+        raise ValueError("Margins must be >= 1.0. A typical range is between 1 and 10.")
+    if not (power > 0):
+        raise ValueError("power must be strictly positive")
+    if D.dim() != 4 or D.shape[2] != 1025 or D.shape[3] != 2 or D.dtype != torch.float32 or not D.is_cuda:
+        raise ValueError("D must be a float32 CUDA tensor [B, T, 1025, 2]")
+    D = D.contiguous()
+    B, Tn = D.shape[0], D.shape[1]
+    new = lambda: torch.empty((B, Tn, 1025), dtype=torch.float32, device=D.device)  # noqa: E731
+    Mh, Mp = new(), new()
+    H, P = (new(), new()) if medians else (None, None)
+    rc = lib().syg_hpss_masks_f32(_ptr(D), B, Tn, int(kh), int(kp), float(power), float(mh), float(mp), _ptr(Mh),
+                                  _ptr(Mp), _ptr(H), _ptr(P), C.c_void_p(_stream_ptr()))
+    check(rc, "syg_hpss_masks_f32")
+    return (Mh, Mp, H, P) if medians else (Mh, Mp)
+
+
+def hpss(y: torch.Tensor, kernel_size=31, power: float = 2.0, margin=1.0, hop_length: Optional[int] = None,
+         win_length: Optional[int] = None, window="hann", center: bool = True, n_fft: int = 2048):
+    """librosa.effects.hpss on clips y [B, L] -> (y_harm, y_perc) [B, L] float32 device tensors:
+    syg_stft2048_c2c_f32 -> syg_hpss_masks_f32 -> syg_istft2048_f32 (both components from one read of D)."""
+    require_gpu()
+    hop = _hpss_stft_args(n_fft, hop_length, win_length, window, center)
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
+        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
+    if y.shape[0] < 1 or y.shape[1] < 1:
+        raise ValueError("hpss: empty input")
+    D = stft2048_c2c(y, hop, True, "hann", 2048)
+    Mh, Mp = hpss_masks(D, kernel_size, power, margin)
+    return istft2048(D, hop, y.shape[1], True, "hann", 2048, mask=(Mh, Mp))
+
+
+def hnr_rows(y_harm: torch.Tensor, y_perc: torch.Tensor, frame_length: int = 2048, hop: Optional[int] = None,
+             center: bool = True, rms: bool = False):
+    """Per-frame HNR of the reference's harmonic_to_noise_ratio from the two components [B, L] (syg_hnr_rows_f32) ->
+    hnr [B, T] float32 (NaN / +-80 rules of the reference), plus (rms_harm, rms_perc) [B, T] when `rms`."""
+    require_gpu()
+    hop = frame_length // 4 if hop is None else int(hop)
+    if frame_length < 1 or hop < 1:
+        raise ValueError("hnr_rows: frame_length and hop must be >= 1")
+    if y_harm.shape != y_perc.shape or y_harm.dim() != 2:
+        raise ValueError("hnr_rows: y_harm and y_perc must have the same shape [B, L]")
+    yh, yp = y_harm, y_perc
+    if yh.stride(1) != 1 or yp.stride(1) != 1 or _ld(yh) != _ld(yp):
+        yh, yp = yh.contiguous(), yp.contiguous()
+    B, L = yh.shape
+    Tn = 1 + (L + 2 * (frame_length // 2) - frame_length) // hop if center else (
+        1 + (L - frame_length) // hop if L >= frame_length else 0)
+    if Tn <= 0:
+        raise ValueError("signal too short for one frame")
+    out = torch.empty((B, Tn), dtype=torch.float32, device=yh.device)
+    rh = torch.empty_like(out) if rms else None
+    rp = torch.empty_like(out) if rms else None
+    rc = lib().syg_hnr_rows_f32(_ptr(yh), _ptr(yp), B, L, _ld(yh), int(frame_length), hop, int(bool(center)), Tn,
+                                _ptr(out), _ptr(rh), _ptr(rp), C.c_void_p(_stream_ptr()))
+    check(rc, "syg_hnr_rows_f32")
+    return (out, rh, rp) if rms else out
