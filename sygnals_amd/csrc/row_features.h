@@ -767,3 +767,14 @@ __device__ __noinline__ float3 row_features(lds_row prow, int lane, float binhz,
   const float2 pv = row_contrast_body<PS, (NBIN > 1025)>(prow, lane, cpl, n_rows_v, may_park_v);
   return make_float3(s, pv.x, pv.y);
 }
+
+// What the free-running kernels of frame lengths 1024 / 4096 / 512 / 256 pass to the row functions, by value (the host
+// fills it: fill_row_args of stft_host.h; all zero: no rows)
+struct RowArgs {
+  float binhz, roll_percent, bw_p;
+  int smask;
+  float* stats_out;                                   // [B, SYG_NSTAT, T] or null
+  float* contrast_out;                                // [B, 2, n_rows, T] or null
+  int n_rows, ascending;                              // contrast plan: see parse_contrast_plan
+  int lo[SYG_MAX_BANDS], hi[SYG_MAX_BANDS], k[SYG_MAX_BANDS];
+};

@@ -27,9 +27,8 @@
 // **2 -> melspectrogram -> power_to_db(ref=np.max) -> mfcc, as called from sygnals/core/features/manager.py:184-187,
 // 198, 219-223 and cepstral.py:106-115; per-frame statistics follow sygnals/core/features/frequency_domain.py:24-386.
 // Index maps and LDS bank behaviour are validated by tools/wave_fft_model_v5.py.
-#include "common.h"
+#include "stft_host.h"
 #include <stdlib.h>
-#include <string.h>
 
 // Issue priority falls as a wave advances through its frame: the SIMD's arbiter otherwise favours the oldest
 // wave, which then idles at barrier A while the youngest finishes alone with nothing to hide its LDS latency.
@@ -1048,12 +1047,7 @@ constexpr size_t lds_bytes() {
 // receive workgroups while the previous batch is gathered -- either waits for a whole launch or makes this launch wait
 // for it (tools/queue_bench.py: 167 -> 256 us for every second launch).  With the CUs set aside both run side by side.
 void persistent_grid(int64_t total_tiles, int waves, int& wgs, int& per) {
-  // the CU count of the CURRENT device, asked at every call (an attribute query, no device properties round trip):
-  // no process-wide cache that a second device or a second thread could read stale
-  int n_cu = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0)
-    n_cu = 256;
+  const int n_cu = device_cu_count();
   int use_cu = n_cu;
   const int r = option(SYG_OPT_RESERVED_CUS);
   if (r > 0 && r < n_cu) use_cu = n_cu - r;
@@ -1072,13 +1066,8 @@ int load_mode() {
 
 int check_common(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
                  const float* window, const float* twiddle, int waves) {
-  SYG_REQUIRE(y && window && twiddle, "stft2048: null pointer argument");
-  SYG_REQUIRE(B >= 1 && L >= 1 && ldy >= L, "stft2048: need B >= 1, L >= 1, ldy >= L (B=%lld L=%lld ldy=%lld)",
-              (long long)B, (long long)L, (long long)ldy);
-  SYG_REQUIRE(hop >= 1, "stft2048: hop must be >= 1 (got %d)", hop);
-  const int64_t Texp = center ? 1 + L / hop : (L >= NFFT ? 1 + (L - NFFT) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp, "stft2048: T=%lld does not match the framing rule (%lld)", (long long)T,
-              (long long)Texp);
+  const int rc = check_clips("stft2048", y, B, L, ldy, NFFT, hop, center, T, window, twiddle);
+  if (rc) return rc;
   SYG_REQUIRE(B * ((T + waves - 1) / waves) < (int64_t)0x7fffffff, "stft2048: grid too large");
   return SYG_OK;
 }
@@ -1128,16 +1117,9 @@ int launch(int load, const float* y, int64_t B, int64_t L, int64_t ldy, int hop,
   const int dma_wide = (hop % 4 == 0) && (pad % 4 == 0) && (ldy % 4 == 0) && (L % 4 == 0) && (((uintptr_t)y) % 16 == 0);
   auto kern = load == 2 ? stft2048_kernel<WAVES, 2, MODE>
                         : load == 1 ? stft2048_kernel<WAVES, 1, MODE> : stft2048_kernel<WAVES, 0, MODE>;
-  {
-    // set at every launch: the attribute belongs to the (function, device) pair, and a per-process "already set"
-    // flag would leave a second device without it
-    const size_t cap = (MODE == 3 || TRI) ? LDS_LIMIT : TRIMEL ? lds_bytes<WAVES, false, TRIMEL_NPASS>() : lds_bytes<WAVES>();
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
-    if (e != hipSuccess) {
-      set_error("stft2048: cannot reserve %zu B LDS: %s", cap, hipGetErrorString(e));
-      return SYG_E_LAUNCH;
-    }
-  }
+  const size_t cap = (MODE == 3 || TRI) ? LDS_LIMIT : TRIMEL ? lds_bytes<WAVES, false, TRIMEL_NPASS>() : lds_bytes<WAVES>();
+  const int rc = reserve_dynamic_lds("stft2048", (const void*)kern, cap);
+  if (rc) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(WAVES * 64), lds, st, y, L, ldy, hop, pad, T,
                      tiles, total_tiles, per, (const float2*)window, (const float2*)twiddle, wpacked, plan, n_mels,
                      mel_out, binhz, roll_percent, bw_p, smask, stats_out, cp, contrast_out, (float2*)cout, dma_wide, mf);
@@ -1152,25 +1134,6 @@ using namespace syg;
 
 namespace syg {
 namespace {
-int parse_contrast_plan(const float* contrast_out, const int32_t* cplan_host, ContrastPlan& cp) {
-  memset(&cp, 0, sizeof(cp));
-  if (!contrast_out) return SYG_OK;
-  SYG_REQUIRE(cplan_host, "stft2048: contrast_out given without cplan_host");
-  cp.n_rows = cplan_host[0];
-  SYG_REQUIRE(cp.n_rows >= 1 && cp.n_rows <= SYG_MAX_BANDS, "stft2048: contrast rows must be in [1, %d]", SYG_MAX_BANDS);
-  for (int r = 0; r < cp.n_rows; ++r) {
-    cp.lo[r] = cplan_host[1 + r];
-    cp.hi[r] = cplan_host[1 + SYG_MAX_BANDS + r];
-    cp.k[r] = cplan_host[1 + 2 * SYG_MAX_BANDS + r];
-    SYG_REQUIRE(cp.lo[r] >= 0 && cp.hi[r] <= NBIN && cp.lo[r] < cp.hi[r] && cp.k[r] >= 1 && cp.k[r] <= cp.hi[r] - cp.lo[r],
-                "stft2048: contrast band %d invalid (lo=%d hi=%d k=%d)", r, cp.lo[r], cp.hi[r], cp.k[r]);
-  }
-  cp.ascending = 1;
-  for (int r = 1; r < cp.n_rows; ++r)
-    if (cp.lo[r] < cp.hi[r - 1] - 1 || cp.hi[r] < cp.hi[r - 1]) cp.ascending = 0;   // (a band may include the bin below it)
-  return SYG_OK;
-}
-
 int parse_mel_plan(const char* who, const int32_t* plan_host, int n_mels, MelPlan& plan) {
   // plan_host: {2 (layout version), waves, steps, n_groups, table_off}
   SYG_REQUIRE(plan_host[0] == 2, "%s: mel plan layout %d, this library needs layout 2 (sygnals_amd._tables.pack_mel_plan)",
@@ -1204,12 +1167,10 @@ extern "C" int syg_stft2048_mel_f32(const float* y, int64_t B, int64_t L, int64_
   const int waves = plan_host[1];
   rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, waves);
   if (rc) return rc;
-  ContrastPlan cp;
-  rc = parse_contrast_plan(contrast_out, cplan_host, cp);
-  if (rc) return rc;
-  if (stats_out) SYG_REQUIRE(sr > 0.f && roll_percent >= 0.f && roll_percent <= 1.f && bw_p > 0.f &&
-                                 (stats_mask & 31) != 0 && stats_mask > 0 && stats_mask < 64 && T < ((int64_t)1 << 27),
-                             "stft2048_mel: invalid statistics parameters");
+  ContrastPlan cp = {};
+  if ((rc = parse_contrast_plan("stft2048", NBIN, contrast_out, cplan_host, cp))) return rc;
+  if (stats_out && ((rc = check_stats_args("stft2048_mel", sr, roll_percent, bw_p, stats_mask)) ||
+                    (rc = check_row_frames("stft2048_mel", T)))) return rc;
   const bool extra = (stats_out != nullptr) || (contrast_out != nullptr);
   const int load = load_mode();
   const float binhz = sr / (float)NFFT;
@@ -1277,13 +1238,10 @@ extern "C" int syg_stft2048_mfcc_tri_f32(const float* y, int64_t B, int64_t L, i
                                          float amin, float top_db, int ref_is_max, float ref_value, float* mfcc_out,
                                          void* stream) {
   SYG_REQUIRE(segtab && dct && mfcc_out, "stft2048_mfcc_tri: null pointer argument");
-  SYG_REQUIRE(n_segtab == SEGTAB_WORDS, "stft2048_mfcc_tri: the piece table has %d words, this library reads %d "
-              "(sygnals_amd._tables.pack_mel_segments)", n_segtab, SEGTAB_WORDS);
-  SYG_REQUIRE(((uintptr_t)segtab) % 16 == 0, "stft2048_mfcc_tri: the piece table must be 16-byte aligned");
-  int rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, 16);
+  int rc = check_segtab("stft2048_mfcc_tri", segtab, n_segtab, SEGTAB_WORDS, n_mels, 127);
+  if (!rc) rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, 16);
   if (rc) return rc;
-  SYG_REQUIRE(n_mels >= 1 && n_mels <= 127 && n_mfcc >= 1 && n_mfcc <= n_mels,
-              "stft2048_mfcc_tri: need 1 <= n_mfcc <= n_mels <= 127 (n_mfcc=%d n_mels=%d)", n_mfcc, n_mels);
+  SYG_REQUIRE(n_mfcc >= 1 && n_mfcc <= n_mels, "stft2048_mfcc_tri: need 1 <= n_mfcc <= n_mels (n_mfcc=%d n_mels=%d)", n_mfcc, n_mels);
   SYG_REQUIRE(amin >= 1.17549435e-38f, "stft2048_mfcc_tri: amin must be strictly positive (a normal float)");
   SYG_REQUIRE(ref_is_max == 0 || ref_is_max == 1, "stft2048_mfcc_tri: ref_is_max must be 0 or 1");
   SYG_REQUIRE(T < ((int64_t)1 << 24), "stft2048_mfcc_tri: clip too long");
@@ -1309,21 +1267,17 @@ extern "C" int syg_stft2048_features_tri_f32(const float* y, int64_t B, int64_t 
                                              float* contrast_out, float* mfcc_out, int mfcc_rows_per_clip, void* stream) {
   SYG_REQUIRE(segtab && dct && mfcc_out, "stft2048_features_tri: null pointer argument");
   SYG_REQUIRE(stats_out || contrast_out, "stft2048_features_tri: no statistics requested (use syg_stft2048_mfcc_tri_f32)");
-  SYG_REQUIRE(n_segtab == SEGTAB_WORDS, "stft2048_features_tri: the piece table has %d words, this library reads %d "
-              "(sygnals_amd._tables.pack_mel_segments)", n_segtab, SEGTAB_WORDS);
-  SYG_REQUIRE(((uintptr_t)segtab) % 16 == 0, "stft2048_features_tri: the piece table must be 16-byte aligned");
-  int rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, 16);
+  int rc = check_segtab("stft2048_features_tri", segtab, n_segtab, SEGTAB_WORDS, n_mels, 127);
+  if (!rc) rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, 16);
   if (rc) return rc;
-  SYG_REQUIRE(n_mels >= 1 && n_mels <= 127 && n_mfcc >= 1 && n_mfcc <= n_mels && mfcc_rows_per_clip >= n_mfcc,
-              "stft2048_features_tri: need 1 <= n_mfcc <= n_mels <= 127 and mfcc_rows_per_clip >= n_mfcc");
+  SYG_REQUIRE(n_mfcc >= 1 && n_mfcc <= n_mels && mfcc_rows_per_clip >= n_mfcc,
+              "stft2048_features_tri: need 1 <= n_mfcc <= n_mels and mfcc_rows_per_clip >= n_mfcc");
   SYG_REQUIRE(amin >= 1.17549435e-38f, "stft2048_features_tri: amin must be strictly positive (a normal float)");
   SYG_REQUIRE(ref_is_max == 0 || ref_is_max == 1, "stft2048_features_tri: ref_is_max must be 0 or 1");
   SYG_REQUIRE(T < ((int64_t)1 << 24), "stft2048_features_tri: clip too long");
-  ContrastPlan cp;
-  rc = parse_contrast_plan(contrast_out, cplan_host, cp);
-  if (rc) return rc;
-  if (stats_out) SYG_REQUIRE(sr > 0.f && roll_percent >= 0.f && roll_percent <= 1.f && bw_p > 0.f && (stats_mask & 31) != 0 &&
-                                 stats_mask > 0 && stats_mask < 64, "stft2048_features_tri: invalid statistics parameters");
+  ContrastPlan cp = {};
+  if ((rc = parse_contrast_plan("stft2048", NBIN, contrast_out, cplan_host, cp))) return rc;
+  if (stats_out && (rc = check_stats_args("stft2048_features_tri", sr, roll_percent, bw_p, stats_mask))) return rc;
   MelPlan plan;
   memset(&plan, 0, sizeof(plan));
   MfccArgs mf;
@@ -1350,20 +1304,15 @@ extern "C" int syg_stft2048_mel_tri_f32(const float* y, int64_t B, int64_t L, in
                                         float* stats_out, const int32_t* cplan_host, float* contrast_out, int waves,
                                         void* stream) {
   SYG_REQUIRE(segtab && mel_out, "stft2048_mel_tri: null pointer argument");
-  SYG_REQUIRE(n_segtab == SEGTAB4_WORDS || n_segtab == SEGTAB_WORDS, "stft2048_mel_tri: the piece table has %d words, this "
-              "library reads %d (four passes, row_base 4) or %d (two passes) -- sygnals_amd._tables.pack_mel_segments", n_segtab,
-              SEGTAB4_WORDS, SEGTAB_WORDS);
-  SYG_REQUIRE(((uintptr_t)segtab) % 16 == 0, "stft2048_mel_tri: the piece table must be 16-byte aligned");
+  // (the four-pass table, row_base 4, or the two-pass table of syg_stft2048_mfcc_tri_f32)
+  int rc = check_segtab("stft2048_mel_tri", segtab, n_segtab, n_segtab == SEGTAB_WORDS ? SEGTAB_WORDS : SEGTAB4_WORDS, n_mels, 255);
+  if (rc) return rc;
   SYG_REQUIRE(waves == 8 || waves == 16, "stft2048_mel_tri: waves must be 8 or 16 (got %d)", waves);
-  int rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, waves);
-  if (rc) return rc;
-  SYG_REQUIRE(n_mels >= 1 && n_mels <= 255, "stft2048_mel_tri: need 1 <= n_mels <= 255 (got %d)", n_mels);
+  if ((rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, waves))) return rc;
   SYG_REQUIRE(T * (int64_t)n_mels < ((int64_t)1 << 29), "stft2048_mel_tri: clip too long (32-bit byte offsets inside a clip's mel block)");
-  ContrastPlan cp;
-  rc = parse_contrast_plan(contrast_out, cplan_host, cp);
-  if (rc) return rc;
-  if (stats_out) SYG_REQUIRE(sr > 0.f && roll_percent >= 0.f && roll_percent <= 1.f && bw_p > 0.f && (stats_mask & 31) != 0 &&
-                                 stats_mask > 0 && stats_mask < 64, "stft2048_mel_tri: invalid statistics parameters");
+  ContrastPlan cp = {};
+  if ((rc = parse_contrast_plan("stft2048", NBIN, contrast_out, cplan_host, cp))) return rc;
+  if (stats_out && (rc = check_stats_args("stft2048_mel_tri", sr, roll_percent, bw_p, stats_mask))) return rc;
   MelPlan plan;
   memset(&plan, 0, sizeof(plan));
   MfccArgs mf;
@@ -1398,11 +1347,9 @@ extern "C" int syg_stft2048_stats_f32(const float* y, int64_t B, int64_t L, int6
   if (rc) return rc;
   SYG_REQUIRE(hop <= 512 && L < ((int64_t)1 << 28), "stft2048_stats: needs hop <= 512 (staged tiles); use syg_stft2048_mel_f32");
   SYG_REQUIRE(T < ((int64_t)1 << 24), "stft2048_stats: clip too long");
-  ContrastPlan cp;
-  rc = parse_contrast_plan(contrast_out, cplan_host, cp);
-  if (rc) return rc;
-  if (stats_out) SYG_REQUIRE(sr > 0.f && roll_percent >= 0.f && roll_percent <= 1.f && bw_p > 0.f && (stats_mask & 31) != 0 &&
-                                 stats_mask > 0 && stats_mask < 64, "stft2048_stats: invalid statistics parameters");
+  ContrastPlan cp = {};
+  if ((rc = parse_contrast_plan("stft2048", NBIN, contrast_out, cplan_host, cp))) return rc;
+  if (stats_out && (rc = check_stats_args("stft2048_stats", sr, roll_percent, bw_p, stats_mask))) return rc;
   MelPlan plan;
   memset(&plan, 0, sizeof(plan));
   MfccArgs mf;

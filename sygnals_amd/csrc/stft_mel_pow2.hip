@@ -14,7 +14,7 @@
 // with power_to_db(ref = max of the clip, amin, top_db) + DCT-II rows (+ lifter): samples in, MFCCs out, one launch.
 // Reference chain: manager.py:184-187, 198, 219-223 -> librosa.stft / melspectrogram / power_to_db; cepstral.py:106-115.
 #include "wave_fft.h"
-#include <string.h>
+#include "stft_host.h"
 
 namespace syg {
 namespace {
@@ -672,13 +672,11 @@ size_t lds_bytes(int n_fft, int Fp, int n_mels, int tp) {
 
 int check_args(const char* who, const float* y, int64_t B, int64_t L, int64_t ldy, int n_fft, int hop, int center, int64_t T,
                const float* window, const float* twiddle, const float* basis_p, int Fp, int n_mels, int power) {
-  SYG_REQUIRE(y && window && twiddle && basis_p, "%s: null pointer argument", who);
-  SYG_REQUIRE(B >= 1 && L >= 1 && ldy >= L, "%s: need B >= 1, L >= 1, ldy >= L", who);
+  SYG_REQUIRE(basis_p, "%s: null pointer argument", who);
   SYG_REQUIRE(n_fft >= 64 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0, "%s: n_fft must be a power of two in [64, 4096] (got %d)",
               who, n_fft);
-  SYG_REQUIRE(hop >= 1, "%s: hop must be >= 1", who);
-  const int64_t Texp = center ? 1 + L / hop : (L >= n_fft ? 1 + (L - n_fft) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp, "%s: T=%lld does not match the framing rule (%lld)", who, (long long)T, (long long)Texp);
+  const int rc = check_clips(who, y, B, L, ldy, n_fft, hop, center, T, window, twiddle);
+  if (rc) return rc;
   SYG_REQUIRE(Fp % 16 == 0 && Fp >= n_fft / 2 + 1 && Fp < n_fft / 2 + 1 + 16, "%s: Fp must be 1 + n_fft/2 rounded up to a multiple of 16 (got %d)",
               who, Fp);
   SYG_REQUIRE(n_mels >= 1 && n_mels <= 256, "%s: n_mels must be in [1, 256]", who);
@@ -702,8 +700,7 @@ extern "C" int syg_stft_mel_pow2_f32(const float* y, int64_t B, int64_t L, int64
   if (n_fft == 1024) {
     const size_t lds = w1024_lds_bytes(n_mels, 0);
     auto kern = stft_mel_w1024_kernel<false>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("stft_mel_pow2: cannot reserve %zu B LDS: %s", lds, hipGetErrorString(e)); return SYG_E_LAUNCH; }
+    if ((rc = reserve_dynamic_lds("stft_mel_pow2", (const void*)kern, lds))) return rc;
     const int tiles = (int)((T + 15) / 16);
     Pow2Mfcc mf;
     memset(&mf, 0, sizeof(mf));
@@ -714,8 +711,7 @@ extern "C" int syg_stft_mel_pow2_f32(const float* y, int64_t B, int64_t L, int64
   }
   if (n_fft == 256) {
     const size_t lds = (size_t)W256Lds::TOTAL * sizeof(float);
-    hipError_t e = hipFuncSetAttribute((const void*)stft_mel_w256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("stft_mel_pow2: cannot reserve %zu B LDS: %s", lds, hipGetErrorString(e)); return SYG_E_LAUNCH; }
+    if ((rc = reserve_dynamic_lds("stft_mel_pow2", (const void*)stft_mel_w256_kernel, lds))) return rc;
     const int tiles = (int)((T + 63) / 64);
     // (twiddle: [W_256^k (256) | W_128^k (128) | W_1024^k (1024)]: the wave FFT's tables come from the third block)
     hipLaunchKernelGGL(stft_mel_w256_kernel, dim3((unsigned)(B * tiles)), dim3(512), lds, (hipStream_t)stream, y, L, ldy, hop,
@@ -725,8 +721,7 @@ extern "C" int syg_stft_mel_pow2_f32(const float* y, int64_t B, int64_t L, int64
   }
   if (n_fft == 512) {
     const size_t lds = (size_t)W512Lds::TOTAL * sizeof(float);
-    hipError_t e = hipFuncSetAttribute((const void*)stft_mel_w512_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("stft_mel_pow2: cannot reserve %zu B LDS: %s", lds, hipGetErrorString(e)); return SYG_E_LAUNCH; }
+    if ((rc = reserve_dynamic_lds("stft_mel_pow2", (const void*)stft_mel_w512_kernel, lds))) return rc;
     const int tiles = (int)((T + 31) / 32);
     // (twiddle: [W_512^k (512) | W_256^k (256) | W_1024^k (1024)]: the wave FFT's tables come from the third block)
     hipLaunchKernelGGL(stft_mel_w512_kernel, dim3((unsigned)(B * tiles)), dim3(512), lds, (hipStream_t)stream, y, L, ldy, hop,
@@ -737,8 +732,7 @@ extern "C" int syg_stft_mel_pow2_f32(const float* y, int64_t B, int64_t L, int64
   const size_t lds = lds_bytes(n_fft, Fp, 0, 0);
   SYG_REQUIRE(lds <= LDS_LIMIT, "stft_mel_pow2: n_fft=%d needs %zu B of LDS", n_fft, lds);
   auto kern = stft_mel_pow2_kernel<NWAVES, false>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) { set_error("stft_mel_pow2: cannot reserve %zu B LDS: %s", lds, hipGetErrorString(e)); return SYG_E_LAUNCH; }
+  if ((rc = reserve_dynamic_lds("stft_mel_pow2", (const void*)kern, lds))) return rc;
   const int tiles = (int)((T + 15) / 16);
   Pow2Mfcc mf;
   memset(&mf, 0, sizeof(mf));
@@ -779,8 +773,7 @@ extern "C" int syg_stft_mfcc_pow2_f32(const float* y, int64_t B, int64_t L, int6
     SYG_REQUIRE(lds <= LDS_LIMIT, "stft_mfcc_pow2: the clip's mel matrix (%d x %d) does not fit the LDS (%zu B > %zu B); use "
                 "syg_stft_mel_pow2_f32 + syg_logmel_dct_f32", n_mels, mf.tp, lds, LDS_LIMIT);
     auto kern = stft_mel_w1024_kernel<true>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { set_error("stft_mfcc_pow2: cannot reserve %zu B LDS: %s", lds, hipGetErrorString(e)); return SYG_E_LAUNCH; }
+    if ((rc = reserve_dynamic_lds("stft_mfcc_pow2", (const void*)kern, lds))) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(512), lds, (hipStream_t)stream, y, L, ldy, hop, center ? 512 : 0, T,
                        window, (const float2*)twiddle, basis_p, n_mels, 2, mel_out, tiles, mf);
     SYG_CHECK_LAUNCH("stft_mfcc_pow2");
@@ -790,8 +783,7 @@ extern "C" int syg_stft_mfcc_pow2_f32(const float* y, int64_t B, int64_t L, int6
   SYG_REQUIRE(lds <= LDS_LIMIT, "stft_mfcc_pow2: the clip's mel matrix (%d x %d) does not fit the LDS (%zu B > %zu B); use "
               "syg_stft_mel_pow2_f32 + syg_logmel_dct_f32", n_mels, mf.tp, lds, LDS_LIMIT);
   auto kern = stft_mel_pow2_kernel<NWAVES, true>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) { set_error("stft_mfcc_pow2: cannot reserve %zu B LDS: %s", lds, hipGetErrorString(e)); return SYG_E_LAUNCH; }
+  if ((rc = reserve_dynamic_lds("stft_mfcc_pow2", (const void*)kern, lds))) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(NWAVES * 64), lds, (hipStream_t)stream, y, L, ldy, n_fft, hop,
                      center ? n_fft / 2 : 0, T, window, (const float2*)twiddle, basis_p, Fp, n_mels, 2, mel_out, tiles, mf);
   SYG_CHECK_LAUNCH("stft_mfcc_pow2");

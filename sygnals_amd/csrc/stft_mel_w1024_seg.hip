@@ -13,7 +13,7 @@
 // features]) -- the call of the reference's own manager tests (tests/test_features_manager.py:58-62, 167-174) -- from one
 // launch, no spectrogram in HBM.  The filterbank is then optional (segtab == nullptr: statistics only).
 #include "wave_fft.h"
-#include <string.h>
+#include "stft_host.h"
 
 namespace syg {
 namespace {
@@ -32,20 +32,11 @@ __device__ __forceinline__ int s1_pos(int k) { return S1_BASE + k + (k >> 4); } 
 #ifndef SYG_S1_WAVES_PER_SIMD
 #define SYG_S1_WAVES_PER_SIMD 4
 #endif
-struct S1Rows {                                       // arguments of the row functions (ROWS kernels)
-  float binhz, roll_percent, bw_p;
-  int smask;
-  float* stats_out;                                   // [B, SYG_NSTAT, T] or null
-  float* contrast_out;                                // [B, 2, n_rows, T] or null
-  int n_rows, ascending;
-  int lo[SYG_MAX_BANDS], hi[SYG_MAX_BANDS], k[SYG_MAX_BANDS];
-};
-
 template <bool ROWS>
 __global__ __launch_bounds__(S1_WAVES * 64, SYG_S1_WAVES_PER_SIMD) void stft_mel_w1024_seg_kernel(
     const float* __restrict__ y, int64_t L, int64_t ldy, int hop, int pad, int64_t T, int64_t pairs_per_clip,
     int64_t n_pairs, const float* __restrict__ win, const float2* __restrict__ tw1024,
-    const float4* __restrict__ segtab, int n_mels, float* __restrict__ mel_out, S1Rows rw) {
+    const float4* __restrict__ segtab, int n_mels, float* __restrict__ mel_out, RowArgs rw) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -203,38 +194,26 @@ namespace syg {
 namespace {
 int w1024_launch(const char* who, const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
                  const float* window, const float* twiddle, const float* segtab, int n_segtab, int n_mels, float* mel_out,
-                 const S1Rows* rows, void* stream) {
-  SYG_REQUIRE(y && window && twiddle, "%s: null pointer argument", who);
-  SYG_REQUIRE(B >= 1 && L >= 1 && ldy >= L, "%s: need B >= 1, L >= 1, ldy >= L", who);
-  SYG_REQUIRE(hop >= 1, "%s: hop must be >= 1", who);
-  const int64_t Texp = center ? 1 + L / hop : (L >= 1024 ? 1 + (L - 1024) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp, "%s: T=%lld does not match the framing rule (%lld)", who, (long long)T, (long long)Texp);
+                 const RowArgs* rows, void* stream) {
+  int rc = check_clips(who, y, B, L, ldy, 1024, hop, center, T, window, twiddle);
+  if (rc) return rc;
   if (segtab != nullptr) {
     SYG_REQUIRE(mel_out, "%s: a piece table without mel_out", who);
-    SYG_REQUIRE(n_segtab == S1_SEG_WORDS, "%s: the piece table has %d words, this library reads %d "
-                "(sygnals_amd._tables.pack_mel_segments_rows)", who, n_segtab, S1_SEG_WORDS);
-    SYG_REQUIRE(((uintptr_t)segtab) % 16 == 0, "%s: the piece table must be 16-byte aligned", who);
-    SYG_REQUIRE(n_mels >= 1 && n_mels <= 255, "%s: n_mels must be in [1, 255]", who);
+    if ((rc = check_segtab(who, segtab, n_segtab, S1_SEG_WORDS, n_mels, 255))) return rc;
   }
   const int64_t ppc = (T + 1) / 2, n_pairs = B * ppc;
   SYG_REQUIRE(n_pairs < ((int64_t)1 << 40), "%s: too many frames", who);
   const int pad = center ? 512 : 0;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
   const size_t lds = ((size_t)S1_WAVES * S1_SCW + 2 * (wfft::TW2_COMPLEX + wfft::TW1_COMPLEX) + S1_SEG_WORDS + 1024 +
                       (rows ? 3 * SYG_MAX_BANDS + S1_WAVES * 2 * 3 * 64 : 0)) * sizeof(float);
   int64_t wgs = (n_pairs + S1_WAVES - 1) / S1_WAVES;
-  const int64_t cap = (int64_t)cus * 2 * 2;            // two workgroups per CU resident (60 KiB of LDS each), two rounds
+  const int64_t cap = (int64_t)device_cu_count() * 2 * 2;   // two workgroups per CU resident (60 KiB of LDS each), two rounds
   if (wgs > cap) wgs = cap;
-  S1Rows rw;
+  RowArgs rw;
   memset(&rw, 0, sizeof(rw));
   if (rows) rw = *rows;
   auto kern = rows ? stft_mel_w1024_seg_kernel<true> : stft_mel_w1024_seg_kernel<false>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    set_error("%s: cannot reserve %zu B LDS: %s", who, lds, hipGetErrorString(e));
-    return SYG_E_LAUNCH;
-  }
+  if ((rc = reserve_dynamic_lds(who, (const void*)kern, lds))) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(S1_WAVES * 64), lds, (hipStream_t)stream, y, L, ldy, hop, pad, T, ppc,
                      n_pairs, window, (const float2*)twiddle, (const float4*)segtab, n_mels, mel_out, rw);
   SYG_CHECK_LAUNCH(who);
@@ -263,28 +242,9 @@ extern "C" int syg_stft_rows_w1024_f32(const float* y, int64_t B, int64_t L, int
                                        float* stats_out, const int32_t* cplan_host, float* contrast_out, void* stream) {
   SYG_REQUIRE(stats_out || contrast_out, "stft_rows_w1024: no statistics requested (use syg_stft_mel_w1024_seg_f32)");
   SYG_REQUIRE((segtab == nullptr) == (mel_out == nullptr), "stft_rows_w1024: segtab and mel_out come together");
-  SYG_REQUIRE(T < ((int64_t)1 << 27), "stft_rows_w1024: clip too long");
-  S1Rows rw;
-  memset(&rw, 0, sizeof(rw));
-  if (stats_out) SYG_REQUIRE(sr > 0.f && roll_percent >= 0.f && roll_percent <= 1.f && bw_p > 0.f && (stats_mask & 31) != 0 &&
-                                 stats_mask > 0 && stats_mask < 64, "stft_rows_w1024: invalid statistics parameters");
-  if (contrast_out) {
-    SYG_REQUIRE(cplan_host, "stft_rows_w1024: contrast_out given without cplan_host");
-    rw.n_rows = cplan_host[0];
-    SYG_REQUIRE(rw.n_rows >= 1 && rw.n_rows <= SYG_MAX_BANDS, "stft_rows_w1024: contrast rows must be in [1, %d]", SYG_MAX_BANDS);
-    for (int r = 0; r < rw.n_rows; ++r) {
-      rw.lo[r] = cplan_host[1 + r];
-      rw.hi[r] = cplan_host[1 + SYG_MAX_BANDS + r];
-      rw.k[r] = cplan_host[1 + 2 * SYG_MAX_BANDS + r];
-      SYG_REQUIRE(rw.lo[r] >= 0 && rw.hi[r] <= 513 && rw.lo[r] < rw.hi[r] && rw.k[r] >= 1 && rw.k[r] <= rw.hi[r] - rw.lo[r],
-                  "stft_rows_w1024: contrast band %d invalid (lo=%d hi=%d k=%d)", r, rw.lo[r], rw.hi[r], rw.k[r]);
-    }
-    rw.ascending = 1;
-    for (int r = 1; r < rw.n_rows; ++r)
-      if (rw.lo[r] < rw.hi[r - 1] - 1 || rw.hi[r] < rw.hi[r - 1]) rw.ascending = 0;
-  }
-  rw.binhz = sr / 1024.f; rw.roll_percent = roll_percent; rw.bw_p = bw_p; rw.smask = stats_mask;
-  rw.stats_out = stats_out; rw.contrast_out = contrast_out;
+  RowArgs rw;
+  const int rc = fill_row_args("stft_rows_w1024", 1024, T, sr, roll_percent, bw_p, stats_mask, stats_out, cplan_host, contrast_out, rw);
+  if (rc) return rc;
   return w1024_launch("stft_rows_w1024", y, B, L, ldy, hop, center, T, window, twiddle, segtab, n_segtab, n_mels, mel_out, &rw,
                       stream);
 }

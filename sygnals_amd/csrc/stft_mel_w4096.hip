@@ -12,8 +12,8 @@
 // ROWS (syg_stft_rows_w4096_f32): the same launch also hands the finished row to the per-frame row functions of
 // row_features.h (spectral statistics, contrast tail means: 2049 bins, two 16-bin blocks per lane), behind the projection
 // (which is skipped without a piece table); the results leave from the lanes that hold them.
-#include <string.h>
 #include "wave_fft.h"
+#include "stft_host.h"
 
 namespace syg {
 namespace {
@@ -49,20 +49,11 @@ __device__ __forceinline__ void w4_split_pow(float2 zk, float2 zm, float2 w, flo
   pm = fmaf(bx, bx, by * by);
 }
 
-struct W4Rows {                                       // arguments of the row functions (ROWS kernel)
-  float binhz, roll_percent, bw_p;
-  int smask;
-  float* stats_out;                                   // [B, SYG_NSTAT, T] or null
-  float* contrast_out;                                // [B, 2, n_rows, T] or null
-  int n_rows, ascending;
-  int lo[SYG_MAX_BANDS], hi[SYG_MAX_BANDS], k[SYG_MAX_BANDS];
-};
-
 template <bool ROWS>
 __global__ __launch_bounds__(W4_WAVES * 64) void stft_mel_w4096_kernel(
     const float* __restrict__ y, int64_t L, int64_t ldy, int hop, int pad, int64_t T, int64_t n_frames,
     const float* __restrict__ win, const float2* __restrict__ tw4096, const float* __restrict__ segtab, int n_mels,
-    float* __restrict__ mel_out, int aligned, W4Rows rw) {
+    float* __restrict__ mel_out, int aligned, RowArgs rw) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -205,50 +196,36 @@ using namespace syg;
 
 static int w4096_launch(const char* who, const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
                         const float* window, const float* twiddle, const float* segtab, int n_segtab, int n_mels,
-                        float* mel_out, const W4Rows* rows, hipStream_t st) {
-  SYG_REQUIRE(y && window && twiddle, "%s: null pointer argument", who);
-  SYG_REQUIRE(B >= 1 && L >= 1 && ldy >= L, "%s: need B >= 1, L >= 1, ldy >= L", who);
-  SYG_REQUIRE(hop >= 1, "%s: hop must be >= 1", who);
-  const int64_t Texp = center ? 1 + L / hop : (L >= W4_N ? 1 + (L - W4_N) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp, "%s: T=%lld does not match the framing rule (%lld)", who, (long long)T, (long long)Texp);
+                        float* mel_out, const RowArgs* rows, hipStream_t st) {
+  int rc = check_clips(who, y, B, L, ldy, W4_N, hop, center, T, window, twiddle);
+  if (rc) return rc;
   if (segtab) {
     SYG_REQUIRE(mel_out, "%s: a piece table without mel_out", who);
-    SYG_REQUIRE(n_segtab == W4_SEG_WORDS, "%s: the piece table has %d words, this library reads %d "
-                "(sygnals_amd._tables.pack_mel_segments(..., n_pass=4))", who, n_segtab, W4_SEG_WORDS);
-    SYG_REQUIRE(((uintptr_t)segtab) % 16 == 0, "%s: tables must be 16-byte aligned", who);
-    SYG_REQUIRE(n_mels >= 1 && n_mels <= 255, "%s: n_mels must be in [1, 255]", who);
+    if ((rc = check_segtab(who, segtab, n_segtab, W4_SEG_WORDS, n_mels, 255))) return rc;
   }
-  SYG_REQUIRE(((uintptr_t)window) % 16 == 0, "%s: tables must be 16-byte aligned", who);
+  SYG_REQUIRE(((uintptr_t)window) % 16 == 0, "%s: the window must be 16-byte aligned", who);
   SYG_REQUIRE(B * T < ((int64_t)1 << 40), "%s: too many frames", who);
   const int pad = center ? W4_N / 2 : 0;
   const int aligned = (hop % 4 == 0) && (ldy % 4 == 0) && (((uintptr_t)y) % 16 == 0);
   const int64_t n_frames = B * T;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
   const size_t lds = (size_t)W4Lds::TOTAL * sizeof(float);
   int64_t wgs = (n_frames + W4_WAVES - 1) / W4_WAVES;
-  const int64_t cap = (int64_t)cus * 2 * 4;          // two workgroups per CU resident; a few rounds each
+  const int64_t cap = (int64_t)device_cu_count() * 2 * 4;   // two workgroups per CU resident; a few rounds each
   if (wgs > cap) wgs = cap;
-  const void* fn = rows ? (const void*)stft_mel_w4096_kernel<true> : (const void*)stft_mel_w4096_kernel<false>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    set_error("%s: cannot reserve %zu B LDS: %s", who, lds, hipGetErrorString(e));
-    return SYG_E_LAUNCH;
-  }
-  W4Rows rw;
-  if (rows) rw = *rows; else memset(&rw, 0, sizeof(rw));
-  if (rows)
-    hipLaunchKernelGGL(stft_mel_w4096_kernel<true>, dim3((unsigned)wgs), dim3(W4_WAVES * 64), lds, st, y, L, ldy, hop, pad, T,
-                       n_frames, window, (const float2*)twiddle, segtab, n_mels, mel_out, aligned, rw);
-  else
-    hipLaunchKernelGGL(stft_mel_w4096_kernel<false>, dim3((unsigned)wgs), dim3(W4_WAVES * 64), lds, st, y, L, ldy, hop, pad, T,
-                       n_frames, window, (const float2*)twiddle, segtab, n_mels, mel_out, aligned, rw);
+  auto kern = rows ? stft_mel_w4096_kernel<true> : stft_mel_w4096_kernel<false>;
+  if ((rc = reserve_dynamic_lds(who, (const void*)kern, lds))) return rc;
+  RowArgs rw;
+  memset(&rw, 0, sizeof(rw));
+  if (rows) rw = *rows;
+  hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(W4_WAVES * 64), lds, st, y, L, ldy, hop, pad, T, n_frames, window,
+                     (const float2*)twiddle, segtab, n_mels, mel_out, aligned, rw);
   SYG_CHECK_LAUNCH(who);
   return SYG_OK;
 }
 
 // y [B, L] (row stride ldy) -> mel_out [B, n_mels, T], power 2, for triangular filterbanks with a four-pass piece table
-// (segtab: 2048 words on the device, 16-byte aligned).  window [4096]; twiddle: W_4096^k, k = 0 .. 4095.
+// (segtab: sygnals_amd._tables.pack_mel_segments(..., n_pass=4), 2048 words on the device, 16-byte aligned).  window [4096];
+// twiddle: W_4096^k, k = 0 .. 4095.
 extern "C" int syg_stft_mel_w4096_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
                                       const float* window, const float* twiddle, const float* segtab, int n_segtab,
                                       int n_mels, float* mel_out, void* stream) {
@@ -265,28 +242,9 @@ extern "C" int syg_stft_rows_w4096_f32(const float* y, int64_t B, int64_t L, int
                                        float* mel_out, float sr, float roll_percent, float bw_p, int stats_mask,
                                        float* stats_out, const int32_t* cplan_host, float* contrast_out, void* stream) {
   SYG_REQUIRE(stats_out || contrast_out, "stft_rows_w4096: no statistics requested");
-  SYG_REQUIRE(T < ((int64_t)1 << 27), "stft_rows_w4096: too many frames per clip");
-  W4Rows rw;
-  memset(&rw, 0, sizeof(rw));
-  if (stats_out) SYG_REQUIRE(sr > 0.f && roll_percent >= 0.f && roll_percent <= 1.f && bw_p > 0.f && (stats_mask & 31) != 0 &&
-                                 stats_mask > 0 && stats_mask < 64, "stft_rows_w4096: invalid statistics parameters");
-  if (contrast_out) {
-    SYG_REQUIRE(cplan_host, "stft_rows_w4096: contrast_out given without cplan_host");
-    rw.n_rows = cplan_host[0];
-    SYG_REQUIRE(rw.n_rows >= 1 && rw.n_rows <= SYG_MAX_BANDS, "stft_rows_w4096: contrast rows must be in [1, %d]", SYG_MAX_BANDS);
-    for (int r = 0; r < rw.n_rows; ++r) {
-      rw.lo[r] = cplan_host[1 + r];
-      rw.hi[r] = cplan_host[1 + SYG_MAX_BANDS + r];
-      rw.k[r] = cplan_host[1 + 2 * SYG_MAX_BANDS + r];
-      SYG_REQUIRE(rw.lo[r] >= 0 && rw.hi[r] <= W4_BINS && rw.lo[r] < rw.hi[r] && rw.k[r] >= 1 && rw.k[r] <= rw.hi[r] - rw.lo[r],
-                  "stft_rows_w4096: contrast band %d invalid (lo=%d hi=%d k=%d)", r, rw.lo[r], rw.hi[r], rw.k[r]);
-    }
-    rw.ascending = 1;
-    for (int r = 1; r < rw.n_rows; ++r)
-      if (rw.lo[r] < rw.hi[r - 1] - 1 || rw.hi[r] < rw.hi[r - 1]) rw.ascending = 0;
-  }
-  rw.binhz = sr / (float)W4_N; rw.roll_percent = roll_percent; rw.bw_p = bw_p; rw.smask = stats_mask;
-  rw.stats_out = stats_out; rw.contrast_out = contrast_out;
+  RowArgs rw;
+  const int rc = fill_row_args("stft_rows_w4096", W4_N, T, sr, roll_percent, bw_p, stats_mask, stats_out, cplan_host, contrast_out, rw);
+  if (rc) return rc;
   return w4096_launch("stft_rows_w4096", y, B, L, ldy, hop, center, T, window, twiddle, segtab, n_segtab, n_mels, mel_out, &rw,
                       (hipStream_t)stream);
 }

@@ -12,7 +12,7 @@
 // HBM (a mel block beside them is a second launch of the projection form: the [band][16 frames] tile's LDS holds the
 // rows' results here).
 #include "wave_fft.h"
-#include <string.h>
+#include "stft_host.h"
 
 namespace syg {
 namespace {
@@ -34,20 +34,11 @@ template <> struct SmallCfg<8> { static constexpr int NFFT = 256, ROW = 160, LOG
 
 __device__ __forceinline__ int ss_pos(int k) { return SS_BASE + k + (k >> 4); }      // == _tables.row_pos + row_base
 
-struct SmallRows {                                    // arguments of the row functions (ROWS kernels)
-  float binhz, roll_percent, bw_p;
-  int smask;
-  float* stats_out;                                   // [B, SYG_NSTAT, T] or null
-  float* contrast_out;                                // [B, 2, n_rows, T] or null
-  int n_rows, ascending;
-  int lo[SYG_MAX_BANDS], hi[SYG_MAX_BANDS], k[SYG_MAX_BANDS];
-};
-
 template <int NF, bool ROWS>
 __global__ __launch_bounds__(SS_WAVES * 64, 4) void stft_mel_wseg_small_kernel(
     const float* __restrict__ y, int64_t L, int64_t ldy, int hop, int pad, int64_t T, int64_t groups_per_clip,
     int64_t n_groups, const float* __restrict__ win, const float2* __restrict__ tw1024,
-    const float4* __restrict__ segtab, int n_mels, float* __restrict__ mel_out, SmallRows rw) {
+    const float4* __restrict__ segtab, int n_mels, float* __restrict__ mel_out, RowArgs rw) {
   typedef SmallCfg<NF> CF;
   constexpr int NBIN = CF::NFFT / 2 + 1, PS = (NF == 4) ? 2 : 3;      // the rows hold 16 |X|^2 / 64 |X|^2 = 4^PS |X|^2
   constexpr int ROW = CF::ROW, NSEQ = NF / 2, SPA = 64 / NSEQ;       // samples of a sequence per 64 elements of z
@@ -275,32 +266,27 @@ __global__ __launch_bounds__(SS_WAVES * 64, 4) void stft_mel_wseg_small_kernel(
 }
 
 template <int NF>
-int launch_small(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T, const float* window,
-                 const float* twiddle, const float* segtab, int n_mels, float* mel_out, hipStream_t st,
-                 const SmallRows* rows = nullptr) {
+int launch_small(const char* who, const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
+                 const float* window, const float* twiddle, const float* segtab, int n_mels, float* mel_out, hipStream_t st,
+                 const RowArgs* rows = nullptr) {
   typedef SmallCfg<NF> CF;
   const int64_t gpc = (T + SS_GF - 1) / SS_GF, n_groups = B * gpc;
-  SYG_REQUIRE(n_groups < ((int64_t)1 << 40), "stft_mel_wseg_small: too many frames");
+  SYG_REQUIRE(n_groups < ((int64_t)1 << 40), "%s: too many frames", who);
   const int pad = center ? CF::NFFT / 2 : 0;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
   const size_t lds = ((size_t)SS_WAVES * NF * CF::ROW + 2 * (wfft::TW2_COMPLEX + wfft::TW1_COMPLEX) + SS_SEG_WORDS +
                       (size_t)SS_WAVES * SS_MAX_MELS * SS_GP + CF::NFFT + (rows ? 3 * SYG_MAX_BANDS : 0)) * sizeof(float);
   int64_t wgs = (n_groups + SS_WAVES - 1) / SS_WAVES;
-  const int64_t cap = (int64_t)cus * 2;                // one workgroup per CU resident (141 / 148 KiB of LDS), two rounds
+  const int64_t cap = (int64_t)device_cu_count() * 2;  // one workgroup per CU resident (141 / 148 KiB of LDS), two rounds
   if (wgs > cap) wgs = cap;
-  SmallRows rw;
+  RowArgs rw;
   memset(&rw, 0, sizeof(rw));
   if (rows) rw = *rows;
   auto kern = rows ? stft_mel_wseg_small_kernel<NF, true> : stft_mel_wseg_small_kernel<NF, false>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    set_error("stft_mel_wseg_small: cannot reserve %zu B LDS: %s", lds, hipGetErrorString(e));
-    return SYG_E_LAUNCH;
-  }
+  const int rc = reserve_dynamic_lds(who, (const void*)kern, lds);
+  if (rc) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(SS_WAVES * 64), lds, st, y, L, ldy, hop, pad, T, gpc, n_groups, window,
                      (const float2*)twiddle, (const float4*)segtab, n_mels, mel_out, rw);
-  SYG_CHECK_LAUNCH("stft_mel_wseg_small");
+  SYG_CHECK_LAUNCH(who);
   return SYG_OK;
 }
 
@@ -315,18 +301,14 @@ using namespace syg;
 extern "C" int syg_stft_mel_wseg_small_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int n_fft, int hop, int center,
                                            int64_t T, const float* window, const float* twiddle, const float* segtab,
                                            int n_segtab, int n_mels, float* mel_out, void* stream) {
-  SYG_REQUIRE(y && window && twiddle && segtab && mel_out, "stft_mel_wseg_small: null pointer argument");
-  SYG_REQUIRE(n_fft == 512 || n_fft == 256, "stft_mel_wseg_small: n_fft must be 512 or 256 (got %d)", n_fft);
-  SYG_REQUIRE(B >= 1 && L >= 1 && ldy >= L, "stft_mel_wseg_small: need B >= 1, L >= 1, ldy >= L");
-  SYG_REQUIRE(hop >= 1, "stft_mel_wseg_small: hop must be >= 1");
-  const int64_t Texp = center ? 1 + L / hop : (L >= n_fft ? 1 + (L - n_fft) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp, "stft_mel_wseg_small: T=%lld does not match the framing rule (%lld)", (long long)T, (long long)Texp);
-  SYG_REQUIRE(n_segtab == SS_SEG_WORDS, "stft_mel_wseg_small: the piece table has %d words, this library reads %d "
-              "(sygnals_amd._tables.pack_mel_segments_rows)", n_segtab, SS_SEG_WORDS);
-  SYG_REQUIRE(((uintptr_t)segtab) % 16 == 0, "stft_mel_wseg_small: the piece table must be 16-byte aligned");
-  SYG_REQUIRE(n_mels >= 1 && n_mels <= SS_MAX_MELS, "stft_mel_wseg_small: n_mels must be in [1, %d]", SS_MAX_MELS);
-  if (n_fft == 512) return launch_small<4>(y, B, L, ldy, hop, center, T, window, twiddle, segtab, n_mels, mel_out, (hipStream_t)stream);
-  return launch_small<8>(y, B, L, ldy, hop, center, T, window, twiddle, segtab, n_mels, mel_out, (hipStream_t)stream);
+  const char* who = "stft_mel_wseg_small";
+  SYG_REQUIRE(segtab && mel_out, "%s: null pointer argument", who);
+  SYG_REQUIRE(n_fft == 512 || n_fft == 256, "%s: n_fft must be 512 or 256 (got %d)", who, n_fft);
+  int rc = check_clips(who, y, B, L, ldy, n_fft, hop, center, T, window, twiddle);
+  if (!rc) rc = check_segtab(who, segtab, n_segtab, SS_SEG_WORDS, n_mels, SS_MAX_MELS);
+  if (rc) return rc;
+  if (n_fft == 512) return launch_small<4>(who, y, B, L, ldy, hop, center, T, window, twiddle, segtab, n_mels, mel_out, (hipStream_t)stream);
+  return launch_small<8>(who, y, B, L, ldy, hop, center, T, window, twiddle, segtab, n_mels, mel_out, (hipStream_t)stream);
 }
 
 // The per-frame statistics / contrast rows of syg_stft2048_mel_f32 for frame lengths 512 / 256 (bins 0 .. n_fft / 2, bin
@@ -336,37 +318,14 @@ extern "C" int syg_stft_rows_wsmall_f32(const float* y, int64_t B, int64_t L, in
                                         int64_t T, const float* window, const float* twiddle, float sr, float roll_percent,
                                         float bw_p, int stats_mask, float* stats_out, const int32_t* cplan_host,
                                         float* contrast_out, void* stream) {
-  SYG_REQUIRE(y && window && twiddle, "stft_rows_wsmall: null pointer argument");
-  SYG_REQUIRE(stats_out || contrast_out, "stft_rows_wsmall: no statistics requested");
-  SYG_REQUIRE(n_fft == 512 || n_fft == 256, "stft_rows_wsmall: n_fft must be 512 or 256 (got %d)", n_fft);
-  SYG_REQUIRE(B >= 1 && L >= 1 && ldy >= L, "stft_rows_wsmall: need B >= 1, L >= 1, ldy >= L");
-  SYG_REQUIRE(hop >= 1, "stft_rows_wsmall: hop must be >= 1");
-  const int64_t Texp = center ? 1 + L / hop : (L >= n_fft ? 1 + (L - n_fft) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp && T < ((int64_t)1 << 27), "stft_rows_wsmall: T=%lld does not match the framing rule (%lld)",
-              (long long)T, (long long)Texp);
-  SmallRows rw;
-  memset(&rw, 0, sizeof(rw));
-  if (stats_out) SYG_REQUIRE(sr > 0.f && roll_percent >= 0.f && roll_percent <= 1.f && bw_p > 0.f && (stats_mask & 31) != 0 &&
-                                 stats_mask > 0 && stats_mask < 64, "stft_rows_wsmall: invalid statistics parameters");
-  if (contrast_out) {
-    SYG_REQUIRE(cplan_host, "stft_rows_wsmall: contrast_out given without cplan_host");
-    rw.n_rows = cplan_host[0];
-    SYG_REQUIRE(rw.n_rows >= 1 && rw.n_rows <= SYG_MAX_BANDS, "stft_rows_wsmall: contrast rows must be in [1, %d]", SYG_MAX_BANDS);
-    for (int r = 0; r < rw.n_rows; ++r) {
-      rw.lo[r] = cplan_host[1 + r];
-      rw.hi[r] = cplan_host[1 + SYG_MAX_BANDS + r];
-      rw.k[r] = cplan_host[1 + 2 * SYG_MAX_BANDS + r];
-      SYG_REQUIRE(rw.lo[r] >= 0 && rw.hi[r] <= n_fft / 2 + 1 && rw.lo[r] < rw.hi[r] && rw.k[r] >= 1 &&
-                      rw.k[r] <= rw.hi[r] - rw.lo[r],
-                  "stft_rows_wsmall: contrast band %d invalid (lo=%d hi=%d k=%d)", r, rw.lo[r], rw.hi[r], rw.k[r]);
-    }
-    rw.ascending = 1;
-    for (int r = 1; r < rw.n_rows; ++r)
-      if (rw.lo[r] < rw.hi[r - 1] - 1 || rw.hi[r] < rw.hi[r - 1]) rw.ascending = 0;
-  }
-  rw.binhz = sr / (float)n_fft; rw.roll_percent = roll_percent; rw.bw_p = bw_p; rw.smask = stats_mask;
-  rw.stats_out = stats_out; rw.contrast_out = contrast_out;
+  const char* who = "stft_rows_wsmall";
+  SYG_REQUIRE(stats_out || contrast_out, "%s: no statistics requested", who);
+  SYG_REQUIRE(n_fft == 512 || n_fft == 256, "%s: n_fft must be 512 or 256 (got %d)", who, n_fft);
+  int rc = check_clips(who, y, B, L, ldy, n_fft, hop, center, T, window, twiddle);
+  RowArgs rw;
+  if (!rc) rc = fill_row_args(who, n_fft, T, sr, roll_percent, bw_p, stats_mask, stats_out, cplan_host, contrast_out, rw);
+  if (rc) return rc;
   if (n_fft == 512)
-    return launch_small<4>(y, B, L, ldy, hop, center, T, window, twiddle, nullptr, 0, nullptr, (hipStream_t)stream, &rw);
-  return launch_small<8>(y, B, L, ldy, hop, center, T, window, twiddle, nullptr, 0, nullptr, (hipStream_t)stream, &rw);
+    return launch_small<4>(who, y, B, L, ldy, hop, center, T, window, twiddle, nullptr, 0, nullptr, (hipStream_t)stream, &rw);
+  return launch_small<8>(who, y, B, L, ldy, hop, center, T, window, twiddle, nullptr, 0, nullptr, (hipStream_t)stream, &rw);
 }

@@ -231,18 +231,47 @@ def _basis_padded(cfg: "MelConfig", n_fft: int):
     return cfg.basis_padded, cfg.Fp
 
 
-def _pow2_front(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax):
+def _clips(y: torch.Tensor, what: str = "y") -> torch.Tensor:
+    """The clips argument of a front end, checked: a float32 device tensor [B, L] with unit stride along a clip (copied if not)."""
     require_gpu()
     if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if not fused_pow2_ok(n_fft, n_mels):
-        raise SygnalsHipError(f"no fused kernel for n_fft={n_fft}, n_mels={n_mels} (powers of two 64 ... 1024; 2048: stft2048_mel)")
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    B, L = y.shape
-    Tn = num_frames(L, n_fft, hop, center)
+        raise ValueError(f"{what} must be a float32 CUDA tensor of shape [B, L]")
+    return y if y.stride(1) == 1 else y.contiguous()
+
+
+def _at_least_one(Tn: int) -> int:
     if Tn <= 0:
         raise ValueError("signal too short for one frame")
+    return Tn
+
+
+def _frames(L: int, n_fft: int, hop: int, center: bool) -> int:
+    """num_frames, or ValueError when the clip holds no frame."""
+    return _at_least_one(num_frames(L, n_fft, hop, center))
+
+
+def _rows_out(B, Tn, want_stats, contrast, device, who=None):
+    """Outputs of the statistics / contrast rows of a fused kernel: (smask, stats [B, 8, Tn] | None, contrast_pv
+    [B, 2, R, Tn] | None, cplan pointer | None -- it keeps the plan array alive).  want_stats: False, True (all rows) or a
+    bit mask; `who`: the rows are what the call is for, so asking for none is an error."""
+    smask = 31 if want_stats is True else int(want_stats or 0)
+    if who and not smask and contrast is None:
+        raise ValueError(f"{who}: no statistics requested (want_stats and contrast are both empty)")
+    stats = torch.zeros((B, 8, Tn), dtype=torch.float32, device=device) if smask else None
+    cpv = cplan_p = None
+    if contrast is not None:
+        cplan = np.ascontiguousarray(contrast, dtype=np.int32)
+        cpv = torch.empty((B, 2, int(cplan[0]), Tn), dtype=torch.float32, device=device)
+        cplan_p = cplan.ctypes.data_as(C.c_void_p)
+    return smask, stats, cpv, cplan_p
+
+
+def _pow2_front(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax):
+    y = _clips(y)
+    if not fused_pow2_ok(n_fft, n_mels):
+        raise SygnalsHipError(f"no fused kernel for n_fft={n_fft}, n_mels={n_mels} (powers of two 64 ... 1024; 2048: stft2048_mel)")
+    B, L = y.shape
+    Tn = _frames(L, n_fft, hop, center)
     cfg = mel_config(sr, n_fft, n_mels, fmin, fmax)
     bp, Fp = _basis_padded(cfg, n_fft)
     win = window_dev(window, n_fft if win_length is None else win_length, n_fft)
@@ -288,56 +317,111 @@ def stft_mfcc_pow2(y: torch.Tensor, sr: float, n_fft: int, hop: int, center: boo
     return mf, mel
 
 
-def w4096_segtab(sr, n_mels, fmin=0.0, fmax=None):
-    """Four-pass piece table of the frame-length-4096 kernel for this filterbank on the device, or None."""
+# ---- the segment-sum kernels of the other frame lengths (stft_mel_w1024_seg.hip, stft_mel_w4096.hip, stft_mel_wseg_small.hip):
+# frame length -> entry points (mel alone / with rows), length of the twiddle table, packer of the piece table and its
+# arguments, largest n_mels; small: the entry points take n_fft and the rows form projects nothing.  The public wrappers
+# below carry the entry points' names without syg_ / _f32 (error messages use them).
+_SMALL = dict(mel="syg_stft_mel_wseg_small_f32", rows="syg_stft_rows_wsmall_f32", tw=1024,
+              pack=T.pack_mel_segments_rows, max_mels=48, small=True)      # (the [band][16 frames] tile holds 48 bands)
+_SEG = {
+    1024: dict(mel="syg_stft_mel_w1024_seg_f32", rows="syg_stft_rows_w1024_f32", tw=1024,
+               pack=T.pack_mel_segments_rows, pack_kw={}, max_mels=255, small=False),
+    4096: dict(mel="syg_stft_mel_w4096_f32", rows="syg_stft_rows_w4096_f32", tw=4096,
+               pack=T.pack_mel_segments, pack_kw=dict(n_pass=4), max_mels=255, small=False),
+    512: dict(_SMALL, pack_kw=dict(rows=4, row_words=296, n_pass=1, block=16)),
+    256: dict(_SMALL, pack_kw=dict(rows=4, row_words=160, n_pass=1, block=8)),
+}
+
+
+def _small_only(who, n_fft):
+    if n_fft not in (512, 256):
+        raise SygnalsHipError(f"{who}: frame length must be 512 or 256")
+
+
+def _segtab(n_fft, sr, n_mels, fmin=0.0, fmax=None):
+    """Piece table of the segment-sum kernel of frame length n_fft for this filterbank on the device, or None."""
+    k = _SEG[n_fft]
+    if n_mels > k["max_mels"]:
+        return None
     fmax = sr / 2.0 if fmax is None else fmax
 
     def build():
         try:
-            basis = T.mel_filterbank(sr, 4096, n_mels, fmin, fmax)
-            return _dev(T.pack_mel_segments(sr, 4096, n_mels, fmin, fmax, basis=basis, n_pass=4).reshape(-1))
+            basis = T.mel_filterbank(sr, n_fft, n_mels, fmin, fmax)
+            return _dev(k["pack"](sr, n_fft, n_mels, fmin, fmax, basis=basis, **k["pack_kw"]).reshape(-1))
         except ValueError:
             return False
-    tab = _cached(("seg4096", float(sr), n_mels, float(fmin), float(fmax)), build)
+    tab = _cached((f"seg{n_fft}", float(sr), n_mels, float(fmin), float(fmax)), build)
     return None if tab is False else tab
+
+
+def _seg_args(k, y, n_fft, hop, center, Tn, window, win_length):
+    """Leading arguments of the entry points of _SEG: clips, framing, window, twiddles."""
+    return (_ptr(y), y.shape[0], y.shape[1], _ld(y)) + ((n_fft,) if k["small"] else ()) + (
+        hop, int(center), Tn, _ptr(window_dev(window, win_length or n_fft, n_fft)), _ptr(twiddle_dev(k["tw"])))
+
+
+def _seg_mel(n_fft, y, sr, hop, center, window, win_length, n_mels, fmin, fmax):
+    """Mel power [B, n_mels, T] from the segment-sum kernel of frame length n_fft (power 2)."""
+    k = _SEG[n_fft]
+    y = _clips(y)
+    tab = _segtab(n_fft, sr, n_mels, fmin, fmax)
+    if tab is None:
+        raise SygnalsHipError(f"{k['mel'][4:-4]}: no piece table for this frame length / filterbank "
+                              "(stft_mel_segments says so with None; stft_mel_pow2 / the generic chain take any filterbank)")
+    Tn = _frames(y.shape[1], n_fft, hop, center)
+    out = torch.empty((y.shape[0], n_mels, Tn), dtype=torch.float32, device=y.device)
+    rc = getattr(lib(), k["mel"])(*_seg_args(k, y, n_fft, hop, center, Tn, window, win_length), _ptr(tab), int(tab.numel()),
+                                  n_mels, _ptr(out), C.c_void_p(_stream_ptr()))
+    check(rc, k["mel"])
+    return out
+
+
+def _seg_rows(n_fft, y, sr, hop, center, window, win_length, n_mels, fmin, fmax, want_stats, roll_percent, bw_p, contrast):
+    """Statistics / contrast rows from the segment-sum kernel of frame length n_fft, with the mel power block when n_mels is
+    given (1024 / 4096).  Returns (mel | None, stats | None, contrast_pv | None)."""
+    k = _SEG[n_fft]
+    who = k["rows"][4:-4]
+    y = _clips(y)
+    B, L = y.shape
+    Tn = _frames(L, n_fft, hop, center)
+    smask, stats, cpv, cplan_p = _rows_out(B, Tn, want_stats, contrast, y.device, who)
+    mel_args, mel = (), None
+    if not k["small"]:
+        tab = None
+        if n_mels is not None:
+            tab = _segtab(n_fft, sr, n_mels, fmin, fmax)
+            if tab is None:
+                raise SygnalsHipError(f"{who}: no piece table for this filterbank")
+            mel = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device)
+        mel_args = (_ptr(tab), int(tab.numel()) if tab is not None else 0, int(n_mels or 0), _ptr(mel))
+    rc = getattr(lib(), k["rows"])(*_seg_args(k, y, n_fft, hop, center, Tn, window, win_length), *mel_args, float(sr),
+                                   float(roll_percent), float(bw_p), smask, _ptr(stats), cplan_p, _ptr(cpv),
+                                   C.c_void_p(_stream_ptr()))
+    check(rc, k["rows"])
+    return mel, stats, cpv
+
+
+def w4096_segtab(sr, n_mels, fmin=0.0, fmax=None):
+    """Four-pass piece table of the frame-length-4096 kernel for this filterbank on the device, or None."""
+    return _segtab(4096, sr, n_mels, fmin, fmax)
 
 
 def w1024_segtab(sr, n_mels, fmin=0.0, fmax=None):
     """Two-row piece table of the frame-length-1024 segment-sum kernel for this filterbank on the device, or None."""
-    fmax = sr / 2.0 if fmax is None else fmax
+    return _segtab(1024, sr, n_mels, fmin, fmax)
 
-    def build():
-        try:
-            basis = T.mel_filterbank(sr, 1024, n_mels, fmin, fmax)
-            return _dev(T.pack_mel_segments_rows(sr, 1024, n_mels, fmin, fmax, basis=basis).reshape(-1))
-        except ValueError:
-            return False
-    tab = _cached(("seg1024", float(sr), n_mels, float(fmin), float(fmax)), build)
-    return None if tab is False else tab
+
+def wsmall_segtab(sr, n_fft, n_mels, fmin=0.0, fmax=None):
+    """Four-row piece table of the frame-length-512 / 256 segment-sum kernel for this filterbank on the device, or None."""
+    return _segtab(n_fft, sr, n_mels, fmin, fmax) if n_fft in (512, 256) else None
 
 
 def stft_mel_w1024_seg(y: torch.Tensor, sr: float, hop: int = 256, center: bool = True, window="hann", win_length=None,
                        n_mels: int = 128, fmin: float = 0.0, fmax=None) -> torch.Tensor:
     """frame_length 1024, power 2: [B, L] clips -> mel power [B, n_mels, T] in one launch, free-running waves (two frames
     per wave transform, mel by segment sums).  Raises SygnalsHipError when the filterbank has no piece table."""
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    tab = w1024_segtab(sr, n_mels, fmin, fmax)
-    if tab is None:
-        raise SygnalsHipError("stft_mel_w1024_seg: no piece table for this filterbank (use stft_mel_pow2)")
-    B, L = y.shape
-    Tn = num_frames(L, 1024, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
-    out = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device)
-    rc = lib().syg_stft_mel_w1024_seg_f32(_ptr(y), B, L, _ld(y), hop, int(center), Tn,
-                                          _ptr(window_dev(window, win_length or 1024, 1024)), _ptr(twiddle_dev(1024)), _ptr(tab),
-                                          int(tab.numel()), n_mels, _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft_mel_w1024_seg_f32")
-    return out
+    return _seg_mel(1024, y, sr, hop, center, window, win_length, n_mels, fmin, fmax)
 
 
 def stft_rows_w1024(y: torch.Tensor, sr: float, hop: int = 256, center: bool = True, window="hann", win_length=None,
@@ -346,114 +430,23 @@ def stft_rows_w1024(y: torch.Tensor, sr: float, hop: int = 256, center: bool = T
     """frame_length 1024: the statistics / contrast rows of stft2048_mel from the segment-sum kernel's launch
     (syg_stft_rows_w1024_f32), with the mel power block when n_mels is given (needs a piece table: w1024_segtab).
     Returns (mel [B, M, T] | None, stats [B, 8, T] | None, contrast_pv [B, 2, R, T] | None)."""
-    smask = 31 if want_stats is True else int(want_stats or 0)
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if not smask and contrast is None:
-        raise ValueError("stft_rows_w1024: no statistics requested (stft_mel_w1024_seg gives the mel block alone)")
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    tab = None
-    if n_mels is not None:
-        tab = w1024_segtab(sr, n_mels, fmin, fmax)
-        if tab is None:
-            raise SygnalsHipError("stft_rows_w1024: no piece table for this filterbank")
-    B, L = y.shape
-    Tn = num_frames(L, 1024, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
-    mel = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device) if tab is not None else None
-    stats = torch.zeros((B, 8, Tn), dtype=torch.float32, device=y.device) if smask else None
-    cpv = cplan_p = None
-    if contrast is not None:
-        cplan = np.ascontiguousarray(contrast, dtype=np.int32)
-        cpv = torch.empty((B, 2, int(cplan[0]), Tn), dtype=torch.float32, device=y.device)
-        cplan_p = cplan.ctypes.data_as(C.c_void_p)
-    rc = lib().syg_stft_rows_w1024_f32(_ptr(y), B, L, _ld(y), hop, int(center), Tn,
-                                       _ptr(window_dev(window, win_length or 1024, 1024)), _ptr(twiddle_dev(1024)), _ptr(tab),
-                                       int(tab.numel()) if tab is not None else 0, int(n_mels or 0), _ptr(mel), float(sr),
-                                       float(roll_percent), float(bw_p), smask, _ptr(stats), cplan_p, _ptr(cpv),
-                                       C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft_rows_w1024_f32")
-    return mel, stats, cpv
-
-
-_SMALL_ROW_WORDS = {512: 296, 256: 160}
-
-
-def wsmall_segtab(sr, n_fft, n_mels, fmin=0.0, fmax=None):
-    """Four-row piece table of the frame-length-512 / 256 segment-sum kernel for this filterbank on the device, or None."""
-    if n_fft not in _SMALL_ROW_WORDS or n_mels > 48:        # (the kernel's [band][16 frames] tile holds 48 bands)
-        return None
-    fmax = sr / 2.0 if fmax is None else fmax
-
-    def build():
-        try:
-            basis = T.mel_filterbank(sr, n_fft, n_mels, fmin, fmax)
-            return _dev(T.pack_mel_segments_rows(sr, n_fft, n_mels, fmin, fmax, basis=basis, rows=4,
-                                                 row_words=_SMALL_ROW_WORDS[n_fft], n_pass=1,
-                                                 block=(8 if n_fft == 256 else 16)).reshape(-1))
-        except ValueError:
-            return False
-    tab = _cached(("segsmall", float(sr), n_fft, n_mels, float(fmin), float(fmax)), build)
-    return None if tab is False else tab
+    return _seg_rows(1024, y, sr, hop, center, window, win_length, n_mels, fmin, fmax, want_stats, roll_percent, bw_p, contrast)
 
 
 def stft_mel_wseg_small(y: torch.Tensor, sr: float, n_fft: int, hop: int, center: bool = True, window="hann", win_length=None,
                         n_mels: int = 128, fmin: float = 0.0, fmax=None) -> torch.Tensor:
     """frame_length 512 / 256, power 2: [B, L] clips -> mel power [B, n_mels, T] in one launch, free-running waves (four /
     eight frames per wave transform, mel by segment sums).  Raises SygnalsHipError without a piece table."""
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    tab = wsmall_segtab(sr, n_fft, n_mels, fmin, fmax)
-    if tab is None:
-        raise SygnalsHipError("stft_mel_wseg_small: no piece table for this frame length / filterbank (use stft_mel_pow2)")
-    B, L = y.shape
-    Tn = num_frames(L, n_fft, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
-    out = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device)
-    rc = lib().syg_stft_mel_wseg_small_f32(_ptr(y), B, L, _ld(y), n_fft, hop, int(center), Tn,
-                                           _ptr(window_dev(window, win_length or n_fft, n_fft)), _ptr(twiddle_dev(1024)),
-                                           _ptr(tab), int(tab.numel()), n_mels, _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft_mel_wseg_small_f32")
-    return out
+    _small_only("stft_mel_wseg_small", n_fft)
+    return _seg_mel(n_fft, y, sr, hop, center, window, win_length, n_mels, fmin, fmax)
 
 
 def stft_rows_wsmall(y: torch.Tensor, sr: float, n_fft: int, hop: int, center: bool = True, window="hann", win_length=None,
                      want_stats=False, roll_percent: float = 0.85, bw_p: float = 2.0, contrast: Optional[np.ndarray] = None):
     """frame_length 512 / 256: the statistics / contrast rows of stft2048_mel from the segment-sum kernel's transform
     (syg_stft_rows_wsmall_f32; nothing is projected).  Returns (stats [B, 8, T] | None, contrast_pv [B, 2, R, T] | None)."""
-    smask = 31 if want_stats is True else int(want_stats or 0)
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if n_fft not in (512, 256):
-        raise SygnalsHipError("stft_rows_wsmall: frame length must be 512 or 256")
-    if not smask and contrast is None:
-        raise ValueError("stft_rows_wsmall: no statistics requested")
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    B, L = y.shape
-    Tn = num_frames(L, n_fft, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
-    stats = torch.zeros((B, 8, Tn), dtype=torch.float32, device=y.device) if smask else None
-    cpv = cplan_p = None
-    if contrast is not None:
-        cplan = np.ascontiguousarray(contrast, dtype=np.int32)
-        cpv = torch.empty((B, 2, int(cplan[0]), Tn), dtype=torch.float32, device=y.device)
-        cplan_p = cplan.ctypes.data_as(C.c_void_p)
-    rc = lib().syg_stft_rows_wsmall_f32(_ptr(y), B, L, _ld(y), n_fft, hop, int(center), Tn,
-                                        _ptr(window_dev(window, win_length or n_fft, n_fft)), _ptr(twiddle_dev(1024)), float(sr),
-                                        float(roll_percent), float(bw_p), smask, _ptr(stats), cplan_p, _ptr(cpv),
-                                        C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft_rows_wsmall_f32")
-    return stats, cpv
+    _small_only("stft_rows_wsmall", n_fft)
+    return _seg_rows(n_fft, y, sr, hop, center, window, win_length, None, 0.0, None, want_stats, roll_percent, bw_p, contrast)[1:]
 
 
 def stft_rows_w4096(y: torch.Tensor, sr: float, hop: int = 1024, center: bool = True, window="hann", win_length=None,
@@ -462,37 +455,7 @@ def stft_rows_w4096(y: torch.Tensor, sr: float, hop: int = 1024, center: bool = 
     """frame_length 4096: the statistics / contrast rows of stft2048_mel from the one-wave-per-frame kernel's launch
     (syg_stft_rows_w4096_f32), with the mel power block when n_mels is given (needs a piece table: w4096_segtab).
     Returns (mel [B, M, T] | None, stats [B, 8, T] | None, contrast_pv [B, 2, R, T] | None)."""
-    smask = 31 if want_stats is True else int(want_stats or 0)
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if not smask and contrast is None:
-        raise ValueError("stft_rows_w4096: no statistics requested (stft_mel_w4096 gives the mel block alone)")
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    tab = None
-    if n_mels is not None:
-        tab = w4096_segtab(sr, n_mels, fmin, fmax)
-        if tab is None:
-            raise SygnalsHipError("stft_rows_w4096: no piece table for this filterbank")
-    B, L = y.shape
-    Tn = num_frames(L, 4096, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
-    mel = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device) if tab is not None else None
-    stats = torch.zeros((B, 8, Tn), dtype=torch.float32, device=y.device) if smask else None
-    cpv = cplan_p = None
-    if contrast is not None:
-        cplan = np.ascontiguousarray(contrast, dtype=np.int32)
-        cpv = torch.empty((B, 2, int(cplan[0]), Tn), dtype=torch.float32, device=y.device)
-        cplan_p = cplan.ctypes.data_as(C.c_void_p)
-    rc = lib().syg_stft_rows_w4096_f32(_ptr(y), B, L, _ld(y), hop, int(center), Tn,
-                                       _ptr(window_dev(window, win_length or 4096, 4096)), _ptr(twiddle_dev(4096)), _ptr(tab),
-                                       int(tab.numel()) if tab is not None else 0, int(n_mels or 0), _ptr(mel), float(sr),
-                                       float(roll_percent), float(bw_p), smask, _ptr(stats), cplan_p, _ptr(cpv),
-                                       C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft_rows_w4096_f32")
-    return mel, stats, cpv
+    return _seg_rows(4096, y, sr, hop, center, window, win_length, n_mels, fmin, fmax, want_stats, roll_percent, bw_p, contrast)
 
 
 def stft_rows_seg(y, sr, n_fft, hop, center=True, window="hann", win_length=None, n_mels=None, fmin=0.0, fmax=None,
@@ -520,7 +483,7 @@ def stft_mel_segments(y, sr, n_fft, hop, center, window, win_length, n_mels, fmi
     frame length / filterbank has none."""
     if n_fft == 1024 and w1024_segtab(sr, n_mels, fmin, fmax) is not None:
         return stft_mel_w1024_seg(y, sr, hop, center, window, win_length, n_mels, fmin, fmax)
-    if n_fft in _SMALL_ROW_WORDS and wsmall_segtab(sr, n_fft, n_mels, fmin, fmax) is not None:
+    if n_fft in (512, 256) and wsmall_segtab(sr, n_fft, n_mels, fmin, fmax) is not None:
         return stft_mel_wseg_small(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax)
     if n_fft == 4096 and w4096_segtab(sr, n_mels, fmin, fmax) is not None:
         return stft_mel_w4096(y, sr, hop, center, window, win_length, n_mels, fmin, fmax)
@@ -531,24 +494,7 @@ def stft_mel_w4096(y: torch.Tensor, sr: float, hop: int = 1024, center: bool = T
                    n_mels: int = 128, fmin: float = 0.0, fmax=None) -> torch.Tensor:
     """frame_length 4096: [B, L] clips -> mel power [B, n_mels, T] in one launch (one wave per frame, mel by segment
     sums).  Raises SygnalsHipError when the filterbank has no four-pass piece table."""
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    tab = w4096_segtab(sr, n_mels, fmin, fmax)
-    if tab is None:
-        raise SygnalsHipError("stft_mel_w4096: no piece table for this filterbank (use the generic chain)")
-    B, L = y.shape
-    Tn = num_frames(L, 4096, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
-    out = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device)
-    rc = lib().syg_stft_mel_w4096_f32(_ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(window_dev(window, win_length or 4096, 4096)),
-                                      _ptr(twiddle_dev(4096)), _ptr(tab), int(tab.numel()), n_mels, _ptr(out),
-                                      C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft_mel_w4096_f32")
-    return out
+    return _seg_mel(4096, y, sr, hop, center, window, win_length, n_mels, fmin, fmax)
 
 
 def stft2048_mel(y: torch.Tensor, sr: float, hop: int = 512, center: bool = True, window="hann",
@@ -561,16 +507,9 @@ def stft2048_mel(y: torch.Tensor, sr: float, hop: int = 512, center: bool = True
     projection: "segments" (syg_stft2048_mel_tri_f32: per-wave segment sums -- the two-pass table where the filterbank has
     one, else the four-pass table -- no barriers in the projection; tri_waves = 16 | 8 waves per workgroup), "matrix"
     (syg_stft2048_mel_f32: block-sparse weights on the matrix cores), "auto": the matrix form wherever it has a plan."""
-    smask = 31 if want_stats is True else int(want_stats or 0)
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if y.stride(1) != 1:
-        y = y.contiguous()
+    y = _clips(y)
     B, L = y.shape
-    Tn = num_frames(L, 2048, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
+    Tn = _frames(L, 2048, hop, center)
     cfg = mel_config(sr, 2048, n_mels, fmin, fmax)
     if projection not in ("auto", "segments", "matrix"):
         raise ValueError("projection must be 'auto', 'segments' or 'matrix'")
@@ -589,13 +528,7 @@ def stft2048_mel(y: torch.Tensor, sr: float, hop: int = 512, center: bool = True
     win = window_dev(window, win_length, 2048)
     tw = twiddle_dev(2048)
     mel = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device)
-    stats = torch.zeros((B, 8, Tn), dtype=torch.float32, device=y.device) if smask else None
-    cpv = None
-    cplan_p = None
-    if contrast is not None:
-        cplan = np.ascontiguousarray(contrast, dtype=np.int32)
-        cpv = torch.empty((B, 2, int(cplan[0]), Tn), dtype=torch.float32, device=y.device)
-        cplan_p = cplan.ctypes.data_as(C.c_void_p)
+    smask, stats, cpv, cplan_p = _rows_out(B, Tn, want_stats, contrast, y.device)
     if tri:
         rc = lib().syg_stft2048_mel_tri_f32(
             _ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(tab), int(tab.numel()),
@@ -623,27 +556,12 @@ def stft2048_stats(y: torch.Tensor, sr: float, hop: int = 512, center: bool = Tr
     functions, nothing projected) -- what spectral_centroid / bandwidth / flatness / rolloff / contrast need
     (manager.py:289-343).  Returns (stats [B, 8, T] | None, contrast_pv [B, 2, R, T] | None), bit-identical to
     stft2048_mel's."""
-    smask = 31 if want_stats is True else int(want_stats or 0)
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if not smask and contrast is None:
-        raise ValueError("stft2048_stats: nothing requested (want_stats and contrast are both empty)")
-    if y.stride(1) != 1:
-        y = y.contiguous()
+    y = _clips(y)
     B, L = y.shape
-    Tn = num_frames(L, 2048, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
+    Tn = _frames(L, 2048, hop, center)
+    smask, stats, cpv, cplan_p = _rows_out(B, Tn, want_stats, contrast, y.device, "stft2048_stats")
     win = window_dev(window, win_length, 2048)
     tw = twiddle_dev(2048)
-    stats = torch.zeros((B, 8, Tn), dtype=torch.float32, device=y.device) if smask else None
-    cpv = None
-    cplan_p = None
-    if contrast is not None:
-        cplan = np.ascontiguousarray(contrast, dtype=np.int32)
-        cpv = torch.empty((B, 2, int(cplan[0]), Tn), dtype=torch.float32, device=y.device)
-        cplan_p = cplan.ctypes.data_as(C.c_void_p)
     rc = lib().syg_stft2048_stats_f32(_ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(win), _ptr(tw), float(sr),
                                       float(roll_percent), float(bw_p), smask or 1, _ptr(stats), cplan_p, _ptr(cpv),
                                       C.c_void_p(_stream_ptr()))
@@ -653,13 +571,9 @@ def stft2048_stats(y: torch.Tensor, sr: float, hop: int = 512, center: bool = Tr
 
 def stft2048_c2c(y: torch.Tensor, hop: int = 512, center: bool = True, window="hann", win_length: int = 2048):
     """Complex STFT, frame-major [B, T, 1025, 2] float32."""
-    require_gpu()
-    if y.stride(1) != 1:
-        y = y.contiguous()
+    y = _clips(y)
     B, L = y.shape
-    Tn = num_frames(L, 2048, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
+    Tn = _frames(L, 2048, hop, center)
     win = window_dev(window, win_length, 2048)
     tw = twiddle_dev(2048)
     out = torch.empty((B, Tn, 1025, 2), dtype=torch.float32, device=y.device)
@@ -915,9 +829,7 @@ def stft_pow2(y: torch.Tensor, n_fft: int, hop: int, center: bool = True, window
         y = y.contiguous()
     B, L = y.shape
     win_length = n_fft if win_length is None else win_length
-    Tn = num_frames(L, n_fft, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
+    Tn = _frames(L, n_fft, hop, center)
     win = window_dev(window, win_length, n_fft)
     out = torch.empty((B, Tn, n_fft // 2 + 1, 2), dtype=torch.float32, device=y.device)
     rc = lib().syg_stft_pow2_c2c_f32(_ptr(y), B, L, _ld(y), n_fft, hop, int(center), Tn, _ptr(win),
@@ -965,9 +877,7 @@ def stft_rows(y: torch.Tensor, n_fft: int, hop: int, center: bool = True, window
     pad = n_fft // 2 if center else 0
     # librosa's count on the padded signal; equals num_frames() for even n_fft, one less for an odd n_fft when hop
     # divides L (the padding is n_fft // 2 on both sides, one sample short of n_fft)
-    Tn = 1 + (L + 2 * pad - n_fft) // hop if L + 2 * pad >= n_fft else 0
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
+    Tn = _at_least_one(1 + (L + 2 * pad - n_fft) // hop if L + 2 * pad >= n_fft else 0)
     yp = y
     if pad or y.stride(1) != 1 or not y.is_contiguous():
         yp = torch.zeros((B, L + 2 * pad), dtype=torch.float32, device=y.device)     # zero padding: data movement only
@@ -1037,15 +947,9 @@ def frame_stats(y: torch.Tensor, frame_length: int = 2048, hop: int = 512, cente
                 mask: int = 0x1FF) -> torch.Tensor:
     """Time-domain frame features of clips y [B, L]: [B, 9, T] float32, rows as FS_ROWS (only the rows
     selected by `mask` are written)."""
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if y.stride(1) != 1:
-        y = y.contiguous()
+    y = _clips(y)
     B, L = y.shape
-    Tn = num_frames(L, frame_length, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
+    Tn = _frames(L, frame_length, hop, center)
     out = torch.zeros((B, 9, Tn), dtype=torch.float32, device=y.device)
     rc = lib().syg_frame_stats_f32(_ptr(y), B, L, _ld(y), int(frame_length), int(hop), int(center), Tn, int(num_bins),
                                    int(mask), _ptr(out), C.c_void_p(_stream_ptr()))
@@ -1800,11 +1704,7 @@ def cqt(y: torch.Tensor, sr: float, hop_length: int = 512, fmin=None, n_bins: in
 # ------------------------------------------------------------------ pitch (yin / pyin)
 def _pitch_setup(y, sr, fmin, fmax, frame_length, win_length, hop, center):
     from . import _pitch as P
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
-    if y.stride(1) != 1:
-        y = y.contiguous()
+    y = _clips(y)
     win_length = int(win_length) if win_length is not None else frame_length // 2
     hop = int(hop) if hop is not None else frame_length // 4
     if not (0 < fmin < fmax <= sr / 2):
@@ -1813,9 +1713,7 @@ def _pitch_setup(y, sr, fmin, fmax, frame_length, win_length, hop, center):
         raise ValueError(f"win_length={win_length} must be a positive integer less than frame_length={frame_length}")
     min_p, max_p = P.periods(sr, fmin, fmax, frame_length, win_length)
     B, L = y.shape
-    Tn = P.num_frames(L, frame_length, hop, center)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
+    Tn = _at_least_one(P.num_frames(L, frame_length, hop, center))
     return P, y, win_length, hop, min_p, max_p, B, L, Tn
 
 
@@ -1979,8 +1877,7 @@ def hpss(y: torch.Tensor, kernel_size=31, power: float = 2.0, margin=1.0, hop_le
     syg_stft2048_c2c_f32 -> syg_hpss_masks_f32 -> syg_istft2048_f32 (both components from one read of D)."""
     require_gpu()
     hop = _hpss_stft_args(n_fft, hop_length, win_length, window, center)
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor of shape [B, L]")
+    y = _clips(y)
     if y.shape[0] < 1 or y.shape[1] < 1:
         raise ValueError("hpss: empty input")
     D = stft2048_c2c(y, hop, True, "hann", 2048)
@@ -2002,10 +1899,8 @@ def hnr_rows(y_harm: torch.Tensor, y_perc: torch.Tensor, frame_length: int = 204
     if yh.stride(1) != 1 or yp.stride(1) != 1 or _ld(yh) != _ld(yp):
         yh, yp = yh.contiguous(), yp.contiguous()
     B, L = yh.shape
-    Tn = 1 + (L + 2 * (frame_length // 2) - frame_length) // hop if center else (
-        1 + (L - frame_length) // hop if L >= frame_length else 0)
-    if Tn <= 0:
-        raise ValueError("signal too short for one frame")
+    Tn = _at_least_one(1 + (L + 2 * (frame_length // 2) - frame_length) // hop if center else (
+        1 + (L - frame_length) // hop if L >= frame_length else 0))
     out = torch.empty((B, Tn), dtype=torch.float32, device=yh.device)
     rh = torch.empty_like(out) if rms else None
     rp = torch.empty_like(out) if rms else None
