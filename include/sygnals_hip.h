@@ -511,6 +511,37 @@ int syg_hnr_rows_f32(const float* y_harm, const float* y_perc, int64_t B, int64_
                      void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Onset detection: librosa 0.10 onset.onset_strength / util.peak_pick / onset.onset_detect as called by detect_onsets,
+ * sygnals/core/audio/features.py:555-619, after any mel front end (mel POWER [B, M, T], T contiguous), and the clip
+ * totals of get_basic_audio_metrics (:508-551).  Parity is unpinned (librosa is not a dependency): the float64
+ * restatement of tests/onset_ref.py is the contract.
+ * syg_onset_strength_f32: S = power_to_db(mel, ref 1.0, amin, top_db relative to the clip's own maximum; top_db < 0:
+ *   no clip), never written out.  d[t] = mean_m max(0, S[m, t + lag] - R[m, t]), t < T - lag, R = S (max_size 1) or
+ *   the maximum of S over mel rows [m - max_size / 2, m - max_size / 2 + max_size - 1] (scipy.ndimage.maximum_filter1d).
+ *   env [B, T_out]: `pad` zeros, then d, cut or zero-filled to T_out <= pad + T; detrend != 0 then applies
+ *   lfilter([1, -1], [1, -0.99]) along each row.  The mel mean is a fixed-order sum: bit-identical from run to run.
+ *   Clips of more than 2048 frames are split over workgroups and need `work`, syg_onset_strength_work_bytes(B, M, T)
+ *   bytes (0 for shorter clips: work may be NULL).  lag >= 1, lag < T, max_size >= 1, amin > 0.
+ * syg_onset_peaks_f32: env [B, T] (row stride ld, shared by energy).  normalize != 0: x = (env - min) / (max - min +
+ *   FLT_MIN) per clip.  Frame n is a candidate when x[n] is the maximum of x[max(0, n - pre_max) : min(T, n + post_max)],
+ *   x[n] >= mean(x[max(0, n - pre_avg) : min(T, n + post_avg)]) + delta (a direct float64 sum over the window) and
+ *   x[n] != 0; candidates are kept left to right, each only if n > last + wait.  backtrack != 0 moves each onset to the
+ *   nearest i at or before it with e[i] <= e[i - 1] and e[i] < e[i + 1] (frame 0 always qualifies), e = energy or, when
+ *   NULL, env.  An all-zero or non-finite clip has no onsets.  frames [B, T] int32: the kept frames in ascending order,
+ *   -1 beyond them; count [B] int32.  No atomics.  Windows and wait >= 0, post_max >= 1, post_avg >= 1, delta finite
+ *   and >= 0.  The cost is T (pre_max + post_max + pre_avg + post_avg) loads per clip.
+ * syg_clip_metrics_f32: y [B, L] (row stride ldy) -> out [B, 2] float32: sum of y^2 (float64 partial sums, fixed-order
+ *   tree, rounded once) and max |y|.
+ * ------------------------------------------------------------------------------- */
+int64_t syg_onset_strength_work_bytes(int64_t B, int M, int64_t T);
+int syg_onset_strength_f32(const float* mel, int64_t B, int M, int64_t T, float amin, float top_db, int lag,
+                           int max_size, int pad, int64_t T_out, int detrend, float* env, void* work, void* stream);
+int syg_onset_peaks_f32(const float* env, int64_t B, int64_t T, int64_t ld, int pre_max, int post_max, int pre_avg,
+                        int post_avg, double delta, int wait, int normalize, int backtrack, const float* energy,
+                        int32_t* frames, int32_t* count, void* stream);
+int syg_clip_metrics_f32(const float* y, int64_t B, int64_t L, int64_t ldy, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Constant-Q transform building blocks: librosa.cqt as called by compute_cqt,
  * sygnals/core/dsp.py:276-284 (recursive per-octave algorithm; the host composes the octaves).
  *   syg_decimate2_f32   y[b, n] = scale * sum_j taps[j] * x[b, 2n + (ntaps-1)/2 - j], n < ceil(L/2)

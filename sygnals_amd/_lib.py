@@ -92,6 +92,10 @@ SIGNATURES = {
     "syg_hpss_masks_f32": (_i, [_p, _l, _l, _i, _i, _d, _d, _d, _p, _p, _p, _p, _p]),
     "syg_istft2048_f32": (_i, [_p, _l, _l, _i, _i, _l, _p, _p, _p, _p, _p, _p, _l, _p]),
     "syg_hnr_rows_f32": (_i, [_p, _p, _l, _l, _l, _i, _i, _i, _l, _p, _p, _p, _p]),
+    "syg_onset_strength_work_bytes": (_l, [_l, _i, _l]),
+    "syg_onset_strength_f32": (_i, [_p, _l, _i, _l, _f, _f, _i, _i, _i, _l, _i, _p, _p, _p]),
+    "syg_onset_peaks_f32": (_i, [_p, _l, _l, _l, _i, _i, _i, _i, _d, _i, _i, _i, _p, _p, _p, _p]),
+    "syg_clip_metrics_f32": (_i, [_p, _l, _l, _l, _p, _p]),
 }
 
 _lib = None

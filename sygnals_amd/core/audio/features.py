@@ -9,6 +9,10 @@ tests/pitch_ref.py is the contract) runs the frame stage and the Viterbi decode 
 rms_energy.  harmonic_to_noise_ratio (:225-316; librosa 0.10 effects.hpss, parity unpinned: the float64 restatement
 of tests/hpss_ref.py is the contract) runs the STFT, the median-filter soft masks, both inverse STFTs and the per-frame
 energy ratio on the device (`syg_stft2048_c2c_f32`, `syg_hpss_masks_f32`, `syg_istft2048_f32`, `syg_hnr_rows_f32`).
+detect_onsets (:555-619; librosa 0.10 onset_detect, parity unpinned: the float64 restatement of tests/onset_ref.py is the
+contract) takes the mel power from the mel front end of the frame length and runs the spectral flux, the normalisation,
+peak_pick and the backtracking on the device (`syg_onset_strength_f32`, `syg_onset_peaks_f32`); get_basic_audio_metrics
+(:508-551) takes its two clip totals from `syg_clip_metrics_f32`.
 """
 from __future__ import annotations
 
@@ -239,3 +243,143 @@ def harmonic_to_noise_ratio(y, sr: int, frame_length: int = 2048, hop_length: Op
         logger.error(f"Error calculating approximate HNR using HPSS: {e}")
         num_frames = 1 + len(y) // hop_length_calc if hop_length_calc > 0 else 0
         return np.full(num_frames, np.nan, dtype=np.float64)
+
+
+# ------------------------------------------------------------------ global metrics, onsets
+def get_basic_audio_metrics(y, sr: int):
+    logger.debug("Calculating basic global audio metrics.")
+    try:
+        y = np.asarray(y)
+        if y.ndim > 1:
+            logger.warning("Input signal is multi-channel. Converting to mono for global RMS/peak calculation.")
+            # the shorter axis is taken for the channels
+            y_mono = (np.mean(y, axis=0) if y.shape[0] < y.shape[1] else np.mean(y, axis=1)).astype(np.float64)
+        else:
+            y_mono = y
+        duration_seconds = y.shape[-1] / float(sr)         # librosa.get_duration(y=y): samples along the last axis
+        rms_global = peak_amplitude = 0.0
+        if y_mono.size > 0:
+            ss, pk = ops.clip_metrics(ops.to_device_f32(y_mono[None, :]))[0].cpu().numpy().astype(np.float64)
+            rms_global = np.sqrt(ss / y_mono.size)
+            peak_amplitude = pk
+        return {"duration_seconds": float(duration_seconds), "rms_global": float(rms_global),
+                "peak_amplitude": float(peak_amplitude)}
+    except Exception as e:
+        logger.error(f"Error calculating basic audio metrics: {e}")
+        raise
+
+
+_PEAK_KWARGS = ("pre_max", "post_max", "pre_avg", "post_avg", "delta", "wait")
+
+
+def _peak_defaults(sr, hop_length, kwargs):
+    """onset_detect's peak_pick defaults, in frames: each is (c * sr) // hop_length, a float floor division."""
+    pk = {"pre_max": 0.03 * sr // hop_length, "post_max": 0.00 * sr // hop_length + 1,
+          "pre_avg": 0.10 * sr // hop_length, "post_avg": 0.10 * sr // hop_length + 1,
+          "wait": 0.03 * sr // hop_length, "delta": 0.07}
+    pk.update({k: kwargs[k] for k in _PEAK_KWARGS if k in kwargs})
+    for k in _PEAK_KWARGS:
+        if pk[k] < 0:
+            raise ValueError(f"{k} must be non-negative")
+    for k in ("post_max", "post_avg"):
+        if pk[k] <= 0:
+            raise ValueError(f"{k} must be positive")
+    for k in _PEAK_KWARGS:
+        if k != "delta":
+            if int(pk[k]) != pk[k]:
+                raise ValueError(f"{k}={pk[k]} must be an integer number of frames")
+            pk[k] = int(pk[k])
+    return pk
+
+
+def _as_clips(y):
+    if hasattr(y, "is_cuda"):
+        y = y if (y.is_cuda and y.dtype == ops.torch.float32) else ops.to_device_f32(y)
+    else:
+        y = ops.to_device_f32(np.atleast_2d(np.asarray(y)))
+    if y.dim() != 2:
+        raise ValueError("Input audio batch must be a 2D array [B, L].")
+    return y
+
+
+def onset_strength_batch(y, sr: int, n_fft: int = 2048, hop_length: int = 512, n_mels: int = 128, fmin: float = 0.0,
+                         fmax: Optional[float] = None, lag: int = 1, max_size: int = 1, center: bool = True,
+                         detrend: bool = False, feature=None, aggregate=None):
+    """librosa.onset.onset_strength of clips y [B, L] (a float32 device tensor or an array) -> float32 [B, T] device
+    tensor.  The log-mel matrix comes from whichever mel front end serves n_fft (`syg_onset_strength_f32` after it)."""
+    if feature is not None or aggregate is not None:
+        raise TypeError("onset_strength_batch: feature= / aggregate= callables are not offloaded on the device backend")
+    from ..features import manager as M               # inside the function: the manager imports this package's users
+    y = _as_clips(y)
+    mel = M.mel_power_batch(y, sr, n_fft, hop_length, center, "hann", n_mels, fmin, fmax)
+    pad = lag + (n_fft // (2 * hop_length) if center else 0)
+    T_out = mel.shape[2] if center else None
+    return ops.onset_strength(mel, lag, max_size, pad, T_out, detrend=detrend)
+
+
+def detect_onsets_batch(y, sr: int, hop_length: int = 512, backtrack: bool = False, energy=None,
+                        normalize: bool = True, **kwargs: Any):
+    """Batched detect_onsets of clips y [B, L] -> (frames [B, T] int32: each clip's onset frames in ascending order,
+    -1 beyond them; count [B] int32), device tensors (`syg_onset_peaks_f32` on onset_strength_batch)."""
+    if set(kwargs) - set(_PEAK_KWARGS):
+        raise TypeError(f"detect_onsets: unsupported librosa arguments on the device backend: "
+                        f"{sorted(set(kwargs) - set(_PEAK_KWARGS))}")
+    pk = _peak_defaults(sr, hop_length, kwargs)
+    env = onset_strength_batch(y, sr, hop_length=hop_length)
+    if energy is not None and not hasattr(energy, "is_cuda"):
+        energy = ops.to_device_f32(np.atleast_2d(np.asarray(energy)))
+    return ops.onset_peaks(env, normalize=normalize, backtrack=backtrack, energy=energy, **pk)
+
+
+def detect_onsets(y=None, *, sr: Optional[int] = None, onset_envelope=None, hop_length: int = 512,
+                  units: str = "frames", **kwargs: Any):
+    if y is None and onset_envelope is None:
+        raise ValueError("Either audio time series 'y' or 'onset_envelope' must be provided.")
+    if y is not None and sr is None:
+        raise ValueError("Sampling rate 'sr' must be provided when using time series 'y'.")
+    if units in ["samples", "time"] and sr is None:
+        raise ValueError(f"Sampling rate 'sr' is required when units='{units}'.")
+    logger.debug(f"Detecting onsets: units={units}, hop_length={hop_length}, kwargs={kwargs}")
+    allowed = set(_PEAK_KWARGS) | {"backtrack", "energy", "normalize"}
+    if set(kwargs) - allowed:
+        raise TypeError(f"detect_onsets: unsupported librosa arguments on the device backend: "
+                        f"{sorted(set(kwargs) - allowed)}")
+    try:
+        if sr is None:                   # an envelope without a rate: librosa's window defaults multiply sr
+            raise TypeError("unsupported operand type(s) for *: 'float' and 'NoneType'")
+        if units not in ("frames", "samples", "time"):
+            raise ValueError(f"Invalid unit type: {units}")
+        backtrack = bool(kwargs.get("backtrack", False))
+        normalize = bool(kwargs.get("normalize", True))
+        energy = kwargs.get("energy")
+        peak = {k: kwargs[k] for k in _PEAK_KWARGS if k in kwargs}
+        if onset_envelope is None:
+            y = np.asarray(y)
+            if y.ndim != 1:
+                raise ValueError("Input audio data must be a 1D array.")
+            if energy is not None:
+                energy = np.asarray(energy)[None, :]
+            frames, count = detect_onsets_batch(y[None, :], sr, hop_length, backtrack, energy, normalize, **peak)
+        else:
+            env = np.asarray(onset_envelope)
+            if env.ndim != 1:
+                raise ValueError("onset_envelope must be a 1D array.")
+            pk = _peak_defaults(sr, hop_length, peak)
+            if env.size == 0:
+                frames = count = None
+            else:
+                if energy is not None:
+                    energy = ops.to_device_f32(np.asarray(energy)[None, :])
+                frames, count = ops.onset_peaks(ops.to_device_f32(env[None, :]), normalize=normalize,
+                                                backtrack=backtrack, energy=energy, **pk)
+        onsets = np.array([], dtype=np.int64) if frames is None else \
+            frames[0, :int(count[0].item())].cpu().numpy().astype(np.int64)
+        if units == "frames":
+            return onsets
+        samples = onsets * int(hop_length)
+        if units == "samples":
+            return samples.astype(np.int64, copy=False)
+        return (samples / float(sr)).astype(np.float64, copy=False)
+    except Exception as e:
+        logger.error(f"Error detecting onsets: {e}")
+        raise

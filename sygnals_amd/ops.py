@@ -1908,3 +1908,61 @@ def hnr_rows(y_harm: torch.Tensor, y_perc: torch.Tensor, frame_length: int = 204
                                 _ptr(out), _ptr(rh), _ptr(rp), C.c_void_p(_stream_ptr()))
     check(rc, "syg_hnr_rows_f32")
     return (out, rh, rp) if rms else out
+
+
+# ------------------------------------------------------------------ onset detection
+def onset_strength(mel: torch.Tensor, lag: int = 1, max_size: int = 1, pad: int = 0, T_out: Optional[int] = None,
+                   amin: float = 1e-10, top_db: Optional[float] = 80.0, detrend: bool = False) -> torch.Tensor:
+    """librosa.onset.onset_strength after the mel front end (syg_onset_strength_f32): mel POWER [B, M, T] -> envelope
+    [B, T_out] float32, `pad` zeros in front (T_out defaults to pad + T - lag, the uncut envelope).  The dB matrix is
+    formed on the fly (ref 1.0, top_db relative to each clip's maximum) and never stored."""
+    require_gpu()
+    if mel.dim() != 3 or mel.dtype != torch.float32 or not mel.is_cuda:
+        raise ValueError("mel must be a float32 CUDA tensor [B, M, T]")
+    if not isinstance(lag, (int, np.integer)) or lag < 1:
+        raise ValueError("lag must be a positive integer")
+    if not isinstance(max_size, (int, np.integer)) or max_size < 1:
+        raise ValueError("max_size must be a positive integer")
+    mel = mel.contiguous()
+    B, M, Tn = mel.shape
+    T_out = int(pad) + Tn - int(lag) if T_out is None else int(T_out)
+    h = lib()
+    wb = h.syg_onset_strength_work_bytes(B, M, Tn)
+    work = torch.empty((wb // 4,), dtype=torch.float32, device=mel.device) if wb > 0 else None
+    env = torch.empty((B, max(T_out, 0)), dtype=torch.float32, device=mel.device)
+    rc = h.syg_onset_strength_f32(_ptr(mel), B, M, Tn, float(amin), float(top_db) if top_db is not None else -1.0,
+                                  int(lag), int(max_size), int(pad), T_out, int(bool(detrend)), _ptr(env), _ptr(work),
+                                  C.c_void_p(_stream_ptr()))
+    check(rc, "syg_onset_strength_f32")
+    return env
+
+
+def onset_peaks(env: torch.Tensor, pre_max: int, post_max: int, pre_avg: int, post_avg: int, delta: float, wait: int,
+                normalize: bool = True, backtrack: bool = False, energy: Optional[torch.Tensor] = None):
+    """util.peak_pick with onset_detect's normalisation and backtracking (syg_onset_peaks_f32) on envelopes [B, T] ->
+    (frames [B, T] int32: the onsets in ascending order, -1 beyond them; count [B] int32), both on the device."""
+    env = _clips(env, "env")
+    B, Tn = env.shape
+    if energy is not None:
+        energy = _clips(energy, "energy")
+        if energy.shape != env.shape:
+            raise ValueError("energy must have the envelope's shape")
+        if _ld(energy) != _ld(env):
+            env, energy = env.contiguous(), energy.contiguous()
+    frames = torch.empty((B, Tn), dtype=torch.int32, device=env.device)
+    count = torch.empty((B,), dtype=torch.int32, device=env.device)
+    rc = lib().syg_onset_peaks_f32(_ptr(env), B, Tn, _ld(env), int(pre_max), int(post_max), int(pre_avg), int(post_avg),
+                                   float(delta), int(wait), int(bool(normalize)), int(bool(backtrack)), _ptr(energy),
+                                   _ptr(frames), _ptr(count), C.c_void_p(_stream_ptr()))
+    check(rc, "syg_onset_peaks_f32")
+    return frames, count
+
+
+def clip_metrics(y: torch.Tensor) -> torch.Tensor:
+    """Per-clip totals of y [B, L] (syg_clip_metrics_f32) -> [B, 2] float32: sum of squares, peak |y|."""
+    y = _clips(y)
+    B, L = y.shape
+    out = torch.empty((B, 2), dtype=torch.float32, device=y.device)
+    rc = lib().syg_clip_metrics_f32(_ptr(y), B, L, _ld(y), _ptr(out), C.c_void_p(_stream_ptr()))
+    check(rc, "syg_clip_metrics_f32")
+    return out
