@@ -546,7 +546,7 @@ int syg_clip_metrics_f32(const float* y, int64_t B, int64_t L, int64_t ldy, floa
  * sygnals/core/dsp.py:276-284 (recursive per-octave algorithm; the host composes the octaves).
  *   syg_decimate2_f32   y[b, n] = scale * sum_j taps[j] * x[b, 2n + (ntaps-1)/2 - j], n < ceil(L/2)
  *                       (zero outside the signal) -- the decimation between octaves
- *   syg_cqt_octave_f32  rectangular-window centred STFT frame (n_fft = 2^k <= 4096, hop) of y [B, L],
+ *   syg_cqt_octave_f32  rectangular-window centred STFT frame (n_fft = 2^k, 8 ... 1024; hop) of y [B, L],
  *                       times the frequency-domain basis [n_filt, n_fft/2+1] complex64 ->
  *                       out[b * out_bstride + (row0 + f) * T + t] complex64; hull_host (host int32
  *                       [2 * n_filt], may be NULL = dense): first non-zero bin and run length of every
@@ -580,12 +580,16 @@ int syg_cqt_octave_bf16x3_f32(const float* y, int64_t B, int64_t L, int64_t ldy,
 
 /* The whole transform of compute_cqt (sygnals/core/dsp.py:231-289) in ONE launch for its usual shape -- hop_length 512, one
  * early decimation, n_oct <= 7 octaves of n_filt <= 16 filters at frame length 256 and hop 256 >> o that share one operand
- * table (sygnals_amd.ops.cqt_pack_bf16x3: [3][2][8][64] 16-byte entries): the stream is read once, every decimation level
+ * table (below): the stream is read once, every decimation level
  * lives in LDS only (syg_decimate2_chain_f32 + n_oct x syg_cqt_octave_bf16x3_f32 write and re-read them through HBM), the
  * same values to the rounding of the float32 sums (the decimator's symmetric taps are paired, the products' k range is
  * summed in four parts).  taps: the 41-tap half-band decimator (zero at the even offsets from its centre, symmetric);
  * scale: sqrt(2); row0_host[n_oct]: first output row of octave o; out [B, n_bins, T] complex (float pairs),
- * out_bstride in complex elements, T <= the smallest centred frame count over the octaves (1 + L_o / hop_o). */
+ * out_bstride in complex elements, T <= the smallest centred frame count over the octaves (1 + L_o / hop_o).
+ * gsplit: the layout of syg_cqt_octave_bf16x3_f32's table at n_fft 256 with ALWAYS two row tiles, whatever n_filt is --
+ * bfloat16 [3 terms][2 row tiles][8 steps][64 lanes][8] = 24576 16-bit words (48 KiB), 16-byte aligned; rows past 2 n_filt
+ * (the whole second tile when n_filt <= 8) are zero (sygnals_amd.ops.cqt_fused_table).  The level-by-level entry above
+ * reads ONE row tile when n_filt <= 8: the two tables differ there. */
 int syg_cqt_fused_f32(const float* y, int64_t B, int64_t L, int64_t ldy, const float* taps, int ntaps, float scale,
                       const void* gsplit, int n_filt, int n_oct, const int32_t* row0_host, int64_t T, float* out,
                       int64_t out_bstride, void* stream);

@@ -1108,13 +1108,14 @@ def cqt_filter_fft(sr, freqs, filter_scale, alpha, sparsity=0.01):
     return out, n_fft
 
 
-def cqt_plan(sr, hop_length=512, fmin=None, n_bins=84, bins_per_octave=12, filter_scale=1.0, sparsity=0.01):
-    """Everything that does not depend on the signal: octave schedule, bases (scalings folded in)."""
+def cqt_plan(sr, hop_length=512, fmin=None, n_bins=84, bins_per_octave=12, filter_scale=1.0, sparsity=0.01, *, tuning=0.0):
+    """Everything that does not depend on the signal: octave schedule, bases (scalings folded in).  tuning: deviation from
+    A440 in fractions of a bin (librosa: fmin * 2 ** (tuning / bins_per_octave))."""
     if fmin is None:
         fmin = note_c1_hz()
     n_oct = int(np.ceil(float(n_bins) / bins_per_octave))
     n_filters = min(bins_per_octave, n_bins)
-    freqs = cqt_frequencies(n_bins, fmin, bins_per_octave)
+    freqs = cqt_frequencies(n_bins, fmin, bins_per_octave, tuning)
     r = 2.0 ** (2.0 / bins_per_octave)
     alpha = (r - 1) / (r + 1)
     lengths_full, cutoff = _wavelet_lengths(freqs, sr, filter_scale, alpha)
@@ -1150,12 +1151,12 @@ def cqt_plan(sr, hop_length=512, fmin=None, n_bins=84, bins_per_octave=12, filte
     return {"early": early, "octaves": octs, "n_bins": n_bins, "scale": 1.0 / np.sqrt(lengths_s), "freqs": freqs}
 
 
-def cqt(y, sr, hop_length=512, fmin=None, n_bins=84, bins_per_octave=12, filter_scale=1.0, sparsity=0.01):
+def cqt(y, sr, hop_length=512, fmin=None, n_bins=84, bins_per_octave=12, filter_scale=1.0, sparsity=0.01, *, tuning=0.0):
     """complex128 [n_bins, 1 + len(y)//hop_length] (librosa.cqt layout), see the deviation note above."""
     y = np.asarray(y, dtype=np.float64)
     if y.ndim != 1:
         raise ValueError("Input data must be a 1D array.")
-    plan = cqt_plan(sr, hop_length, fmin, n_bins, bins_per_octave, filter_scale, sparsity)
+    plan = cqt_plan(sr, hop_length, fmin, n_bins, bins_per_octave, filter_scale, sparsity, tuning=tuning)
     my_y = y
     for _ in range(plan["early"]):
         my_y = cqt_resample2(my_y)

@@ -25,6 +25,21 @@ def c1_hz() -> float:
 
 DECIMATOR_TAPS, DECIMATOR_BETA = 41, 10.0
 
+# What the octave entry points of csrc/cqt.hip take (their own argument checks say the same):
+BF16X3_NFFT, BF16X3_MAXFILT = (128, 256), 16          # syg_cqt_octave_bf16x3_f32: two 16-row tiles of (re, im) rows
+GEMM_NFFT, GEMM_MAXFILT = (128, 256, 512), 64         # syg_cqt_octave_gemm_f32
+RFFT_MAXFILT = 24                                     # syg_cqt_octave_f32: filters per call (MAXFILT); more go in row groups
+RFFT_MAX_NFFT = 1024                                  # ... and the longest frame whose eight transforms fit one workgroup's LDS
+CQT_MODES = ("bf16x3", "gemm", "fft")
+
+
+def bf16x3_takes(n_fft: int, n_filt: int) -> bool:
+    return n_fft in BF16X3_NFFT and 1 <= n_filt <= BF16X3_MAXFILT
+
+
+def gemm_takes(n_fft: int, n_filt: int) -> bool:
+    return n_fft in GEMM_NFFT and 1 <= n_filt <= GEMM_MAXFILT
+
 
 def decimation_taps() -> np.ndarray:
     """The octave decimator: a 41-tap half-band FIR, Kaiser window beta 10 (module docstring).  A half-band filter is
@@ -106,12 +121,19 @@ class CqtPlan:
             o["n"] = len(rows)
         self.freqs = freqs
         self.hop_length = int(hop_length)
+        self.bins_per_octave, self.filter_scale = bpo, float(filter_scale)
+        self._one_launch = None
 
     def one_launch_shape(self) -> bool:
         """True when syg_cqt_fused_f32 can take the whole transform: hop_length 512, one early decimation, at most seven
         octaves at frame length 256 and hop 256 >> o with the same number (<= 16) of unclipped filters, and ONE operand
         table -- the octaves' bases are the same matrix up to rounding (the decimator's sqrt(2) and the scalings above
         cancel).  48 / 44.1 kHz with the default 84 bins qualify; 22.05 kHz (no early decimation) and hop 1024 do not."""
+        if self._one_launch is None:
+            self._one_launch = self._one_launch_shape()
+        return self._one_launch
+
+    def _one_launch_shape(self) -> bool:
         oc = self.octaves
         if self.hop_length != 512 or self.early != 1 or not 1 <= len(oc) <= 7 or not 1 <= oc[0]["n"] <= 16:
             return False
@@ -120,3 +142,37 @@ class CqtPlan:
         return all(o["n_fft"] == 256 and o["hop"] == (256 >> i) and o["skip"] == 0 and o["n"] == oc[0]["n"]
                    and o["basis"].shape == b0.shape and float(np.abs(o["basis"] - b0).max()) <= tol
                    for i, o in enumerate(oc))
+
+
+def cqt_route(plan: CqtPlan, mode: str = "bf16x3", fused: bool = True):
+    """Which entry point every octave of `plan` runs on -- the one place that decides it (ops.cqt launches what this
+    returns; tests/test_host_logic.py pins it).  mode: settings.cqt_mode, fused: settings.cqt_fused.
+    Returns (one_launch, calls):
+      one_launch True   the whole transform is ONE call: calls = [("syg_cqt_fused_f32", 256, n_filt, 2)]
+      one_launch False  calls[i] = (entry point, n_fft, n_filt, tiles) of octave i, top octave first (entry point None
+                        for an octave without rows).  tiles: 16-row tiles of the operand table for the two matrix forms
+                        ((2 n_filt + 15) // 16; the kernels' template argument is 2 where the tiles pair up -- bf16x3
+                        with two tiles, gemm with an even count at n_fft <= 256 -- and 1 otherwise); for
+                        syg_cqt_octave_f32 the number of calls, each with a row group of at most RFFT_MAXFILT filters.
+    Raises ValueError, before anything is launched, for an octave no kernel serves: one that only the rfft form could
+    take with a frame longer than RFFT_MAX_NFFT samples."""
+    if mode not in CQT_MODES:
+        raise ValueError(f"cqt_mode must be one of {CQT_MODES}, got {mode!r}")
+    if fused and mode == "bf16x3" and plan.one_launch_shape():
+        return True, [("syg_cqt_fused_f32", 256, plan.octaves[0]["n"], 2)]
+    calls = []
+    for o in plan.octaves:
+        n_fft, n = o["n_fft"], o["n"]
+        if n < 1:
+            calls.append((None, n_fft, 0, 0))
+        elif mode == "bf16x3" and bf16x3_takes(n_fft, n):
+            calls.append(("syg_cqt_octave_bf16x3_f32", n_fft, n, (2 * n + 15) // 16))
+        elif mode != "fft" and gemm_takes(n_fft, n):
+            calls.append(("syg_cqt_octave_gemm_f32", n_fft, n, (2 * n + 15) // 16))
+        elif n_fft <= RFFT_MAX_NFFT:
+            calls.append(("syg_cqt_octave_f32", n_fft, n, -(-n // RFFT_MAXFILT)))
+        else:
+            raise ValueError(f"cqt: bins_per_octave={plan.bins_per_octave} with filter_scale={plan.filter_scale:g} needs an "
+                             f"octave frame length of {n_fft} samples; the device kernels take at most {RFFT_MAX_NFFT} "
+                             f"(cqt_mode={mode!r}): lower filter_scale or bins_per_octave")
+    return False, calls

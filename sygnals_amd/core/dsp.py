@@ -109,7 +109,11 @@ def compute_cqt(y, sr: int, hop_length: Optional[int] = 512, fmin: Optional[floa
 
     Accepted librosa keyword arguments: tuning (default 0.0), filter_scale (1), sparsity (0.01); the fixed choices
     norm=1, window='hann', scale=True, pad_mode='constant' may be passed but not changed.  The decimation filter
-    differs from librosa's soxr_hq resampler (see sygnals_amd/_cqt.py).
+    differs from librosa's soxr_hq resampler (see sygnals_amd/_cqt.py).  Served: every combination of
+    bins_per_octave and filter_scale whose octave frames (the power of two above the longest wavelet) are at most 1024
+    samples -- with the default fmin at 48 kHz and hop 512, 60 bins per octave at filter_scale 1, 36 at 1.5, 24 at
+    2.5 and 12 at 5 are served, 64 at 1 is not; what is not, ops.cqt refuses with a ValueError that names the two parameters
+    (tests/cqt_cases.py: the tested settings).
     """
     y = np.asarray(y)
     if y.ndim != 1:

@@ -908,19 +908,17 @@ extern "C" int syg_cqt_octave_f32(const float* y, int64_t B, int64_t L, int64_t 
                                   const float* twiddle, const float* basis, int n_filt, const int32_t* hull_host,
                                   float* out, int64_t out_bstride, int row0, void* stream) {
   SYG_REQUIRE(y && twiddle && basis && out, "cqt_octave: null pointer argument");
-  SYG_REQUIRE(is_pow2(n_fft) && n_fft >= 8 && n_fft <= 4096, "cqt_octave: n_fft must be a power of two in [8, 4096]");
+  // (eight frames a workgroup, 3 n_fft / 2 + 1 complex values each: n_fft = 1024 takes 96 KiB of the 160 KiB of LDS, 2048 would
+  //  take 192 KiB)
+  SYG_REQUIRE(is_pow2(n_fft) && n_fft >= 8 && n_fft <= 1024, "cqt_octave: n_fft must be a power of two in [8, 1024] (got %d)",
+              n_fft);
   SYG_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && ldy >= L && hop >= 1, "cqt_octave: bad B/L/ldy/hop");
   SYG_REQUIRE(T >= 1 && T <= 1 + L / hop, "cqt_octave: T=%lld exceeds the centred frame count %lld", (long long)T,
               (long long)(1 + L / hop));
   SYG_REQUIRE(n_filt >= 1 && n_filt <= MAXFILT, "cqt_octave: n_filt must be in [1, %d]", MAXFILT);
-  SYG_REQUIRE(row0 >= 0 && out_bstride >= (int64_t)(row0 + n_filt) * T, "cqt_octave: output rows out of range");
+  SYG_REQUIRE(row0 >= 0 && out_bstride >= ((int64_t)row0 + n_filt) * T, "cqt_octave: output rows out of range");
   const int M = n_fft / 2;
   const size_t lds = (size_t)FPW * (2 * M + M + 1) * sizeof(float2);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)cqt_octave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) { set_error("cqt_octave: cannot reserve LDS: %s", hipGetErrorString(e)); return SYG_E_LAUNCH; }
-  }
   const int64_t gx = (T + FPW - 1) / FPW;
   SYG_REQUIRE(gx < (int64_t)0x7fffffff, "cqt_octave: grid too large");
   // hull_host: [2 * n_filt] = first non-zero bin and run length of every basis row (NULL: rows are dense)
@@ -931,9 +929,14 @@ extern "C" int syg_cqt_octave_f32(const float* y, int64_t B, int64_t L, int64_t 
     if (hull_host && f < n_filt) {
       hull.k0[f] = hull_host[f];
       hull.len[f] = hull_host[n_filt + f];
-      SYG_REQUIRE(hull.k0[f] >= 0 && hull.len[f] >= 0 && hull.k0[f] + hull.len[f] <= M + 1,
+      SYG_REQUIRE(hull.k0[f] >= 0 && hull.len[f] >= 0 && hull.k0[f] <= M + 1 && hull.len[f] <= M + 1 - hull.k0[f],
                   "cqt_octave: non-zero run of filter %d out of range (k0=%d len=%d)", f, hull.k0[f], hull.len[f]);
     }
+  }
+  if (lds > 64 * 1024) {                         // (after every argument check: this is the first device call)
+    hipError_t e = hipFuncSetAttribute((const void*)cqt_octave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds);
+    if (e != hipSuccess) { set_error("cqt_octave: cannot reserve LDS: %s", hipGetErrorString(e)); return SYG_E_LAUNCH; }
   }
   hipLaunchKernelGGL(cqt_octave_kernel, dim3((unsigned)gx, (unsigned)B), dim3(FPW * 64), lds, (hipStream_t)stream, y, L,
                      ldy, n_fft, hop, T, (const float2*)twiddle, (const float2*)basis, n_filt, hull, (float2*)out,
@@ -952,7 +955,7 @@ extern "C" int syg_cqt_octave_gemm_f32(const float* y, int64_t B, int64_t L, int
   SYG_REQUIRE(T >= 1 && T <= 1 + L / hop, "cqt_octave_gemm: T=%lld exceeds the centred frame count %lld", (long long)T,
               (long long)(1 + L / hop));
   SYG_REQUIRE(n_filt >= 1 && n_filt <= 64, "cqt_octave_gemm: n_filt must be in [1, 64]");
-  SYG_REQUIRE(row0 >= 0 && out_bstride >= (int64_t)(row0 + n_filt) * T, "cqt_octave_gemm: output rows out of range");
+  SYG_REQUIRE(row0 >= 0 && out_bstride >= ((int64_t)row0 + n_filt) * T, "cqt_octave_gemm: output rows out of range");
   const int n_rowtiles = (2 * n_filt + 15) / 16;
   const int64_t ntiles = (T + 15) / 16;
   // two row tiles per wave when they come in pairs and the operands fit the registers (n_fft <= 256: 128 + 64 VGPRs)
@@ -986,7 +989,7 @@ extern "C" int syg_cqt_octave_bf16x3_f32(const float* y, int64_t B, int64_t L, i
   SYG_REQUIRE(T >= 1 && T <= 1 + L / hop, "cqt_octave_bf16x3: T=%lld exceeds the centred frame count %lld", (long long)T,
               (long long)(1 + L / hop));
   SYG_REQUIRE(n_filt >= 1 && n_filt <= 16, "cqt_octave_bf16x3: n_filt must be in [1, 16] (two 16-row tiles)");
-  SYG_REQUIRE(row0 >= 0 && out_bstride >= (int64_t)(row0 + n_filt) * T, "cqt_octave_bf16x3: output rows out of range");
+  SYG_REQUIRE(row0 >= 0 && out_bstride >= ((int64_t)row0 + n_filt) * T, "cqt_octave_bf16x3: output rows out of range");
   SYG_REQUIRE(((uintptr_t)gsplit) % 16 == 0, "cqt_octave_bf16x3: operand table must be 16-byte aligned");
   const int rt = (2 * n_filt + 15) / 16;
   const int64_t ntiles = (T + 15) / 16;

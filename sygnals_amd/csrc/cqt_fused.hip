@@ -527,7 +527,8 @@ using namespace syg;
 // y [B, L] -> out [B, n_bins, T] complex (interleaved float pairs; octave o fills rows row0[o] .. row0[o] + n_filt - 1),
 // the transform cqt.hip's kernels compute level by level -- one early decimation, then octave o = 0 .. n_oct - 1 at frame
 // length 256 and hop 256 >> o on the signal decimated o + 1 times, every octave with the operand table `gsplit`
-// (sygnals_amd.ops.cqt_pack_bf16x3: [3][2][8][64] 16-byte entries) -- in one launch.  taps: the 41-tap half-band
+// (sygnals_amd.ops.cqt_fused_table: ALWAYS [3 terms][2 row tiles][8 steps][64 lanes] 16-byte entries, 48 KiB, the second tile zero
+// when n_filt <= 8: the multiplying waves index it so whatever n_filt is) -- in one launch.  taps: the 41-tap half-band
 // decimator (zero at the even offsets from its centre, symmetric), scale: sqrt(2).  T: at most the smallest centred frame count over the octaves.
 extern "C" int syg_cqt_fused_f32(const float* y, int64_t B, int64_t L, int64_t ldy, const float* taps, int ntaps, float scale,
                                  const void* gsplit, int n_filt, int n_oct, const int32_t* row0_host, int64_t T, float* out,
@@ -551,7 +552,7 @@ extern "C" int syg_cqt_fused_f32(const float* y, int64_t B, int64_t L, int64_t l
   memset(&P, 0, sizeof(P));
   for (int o = 0; o < n_oct; ++o) {
     P.row0[o] = row0_host[o];
-    SYG_REQUIRE(P.row0[o] >= 0 && out_bstride >= (int64_t)(P.row0[o] + n_filt) * T, "cqt_fused: output rows out of range");
+    SYG_REQUIRE(P.row0[o] >= 0 && out_bstride >= ((int64_t)P.row0[o] + n_filt) * T, "cqt_fused: output rows out of range");
   }
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;

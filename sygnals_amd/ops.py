@@ -1517,17 +1517,18 @@ def _bf16_rne(x32: np.ndarray) -> np.ndarray:
     return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
 
 
-def cqt_pack_bf16x3(basis: np.ndarray, n_fft: int) -> np.ndarray:
+def cqt_pack_bf16x3(basis: np.ndarray, n_fft: int, row_tiles: Optional[int] = None) -> np.ndarray:
     """Operand table of syg_cqt_octave_bf16x3_f32: float32(G) (cqt_pack_gemm's matrix) split into three bfloat16 terms
     hi + mid + lo (hi = bf16(g), mid = bf16(g - hi), lo = bf16(g - hi - mid); the two differences are exact in
     float32), packed uint16 [3][row tile][n_fft / 32][64 lanes][8]: entry (p, mt, s, lane, j) = term p of
-    G[32 s + 8 (lane >> 4) + j][16 mt + (lane & 15)]."""
+    G[32 s + 8 (lane >> 4) + j][16 mt + (lane & 15)].  Row tiles: (2 n_filt + 15) // 16 -- ONE for eight filters or
+    fewer, which is what the level-by-level kernels index -- or `row_tiles` if that is more (the added tiles are zero)."""
     basis = np.asarray(basis, dtype=np.complex128)
     nf, F = basis.shape
     k = np.arange(F)[:, None]
     n = np.arange(n_fft)[None, :]
     g = basis @ np.exp(-2j * np.pi * ((k * n) % n_fft) / n_fft)
-    ntile = (2 * nf + 15) // 16
+    ntile = max((2 * nf + 15) // 16, int(row_tiles or 0))
     G = np.zeros((n_fft, 16 * ntile), dtype=np.float32)
     G[:, 0:2 * nf:2] = g.real.T
     G[:, 1:2 * nf:2] = g.imag.T
@@ -1547,6 +1548,15 @@ def cqt_pack_bf16x3(basis: np.ndarray, n_fft: int) -> np.ndarray:
                 for j in range(8):
                     out[p, mt, s_, :, j] = term[32 * s_ + 8 * (lane >> 4) + j, 16 * mt + (lane & 15)]
     return np.ascontiguousarray(out)
+
+
+def cqt_fused_table(basis: np.ndarray) -> np.ndarray:
+    """Operand table of syg_cqt_fused_f32 for the octaves' common basis [n_filt <= 16, 129]: cqt_pack_bf16x3 at frame length
+    256 with ALWAYS two row tiles, uint16 [3][2][8][64][8] -- the kernel's waves index it as [term][tile][step][lane]
+    whatever n_filt is (the second tile is zero for eight filters or fewer; its rows are never stored)."""
+    tab = cqt_pack_bf16x3(basis, 256, row_tiles=2)
+    assert tab.shape == (3, 2, 8, 64, 8), tab.shape
+    return tab
 
 
 def decimate2(x: torch.Tensor, taps: torch.Tensor, scale: float) -> torch.Tensor:
@@ -1595,14 +1605,19 @@ def decimate2_chain(x: torch.Tensor, taps: torch.Tensor, scale: float, levels: i
 
 def cqt(y: torch.Tensor, sr: float, hop_length: int = 512, fmin=None, n_bins: int = 84, bins_per_octave: int = 12,
         tuning: float = 0.0, filter_scale: float = 1.0, sparsity: float = 0.01) -> torch.Tensor:
-    """Constant-Q transform of y [B, L] -> complex [B, n_bins, T, 2] float32, T = 1 + L // hop_length."""
-    from ._cqt import CqtPlan, decimation_taps
+    """Constant-Q transform of y [B, L] -> complex [B, n_bins, T, 2] float32, T = 1 + L // hop_length.
+    Every octave runs on the entry point _cqt.cqt_route names: frame lengths 128 / 256 with <= 16 filters on the bfloat16-split
+    matrix form (or, for the usual shape, the whole transform in one launch), 128 / 256 / 512 with <= 64 filters on the fp32
+    matrix form, anything else up to frame length 1024 on rfft x sparse rows in groups of 24 filters; a combination of
+    bins_per_octave and filter_scale whose octaves need a longer frame raises ValueError before anything is launched."""
+    from ._cqt import CqtPlan, RFFT_MAXFILT, bf16x3_takes, cqt_route, decimation_taps, gemm_takes
     require_gpu()
     key = ("cqt", float(sr), int(hop_length), None if fmin is None else float(fmin), int(n_bins), int(bins_per_octave),
            float(tuning), float(filter_scale), float(sparsity))
 
     def build():
         p = CqtPlan(sr, hop_length, fmin, n_bins, bins_per_octave, tuning, filter_scale, sparsity)
+        cqt_route(p, "fft", False)      # an octave frame no kernel takes (> 1024 samples) is refused here, in every mode
         for o in p.octaves:
             b = o["basis"]
             b32 = np.stack([b.real, b.imag], axis=-1).astype(np.float32)
@@ -1610,17 +1625,32 @@ def cqt(y: torch.Tensor, sr: float, hop_length: int = 512, fmin=None, n_bins: in
             nz = (b32[..., 0] != 0) | (b32[..., 1] != 0)          # librosa's sparsified basis: a short run per row
             k0 = np.array([int(np.argmax(r)) if r.any() else 0 for r in nz], dtype=np.int32)
             k1 = np.array([int(len(r) - np.argmax(r[::-1])) if r.any() else 0 for r in nz], dtype=np.int32)
-            o["hull"] = np.ascontiguousarray(np.concatenate([k0, k1 - k0]).astype(np.int32))
-            o["gpacked_dev"] = _dev(cqt_pack_gemm(b, o["n_fft"])) if o["n_fft"] in (128, 256, 512) and len(b) <= 64 else None
+            hull = np.ascontiguousarray(np.concatenate([k0, k1 - k0]).astype(np.int32))
+            # syg_cqt_octave_f32 takes RFFT_MAXFILT filters a call: (first filter, count, hull of the group)
+            o["fft_groups"] = [(g, min(RFFT_MAXFILT, len(b) - g),
+                                np.ascontiguousarray(hull.reshape(2, -1)[:, g:g + RFFT_MAXFILT].ravel()))
+                               for g in range(0, len(b), RFFT_MAXFILT)]
+            o["gpacked_dev"] = _dev(cqt_pack_gemm(b, o["n_fft"])) if gemm_takes(o["n_fft"], len(b)) else None
             o["gsplit_dev"] = (torch.from_numpy(cqt_pack_bf16x3(b, o["n_fft"]).view(np.int16)).to(require_gpu())
-                               if o["n_fft"] in (128, 256) and len(b) <= 16 else None)
+                               if bf16x3_takes(o["n_fft"], len(b)) else None)
         p.taps_dev = _dev(decimation_taps().astype(np.float32))
-        # the one-launch form (syg_cqt_fused_f32) where the plan has its shape (CqtPlan.one_launch_shape)
+        # the one-launch form (syg_cqt_fused_f32) where the plan has its shape (CqtPlan.one_launch_shape): its table always
+        # has two row tiles (cqt_fused_table), so eight filters or fewer do not share octave 0's one-tile table
         oc = p.octaves
-        p.fused_ok = p.one_launch_shape() and oc[0].get("gsplit_dev") is not None
+        p.fused_tab_dev = None
+        if p.one_launch_shape():
+            p.fused_tab_dev = (oc[0]["gsplit_dev"] if oc[0]["n"] > 8 else
+                               torch.from_numpy(cqt_fused_table(oc[0]["basis"]).view(np.int16)).to(require_gpu()))
+            assert p.fused_tab_dev.numel() == 3 * 2 * 8 * 64 * 8
         p.row0 = np.ascontiguousarray([o["row0"] for o in oc], dtype=np.int32)
+        p.routes = {}
         return p
     plan = _cached(key, build)
+    # which entry point each octave runs on (_cqt.cqt_route: raises here, before any launch, for an octave nothing serves)
+    rkey = (settings.cqt_mode, bool(settings.cqt_fused))
+    if rkey not in plan.routes:
+        plan.routes[rkey] = cqt_route(plan, *rkey)
+    one_launch, route = plan.routes[rkey]
     if y.stride(1) != 1:
         y = y.contiguous()
     B, L = y.shape
@@ -1637,17 +1667,15 @@ def cqt(y: torch.Tensor, sr: float, hop_length: int = 512, fmin=None, n_bins: in
             Lc = (Lc + 1) // 2
     out = torch.empty((B, plan.n_bins, Tn, 2), dtype=torch.float32, device=y.device)      # every row is written
     s2 = float(np.sqrt(2.0))
-    if settings.cqt_fused and settings.cqt_mode == "bf16x3" and plan.fused_ok and Tn >= 1:
+    if one_launch:
         rc = lib().syg_cqt_fused_f32(_ptr(y), B, L, _ld(y), _ptr(plan.taps_dev), plan.taps_dev.numel(), s2,
-                                     _ptr(plan.octaves[0]["gsplit_dev"]), plan.octaves[0]["n"], len(plan.octaves),
+                                     _ptr(plan.fused_tab_dev), plan.octaves[0]["n"], len(plan.octaves),
                                      plan.row0.ctypes.data_as(C.c_void_p), Tn, _ptr(out), plan.n_bins * Tn,
                                      C.c_void_p(_stream_ptr()))
         check(rc, "syg_cqt_fused_f32")
         return out
-    # octave kernel: "bf16x3" (default: the framed product with bfloat16-split operands, fp32-equivalent), "gemm" (the
-    # single-instruction fp32 MFMA form), "fft" (rfft x sparse rows; also what other frame lengths take)
-    mode = settings.cqt_mode
-    use_gemm = mode != "fft"
+    # octave kernel (route): "bf16x3" (default: the framed product with bfloat16-split operands, fp32-equivalent), "gemm"
+    # (the single-instruction fp32 MFMA form), "fft" (rfft x sparse rows; also what other frame lengths take)
     # settings.cqt_streams = 2: the decimation chain (memory-bound) on the caller's stream, the octave products
     # (matrix-core bound, no LDS) on a side stream, so that octave i runs beside the decimation towards octave i + 1.
     # Measured on one 1-hour stream: 1.03 ms against 1.05 ms on one stream -- the two kernels slow each other down by
@@ -1672,27 +1700,29 @@ def cqt(y: torch.Tensor, sr: float, hop_length: int = 512, fmin=None, n_bins: in
         for _ in range(plan.early):
             cur = decimate2(cur, plan.taps_dev, s2)
     for oi, o in enumerate(plan.octaves):
-        if o["n"] > 0:
+        entry = route[oi][0]
+        if entry is not None:
             if two:
                 ev = torch.cuda.Event()
                 ev.record(main)                   # `cur` has been produced on the main stream
                 side.wait_event(ev)
                 cur.record_stream(side)
             sp = C.c_void_p(side.cuda_stream)
-            if mode == "bf16x3" and o.get("gsplit_dev") is not None:
+            if entry == "syg_cqt_octave_bf16x3_f32":
                 rc = lib().syg_cqt_octave_bf16x3_f32(_ptr(cur), B, cur.shape[1], _ld(cur), o["n_fft"], o["hop"], Tn,
                                                      _ptr(o["gsplit_dev"]), o["n"], _ptr(out), plan.n_bins * Tn, o["row0"], sp)
-                check(rc, "syg_cqt_octave_bf16x3_f32")
-            elif use_gemm and o.get("gpacked_dev") is not None:
+                check(rc, entry)
+            elif entry == "syg_cqt_octave_gemm_f32":
                 rc = lib().syg_cqt_octave_gemm_f32(_ptr(cur), B, cur.shape[1], _ld(cur), o["n_fft"], o["hop"], Tn,
                                                    _ptr(o["gpacked_dev"]), o["n"], _ptr(out), plan.n_bins * Tn, o["row0"], sp)
-                check(rc, "syg_cqt_octave_gemm_f32")
+                check(rc, entry)
             else:
-                rc = lib().syg_cqt_octave_f32(_ptr(cur), B, cur.shape[1], _ld(cur), o["n_fft"], o["hop"], Tn,
-                                              _ptr(twiddle_rfft_dev(o["n_fft"])), _ptr(o["basis_dev"]), o["n"],
-                                              o["hull"].ctypes.data_as(C.c_void_p), _ptr(out),
-                                              plan.n_bins * Tn, o["row0"], sp)
-                check(rc, "syg_cqt_octave_f32")
+                for g0, ng, hull in o["fft_groups"]:
+                    rc = lib().syg_cqt_octave_f32(_ptr(cur), B, cur.shape[1], _ld(cur), o["n_fft"], o["hop"], Tn,
+                                                  _ptr(twiddle_rfft_dev(o["n_fft"])), _ptr(o["basis_dev"][g0:g0 + ng]), ng,
+                                                  hull.ctypes.data_as(C.c_void_p), _ptr(out),
+                                                  plan.n_bins * Tn, o["row0"] + g0, sp)
+                    check(rc, entry)
         if o["decimate_after"] and oi + 1 < len(plan.octaves):
             lvl += 1
             cur = levels[lvl] if chain else decimate2(cur, plan.taps_dev, s2)

@@ -10,6 +10,7 @@ from numpy.testing import assert_allclose, assert_array_equal
 
 from oracle import cpu_ref as O
 from sygnals_amd import _tables as T
+from tests.cqt_cases import CASES as CQT_CASES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -278,6 +279,132 @@ def test_cqt_plan_matches_oracle(sr, hop, n_bins):
         CqtPlan(8000)
     with pytest.raises(ValueError, match="multiple of 2"):
         CqtPlan(48000, hop_length=48)
+
+
+def _cqt_plan_pair(c):
+    from sygnals_amd._cqt import CqtPlan
+    p = CqtPlan(c.sr, c.hop, c.fmin, c.n_bins, c.bpo, c.tuning, c.filter_scale, c.sparsity)
+    q = O.cqt_plan(c.sr, c.hop, c.fmin, c.n_bins, c.bpo, c.filter_scale, c.sparsity, tuning=c.tuning)
+    return p, q
+
+
+@pytest.mark.parametrize("case", sorted(CQT_CASES))
+def test_cqt_plan_matches_oracle_across_parameters(case):
+    """The host plan against the oracle's over the parameter table of tests/cqt_cases.py (bins per octave 1 ... 36, filter
+    scale 0.25 ... 2, tuning, sparsity 0, clipped lowest octaves, hops with few or no factors of two): early decimations,
+    per octave frame length, hop, first row, row count and the basis with every scaling folded in."""
+    from tests.cqt_cases import CASES, ROUTES
+    c = CASES[case]
+    p, q = _cqt_plan_pair(c)
+    assert p.early == q["early"] == ROUTES[case][1] and len(p.octaves) == len(q["octaves"])
+    assert_allclose(p.freqs, O.cqt_frequencies(c.n_bins, c.fmin or O.note_c1_hz(), c.bpo, c.tuning), rtol=1e-15)
+    end = c.n_bins
+    for a, b in zip(p.octaves, q["octaves"]):
+        nb = b["basis"].shape[0]
+        rows = np.arange(max(end - nb, 0), end)
+        assert len(rows) == nb                  # (the oracle's slice of the frequencies clips the lowest octave itself)
+        ref = b["basis"] * q["scale"][rows][:, None]
+        assert a["n_fft"] == b["n_fft"] and a["hop"] == b["hop"] and a["row0"] == rows[0] and a["n"] == len(rows)
+        assert a["basis"].shape == ref.shape
+        assert_allclose(a["basis"], ref, rtol=1e-12, atol=1e-15)
+        end -= nb
+    assert end == 0
+
+
+def test_cqt_oracle_tuning_is_a_shift_of_fmin():
+    """oracle.cpu_ref.cqt(tuning=t) is librosa's rule fmin * 2 ** (t / bins_per_octave): the same numbers as the shifted fmin,
+    and not the untuned transform."""
+    rng = np.random.default_rng(3)
+    y = rng.standard_normal(6000)
+    for bpo, t in ((12, 0.37), (24, -0.5)):
+        a = O.cqt(y, 48000, n_bins=3 * bpo, bins_per_octave=bpo, fmin=440.0, tuning=t)
+        b = O.cqt(y, 48000, n_bins=3 * bpo, bins_per_octave=bpo, fmin=440.0 * 2.0 ** (t / bpo))
+        assert_allclose(a, b, rtol=1e-12, atol=1e-15 * np.abs(b).max())
+        assert np.abs(a - O.cqt(y, 48000, n_bins=3 * bpo, bins_per_octave=bpo, fmin=440.0)).max() > 1e-3 * np.abs(b).max()
+
+
+@pytest.mark.parametrize("case", sorted(CQT_CASES))
+def test_cqt_route_is_pinned(case):
+    """Which entry point every octave runs on (sygnals_amd._cqt.cqt_route, the function ops.cqt launches from), for every
+    row of the table and the three modes: this is what the coverage claims of tests/test_gpu_cqt_params.py rest on."""
+    from sygnals_amd._cqt import CqtPlan, cqt_route
+    from tests.cqt_cases import CASES, MODES, ROUTES
+    c = CASES[case]
+    p = CqtPlan(c.sr, c.hop, c.fmin, c.n_bins, c.bpo, c.tuning, c.filter_scale, c.sparsity)
+    one, early, *per_mode = ROUTES[case]
+    assert p.one_launch_shape() == one
+    for mode, want in zip(MODES, per_mode):
+        assert cqt_route(p, mode, fused=False) == (False, want), mode
+        if one and mode == "bf16x3":
+            assert cqt_route(p, mode, fused=True) == (True, [("syg_cqt_fused_f32", 256, p.octaves[0]["n"], 2)])
+        else:
+            assert cqt_route(p, mode, fused=True) == (False, want), mode
+    with pytest.raises(ValueError, match="cqt_mode"):
+        cqt_route(p, "fp64")
+
+
+def test_cqt_route_covers_every_instantiation():
+    """The table reaches every instantiation of the three octave kernels that the entry points can launch: frame length x
+    (one | paired row tiles), odd tile counts, row groups of the rfft form, and the one-launch form at 8, 12 and 16 filters."""
+    from tests.cqt_cases import ROUTES
+    seen, fused = set(), set()
+    for case, (one, early, *per_mode) in ROUTES.items():
+        for calls in per_mode:
+            for entry, n_fft, n, tiles in calls:
+                kind = entry[len("syg_cqt_octave_"):-len("_f32")] if entry != "syg_cqt_octave_f32" else "rfft"
+                paired = {"bf16x3": tiles == 2, "gemm": tiles % 2 == 0 and n_fft <= 256, "rfft": False}[kind]
+                seen.add((kind, n_fft, 2 if paired else 1))
+                if kind != "rfft":
+                    seen.add((kind, "tiles", tiles))
+                else:
+                    seen.add((kind, "groups", tiles))
+        if one:
+            fused.add(per_mode[0][0][2])
+    assert {("bf16x3", n, r) for n in (128, 256) for r in (1, 2)} <= seen
+    assert {("gemm", n, r) for n in (128, 256) for r in (1, 2)} | {("gemm", 512, 1)} <= seen
+    assert {("gemm", "tiles", t) for t in (1, 2, 3, 5)} <= seen
+    assert {("rfft", n, 1) for n in (32, 64, 128, 256, 512, 1024)} | {("rfft", "groups", 2)} <= seen
+    assert fused == {8, 12, 16}
+
+
+def test_cqt_route_refuses_what_no_kernel_serves():
+    """An octave that only the rfft form could take, with a frame longer than its 1024 samples (eight transforms of a
+    workgroup no longer fit the LDS), is refused by the routing -- before ops.cqt launches anything -- in words that name
+    the parameters; 36 bins per octave at filter scale 1 (frame length 1024, 36 filters) is served in two row groups."""
+    from sygnals_amd._cqt import CqtPlan, cqt_route
+    for kw in (dict(n_bins=252, bins_per_octave=36, filter_scale=2.0), dict(n_bins=336, bins_per_octave=48, filter_scale=2.0)):
+        p = CqtPlan(48000, 512, None, **kw)
+        assert p.octaves[0]["n_fft"] == 2048
+        for mode in ("bf16x3", "gemm", "fft"):
+            with pytest.raises(ValueError, match=r"bins_per_octave=\d+ with filter_scale=\S+ needs an octave frame length of 2048"):
+                cqt_route(p, mode)
+    p = CqtPlan(48000, 512, None, 252, 36)
+    assert cqt_route(p)[1] == 7 * [("syg_cqt_octave_f32", 1024, 36, 2)]
+
+
+@pytest.mark.parametrize("n_filt", [1, 8, 9, 12, 16])
+def test_cqt_one_launch_table_always_has_two_row_tiles(n_filt):
+    """cqt_fused_kernel indexes its operands as [3 terms][2 row tiles][8 steps][64 lanes] 16-byte entries whatever n_filt is
+    (cqt_fused.hip: gsplit[((p * 2 + rt) * 8 + ss) * 64 + lane]), so the table ops.cqt hands to syg_cqt_fused_f32 has
+    3 * 2 * 8 * 64 * 8 16-bit words for every filter count the entry accepts.  (The level-by-level table of eight filters
+    or fewer has ONE row tile, half of that: sharing it made the one-launch kernel read the `lo` term for `mid` and 24 KiB
+    past the end.)  The first tile equals the level-by-level table; a second tile that holds no filter is zero."""
+    from sygnals_amd import ops
+    from sygnals_amd._cqt import CqtPlan
+    basis = CqtPlan(48000, 512, None, 112, 16, filter_scale=0.5).octaves[0]["basis"][:n_filt]
+    assert basis.shape == (n_filt, 129)
+    tab = ops.cqt_fused_table(basis)
+    assert tab.dtype == np.uint16 and tab.size == 3 * 2 * 8 * 64 * 8 and tab.shape == (3, 2, 8, 64, 8)
+    level = ops.cqt_pack_bf16x3(basis, 256)
+    assert level.shape == (3, 1 if n_filt <= 8 else 2, 8, 64, 8)
+    assert_array_equal(tab[:, :level.shape[1]], level)
+    if n_filt <= 8:
+        assert not tab[:, 1].any()
+    # rows past 2 n_filt are zero in every term (the kernel multiplies them; it never stores them)
+    lane_row = np.arange(64) & 15
+    for mt in range(2):
+        dead = 16 * mt + lane_row >= 2 * n_filt
+        assert not tab[:, mt][:, :, dead].any()
 
 
 def test_wave_fft_index_model_is_exact_and_conflict_free():
