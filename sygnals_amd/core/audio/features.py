@@ -312,8 +312,17 @@ def onset_strength_batch(y, sr: int, n_fft: int = 2048, hop_length: int = 512, n
     from ..features import manager as M               # inside the function: the manager imports this package's users
     y = _as_clips(y)
     mel = M.mel_power_batch(y, sr, n_fft, hop_length, center, "hann", n_mels, fmin, fmax)
+    if not isinstance(lag, (int, np.integer)) or lag < 1:
+        raise ValueError("lag must be a positive integer")
+    if not isinstance(max_size, (int, np.integer)) or max_size < 1:
+        raise ValueError("max_size must be a positive integer")
     pad = lag + (n_fft // (2 * hop_length) if center else 0)
-    T_out = mel.shape[2] if center else None
+    Tn = mel.shape[2]
+    if Tn <= lag:
+        # no frame has a frame `lag` before it: the flux is empty and librosa returns its padding alone (the C entry
+        # refuses lag >= T, so the mirror answers before the call)
+        return ops.torch.zeros((mel.shape[0], Tn if center else pad), dtype=ops.torch.float32, device=mel.device)
+    T_out = Tn if center else None
     return ops.onset_strength(mel, lag, max_size, pad, T_out, detrend=detrend)
 
 

@@ -5,8 +5,9 @@
 //
 // Strength (onset_flux_kernel): a workgroup owns one clip, or a slice of 256 output frames of a long clip.  It takes the
 // clip's largest mel power (its own pass over the clip, or the partial maxima of onset_max_kernel), which fixes the
-// top_db floor, then forms d[t] = mean_m max(0, S[m, t + lag] - ref[m, t]) with the dB conversion and the clip applied to
-// the powers as they are loaded: the dB matrix never exists in memory.  power_to_db is monotone, so the running maximum
+// top_db floor, then forms d[t] = mean_m max(0, S[m, t + lag] - ref[m, t]) with the clip applied to the powers as they
+// are loaded and each rise taken as 10 log10 of the ratio of the two clipped powers: the dB matrix never exists in
+// memory, and no two rounded dB values are subtracted.  power_to_db is monotone, so the running maximum
 // of the "superflux" reference (max_size > 1) is taken on the powers and converted once; scipy's reflected edges only
 // repeat values the clipped window already holds.  A lane owns a frame (loads run along T, coalesced); the four waves
 // own a quarter of the mel rows each, summed in row order, and the four partial sums are combined in a fixed order:
@@ -86,9 +87,28 @@ __global__ __launch_bounds__(FT) void onset_flux_kernel(FluxArgs A) {
   }
   mx = block_max4(mx, red, tid);
   const float amin = A.amin;
-  // log_spec.max() - top_db with ref = 1.0 (the same expressions as logmel_dct_kernel)
-  const float flo = (A.top_db >= 0.f) ? SYG_DB_PER_LOG2 * syg_log2(fmaxf(amin, mx)) - A.top_db : -3.4e38f;
-  auto db = [&](float x) { return fmaxf(SYG_DB_PER_LOG2 * syg_log2(fmaxf(amin, x)), flo); };
+  // The top_db floor as a POWER, max(amin, mx) 10^(-top_db / 10), held as fhi (1 + flo_rel ln 2) (float64, once a
+  // thread): the clip to it is the dB clip, power_to_db being monotone.  A rise S[a] - S[b] is then 10 log10 of one
+  // ratio, not the difference of two rounded dB values of some tens: r = a / b, its residual by one fma, log2 of the two
+  // together.  Its error is relative to the rise itself, and the envelope sums rises that are all >= 0, so the error of
+  // a frame is relative to that frame however small it is next to the dB values.
+  const double fd = (A.top_db >= 0.f) ? (double)fmaxf(amin, mx) * exp2(-(double)A.top_db / (double)SYG_DB_PER_LOG2) : 0.0;
+  const float fhi = (float)fd;
+  const float flo_rel = fhi > 0.f ? (float)((fd - (double)fhi) / (double)fhi * 1.4426950408889634) : 0.f;
+  auto rise = [&](float xa, float xb) {
+    xa = fmaxf(amin, xa); xb = fmaxf(amin, xb);
+    // floored: at or below the exact floor (fhi itself is below it only when the remainder is positive)
+    const bool fa = xa < fhi || (xa == fhi && flo_rel > 0.f), fb = xb < fhi || (xb == fhi && flo_rel > 0.f);
+    const float a = fa ? fhi : xa, b = fb ? fhi : xb;
+    const float r = a * __builtin_amdgcn_rcpf(b);
+    if (!(r > 0x1p-40f && r < 0x1p40f))          // ratio or reciprocal out of range (an amin far below 1e-30)
+      return fmaxf(0.f, SYG_DB_PER_LOG2 * (syg_log2(a) - syg_log2(b)));
+    const float e = fmaf(-r, b, a);              // a - r b exactly: a / b = r (1 + e / a)
+    float l = syg_log2(r) + 1.44269504f * (e * __builtin_amdgcn_rcpf(a));
+    l += fa ? flo_rel : 0.f;
+    l -= fb ? flo_rel : 0.f;
+    return fmaxf(0.f, SYG_DB_PER_LOG2 * l);
+  };
   const int m0 = (w * M) / 4, m1 = ((w + 1) * M) / 4;
   const int k = A.max_size, h = k / 2, lag = A.lag;
   const int64_t j0 = OWN_MAX ? 0 : s * FSL, j1 = OWN_MAX ? A.T_out : min(j0 + FSL, A.T_out);
@@ -101,14 +121,14 @@ __global__ __launch_bounds__(FT) void onset_flux_kernel(FluxArgs A) {
       if (k == 1) {
         for (int m = m0; m < m1; ++m) {
           const float* row = P + (int64_t)m * T + t;
-          acc += fmaxf(0.f, db(row[lag]) - db(row[0]));
+          acc += rise(row[lag], row[0]);
         }
       } else {
         for (int m = m0; m < m1; ++m) {
           const int lo = max(0, m - h), hi = min(M - 1, m - h + k - 1);
           float r = P[(int64_t)lo * T + t];
           for (int q = lo + 1; q <= hi; ++q) r = fmaxf(r, P[(int64_t)q * T + t]);
-          acc += fmaxf(0.f, db(P[(int64_t)m * T + t + lag]) - db(r));
+          acc += rise(P[(int64_t)m * T + t + lag], r);
         }
       }
     }

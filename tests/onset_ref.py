@@ -26,7 +26,7 @@ def onset_strength_from_db(S, n_fft=2048, hop_length=512, lag=1, max_size=1, cen
         raise ValueError("max_size must be a positive integer")
     T = S.shape[1]
     ref = S if max_size == 1 else scipy.ndimage.maximum_filter1d(S, max_size, axis=0)
-    d = np.mean(np.maximum(0.0, S[:, lag:] - ref[:, :T - lag]), axis=0)
+    d = np.mean(np.maximum(0.0, S[:, lag:] - ref[:, :max(T - lag, 0)]), axis=0)     # (librosa: ref[..., :-lag])
     pad = lag + (n_fft // (2 * hop_length) if center else 0)
     env = np.concatenate([np.zeros(pad), d])
     if detrend:
@@ -262,3 +262,36 @@ def silence_unsure(rms, threshold_db):
     rms = np.asarray(rms, dtype=np.float64)
     thr = rms.max() * 10.0 ** (threshold_db / 20.0)
     return np.abs(rms - thr) <= 10 * TOL * thr
+
+
+# ---------------------------------------------------------------------------- what the parameter sweep adds
+def flux_envelope(S, lag=1, max_size=1, pad=0, T_out=None, detrend=False):
+    """The envelope as syg_onset_strength_f32 states it: `pad` zeros in front of the flux of the dB matrix S [M, T], detrended
+    when asked, cut to T_out frames (default: uncut, pad + T - lag).  onset_strength_from_db is this with
+    pad = lag + n_fft // (2 hop), T_out = T (centre) and with pad = lag, uncut (no centre)."""
+    S = np.asarray(S, dtype=np.float64)
+    d = onset_strength_from_db(S, lag=lag, max_size=max_size, center=False)[lag:]
+    env = np.concatenate([np.zeros(pad), d])
+    if detrend:
+        env = scipy.signal.lfilter([1.0, -1.0], [1.0, -0.99], env)
+    return env if T_out is None else env[:T_out]
+
+
+def e2e_reference_with(sr, hop, Y, backtrack_=False, **peak):
+    """e2e_reference with peak_pick arguments other than the defaults (and backtracking): per clip (onset frames, unsure
+    mask at 10 * TOL).  Backtracking moves onsets that are already decided, so the unsure rule is the same."""
+    out = []
+    pk = default_windows(sr, hop)
+    pk.update(peak)
+    for y in Y:
+        env = onset_strength(y, sr, hop_length=hop)
+        on = onset_detect(onset_envelope=env, sr=sr, hop_length=hop, backtrack_=backtrack_, **peak)
+        un = unsure_frames(normalize(env), pk["pre_max"], pk["post_max"], pk["pre_avg"], pk["post_avg"], pk["delta"],
+                           10 * TOL) if env.any() else np.zeros(len(env), dtype=bool)
+        out.append((on, un))
+    return out
+
+
+def peak_margin(pre_avg, post_avg):
+    """The margin of the peaks-alone tests: (W + 4) 2^-24 for a mean window of W frames."""
+    return (pre_avg + post_avg + 4) * 2.0 ** -24
