@@ -50,12 +50,15 @@ const char* syg_last_error(void);
  *   SYG_OPT_SOS_CLIP      1 (default) | 0: clip-resident form of syg_sosfiltfilt_f32 / the chunked form only
  *   SYG_OPT_CQT_STAGED    -1 (default: where it pays) | 0 (never) | 1 | 2 (also at hop = n_fft / 2): staged form of
  *                         syg_cqt_octave_bf16x3_f32
+ *   SYG_OPT_DWT_FORM      1 (default: the clip-resident kernels wherever a row fits) | 0: syg_dwt_f32 / syg_idwt_f32 run
+ *                         one launch per level with the approximations through the workspace
  * syg_set_option returns SYG_OK or SYG_E_INVALID (unknown key / value out of range); syg_get_option the current value. */
 #define SYG_OPT_RESERVED_CUS 0
 #define SYG_OPT_STFT_LOAD 1
 #define SYG_OPT_SOS_CLIP 2
 #define SYG_OPT_CQT_STAGED 3
-#define SYG_OPT_COUNT 4
+#define SYG_OPT_DWT_FORM 4
+#define SYG_OPT_COUNT 5
 int syg_set_option(int key, int value);
 int syg_get_option(int key);
 
@@ -664,6 +667,46 @@ int syg_affine_cols_f32(const float* x, int64_t n, int64_t F, const double* sub,
                         float* out, void* stream);
 int syg_col_quantiles_f32(const float* x, int64_t n, int64_t F, const double* q, int nq, double* out, void* stream);
 int syg_zoom_f32(const float* img, int H, int W, int H2, int W2, int order, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Discrete wavelet transform: pywt.wavedec / pywt.waverec (PyWavelets 1.x) as called at sygnals/core/transforms.py:74
+ * and :110, for orthogonal filter banks of F = 2 ... 20 taps (F even; sygnals_amd/_wavelets.py computes the Daubechies
+ * family) and the signal extension modes below.  One level of a length-N input gives (N + F - 1) / 2 coefficients:
+ *     cA[o] = sum_j dec_lo[j] ext(x)[2 o + 1 - j],  cD[o] likewise with dec_hi;
+ * one synthesis level of K pairs gives 2 K - F + 2 samples,
+ *     y[n] = sum_k a[k] rec_lo[n + F - 2 - 2 k] + d[k] rec_hi[n + F - 2 - 2 k].
+ * All arithmetic is float32, every sum a chain of fused multiply-adds in a fixed order.
+ *
+ *   syg_dwt_lengths      lens_host [levels + 1] (HOST) <- the wavedec order [cA_n, cD_n, ..., cD_1]; returns their sum
+ *                        (the packed row length), -1 on error
+ *   syg_dwt_fits         1: the clip-resident form (one workgroup a clip, all levels in one launch, the running
+ *                        approximation in LDS) takes rows of L samples; 0: the streaming form (one level a pass until
+ *                        the rest fits).  The rule: the first two approximations fit 160 KiB of LDS
+ *   syg_dwt_work_bytes   workspace of the streaming form (0 when the row is resident or levels = 1), -1 on error
+ *   syg_dwt_f32          x [B, L] (row stride ldx), dec_lo / dec_hi [F] float32 DEVICE arrays -> out [B, total] (row
+ *                        stride ldout): one packed row a clip, [cA_n | cD_n | ... | cD_1] with the lengths of
+ *                        syg_dwt_lengths
+ *   syg_idwt_length      output length that follows from lens_host (HOST, [levels + 1], the same order): at each level
+ *                        the approximation must be as long as the detail or one longer (its last sample is dropped, as
+ *                        pywt.waverec does), and a level needs at least F / 2 pairs; -1 on inconsistent lens
+ *   syg_idwt_work_bytes  workspace of syg_idwt_f32 for these lens (0 when every level is resident), -1 on error
+ *   syg_idwt_f32         coeffs [B, sum(lens)] (row stride ldc) in the packed layout, rec_lo / rec_hi [F] float32 DEVICE
+ *                        arrays -> y [B, syg_idwt_length] (row stride ldy)
+ * ------------------------------------------------------------------------------- */
+#define SYG_DWT_ZERO 0
+#define SYG_DWT_CONSTANT 1
+#define SYG_DWT_SYMMETRIC 2
+#define SYG_DWT_REFLECT 3
+#define SYG_DWT_PERIODIC 4
+int64_t syg_dwt_lengths(int64_t L, int F, int levels, int64_t* lens_host);
+int syg_dwt_fits(int64_t L, int F, int levels);
+int64_t syg_dwt_work_bytes(int64_t B, int64_t L, int F, int levels);
+int syg_dwt_f32(const float* x, int64_t B, int64_t L, int64_t ldx, const float* dec_lo, const float* dec_hi, int F,
+                int mode, int levels, float* out, int64_t ldout, void* work, void* stream);
+int64_t syg_idwt_length(const int64_t* lens_host, int levels, int F);
+int64_t syg_idwt_work_bytes(int64_t B, const int64_t* lens_host, int levels, int F);
+int syg_idwt_f32(const float* coeffs, int64_t B, int64_t ldc, const int64_t* lens_host, int levels, const float* rec_lo,
+                 const float* rec_hi, int F, float* y, int64_t ldy, void* work, void* stream);
 
 #ifdef __cplusplus
 }

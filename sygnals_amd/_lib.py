@@ -96,6 +96,13 @@ SIGNATURES = {
     "syg_onset_strength_f32": (_i, [_p, _l, _i, _l, _f, _f, _i, _i, _i, _l, _i, _p, _p, _p]),
     "syg_onset_peaks_f32": (_i, [_p, _l, _l, _l, _i, _i, _i, _i, _d, _i, _i, _i, _p, _p, _p, _p]),
     "syg_clip_metrics_f32": (_i, [_p, _l, _l, _l, _p, _p]),
+    "syg_dwt_lengths": (_l, [_l, _i, _i, _p]),
+    "syg_dwt_fits": (_i, [_l, _i, _i]),
+    "syg_dwt_work_bytes": (_l, [_l, _l, _i, _i]),
+    "syg_dwt_f32": (_i, [_p, _l, _l, _l, _p, _p, _i, _i, _i, _p, _l, _p, _p]),
+    "syg_idwt_length": (_l, [_p, _i, _i]),
+    "syg_idwt_work_bytes": (_l, [_l, _p, _i, _i]),
+    "syg_idwt_f32": (_i, [_p, _l, _l, _p, _i, _p, _p, _i, _p, _l, _p, _p]),
 }
 
 _lib = None

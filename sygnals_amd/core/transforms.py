@@ -1,12 +1,18 @@
-"""Device-backed mirror of the FFT-based part of sygnals/core/transforms.py: hilbert_transform :119-151.
+"""Device-backed mirror of sygnals/core/transforms.py: discrete_wavelet_transform :22-79,
+inverse_discrete_wavelet_transform :81-115 (pywt.wavedec / waverec: the Daubechies family haar, db1 ... db10 and the modes
+symmetric, reflect, periodic, constant and zero; sygnals_amd/_wavelets.py, csrc/dwt.hip) and hilbert_transform :119-151.
 
-The wavelet (PyWavelets) and numerical-Laplace functions of that module are outside the hot path.
+`dwt_batch` / `idwt_batch` are the batched forms that keep the coefficients on the device.  The numerical-Laplace
+function of that module is outside the hot path.
 """
 from __future__ import annotations
 
-import numpy as np
+from typing import List, Optional
 
-from .. import ops
+import numpy as np
+import torch
+
+from .. import _wavelets, ops
 from .dsp import _c128, analytic_batch
 
 
@@ -18,3 +24,47 @@ def hilbert_transform(data) -> np.ndarray:
     if data.size == 0:
         raise ValueError("N must be positive.")
     return _c128(analytic_batch(ops.to_device_f32(data[None, :])))[0].astype(np.complex128, copy=False)
+
+
+def dwt_batch(y: torch.Tensor, wavelet: str = "db4", level: Optional[int] = None, mode: str = "symmetric"):
+    """Multi-level DWT of every clip of y [B, L] (float32, on the device) -> (packed [B, total] device tensor, lens):
+    row b is [cA_n | cD_n | ... | cD_1] of clip b and `lens` the lengths of those arrays (ops.dwt)."""
+    return ops.dwt(y, wavelet, level, mode)
+
+
+def idwt_batch(packed: torch.Tensor, lens, wavelet: str = "db4", mode: str = "symmetric") -> torch.Tensor:
+    """Inverse of dwt_batch: packed [B, sum(lens)] -> [B, L'] on the device (ops.idwt)."""
+    return ops.idwt(packed, lens, wavelet, mode)
+
+
+def discrete_wavelet_transform(data, wavelet: str = "db4", level: Optional[int] = None,
+                               mode: str = "symmetric") -> List[np.ndarray]:
+    """pywt.wavedec: [cA_n, cD_n, ..., cD_1], float64 arrays."""
+    data = np.asarray(data)
+    if data.ndim != 1:
+        raise ValueError("Input data must be a 1D array.")
+    if data.size == 0:
+        raise ValueError("Input data must hold at least one sample.")
+    if level is None:
+        try:
+            level = max(1, _wavelets.dwt_max_level(data.size, _wavelets.filter_length(wavelet)))
+        except ValueError as e:
+            raise ValueError(f"Invalid wavelet name '{wavelet}' or error calculating max level.") from e
+    elif isinstance(level, bool) or not isinstance(level, int) or level < 1:
+        raise ValueError(f"Decomposition level must be an integer >= 1, got {level}.")
+    packed, lens = ops.dwt(ops.to_device_f32(data[None, :]), wavelet, level, mode)
+    row = packed[0].cpu().numpy().astype(np.float64)
+    return [c.copy() for c in np.split(row, np.cumsum(lens)[:-1])]
+
+
+def inverse_discrete_wavelet_transform(coeffs, wavelet: str, mode: str = "symmetric") -> np.ndarray:
+    """pywt.waverec of [cA_n, cD_n, ..., cD_1] -> float64 signal."""
+    if not isinstance(coeffs, list) or len(coeffs) < 2:
+        raise ValueError("Input 'coeffs' must be a list containing at least cA and cD coefficients.")
+    arrs = [np.asarray(c, dtype=np.float32) for c in coeffs]
+    if any(a.ndim != 1 for a in arrs):
+        raise ValueError("Every coefficient array must be 1D.")
+    lens = [a.size for a in arrs]
+    _wavelets.waverec_length(lens, _wavelets.filter_length(wavelet))         # refuses mismatched lengths before a copy
+    y = ops.idwt(ops.to_device_f32(np.concatenate(arrs)[None, :]), lens, wavelet, mode)
+    return y[0].cpu().numpy().astype(np.float64)

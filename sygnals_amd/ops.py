@@ -99,7 +99,7 @@ class _Settings:
       cqt_chain             True: up to three decimation levels per pass; False: one launch per level
       cqt_fused             True: the one-launch form (syg_cqt_fused_f32) where the plan has its shape; False: level by level
       one_launch_features   True: extract_features routes MFCC + statistics / contrast requests to the one-launch kernels
-    Options that live in the library (syg_set_option): reserved_cus, stft_load, sos_clip, cqt_staged."""
+    Options that live in the library (syg_set_option): reserved_cus, stft_load, sos_clip, cqt_staged, dwt_form."""
     waves = T.WAVES
     cqt_mode = "bf16x3"
     cqt_streams = 1
@@ -109,11 +109,11 @@ class _Settings:
 
 
 settings = _Settings()
-_LIB_OPTIONS = {"reserved_cus": 0, "stft_load": 1, "sos_clip": 2, "cqt_staged": 3}      # SYG_OPT_* of include/sygnals_hip.h
+_LIB_OPTIONS = {"reserved_cus": 0, "stft_load": 1, "sos_clip": 2, "cqt_staged": 3, "dwt_form": 4}      # SYG_OPT_* of include/sygnals_hip.h
 
 
 def set_option(name: str, value: int) -> None:
-    """syg_set_option by name (reserved_cus | stft_load | sos_clip | cqt_staged)."""
+    """syg_set_option by name (reserved_cus | stft_load | sos_clip | cqt_staged | dwt_form)."""
     check(lib().syg_set_option(_LIB_OPTIONS[name], int(value)), "syg_set_option")
 
 
@@ -1996,3 +1996,73 @@ def clip_metrics(y: torch.Tensor) -> torch.Tensor:
     rc = lib().syg_clip_metrics_f32(_ptr(y), B, L, _ld(y), _ptr(out), C.c_void_p(_stream_ptr()))
     check(rc, "syg_clip_metrics_f32")
     return out
+
+
+# ------------------------------------------------------------------ discrete wavelet transform
+def _wavelet_dev(wavelet):
+    """The four filters of a served wavelet as float32 device arrays (dec_lo, dec_hi, rec_lo, rec_hi) and their length."""
+    from . import _wavelets as W
+    order = W.filter_length(wavelet) // 2           # raises ValueError for a wavelet that is not served
+    return _cached(("dwt", order), lambda: tuple(_dev(f.astype(np.float32)) for f in W.filters(wavelet))), 2 * order
+
+
+def dwt_fits(L: int, wavelet="db4", level: int = 1) -> bool:
+    """True when rows of L samples take the clip-resident form of syg_dwt_f32 (the library owns the rule)."""
+    from . import _wavelets as W
+    return bool(lib().syg_dwt_fits(int(L), W.filter_length(wavelet), int(level)))
+
+
+def dwt(y: torch.Tensor, wavelet="db4", level: Optional[int] = None, mode: str = "symmetric"):
+    """pywt.wavedec of every row of y [B, L] (syg_dwt_f32) -> (packed [B, total] float32 device tensor, lens): row b is
+    [cA_n | cD_n | ... | cD_1] of clip b, `lens` the lengths of those arrays in that order (a list of ints), so a row is
+    directly a feature vector and `packed.split(lens, dim=1)` the coefficient arrays.  `level=None` is
+    max(1, dwt_max_level); a level above the maximum warns, as PyWavelets does."""
+    from . import _wavelets as W
+    y = _clips(y)
+    B, L = y.shape
+    if L < 1:
+        raise ValueError("y must hold at least one sample")
+    code = W.mode_code(mode)
+    (dec_lo, dec_hi, _, _), F = _wavelet_dev(wavelet)
+    level = W.resolve_level(L, F, level)
+    h = lib()
+    lens_c = (C.c_int64 * (level + 1))()
+    total = h.syg_dwt_lengths(L, F, level, C.cast(lens_c, C.c_void_p))
+    if total < 0:
+        check(-1, "syg_dwt_lengths")
+    wb = h.syg_dwt_work_bytes(B, L, F, level)
+    work = torch.empty((wb // 4,), dtype=torch.float32, device=y.device) if wb > 0 else None
+    out = torch.empty((B, total), dtype=torch.float32, device=y.device)
+    rc = h.syg_dwt_f32(_ptr(y), B, L, _ld(y), _ptr(dec_lo), _ptr(dec_hi), F, code, level, _ptr(out), total, _ptr(work),
+                       C.c_void_p(_stream_ptr()))
+    check(rc, "syg_dwt_f32")
+    return out, [int(v) for v in lens_c]
+
+
+def idwt(packed: torch.Tensor, lens, wavelet="db4", mode: str = "symmetric") -> torch.Tensor:
+    """pywt.waverec of every row of `packed` [B, sum(lens)] (the layout of `dwt`, lens = [len cA_n, len cD_n, ...,
+    len cD_1]; syg_idwt_f32) -> [B, L'] float32.  Where an approximation is one sample longer than its detail its last
+    sample is dropped, as pywt.waverec does; any other mismatch is a ValueError.  The served modes extend nothing on the
+    way back, so `mode` is only checked."""
+    from . import _wavelets as W
+    packed = _clips(packed, "packed")
+    W.mode_code(mode)
+    (_, _, rec_lo, rec_hi), F = _wavelet_dev(wavelet)
+    lens = [int(v) for v in lens]
+    Lout = W.waverec_length(lens, F)
+    B = packed.shape[0]
+    if packed.shape[1] != sum(lens):
+        raise ValueError(f"packed rows hold {packed.shape[1]} coefficients, lens adds up to {sum(lens)}")
+    levels = len(lens) - 1
+    h = lib()
+    lens_c = (C.c_int64 * len(lens))(*lens)
+    lp = C.cast(lens_c, C.c_void_p)
+    wb = h.syg_idwt_work_bytes(B, lp, levels, F)
+    if wb < 0:
+        check(-1, "syg_idwt_work_bytes")
+    work = torch.empty((wb // 4,), dtype=torch.float32, device=packed.device) if wb > 0 else None
+    y = torch.empty((B, Lout), dtype=torch.float32, device=packed.device)
+    rc = h.syg_idwt_f32(_ptr(packed), B, _ld(packed), lp, levels, _ptr(rec_lo), _ptr(rec_hi), F, _ptr(y), Lout, _ptr(work),
+                        C.c_void_p(_stream_ptr()))
+    check(rc, "syg_idwt_f32")
+    return y
