@@ -21,7 +21,11 @@ FLAGS="--offload-arch=gfx950 -O3 -fPIC -fno-strict-aliasing -fno-slp-vectorize -
 compile_one() {
   s="sygnals_amd/csrc/$1.hip"; o="$OBJ/$1.o"
   [ -f "$s" ] || exit 0
-  if [ ! -f "$o" ] || [ "$s" -nt "$o" ] || [ sygnals_amd/csrc/common.h -nt "$o" ] || [ sygnals_amd/csrc/mel_segments.h -nt "$o" ] || [ sygnals_amd/csrc/wave_fft.h -nt "$o" ] || [ sygnals_amd/csrc/row_features.h -nt "$o" ] || [ sygnals_amd/csrc/stft_dev.h -nt "$o" ] || [ sygnals_amd/csrc/stft_host.h -nt "$o" ] || [ include/sygnals_hip.h -nt "$o" ]; then
+  stale=0                                    # no object yet, or the source or ANY header is newer than it
+  for dep in "$s" sygnals_amd/csrc/*.h include/sygnals_hip.h; do
+    [ -f "$o" ] && [ ! "$dep" -nt "$o" ] || stale=1
+  done
+  if [ $stale = 1 ]; then
     /opt/rocm/bin/hipcc $FLAGS -c "$s" -o "$o" 2> >(grep -v "is not a recognized feature for this target" >&2)
   fi
 }

@@ -11,6 +11,8 @@ from functools import lru_cache
 
 import numpy as np
 
+from .ops import num_frames  # noqa: F401  (the one frame-count rule, under the name callers of this module use)
+
 TINY = float(np.finfo(np.float64).tiny)
 N_THRESHOLDS = 100
 BETA = (2, 18)
@@ -45,12 +47,6 @@ def n_pitch_bins(fmin: float, fmax: float) -> int:
 def transition_width(sr: float, hop: int) -> int:
     """round(35.92 * 12 * hop / sr) * 10 + 1 (Python's round: half to even)."""
     return int(round(MAX_TRANSITION_RATE * 12 * hop / sr)) * BINS_PER_SEMITONE + 1
-
-
-def num_frames(L: int, frame_length: int, hop: int, center: bool) -> int:
-    if center:
-        return 1 + L // hop
-    return 1 + (L - frame_length) // hop if L >= frame_length else 0
 
 
 def cand_stride(n_lag: int) -> int:

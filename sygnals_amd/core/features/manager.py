@@ -114,9 +114,7 @@ def extract_features_batch(y, sr: int, features: List[str], frame_length: int = 
             # the reference frames the signal padded by frame_length // 2 on both sides (manager.py:268-271, librosa's
             # rms / zcr likewise): with an ODD frame_length that is one sample short of the last frame whenever hop
             # divides len(y); those rows come out one frame short and are NaN-padded (manager.py:378-386)
-            t_rows = Tn
-            if center:
-                t_rows = min(Tn, 1 + (L + 2 * (frame_length // 2) - frame_length) // hop_length)
+            t_rows = ops.num_frames_padded(L, frame_length, hop_length, center)       # (Tn or Tn - 1)
             cache["tstats"] = ({k: v[:, :t_rows] for k, v in tstats.items()}, t_rows)
         return cache["tstats"]
 

@@ -4,7 +4,7 @@
 //   cqt_octave_kernel  one octave: rectangular-window STFT frame (n_fft = 2^k) -> rfft in LDS -> n_filt complex dot
 //                      products with the frequency-domain constant-Q basis -> out[b, row0 + f, t]
 // One 64-lane wave per frame, FRAMES_PER_WG frames per workgroup (their outputs are adjacent in t).
-#include "common.h"
+#include "host.h"
 #include <stdlib.h>
 
 namespace syg {
@@ -826,8 +826,6 @@ __global__ __launch_bounds__(MAXC == 5 ? 512 : MAXC == 3 ? 768 : 1024) void cqt_
   CQS_STAMP(2);
 }
 
-bool is_pow2(int n) { return n >= 2 && (n & (n - 1)) == 0; }
-
 }  // namespace
 }  // namespace syg
 
@@ -882,12 +880,7 @@ extern "C" int syg_decimate2_chain_f32(const float* x, int64_t B, int64_t L, int
     }
     return SYG_OK;
   }
-  int dev = 0, n_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) {
-    set_error("decimate2_chain: cannot query the device");
-    return SYG_E_LAUNCH;
-  }
+  const int n_cu = device_cu_count();
   const int nf = levels == 4 ? DecChain<4>::NF : levels == 3 ? DecChain<3>::NF : DecChain<2>::NF;
   const int64_t ntiles = (o.len[levels] + nf - 1) / nf;
   int64_t blocks = ((ntiles + 7) / 8) * 8;                      // a multiple of 8: a workgroup keeps its XCD
@@ -933,11 +926,8 @@ extern "C" int syg_cqt_octave_f32(const float* y, int64_t B, int64_t L, int64_t 
                   "cqt_octave: non-zero run of filter %d out of range (k0=%d len=%d)", f, hull.k0[f], hull.len[f]);
     }
   }
-  if (lds > 64 * 1024) {                         // (after every argument check: this is the first device call)
-    hipError_t e = hipFuncSetAttribute((const void*)cqt_octave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) { set_error("cqt_octave: cannot reserve LDS: %s", hipGetErrorString(e)); return SYG_E_LAUNCH; }
-  }
+  // (after every argument check: this is the first device call)
+  if (const int rc = reserve_dynamic_lds("cqt_octave", (const void*)cqt_octave_kernel, lds)) return rc;
   hipLaunchKernelGGL(cqt_octave_kernel, dim3((unsigned)gx, (unsigned)B), dim3(FPW * 64), lds, (hipStream_t)stream, y, L,
                      ldy, n_fft, hop, T, (const float2*)twiddle, (const float2*)basis, n_filt, hull, (float2*)out,
                      out_bstride, row0);
@@ -1016,12 +1006,7 @@ extern "C" int syg_cqt_octave_bf16x3_f32(const float* y, int64_t B, int64_t L, i
     if (nwv > wcap) nwv = wcap;
     if (!off && worth && shape_ok && ((uintptr_t)y) % 16 == 0 && (B == 1 || ldy % 4 == 0) && ncopy * nchunks <= 5 * 64 &&
         nwv >= 4) {
-      int dev = 0, n_cu = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) {
-        set_error("cqt_octave_bf16x3: cannot query the device");
-        return SYG_E_LAUNCH;
-      }
+      const int n_cu = device_cu_count();
       const size_t lds = atab_bytes + (size_t)nwv * wave_bytes;
       int64_t gx = ((int64_t)n_cu + B - 1) / B;    // one workgroup per CU over the batch
       if (gx * nwv > ntiles) gx = (ntiles + nwv - 1) / nwv;
@@ -1029,9 +1014,8 @@ extern "C" int syg_cqt_octave_bf16x3_f32(const float* y, int64_t B, int64_t L, i
       const dim3 grid((unsigned)gx, (unsigned)B), block(nwv * 64);
 #define SYG_CQT_ST(N, R, C)                                                                                          \
   do {                                                                                                               \
-    hipError_t e2 = hipFuncSetAttribute((const void*)cqt_bf16x3_staged_kernel<N, R, C>,                              \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                       \
-    if (e2 != hipSuccess) { set_error("cqt_octave_bf16x3: cannot reserve LDS: %s", hipGetErrorString(e2)); return SYG_E_LAUNCH; } \
+    const int rc = reserve_dynamic_lds("cqt_octave_bf16x3", (const void*)cqt_bf16x3_staged_kernel<N, R, C>, lds);    \
+    if (rc) return rc;                                                                                               \
     hipLaunchKernelGGL((cqt_bf16x3_staged_kernel<N, R, C>), grid, block, lds, st, y, L, ldy, hop, T,                 \
                        (const uint4*)gsplit, n_filt, (float2*)out, out_bstride, row0, nchunks, cplane, ncopy, sh);   \
   } while (0)

@@ -35,7 +35,7 @@
 // chunk c of a window at slot c + (c >> log2(hop / 8)): the sixteen frames of a ds_read_b128 group fall on sixteen bank
 // groups, checked by enumeration).  150 VGPRs: three waves per SIMD.
 #include <string.h>
-#include "common.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -554,8 +554,7 @@ extern "C" int syg_cqt_fused_f32(const float* y, int64_t B, int64_t L, int64_t l
     P.row0[o] = row0_host[o];
     SYG_REQUIRE(P.row0[o] >= 0 && out_bstride >= ((int64_t)P.row0[o] + n_filt) * T, "cqt_fused: output rows out of range");
   }
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+  const int cus = device_cu_count();
   // segments: whole steps, at least eight (the lead-in costs six), about one per CU
   const int64_t steps = (T * 512 + CF_STEP - 1) / CF_STEP;
   int64_t per = (steps * B + cus - 1) / cus;
@@ -565,11 +564,7 @@ extern "C" int syg_cqt_fused_f32(const float* y, int64_t B, int64_t L, int64_t l
   SYG_REQUIRE((int64_t)P.n_seg * B < ((int64_t)1 << 31), "cqt_fused: too many segments");
   P.L = L; P.ldy = ldy; P.T = T; P.out_bstride = out_bstride; P.n_oct = n_oct; P.n_filt = n_filt; P.scale = scale;
   const size_t lds = (size_t)CF_LDS_FLOATS * sizeof(float);
-  hipError_t e = hipFuncSetAttribute((const void*)cqt_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) {
-    set_error("cqt_fused: cannot reserve %zu B LDS: %s", lds, hipGetErrorString(e));
-    return SYG_E_LAUNCH;
-  }
+  if (const int rc = reserve_dynamic_lds("cqt_fused", (const void*)cqt_fused_kernel, lds)) return rc;
   hipLaunchKernelGGL(cqt_fused_kernel, dim3((unsigned)(P.n_seg * B)), dim3(CF_BLOCK), lds, (hipStream_t)stream, y, taps,
                      (const uint4*)gsplit, (float2*)out, P);
   SYG_CHECK_LAUNCH("cqt_fused");

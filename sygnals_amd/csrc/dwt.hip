@@ -32,7 +32,7 @@
 // last one writes global memory, what lies between ping-pongs in LDS) for as long as a level's input and the input of
 // the level before it fit the 40960 floats together -- the mirror of the analysis rule; idwt_level_kernel runs the finer
 // levels of a longer row one a pass through the workspace.
-#include "common.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -296,7 +296,6 @@ __global__ __launch_bounds__(DT) void idwt_level_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------ host side
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 int64_t level_len(int64_t N, int F) { return (N + F - 1) / 2; }
 int64_t even_up(int64_t n) { return (n + 1) & ~(int64_t)1; }
 
@@ -326,15 +325,6 @@ bool filter_ok(int F) { return F >= 2 && F <= DWT_FMAX && (F & 1) == 0; }
 
 int block_for(int64_t n) { return (int)(n >= RT ? RT : (n <= 64 ? 64 : ceil_div(n, 64) * 64)); }
 
-template <typename Kern>
-int reserve_lds(Kern k, size_t bytes, const char* who) {
-  if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) { set_error("%s: cannot reserve LDS: %s", who, hipGetErrorString(e)); return SYG_E_LAUNCH; }
-  }
-  return SYG_OK;
-}
-
 // the levels [0, nlev) of a length-N input by the clip-resident kernel; dend: end of the first level's cD in the row
 int launch_dwt_clip(const float* src, int64_t ldsrc, int64_t B, int64_t N, int nlev, const float* lo, const float* hi,
                     int F, int mode, float* out, int64_t ldout, int64_t dend, hipStream_t st) {
@@ -345,7 +335,7 @@ int launch_dwt_clip(const float* src, int64_t ldsrc, int64_t B, int64_t N, int n
   const size_t bytes = nlev == 1 ? 0 : (nlev == 2 ? (size_t)ca * 4 : (size_t)(ca + cb) * 4);
 #define CALL(FF)                                                                                               \
   {                                                                                                            \
-    const int rc = reserve_lds(dwt_clip_kernel<FF>, bytes, "dwt");                                             \
+    const int rc = reserve_dynamic_lds("dwt", (const void*)dwt_clip_kernel<FF>, bytes);                        \
     if (rc != SYG_OK) return rc;                                                                               \
     hipLaunchKernelGGL(dwt_clip_kernel<FF>, dim3((unsigned)B), dim3(block_for(n1)), bytes, st, src, ldsrc, (int)N, \
                        nlev, lo, hi, mode, out, ldout, dend, capA);                                            \
@@ -531,7 +521,7 @@ extern "C" int syg_idwt_f32(const float* coeffs, int64_t B, int64_t ldc, const i
     const int nt = block_for(K[r - 1]);
 #define CALL(FF)                                                                                                  \
   {                                                                                                               \
-    const int rc = reserve_lds(idwt_clip_kernel<FF>, bytes, "idwt");                                              \
+    const int rc = reserve_dynamic_lds("idwt", (const void*)idwt_clip_kernel<FF>, bytes);                         \
     if (rc != SYG_OK) return rc;                                                                                  \
     hipLaunchKernelGGL(idwt_clip_kernel<FF>, dim3((unsigned)B), dim3(nt), bytes, st, coeffs, ldc, lens_host[0], P, r, \
                        rec_lo, rec_hi, dst, ldd, (int)ca);                                                        \

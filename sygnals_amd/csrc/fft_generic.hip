@@ -7,7 +7,7 @@
 //   scipy.signal.welch              (compute_psd_welch, sygnals/core/dsp.py:545-555)
 // One workgroup per transform; the two ping-pong buffers live in LDS (<= 128 KiB for
 // n = 8192), so every transform reads its input once and writes its output once.
-#include "common.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -438,19 +438,7 @@ __global__ void pack_real_kernel(const float* __restrict__ x, int64_t len, int64
   }
 }
 
-bool is_pow2(int n) { return n >= 2 && (n & (n - 1)) == 0; }
 int fft_threads(int n) { int t = n / 4; if (t < 64) t = 64; if (t > 1024) t = 1024; return t; }
-
-int set_lds(const void* fn, size_t bytes, const char* what) {
-  if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-      set_error("%s: cannot reserve %zu B of LDS: %s", what, bytes, hipGetErrorString(e));
-      return SYG_E_LAUNCH;
-    }
-  }
-  return SYG_OK;
-}
 
 }  // namespace
 int welch_wave_launch(const float* x, int64_t B, int64_t ldx, int step, int64_t nseg, const float* window,
@@ -477,7 +465,7 @@ extern "C" int syg_fft_pow2_c2c_f32(const float* in, float* out, int64_t batch, 
   SYG_REQUIRE(is_pow2(n) && n <= MAX_N, "fft_pow2: n must be a power of two in [2, %d] (got %d)", MAX_N, n);
   SYG_REQUIRE(batch >= 1 && batch < (int64_t)0x7fffffff, "fft_pow2: bad batch %lld", (long long)batch);
   const size_t lds = (size_t)n * 2 * sizeof(float2);
-  int rc = set_lds((const void*)fft_pow2_kernel, lds, "fft_pow2");
+  int rc = reserve_dynamic_lds("fft_pow2", (const void*)fft_pow2_kernel, lds);
   if (rc) return rc;
   hipLaunchKernelGGL(fft_pow2_kernel, dim3((unsigned)batch), dim3(fft_threads(n)), lds, (hipStream_t)stream,
                      (const float2*)in, (float2*)out, n, inverse, (const float2*)twiddle);
@@ -492,13 +480,12 @@ extern "C" int syg_stft_pow2_c2c_f32(const float* y, int64_t B, int64_t L, int64
   SYG_REQUIRE(is_pow2(n_fft) && n_fft >= 8 && n_fft <= 2 * MAX_N,
               "stft_pow2: n_fft must be a power of two in [8, %d] (got %d)", 2 * MAX_N, n_fft);
   SYG_REQUIRE(B >= 1 && L >= 1 && ldy >= L && hop >= 1, "stft_pow2: bad B/L/ldy/hop");
-  const int64_t Texp = center ? 1 + L / hop : (L >= n_fft ? 1 + (L - n_fft) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp, "stft_pow2: T=%lld does not match the framing rule (%lld)", (long long)T,
-              (long long)Texp);
+  int rc = check_framing("stft_pow2", T, frames_expected(L, n_fft, hop, center));
+  if (rc) return rc;
   SYG_REQUIRE(B * T < (int64_t)0x7fffffff, "stft_pow2: grid too large");
   const int M = n_fft / 2;
   const size_t lds = (size_t)M * 2 * sizeof(float2);
-  int rc = set_lds((const void*)stft_pow2_kernel, lds, "stft_pow2");
+  rc = reserve_dynamic_lds("stft_pow2", (const void*)stft_pow2_kernel, lds);
   if (rc) return rc;
   hipLaunchKernelGGL(stft_pow2_kernel, dim3((unsigned)(B * T)), dim3(fft_threads(M)), lds, (hipStream_t)stream, y, L,
                      ldy, n_fft, hop, center ? n_fft / 2 : 0, T, window, (const float2*)twiddle, (float2*)out);
@@ -571,7 +558,7 @@ extern "C" int syg_welch_f32(const float* x, int64_t B, int64_t L, int64_t ldx, 
   SYG_REQUIRE(nseg >= 1, "welch: no complete segment");
   const int M = nfft / 2, F = M + 1;
   const size_t lds = (size_t)M * 2 * sizeof(float2);
-  int rc = set_lds((const void*)welch_partial_kernel, lds, "welch");
+  int rc = reserve_dynamic_lds("welch", (const void*)welch_partial_kernel, lds);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   int nblk = welch_nblk(B);
@@ -609,7 +596,7 @@ extern "C" int syg_fft_pow2_strided_ex_f32(const float* in, float* out, int64_t 
       const bool kfast = out_es == 1;
       const void* fn = kfast ? (const void*)fft_cols_kernel<true> : (const void*)fft_cols_kernel<false>;
       const size_t lds = (size_t)2 * ((size_t)(n + COLS_PAD) << cb_log) * sizeof(float2);
-      int rc = set_lds(fn, lds, "fft_pow2_strided(cols)");
+      int rc = reserve_dynamic_lds("fft_pow2_strided(cols)", fn, lds);
       if (rc) return rc;
       const dim3 grid((unsigned)(batch >> cb_log), (unsigned)outer);
       if (kfast)
@@ -625,7 +612,7 @@ extern "C" int syg_fft_pow2_strided_ex_f32(const float* in, float* out, int64_t 
     }
   }
   const size_t lds = (size_t)n * 2 * sizeof(float2);
-  int rc = set_lds((const void*)fft_pow2_strided_kernel, lds, "fft_pow2_strided");
+  int rc = reserve_dynamic_lds("fft_pow2_strided", (const void*)fft_pow2_strided_kernel, lds);
   if (rc) return rc;
   hipLaunchKernelGGL(fft_pow2_strided_kernel, dim3((unsigned)batch, (unsigned)outer), dim3(fft_threads(n)), lds,
                      (hipStream_t)stream, (const float2*)in, (float2*)out, n, inverse, (const float2*)twiddle, in_os,

@@ -8,7 +8,7 @@
 // stride s (product of the radices done) reads a[j] = x[q + s (p + j m)], m = N / (s R), p = i / s, q = i mod s,
 // transforms the R points in registers and writes y[q + s (R p + j)] = a[j] W_N^(j p s); input and output in natural
 // order.  Same strided addressing and four-step twiddle as syg_fft_pow2_strided_c2c_f32.
-#include "common.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -232,10 +232,7 @@ extern "C" int syg_fft_mixed_strided_ex_f32(const float* in, float* out, int64_t
       const bool kfast = out_es == 1;
       const void* fn = kfast ? (const void*)fft_mixed_cols_kernel<true> : (const void*)fft_mixed_cols_kernel<false>;
       const size_t clds = (size_t)2 * ((size_t)(n + MCOLS_PAD) << cb_log) * sizeof(float2);
-      if (clds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds);
-        if (e != hipSuccess) { set_error("fft_mixed(cols): cannot reserve %zu B of LDS", clds); return SYG_E_LAUNCH; }
-      }
+      if (const int rc = reserve_dynamic_lds("fft_mixed(cols)", fn, clds)) return rc;
       const dim3 grid((unsigned)(batch >> cb_log), (unsigned)outer);
       if (kfast)
         hipLaunchKernelGGL(fft_mixed_cols_kernel<true>, grid, dim3(MCOLS_NT), clds, (hipStream_t)stream,
@@ -250,11 +247,7 @@ extern "C" int syg_fft_mixed_strided_ex_f32(const float* in, float* out, int64_t
     }
   }
   const size_t lds = (size_t)n * 2 * sizeof(float2);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)fft_mixed_strided_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) { set_error("fft_mixed: cannot reserve %zu B of LDS", lds); return SYG_E_LAUNCH; }
-  }
+  if (const int rc = reserve_dynamic_lds("fft_mixed", (const void*)fft_mixed_strided_kernel, lds)) return rc;
   int nt = n / 8;
   nt = nt < 64 ? 64 : (nt > 1024 ? 1024 : ((nt + 63) / 64) * 64);
   hipLaunchKernelGGL(fft_mixed_strided_kernel, dim3((unsigned)batch, (unsigned)outer), dim3(nt), lds,

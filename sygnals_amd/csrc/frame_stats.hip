@@ -20,7 +20,7 @@
 // extrema are exact as before; the moment formulas run in float64 on the accumulated sums.  Measured against the
 // float64 reference: <= 3e-7 of each row's peak (gate 1e-5).  Two passes over the frame (mean first, then central
 // moments + histogram): a frame is at most a few KiB and stays in L1/L2.
-#include "common.h"
+#include "host.h"
 #include <type_traits>
 
 namespace syg {
@@ -358,9 +358,7 @@ extern "C" int syg_frame_stats_f32(const float* y, int64_t B, int64_t L, int64_t
   SYG_REQUIRE(y && out, "frame_stats: null pointer argument");
   SYG_REQUIRE(B >= 1 && L >= 1 && ldy >= L, "frame_stats: need B >= 1, L >= 1, ldy >= L");
   SYG_REQUIRE(frame_length >= 1 && hop >= 1, "frame_stats: frame_length and hop must be >= 1");
-  const int64_t Texp = center ? 1 + L / hop : (L >= frame_length ? 1 + (L - frame_length) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp, "frame_stats: T=%lld does not match the framing rule (%lld)", (long long)T,
-              (long long)Texp);
+  if (const int rc = check_framing("frame_stats", T, frames_expected(L, frame_length, hop, center))) return rc;
   SYG_REQUIRE(mask > 0 && mask < (1 << SYG_NFSTAT), "frame_stats: mask must select at least one of the %d rows",
               SYG_NFSTAT);
   SYG_REQUIRE(num_bins >= 1 && num_bins <= FS_MAXBINS, "frame_stats: num_bins must be in [1, %d] (got %d)", FS_MAXBINS,

@@ -23,6 +23,7 @@
 #include <float.h>
 #include <math.h>
 #include "wave_fft.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -356,14 +357,6 @@ __global__ __launch_bounds__(HPW * 64) void hnr_rows_kernel(HnrArgs A) {
   if (A.rp) A.rp[f] = (float)rp;
 }
 
-int n_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                              hipSuccess || cus <= 0)
-    cus = 256;
-  return cus;
-}
-
 }  // namespace
 }  // namespace syg
 
@@ -414,7 +407,7 @@ extern "C" int syg_istft2048_f32(const float* D, int64_t B, int64_t T, int hop, 
   IstftArgs A{(const float2*)D, T, nframes, length, ldy, nseg, B * nseg * ncomp, window, {mask_a, mask_b}, {y_a, y_b},
               ncomp};
   int64_t blocks = (A.nwaves + IPW - 1) / IPW;
-  const int64_t cap = (int64_t)n_cus() * 64;
+  const int64_t cap = (int64_t)device_cu_count() * 64;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(istft2048_kernel, dim3((unsigned)blocks), dim3(IPW * 64), 0, (hipStream_t)stream, A,
                      (const float2*)twiddle);
@@ -428,10 +421,8 @@ extern "C" int syg_hnr_rows_f32(const float* y_harm, const float* y_perc, int64_
   SYG_REQUIRE(y_harm && y_perc && hnr_out, "hnr_rows: null pointer argument (y_harm / y_perc / hnr_out)");
   SYG_REQUIRE(B >= 1 && L >= 1 && ldy >= L, "hnr_rows: bad B / L / ldy");
   SYG_REQUIRE(frame_length >= 1 && hop >= 1 && (center == 0 || center == 1), "hnr_rows: bad frame_length / hop / center");
-  const int64_t Texp = center ? 1 + (L + 2 * (frame_length / 2) - frame_length) / hop
-                              : (L >= frame_length ? 1 + (L - frame_length) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp, "hnr_rows: T = %lld does not follow the framing rule (%lld)", (long long)T,
-              (long long)Texp);
+  // (librosa.feature.rms's count on the padded signal, not frames_expected)
+  if (const int rc = check_framing("hnr_rows", T, frames_padded(L, frame_length, hop, center))) return rc;
   HnrArgs A{y_harm, y_perc, L, ldy, frame_length, hop, center, T, B * T, hnr_out, rms_harm_out, rms_perc_out};
   const int64_t blocks = (A.nframes + HPW - 1) / HPW;
   SYG_REQUIRE(blocks < 0x7fffffff, "hnr_rows: too many frames");

@@ -5,7 +5,7 @@
 // One workgroup per clip.  The clip's [M, T] mel matrix (15 KB at the headline config) is
 // L2-resident from the producing kernel; the DCT is the 16x16x4 f32 MFMA with the DCT rows
 // as the A operand and 16 frames as the B operand.
-#include "common.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -277,11 +277,7 @@ extern "C" int syg_feature_block_f32(const float* mel, int64_t B, int M, int64_t
   const size_t lds = mel ? (size_t)M * (size_t)T * sizeof(float) : 0;       // (mel == NULL: only the statistics / contrast rows)
   SYG_REQUIRE(lds <= 150 * 1024, "feature_block: the clip's dB matrix (%d x %lld) does not fit LDS; use "
               "syg_logmel_dct_f32 + syg_contrast_db_f32", M, (long long)T);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)feature_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) { set_error("feature_block: cannot reserve %zu B of LDS", lds); return SYG_E_LAUNCH; }
-  }
+  if (const int rc = reserve_dynamic_lds("feature_block", (const void*)feature_block_kernel, lds)) return rc;
   hipLaunchKernelGGL(feature_block_kernel, dim3((unsigned)B), dim3(NT), lds, (hipStream_t)stream, mel, M, T, dct, K, amin,
                      top_db, stats, binhz, contrast_pv, R, c_amin, c_top_db, block_out);
   SYG_CHECK_LAUNCH("feature_block");
@@ -300,10 +296,7 @@ extern "C" int syg_logmel_dct_f32(float* mel, int64_t B, int M, int64_t T, const
   SYG_REQUIRE(B < (int64_t)0x7fffffff, "logmel_dct: batch too large");
   const size_t lds = (size_t)M * (size_t)T * sizeof(float);
   if (ref_is_max != 2 && lds <= 144 * 1024 && M <= 128) {
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)logmel_dct_lds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { set_error("logmel_dct: cannot reserve %zu B of LDS", lds); return SYG_E_LAUNCH; }
-    }
+    if (const int rc = reserve_dynamic_lds("logmel_dct", (const void*)logmel_dct_lds_kernel<true>, lds)) return rc;
     hipLaunchKernelGGL(logmel_dct_lds_kernel<true>, dim3((unsigned)B), dim3(NTL), lds, (hipStream_t)stream, mel, M, T, dct, K,
                        lifter, amin, top_db, ref_is_max, ref_value, logmel_out, mfcc_out);
     SYG_CHECK_LAUNCH("logmel_dct");
@@ -327,10 +320,7 @@ extern "C" int syg_mel_mfcc_f32(float* mel, int64_t B, int M, int64_t T, const f
   SYG_REQUIRE(K >= 1 && K <= M, "mel_mfcc: need 1 <= K <= M (K=%d M=%d)", K, M);
   const size_t lds = (size_t)M * (size_t)T * sizeof(float);
   if (lds <= 144 * 1024 && M <= 128) {
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)logmel_dct_lds_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) { set_error("mel_mfcc: cannot reserve %zu B of LDS", lds); return SYG_E_LAUNCH; }
-    }
+    if (const int rc = reserve_dynamic_lds("mel_mfcc", (const void*)logmel_dct_lds_kernel<false>, lds)) return rc;
     hipLaunchKernelGGL(logmel_dct_lds_kernel<false>, dim3((unsigned)B), dim3(NTL), lds, (hipStream_t)stream, mel, M, T, dct, K,
                        lifter, amin, top_db, ref_is_max, ref_value, (float*)nullptr, mfcc_out);
     SYG_CHECK_LAUNCH("mel_mfcc");

@@ -4,7 +4,7 @@
 // (scipy.ndimage.zoom, order 0 / 1, mode='nearest').  Small matrices ([frames, features]); everything is a
 // column-wise reduction or an element-wise map, NaN-aware like scikit-learn's fit (NaNs are ignored in the statistics
 // and pass through the transform).
-#include "common.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -172,11 +172,7 @@ extern "C" int syg_col_quantiles_f32(const float* x, int64_t n, int64_t F, const
   int np2 = 2;
   while (np2 < n) np2 <<= 1;
   const size_t lds = (size_t)np2 * sizeof(float);
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)col_quantiles_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) { set_error("col_quantiles: cannot reserve %zu B of LDS", lds); return SYG_E_LAUNCH; }
-  }
+  if (const int rc = reserve_dynamic_lds("col_quantiles", (const void*)col_quantiles_kernel, lds)) return rc;
   hipLaunchKernelGGL(col_quantiles_kernel, dim3((unsigned)F), dim3(256), lds, (hipStream_t)stream, x, n, F, np2, q, nq,
                      out);
   SYG_CHECK_LAUNCH("col_quantiles");

@@ -29,7 +29,7 @@
 // Clip metrics (clip_metrics_kernel): sum of squares (float64 per thread, fixed-order tree) and peak |y| of a clip.
 #include <float.h>
 #include <math.h>
-#include "common.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -343,8 +343,6 @@ __global__ __launch_bounds__(CT) void clip_metrics_kernel(const float* y, int64_
   }
   if (tid == 0) { out[2 * blockIdx.x] = (float)ss[0]; out[2 * blockIdx.x + 1] = pk[0]; }
 }
-
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 }  // namespace
 }  // namespace syg

@@ -22,6 +22,7 @@
 // exact.  Backpointers (uint16) go to the caller's workspace; one thread backtracks.
 #include <float.h>
 #include "wave_fft.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -463,14 +464,6 @@ __global__ __launch_bounds__(1024) void pyin_viterbi_kernel(VitArgs A) {
   }
 }
 
-int n_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      cus <= 0)
-    cus = 256;
-  return cus;
-}
-
 }  // namespace
 }  // namespace syg
 
@@ -498,9 +491,7 @@ extern "C" int syg_pitch_frames_f32(const float* y, int64_t B, int64_t L, int64_
               "pitch_frames: need 1 <= min_period < max_period (got %d, %d): fmin / fmax / win_length leave no lag range",
               min_period, max_period);
   SYG_REQUIRE(max_period <= NF - win_length - 1, "pitch_frames: max_period %d > frame_length - win_length - 1", max_period);
-  const int64_t Texp = center ? 1 + L / hop : (L >= NF ? 1 + (L - NF) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp, "pitch_frames: T = %lld does not follow the framing rule (%lld)", (long long)T,
-              (long long)Texp);
+  if (const int rc = check_framing("pitch_frames", T, frames_expected(L, NF, hop, center))) return rc;
   const int n_lag = max_period - min_period + 1;
   SYG_REQUIRE(mode == 0 || (K >= (n_lag + 1) / 2 + 1 && K <= 4096), "pitch_frames: K must be >= ceil(n_lag / 2) + 1 = %d",
               (n_lag + 1) / 2 + 1);
@@ -509,7 +500,7 @@ extern "C" int syg_pitch_frames_f32(const float* y, int64_t B, int64_t L, int64_
   FrameArgs A{y, L, ldy, win_length, hop, center, T, B * T, sr, min_period, max_period, n_lag, mode, trough_threshold,
               fmin, n_bins, ptab, K, f0_out, cand_bin, cand_prob, cand_count, voiced_prob, cmndf_out};
   int64_t blocks = (A.nframes + PW - 1) / PW;
-  const int64_t cap = (int64_t)n_cus() * 16;
+  const int64_t cap = (int64_t)device_cu_count() * 16;
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(pitch_frames_kernel, dim3((unsigned)blocks), dim3(PW * 64), 0, (hipStream_t)stream, A,
                      (const float2*)twiddle);
@@ -537,11 +528,7 @@ extern "C" int syg_pyin_viterbi_f32(const int* cand_bin, const float* cand_prob,
               (long long)need, (long long)work_bytes);
   const size_t lds = (size_t)(5 * n_bins) * sizeof(double) + 16 * sizeof(double) + 16 * sizeof(int);
   SYG_REQUIRE(lds <= 160 * 1024, "pyin_viterbi: n_bins %d needs %zu bytes of LDS", n_bins, lds);
-  if (hipFuncSetAttribute((const void*)pyin_viterbi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-      hipSuccess) {
-    set_error("pyin_viterbi: cannot set %zu bytes of LDS", lds);
-    return SYG_E_LAUNCH;
-  }
+  if (const int rc = reserve_dynamic_lds("pyin_viterbi", (const void*)pyin_viterbi_kernel, lds)) return rc;
   VitArgs A{cand_bin, cand_prob, cand_count, voiced_prob, T, K, n_bins, half_width, R,
             ltab, ltab + (int64_t)R * (2 * half_width + 1), lconst_host[0], lconst_host[1], lconst_host[2], fmin,
             (uint16_t*)work, f0_out, voiced_out, state_out};

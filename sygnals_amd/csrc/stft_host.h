@@ -1,9 +1,9 @@
 // Host side of the fused STFT front ends (stft_mel.hip, stft_mel_pow2.hip, stft_mel_w1024_seg.hip, stft_mel_w4096.hip,
-// stft_mel_wseg_small.hip): the argument checks their entry points share, the contrast plan and row arguments a rows
-// entry point hands to its kernel, and the two device queries in front of a launch.  No device code.  `who` names the
-// entry point in the message; every check returns SYG_OK or sets the last error and returns the code to pass on.
+// stft_mel_wseg_small.hip) on top of host.h: the argument checks their entry points share and the contrast plan and row
+// arguments a rows entry point hands to its kernel.  No device code.  `who` names the entry point in the message; every
+// check returns SYG_OK or sets the last error and returns the code to pass on.
 #pragma once
-#include "common.h"
+#include "host.h"
 #include <string.h>
 
 namespace syg {
@@ -15,9 +15,7 @@ inline int check_clips(const char* who, const float* y, int64_t B, int64_t L, in
   SYG_REQUIRE(B >= 1 && L >= 1 && ldy >= L, "%s: need B >= 1, L >= 1, ldy >= L (B=%lld L=%lld ldy=%lld)", who, (long long)B,
               (long long)L, (long long)ldy);
   SYG_REQUIRE(hop >= 1, "%s: hop must be >= 1 (got %d)", who, hop);
-  const int64_t Texp = center ? 1 + L / hop : (L >= n_fft ? 1 + (L - n_fft) / hop : 0);
-  SYG_REQUIRE(T >= 1 && T == Texp, "%s: T=%lld does not match the framing rule (%lld)", who, (long long)T, (long long)Texp);
-  return SYG_OK;
+  return check_framing(who, T, frames_expected(L, n_fft, hop, center));
 }
 
 // frames-per-clip limit of the entry points with statistics / contrast rows (below it a clip's [SYG_NSTAT, T] float
@@ -77,25 +75,6 @@ inline int check_segtab(const char* who, const float* segtab, int n_segtab, int 
   SYG_REQUIRE(((uintptr_t)segtab) % 16 == 0, "%s: the piece table must be 16-byte aligned", who);
   SYG_REQUIRE(n_mels >= 1 && n_mels <= max_mels, "%s: n_mels must be in [1, %d] (got %d)", who, max_mels, n_mels);
   return SYG_OK;
-}
-
-// CU count of the CURRENT device, asked at every call (an attribute query, no device properties round trip): no
-// process-wide cache that a second device or a second thread could read stale.  256 if the query fails.
-inline int device_cu_count() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      cus <= 0)
-    cus = 256;
-  return cus;
-}
-
-// Set at every launch: the attribute belongs to the (function, device) pair, and a per-process "already set" flag would
-// leave a second device without it.
-inline int reserve_dynamic_lds(const char* who, const void* kernel, size_t bytes) {
-  const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess) return SYG_OK;
-  set_error("%s: cannot reserve %zu B LDS: %s", who, bytes, hipGetErrorString(e));
-  return SYG_E_LAUNCH;
 }
 
 }  // namespace syg

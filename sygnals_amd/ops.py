@@ -30,6 +30,12 @@ def _stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _call(name: str, *args) -> None:
+    """The entry `name` of the library on the current stream (its last argument); a non-zero status raises under that
+    name.  (`lib` is looked up here, at call time: tests replace it with a spy.)"""
+    check(getattr(lib(), name)(*args, C.c_void_p(_stream_ptr())), name)
+
+
 def _ld(t: torch.Tensor) -> int:
     """Row stride in elements (a size-1 leading axis may carry an arbitrary stride)."""
     return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
@@ -83,10 +89,18 @@ def twiddle_dev(n) -> torch.Tensor:
 
 
 def num_frames(L: int, n_fft: int, hop: int, center: bool) -> int:
-    """Frame-count rule of sygnals/core/features/manager.py:149-157."""
+    """Frame-count rule of sygnals/core/features/manager.py:149-157 (frames_expected of csrc/host.h)."""
     if center:
         return 1 + L // hop
     return 1 + (L - n_fft) // hop if L >= n_fft else 0
+
+
+def num_frames_padded(L: int, frame: int, hop: int, center: bool) -> int:
+    """librosa's count on the signal padded by frame // 2 on both sides (frames_padded of csrc/host.h): num_frames() for
+    an even frame length, one less for an odd one when hop divides L (the padding is one sample short of the frame)."""
+    if center:
+        return 1 + (L + 2 * (frame // 2) - frame) // hop
+    return 1 + (L - frame) // hop if L >= frame else 0
 
 
 # ------------------------------------------------------------------ fused 2048 path
@@ -286,9 +300,8 @@ def stft_mel_pow2(y: torch.Tensor, sr: float, n_fft: int, hop: int, center: bool
     """Fused STFT(n_fft = 64 ... 1024) -> |X|^power -> mel [B, n_mels, T]: one launch, no spectrogram in HBM."""
     y, B, L, Tn, bp, Fp, win, tw = _pow2_front(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax)
     mel = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device)
-    rc = lib().syg_stft_mel_pow2_f32(_ptr(y), B, L, y.stride(0), n_fft, hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(bp),
-                                     Fp, n_mels, int(power), _ptr(mel), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft_mel_pow2_f32")
+    _call("syg_stft_mel_pow2_f32", _ptr(y), B, L, y.stride(0), n_fft, hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(bp),
+          Fp, n_mels, int(power), _ptr(mel))
     return mel
 
 
@@ -309,11 +322,9 @@ def stft_mfcc_pow2(y: torch.Tensor, sr: float, n_fft: int, hop: int, center: boo
     lif = None if lw is None else _dev(lw)
     mf = torch.empty((B, n_mfcc, Tn), dtype=torch.float32, device=y.device)
     mel = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device) if keep_mel else None
-    rc = lib().syg_stft_mfcc_pow2_f32(_ptr(y), B, L, y.stride(0), n_fft, hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(bp),
-                                      Fp, n_mels, _ptr(dct), n_mfcc, None if lif is None else _ptr(lif), float(amin),
-                                      -1.0 if top_db is None else float(top_db), 1, 1.0,
-                                      None if mel is None else _ptr(mel), _ptr(mf), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft_mfcc_pow2_f32")
+    _call("syg_stft_mfcc_pow2_f32", _ptr(y), B, L, y.stride(0), n_fft, hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(bp),
+          Fp, n_mels, _ptr(dct), n_mfcc, None if lif is None else _ptr(lif), float(amin),
+          -1.0 if top_db is None else float(top_db), 1, 1.0, None if mel is None else _ptr(mel), _ptr(mf))
     return mf, mel
 
 
@@ -371,9 +382,8 @@ def _seg_mel(n_fft, y, sr, hop, center, window, win_length, n_mels, fmin, fmax):
                               "(stft_mel_segments says so with None; stft_mel_pow2 / the generic chain take any filterbank)")
     Tn = _frames(y.shape[1], n_fft, hop, center)
     out = torch.empty((y.shape[0], n_mels, Tn), dtype=torch.float32, device=y.device)
-    rc = getattr(lib(), k["mel"])(*_seg_args(k, y, n_fft, hop, center, Tn, window, win_length), _ptr(tab), int(tab.numel()),
-                                  n_mels, _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, k["mel"])
+    _call(k["mel"], *_seg_args(k, y, n_fft, hop, center, Tn, window, win_length), _ptr(tab), int(tab.numel()), n_mels,
+          _ptr(out))
     return out
 
 
@@ -395,10 +405,8 @@ def _seg_rows(n_fft, y, sr, hop, center, window, win_length, n_mels, fmin, fmax,
                 raise SygnalsHipError(f"{who}: no piece table for this filterbank")
             mel = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device)
         mel_args = (_ptr(tab), int(tab.numel()) if tab is not None else 0, int(n_mels or 0), _ptr(mel))
-    rc = getattr(lib(), k["rows"])(*_seg_args(k, y, n_fft, hop, center, Tn, window, win_length), *mel_args, float(sr),
-                                   float(roll_percent), float(bw_p), smask, _ptr(stats), cplan_p, _ptr(cpv),
-                                   C.c_void_p(_stream_ptr()))
-    check(rc, k["rows"])
+    _call(k["rows"], *_seg_args(k, y, n_fft, hop, center, Tn, window, win_length), *mel_args, float(sr), float(roll_percent),
+          float(bw_p), smask, _ptr(stats), cplan_p, _ptr(cpv))
     return mel, stats, cpv
 
 
@@ -530,17 +538,13 @@ def stft2048_mel(y: torch.Tensor, sr: float, hop: int = 512, center: bool = True
     mel = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device)
     smask, stats, cpv, cplan_p = _rows_out(B, Tn, want_stats, contrast, y.device)
     if tri:
-        rc = lib().syg_stft2048_mel_tri_f32(
-            _ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(tab), int(tab.numel()),
-            n_mels, _ptr(mel), float(sr), float(roll_percent), float(bw_p), smask, _ptr(stats), cplan_p, _ptr(cpv),
-            int(tri_waves), C.c_void_p(_stream_ptr()))
-        check(rc, "syg_stft2048_mel_tri_f32")
+        _call("syg_stft2048_mel_tri_f32", _ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(tab),
+              int(tab.numel()), n_mels, _ptr(mel), float(sr), float(roll_percent), float(bw_p), smask, _ptr(stats), cplan_p,
+              _ptr(cpv), int(tri_waves))
         return mel, stats, cpv
-    rc = lib().syg_stft2048_mel_f32(
-        _ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(cfg.wpacked),
-        cfg.plan.ctypes.data_as(C.c_void_p), n_mels, _ptr(mel), float(sr), float(roll_percent), float(bw_p),
-        smask, _ptr(stats), cplan_p, _ptr(cpv), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft2048_mel_f32")
+    _call("syg_stft2048_mel_f32", _ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(cfg.wpacked),
+          cfg.plan.ctypes.data_as(C.c_void_p), n_mels, _ptr(mel), float(sr), float(roll_percent), float(bw_p), smask,
+          _ptr(stats), cplan_p, _ptr(cpv))
     return mel, stats, cpv
 
 
@@ -562,10 +566,8 @@ def stft2048_stats(y: torch.Tensor, sr: float, hop: int = 512, center: bool = Tr
     smask, stats, cpv, cplan_p = _rows_out(B, Tn, want_stats, contrast, y.device, "stft2048_stats")
     win = window_dev(window, win_length, 2048)
     tw = twiddle_dev(2048)
-    rc = lib().syg_stft2048_stats_f32(_ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(win), _ptr(tw), float(sr),
-                                      float(roll_percent), float(bw_p), smask or 1, _ptr(stats), cplan_p, _ptr(cpv),
-                                      C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft2048_stats_f32")
+    _call("syg_stft2048_stats_f32", _ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(win), _ptr(tw), float(sr),
+          float(roll_percent), float(bw_p), smask or 1, _ptr(stats), cplan_p, _ptr(cpv))
     return stats, cpv
 
 
@@ -577,9 +579,7 @@ def stft2048_c2c(y: torch.Tensor, hop: int = 512, center: bool = True, window="h
     win = window_dev(window, win_length, 2048)
     tw = twiddle_dev(2048)
     out = torch.empty((B, Tn, 1025, 2), dtype=torch.float32, device=y.device)
-    rc = lib().syg_stft2048_c2c_f32(_ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(win), _ptr(tw),
-                                    _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft2048_c2c_f32")
+    _call("syg_stft2048_c2c_f32", _ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(out))
     return out
 
 
@@ -610,10 +610,8 @@ def logmel_dct(mel: torch.Tensor, n_mfcc: Optional[int] = 13, dct_type: int = 2,
         ref_is_max, ref_value = 1, 1.0
     else:
         ref_is_max, ref_value = 0, float(ref)
-    rc = lib().syg_logmel_dct_f32(_ptr(mel), B, M, Tn, _ptr(dct), K, _ptr(lif), float(amin),
-                                  float(top_db) if top_db is not None else -1.0, ref_is_max, ref_value,
-                                  _ptr(logmel), _ptr(mf), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_logmel_dct_f32")
+    _call("syg_logmel_dct_f32", _ptr(mel), B, M, Tn, _ptr(dct), K, _ptr(lif), float(amin),
+          float(top_db) if top_db is not None else -1.0, ref_is_max, ref_value, _ptr(logmel), _ptr(mf))
     return (logmel if keep_mel else mel), mf
 
 
@@ -636,10 +634,8 @@ def mel_mfcc(mel: torch.Tensor, n_mfcc: int = 13, dct_type: int = 2, norm="ortho
         ref_is_max, ref_value = 1, 1.0
     else:
         ref_is_max, ref_value = 0, float(ref)
-    rc = lib().syg_mel_mfcc_f32(_ptr(mel), B, M, Tn, _ptr(dct), K, _ptr(lif), float(amin),
-                                float(top_db) if top_db is not None else -1.0, ref_is_max, ref_value, _ptr(mf),
-                                C.c_void_p(_stream_ptr()))
-    check(rc, "syg_mel_mfcc_f32")
+    _call("syg_mel_mfcc_f32", _ptr(mel), B, M, Tn, _ptr(dct), K, _ptr(lif), float(amin),
+          float(top_db) if top_db is not None else -1.0, ref_is_max, ref_value, _ptr(mf))
     return mf
 
 
@@ -816,9 +812,7 @@ def fft_pow2(x: torch.Tensor, inverse: bool = False) -> torch.Tensor:
     x = x.contiguous()
     batch, n, _ = x.shape
     out = torch.empty_like(x)
-    rc = lib().syg_fft_pow2_c2c_f32(_ptr(x), _ptr(out), batch, n, int(inverse), _ptr(twiddle_dev(n)),
-                                    C.c_void_p(_stream_ptr()))
-    check(rc, "syg_fft_pow2_c2c_f32")
+    _call("syg_fft_pow2_c2c_f32", _ptr(x), _ptr(out), batch, n, int(inverse), _ptr(twiddle_dev(n)))
     return out
 
 
@@ -832,9 +826,8 @@ def stft_pow2(y: torch.Tensor, n_fft: int, hop: int, center: bool = True, window
     Tn = _frames(L, n_fft, hop, center)
     win = window_dev(window, win_length, n_fft)
     out = torch.empty((B, Tn, n_fft // 2 + 1, 2), dtype=torch.float32, device=y.device)
-    rc = lib().syg_stft_pow2_c2c_f32(_ptr(y), B, L, _ld(y), n_fft, hop, int(center), Tn, _ptr(win),
-                                     _ptr(twiddle_rfft_dev(n_fft)), _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_stft_pow2_c2c_f32")
+    _call("syg_stft_pow2_c2c_f32", _ptr(y), B, L, _ld(y), n_fft, hop, int(center), Tn, _ptr(win),
+          _ptr(twiddle_rfft_dev(n_fft)), _ptr(out))
     return out
 
 
@@ -861,9 +854,8 @@ def pack_frames(y: torch.Tensor, n_rows: int, length: int, step: int, first: int
     dcode = detrend_code(detrend)
     work = torch.empty(lib().syg_pack_rows_work_bytes(rows) // 8, dtype=torch.float64, device=y.device) if dcode else None
     base = y.data_ptr() + 4 * first * step
-    rc = lib().syg_pack_frames_f32(C.c_void_p(base), rows, length, step, n_rows, Lp, _ptr(window), dcode, 0, int(cplx),
-                                   _ptr(out), n_out, _ptr(work), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_pack_frames_f32")
+    _call("syg_pack_frames_f32", C.c_void_p(base), rows, length, step, n_rows, Lp, _ptr(window), dcode, 0, int(cplx),
+          _ptr(out), n_out, _ptr(work))
     return out
 
 
@@ -875,9 +867,7 @@ def stft_rows(y: torch.Tensor, n_fft: int, hop: int, center: bool = True, window
     B, L = y.shape
     win_length = n_fft if win_length is None else win_length
     pad = n_fft // 2 if center else 0
-    # librosa's count on the padded signal; equals num_frames() for even n_fft, one less for an odd n_fft when hop
-    # divides L (the padding is n_fft // 2 on both sides, one sample short of n_fft)
-    Tn = _at_least_one(1 + (L + 2 * pad - n_fft) // hop if L + 2 * pad >= n_fft else 0)
+    Tn = _at_least_one(num_frames_padded(L, n_fft, hop, center))       # librosa's count on the padded signal
     yp = y
     if pad or y.stride(1) != 1 or not y.is_contiguous():
         yp = torch.zeros((B, L + 2 * pad), dtype=torch.float32, device=y.device)     # zero padding: data movement only
@@ -906,8 +896,7 @@ def cabs_pow(x: torch.Tensor, power: int = 1) -> torch.Tensor:
     require_gpu()
     x = x.contiguous()
     out = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
-    rc = lib().syg_cabs_pow_f32(_ptr(x), out.numel(), int(power), _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_cabs_pow_f32")
+    _call("syg_cabs_pow_f32", _ptr(x), out.numel(), int(power), _ptr(out))
     return out
 
 
@@ -918,8 +907,7 @@ def mel_dense(P: torch.Tensor, basis: torch.Tensor) -> torch.Tensor:
     B, Tn, F = P.shape
     M = basis.shape[0]
     out = torch.empty((B, M, Tn), dtype=torch.float32, device=P.device)
-    rc = lib().syg_mel_dense_f32(_ptr(P), B, Tn, F, _ptr(basis), M, _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_mel_dense_f32")
+    _call("syg_mel_dense_f32", _ptr(P), B, Tn, F, _ptr(basis), M, _ptr(out))
     return out
 
 
@@ -933,9 +921,7 @@ def spectral_stats(mag: torch.Tensor, freqs: torch.Tensor, roll_percent: float =
     mag = mag.contiguous()
     N, F = mag.shape
     out = torch.empty((8, N), dtype=torch.float32, device=mag.device)
-    rc = lib().syg_spectral_stats_f32(_ptr(mag), N, F, _ptr(freqs), float(roll_percent), float(bw_p), _ptr(out),
-                                      C.c_void_p(_stream_ptr()))
-    check(rc, "syg_spectral_stats_f32")
+    _call("syg_spectral_stats_f32", _ptr(mag), N, F, _ptr(freqs), float(roll_percent), float(bw_p), _ptr(out))
     return out
 
 
@@ -951,9 +937,8 @@ def frame_stats(y: torch.Tensor, frame_length: int = 2048, hop: int = 512, cente
     B, L = y.shape
     Tn = _frames(L, frame_length, hop, center)
     out = torch.zeros((B, 9, Tn), dtype=torch.float32, device=y.device)
-    rc = lib().syg_frame_stats_f32(_ptr(y), B, L, _ld(y), int(frame_length), int(hop), int(center), Tn, int(num_bins),
-                                   int(mask), _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_frame_stats_f32")
+    _call("syg_frame_stats_f32", _ptr(y), B, L, _ld(y), int(frame_length), int(hop), int(center), Tn, int(num_bins),
+          int(mask), _ptr(out))
     return out
 
 
@@ -963,8 +948,7 @@ def rms_from_spec(S: torch.Tensor, frame_length: int) -> torch.Tensor:
     S = S.contiguous()
     N, F = S.shape
     out = torch.empty((N,), dtype=torch.float32, device=S.device)
-    rc = lib().syg_rms_from_spec_f32(_ptr(S), N, F, int(frame_length), _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_rms_from_spec_f32")
+    _call("syg_rms_from_spec_f32", _ptr(S), N, F, int(frame_length), _ptr(out))
     return out
 
 
@@ -975,9 +959,7 @@ def contrast_pv(mag: torch.Tensor, cplan: np.ndarray) -> torch.Tensor:
     N, F = mag.shape
     cplan = np.ascontiguousarray(cplan, dtype=np.int32)
     out = torch.empty((2, int(cplan[0]), N), dtype=torch.float32, device=mag.device)
-    rc = lib().syg_contrast_pv_f32(_ptr(mag), N, F, cplan.ctypes.data_as(C.c_void_p), _ptr(out),
-                                   C.c_void_p(_stream_ptr()))
-    check(rc, "syg_contrast_pv_f32")
+    _call("syg_contrast_pv_f32", _ptr(mag), N, F, cplan.ctypes.data_as(C.c_void_p), _ptr(out))
     return out
 
 
@@ -998,11 +980,8 @@ def sosfiltfilt(x: torch.Tensor, sos: np.ndarray, zi: np.ndarray, padlen: int) -
     # (0 bytes: the clip-resident form keeps the clip in registers and needs no workspace)
     work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device) if nbytes > 0 else None
     y = torch.empty((B, L), dtype=torch.float32, device=x.device)
-    rc = lib().syg_sosfiltfilt_f32(_ptr(x), B, L, _ld(x), sos.ctypes.data_as(C.c_void_p),
-                                   zi.ctypes.data_as(C.c_void_p), S, int(padlen), _ptr(y), _ld(y),
-                                   None if work is None else _ptr(work),
-                                   C.c_void_p(_stream_ptr()))
-    check(rc, "syg_sosfiltfilt_f32")
+    _call("syg_sosfiltfilt_f32", _ptr(x), B, L, _ld(x), sos.ctypes.data_as(C.c_void_p), zi.ctypes.data_as(C.c_void_p), S,
+          int(padlen), _ptr(y), _ld(y), None if work is None else _ptr(work))
     return y
 
 
@@ -1030,10 +1009,8 @@ def welch(x: torch.Tensor, nperseg: int, noverlap: int, nfft: int, window_host: 
     nbytes = lib().syg_welch_work_bytes(B, nfft)
     work = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
     out = torch.empty((B, nfft // 2 + 1), dtype=torch.float32, device=x.device)
-    rc = lib().syg_welch_f32(_ptr(x), B, L, _ld(x), nperseg, nperseg - noverlap, nfft, _ptr(win),
-                             _ptr(twiddle_rfft_dev(nfft)), detrend_code(detrend), float(scale), _ptr(out), _ptr(work),
-                             C.c_void_p(_stream_ptr()))
-    check(rc, "syg_welch_f32")
+    _call("syg_welch_f32", _ptr(x), B, L, _ld(x), nperseg, nperseg - noverlap, nfft, _ptr(win), _ptr(twiddle_rfft_dev(nfft)),
+          detrend_code(detrend), float(scale), _ptr(out), _ptr(work))
     return out
 
 
@@ -1050,16 +1027,15 @@ def welch_rows(x: torch.Tensor, nperseg: int, noverlap: int, nfft: int, window_h
     F = nfft // 2 + 1
     out = torch.empty((B, F), dtype=torch.float32, device=x.device)
     acc = torch.empty(F, dtype=torch.float64, device=x.device)
-    st = C.c_void_p(_stream_ptr())
     x = x.contiguous()
     for b in range(B):
         for s0 in range(0, nseg, MAX_ROWS):
             sc = min(MAX_ROWS, nseg - s0)
             X = fft_any(pack_frames(x[b:b + 1], sc, nperseg, step, s0, nfft, window=win, detrend=detrend))
             P = torch.empty((sc, F), dtype=torch.float32, device=x.device)
-            check(lib().syg_psd_onesided_f32(_ptr(X), sc, nfft, float(scale), _ptr(P), st), "syg_psd_onesided_f32")
-            check(lib().syg_col_mean_f32(_ptr(P), sc, F, _ptr(acc), int(s0 == 0), int(s0 + sc == nseg), float(nseg),
-                                         _ptr(out[b]), st), "syg_col_mean_f32")
+            _call("syg_psd_onesided_f32", _ptr(X), sc, nfft, float(scale), _ptr(P))
+            _call("syg_col_mean_f32", _ptr(P), sc, F, _ptr(acc), int(s0 == 0), int(s0 + sc == nseg), float(nseg),
+                  _ptr(out[b]))
     return out
 
 
@@ -1072,9 +1048,7 @@ def contrast_db(pv: torch.Tensor, amin: float = 1e-10, top_db: Optional[float] =
     pv = pv.contiguous()
     B, two, R, Tn = pv.shape
     out = torch.empty((B, R, Tn), dtype=torch.float32, device=pv.device)
-    rc = lib().syg_contrast_db_f32(_ptr(pv), B, R, Tn, float(amin), float(top_db) if top_db is not None else -1.0,
-                                   _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_contrast_db_f32")
+    _call("syg_contrast_db_f32", _ptr(pv), B, R, Tn, float(amin), float(top_db) if top_db is not None else -1.0, _ptr(out))
     return out
 
 
@@ -1084,10 +1058,8 @@ MAX_LDS_FFT = 8192
 
 def _fft_strided(x, out, outer, batch, n, inverse, strides, bign=0, scale=1.0):
     in_os, in_bs, in_es, out_os, out_bs, out_es = strides
-    rc = lib().syg_fft_pow2_strided_c2c_f32(_ptr(x), _ptr(out), outer, batch, n, int(inverse), _ptr(twiddle_dev(n)),
-                                            in_os, in_bs, in_es, out_os, out_bs, out_es, bign, float(scale),
-                                            C.c_void_p(_stream_ptr()))
-    check(rc, "syg_fft_pow2_strided_c2c_f32")
+    _call("syg_fft_pow2_strided_c2c_f32", _ptr(x), _ptr(out), outer, batch, n, int(inverse), _ptr(twiddle_dev(n)), in_os,
+          in_bs, in_es, out_os, out_bs, out_es, bign, float(scale))
 
 
 def fft_pow2_any(x: torch.Tensor, inverse: bool = False) -> torch.Tensor:
@@ -1116,9 +1088,7 @@ def cmul(a: torch.Tensor, b: torch.Tensor, conj_b: bool = False, out: Optional[t
     """a [.., na, 2] * b [nb, 2] broadcast over i mod nb."""
     a = a.contiguous(); b = b.contiguous()
     out = torch.empty_like(a) if out is None else out
-    rc = lib().syg_cmul_c64(_ptr(a), _ptr(b), _ptr(out), a.numel() // 2, b.numel() // 2, int(conj_b),
-                            C.c_void_p(_stream_ptr()))
-    check(rc, "syg_cmul_c64")
+    _call("syg_cmul_c64", _ptr(a), _ptr(b), _ptr(out), a.numel() // 2, b.numel() // 2, int(conj_b))
     return out
 
 
@@ -1128,9 +1098,7 @@ def pack_real(x: torch.Tensor, n: int, window: Optional[torch.Tensor] = None) ->
         x = x.contiguous()
     rows, ln = x.shape
     out = torch.empty((rows, n, 2), dtype=torch.float32, device=x.device)
-    rc = lib().syg_pack_real_c64(_ptr(x), rows, ln, _ld(x), _ptr(window), _ptr(out), n,
-                                 C.c_void_p(_stream_ptr()))
-    check(rc, "syg_pack_real_c64")
+    _call("syg_pack_real_c64", _ptr(x), rows, ln, _ld(x), _ptr(window), _ptr(out), n)
     return out
 
 
@@ -1186,10 +1154,8 @@ def _is_smooth(n: int) -> bool:
 
 def _fft_mixed_strided(x, out, outer, batch, n, inverse, strides, bign=0, scale=1.0):
     in_os, in_bs, in_es, out_os, out_bs, out_es = strides
-    rc = lib().syg_fft_mixed_strided_c2c_f32(_ptr(x), _ptr(out), outer, batch, n, int(inverse), _ptr(twiddle_dev(n)),
-                                             in_os, in_bs, in_es, out_os, out_bs, out_es, bign, float(scale),
-                                             C.c_void_p(_stream_ptr()))
-    check(rc, "syg_fft_mixed_strided_c2c_f32")
+    _call("syg_fft_mixed_strided_c2c_f32", _ptr(x), _ptr(out), outer, batch, n, int(inverse), _ptr(twiddle_dev(n)), in_os,
+          in_bs, in_es, out_os, out_bs, out_es, bign, float(scale))
 
 
 def fft_smooth(x: torch.Tensor, inverse: bool = False) -> torch.Tensor:
@@ -1256,7 +1222,7 @@ def col_stats(x: torch.Tensor) -> torch.Tensor:
     x = _mat32(x)
     n, F = x.shape
     out = torch.empty((5, F), dtype=torch.float64, device=x.device)
-    check(lib().syg_col_stats_f32(_ptr(x), n, F, _ptr(out), C.c_void_p(_stream_ptr())), "syg_col_stats_f32")
+    _call("syg_col_stats_f32", _ptr(x), n, F, _ptr(out))
     return out
 
 
@@ -1269,8 +1235,7 @@ def affine_cols(x: torch.Tensor, sub, mul, add) -> torch.Tensor:
     if any(v.shape != (F,) for v in vecs):
         raise ValueError(f"sub / mul / add must have length {F}")
     out = torch.empty_like(x)
-    check(lib().syg_affine_cols_f32(_ptr(x), n, F, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(out),
-                                    C.c_void_p(_stream_ptr())), "syg_affine_cols_f32")
+    _call("syg_affine_cols_f32", _ptr(x), n, F, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), _ptr(out))
     return out
 
 
@@ -1283,8 +1248,7 @@ def col_quantiles(x: torch.Tensor, q) -> torch.Tensor:
         raise ValueError("q must be fractions in [0, 1]")
     qd = torch.from_numpy(qv).to(x.device)
     out = torch.empty((qv.size, F), dtype=torch.float64, device=x.device)
-    check(lib().syg_col_quantiles_f32(_ptr(x), n, F, _ptr(qd), int(qv.size), _ptr(out), C.c_void_p(_stream_ptr())),
-          "syg_col_quantiles_f32")
+    _call("syg_col_quantiles_f32", _ptr(x), n, F, _ptr(qd), int(qv.size), _ptr(out))
     return out
 
 
@@ -1294,7 +1258,7 @@ def zoom2d(img: torch.Tensor, out_shape, order: int = 1) -> torch.Tensor:
     H, W = img.shape
     H2, W2 = int(out_shape[0]), int(out_shape[1])
     out = torch.empty((H2, W2), dtype=torch.float32, device=img.device)
-    check(lib().syg_zoom_f32(_ptr(img), H, W, H2, W2, int(order), _ptr(out), C.c_void_p(_stream_ptr())), "syg_zoom_f32")
+    _call("syg_zoom_f32", _ptr(img), H, W, H2, W2, int(order), _ptr(out))
     return out
 
 
@@ -1315,9 +1279,7 @@ def pcm_to_f32(pcm: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
         out = torch.empty((B, L), dtype=torch.float32, device=pcm.device)
     elif out.shape != (B, L) or out.dtype != torch.float32 or out.stride(1) != 1:
         raise ValueError("out must be a float32 [B, L] tensor with unit inner stride")
-    rc = lib().syg_pcm_to_f32(_ptr(pcm), _PCM_BITS[pcm.dtype], B, L, Cn, L * Cn, _ptr(out), _ld(out),
-                              C.c_void_p(_stream_ptr()))
-    check(rc, "syg_pcm_to_f32")
+    _call("syg_pcm_to_f32", _ptr(pcm), _PCM_BITS[pcm.dtype], B, L, Cn, L * Cn, _ptr(out), _ld(out))
     return out
 
 
@@ -1337,9 +1299,8 @@ def pack_rows(x: torch.Tensor, n: int, window: Optional[torch.Tensor] = None, de
     dcode = detrend_code(detrend)
     if dcode:
         work = torch.empty(lib().syg_pack_rows_work_bytes(rows) // 8, dtype=torch.float64, device=x.device)
-    rc = lib().syg_pack_rows_f32(_ptr(x), rows, ln, _ld(x), _ptr(window), dcode, int(bool(reverse)),
-                                 int(bool(cplx)), _ptr(out), n, _ptr(work), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_pack_rows_f32")
+    _call("syg_pack_rows_f32", _ptr(x), rows, ln, _ld(x), _ptr(window), dcode, int(bool(reverse)), int(bool(cplx)),
+          _ptr(out), n, _ptr(work))
     return out
 
 
@@ -1368,8 +1329,7 @@ def rfft_conv(x: torch.Tensor, k: torch.Tensor, reverse_k: bool = False) -> torc
     if za is None:
         za = fft_any(pack_rows(x, M).view(B, H, 2))
     zb = fft_any(pack_rows(k, M, reverse=reverse_k).view(Bk, H, 2))
-    rc = lib().syg_rconv_spectrum_c64(_ptr(za), _ptr(zb), B, Bk, H, _ptr(za), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_rconv_spectrum_c64")
+    _call("syg_rconv_spectrum_c64", _ptr(za), _ptr(zb), B, Bk, H, _ptr(za))
     return fft_any(za, True).view(B, M)[:, : n + m - 1]
 
 
@@ -1414,10 +1374,8 @@ def fft_pair_rows(x: torch.Tensor, H: int):
 
 def _strided_ex(kind, x, out, outer, batch, n, inverse, strides, bign=0, scale=1.0, flags=0, mask_n=0, in_valid=0):
     in_os, in_bs, in_es, out_os, out_bs, out_es = strides
-    fn = lib().syg_fft_pow2_strided_ex_f32 if kind == "pow2" else lib().syg_fft_mixed_strided_ex_f32
-    rc = fn(_ptr(x), _ptr(out), outer, batch, n, int(inverse), _ptr(twiddle_dev(n)), in_os, in_bs, in_es, out_os, out_bs,
-            out_es, bign, float(scale), int(flags), int(mask_n), int(in_valid), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_fft_%s_strided_ex_f32" % kind)
+    _call("syg_fft_%s_strided_ex_f32" % kind, _ptr(x), _ptr(out), outer, batch, n, int(inverse), _ptr(twiddle_dev(n)), in_os,
+          in_bs, in_es, out_os, out_bs, out_es, bign, float(scale), int(flags), int(mask_n), int(in_valid))
 
 
 def analytic_fused(x: torch.Tensor, magnitude: bool):
@@ -1456,8 +1414,7 @@ def analytic_signal(x: torch.Tensor) -> torch.Tensor:
         if fused is not None:
             return fused
     X = fft_any(pack_rows(x, n, cplx=True))
-    rc = lib().syg_analytic_mask_c64(_ptr(X), B, n, C.c_void_p(_stream_ptr()))
-    check(rc, "syg_analytic_mask_c64")
+    _call("syg_analytic_mask_c64", _ptr(X), B, n)
     return fft_any(X, True)
 
 
@@ -1468,8 +1425,7 @@ def periodogram(x: torch.Tensor, nfft: int, window_host: Optional[np.ndarray], d
     win = None if window_host is None else _dev(np.asarray(window_host, dtype=np.float32))
     X = fft_any(pack_rows(x, nfft, window=win, detrend=detrend, cplx=True))
     out = torch.empty((B, nfft // 2 + 1), dtype=torch.float32, device=x.device)
-    rc = lib().syg_psd_onesided_f32(_ptr(X), B, nfft, float(scale), _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_psd_onesided_f32")
+    _call("syg_psd_onesided_f32", _ptr(X), B, nfft, float(scale), _ptr(out))
     return out
 
 
@@ -1566,9 +1522,7 @@ def decimate2(x: torch.Tensor, taps: torch.Tensor, scale: float) -> torch.Tensor
         x = x.contiguous()
     B, L = x.shape
     y = torch.empty((B, (L + 1) // 2), dtype=torch.float32, device=x.device)
-    rc = lib().syg_decimate2_f32(_ptr(x), B, L, _ld(x), _ptr(taps), taps.numel(), float(scale), _ptr(y), _ld(y),
-                                 C.c_void_p(_stream_ptr()))
-    check(rc, "syg_decimate2_f32")
+    _call("syg_decimate2_f32", _ptr(x), B, L, _ld(x), _ptr(taps), taps.numel(), float(scale), _ptr(y), _ld(y))
     return y
 
 
@@ -1594,9 +1548,7 @@ def decimate2_chain(x: torch.Tensor, taps: torch.Tensor, scale: float, levels: i
             ys.append(torch.empty((B, lens), dtype=torch.float32, device=x.device) if need else None)
         yp = (C.c_void_p * n)(*[(_ptr(t) if t is not None else None) for t in ys])
         ld = (C.c_int64 * n)(*[(_ld(t) if t is not None else 0) for t in ys])
-        rc = lib().syg_decimate2_chain_f32(_ptr(cur), B, L, _ld(cur), _ptr(taps), taps.numel(), float(scale), n, yp, ld,
-                                           C.c_void_p(_stream_ptr()))
-        check(rc, "syg_decimate2_chain_f32")
+        _call("syg_decimate2_chain_f32", _ptr(cur), B, L, _ld(cur), _ptr(taps), taps.numel(), float(scale), n, yp, ld)
         out += [t if keep[s + j] else None for j, t in enumerate(ys)]
         cur = ys[-1]
         s += n
@@ -1668,11 +1620,9 @@ def cqt(y: torch.Tensor, sr: float, hop_length: int = 512, fmin=None, n_bins: in
     out = torch.empty((B, plan.n_bins, Tn, 2), dtype=torch.float32, device=y.device)      # every row is written
     s2 = float(np.sqrt(2.0))
     if one_launch:
-        rc = lib().syg_cqt_fused_f32(_ptr(y), B, L, _ld(y), _ptr(plan.taps_dev), plan.taps_dev.numel(), s2,
-                                     _ptr(plan.fused_tab_dev), plan.octaves[0]["n"], len(plan.octaves),
-                                     plan.row0.ctypes.data_as(C.c_void_p), Tn, _ptr(out), plan.n_bins * Tn,
-                                     C.c_void_p(_stream_ptr()))
-        check(rc, "syg_cqt_fused_f32")
+        _call("syg_cqt_fused_f32", _ptr(y), B, L, _ld(y), _ptr(plan.taps_dev), plan.taps_dev.numel(), s2,
+              _ptr(plan.fused_tab_dev), plan.octaves[0]["n"], len(plan.octaves), plan.row0.ctypes.data_as(C.c_void_p), Tn,
+              _ptr(out), plan.n_bins * Tn)
         return out
     # octave kernel (route): "bf16x3" (default: the framed product with bfloat16-split operands, fp32-equivalent), "gemm"
     # (the single-instruction fp32 MFMA form), "fft" (rfft x sparse rows; also what other frame lengths take)
@@ -1770,11 +1720,9 @@ def pitch_frames(y: torch.Tensor, sr: float, fmin: float, fmax: float, frame_len
         ptab = _cached(("pyin_tab", K), lambda: _dev(P.pyin_device_table(K)))
     else:
         raise ValueError(f"Unsupported pitch estimation method: {mode}. Choose 'pyin' or 'yin'.")
-    rc = lib().syg_pitch_frames_f32(_ptr(y), B, L, _ld(y), int(frame_length), win_length, hop, int(center), Tn, float(sr),
-                                    min_p, max_p, 0 if mode == "yin" else 1, float(trough_threshold), float(fmin), n_bins,
-                                    _ptr(ptab), K, _ptr(twiddle_dev(2048)), _ptr(f0), _ptr(cb), _ptr(cp), _ptr(cc),
-                                    _ptr(vp), _ptr(cm), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_pitch_frames_f32")
+    _call("syg_pitch_frames_f32", _ptr(y), B, L, _ld(y), int(frame_length), win_length, hop, int(center), Tn, float(sr),
+          min_p, max_p, 0 if mode == "yin" else 1, float(trough_threshold), float(fmin), n_bins, _ptr(ptab), K,
+          _ptr(twiddle_dev(2048)), _ptr(f0), _ptr(cb), _ptr(cp), _ptr(cc), _ptr(vp), _ptr(cm))
     out.update(f0=f0, cand_bin=cb, cand_prob=cp, cand_count=cc, voiced_prob=vp, cmndf=cm)
     return out
 
@@ -1796,11 +1744,9 @@ def pyin_viterbi(cand_bin: torch.Tensor, cand_prob: torch.Tensor, cand_count: to
     f0 = torch.empty((B, Tn), dtype=torch.float32, device=dev)
     voiced = torch.empty((B, Tn), dtype=torch.uint8, device=dev)
     state = torch.empty((B, Tn), dtype=torch.int32, device=dev)
-    rc = lib().syg_pyin_viterbi_f32(_ptr(cand_bin.contiguous()), _ptr(cand_prob.contiguous()), _ptr(cand_count.contiguous()),
-                                    _ptr(voiced_prob.contiguous()), B, Tn, K, int(n_bins), h, _ptr(ltab), R,
-                                    lconst.ctypes.data_as(C.c_void_p), float(fmin), _ptr(work), wb, _ptr(f0), _ptr(voiced),
-                                    _ptr(state), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_pyin_viterbi_f32")
+    _call("syg_pyin_viterbi_f32", _ptr(cand_bin.contiguous()), _ptr(cand_prob.contiguous()), _ptr(cand_count.contiguous()),
+          _ptr(voiced_prob.contiguous()), B, Tn, K, int(n_bins), h, _ptr(ltab), R, lconst.ctypes.data_as(C.c_void_p),
+          float(fmin), _ptr(work), wb, _ptr(f0), _ptr(voiced), _ptr(state))
     return f0, voiced.bool(), state
 
 
@@ -1869,11 +1815,9 @@ def istft2048(D: torch.Tensor, hop: int = 512, length: Optional[int] = None, cen
         if m is not None and (m.shape != (B, Tn, 1025) or m.dtype != torch.float32):
             raise ValueError("mask must be float32 [B, T, 1025]")
     outs = [torch.zeros((B, ld), dtype=torch.float32, device=D.device) for _ in masks]
-    rc = lib().syg_istft2048_f32(_ptr(D), B, Tn, int(hop), int(bool(center)), length, _ptr(window64_dev()),
-                                 _ptr(twiddle_dev(2048)), _ptr(masks[0]), _ptr(outs[0]),
-                                 _ptr(masks[1]) if two else None, _ptr(outs[1]) if two else None, ld,
-                                 C.c_void_p(_stream_ptr()))
-    check(rc, "syg_istft2048_f32")
+    _call("syg_istft2048_f32", _ptr(D), B, Tn, int(hop), int(bool(center)), length, _ptr(window64_dev()),
+          _ptr(twiddle_dev(2048)), _ptr(masks[0]), _ptr(outs[0]), _ptr(masks[1]) if two else None,
+          _ptr(outs[1]) if two else None, ld)
     outs = [o[:, :length] for o in outs]
     return tuple(outs) if two else outs[0]
 
@@ -1895,9 +1839,8 @@ def hpss_masks(D: torch.Tensor, kernel_size=31, power: float = 2.0, margin=1.0, 
     new = lambda: torch.empty((B, Tn, 1025), dtype=torch.float32, device=D.device)  # noqa: E731
     Mh, Mp = new(), new()
     H, P = (new(), new()) if medians else (None, None)
-    rc = lib().syg_hpss_masks_f32(_ptr(D), B, Tn, int(kh), int(kp), float(power), float(mh), float(mp), _ptr(Mh),
-                                  _ptr(Mp), _ptr(H), _ptr(P), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_hpss_masks_f32")
+    _call("syg_hpss_masks_f32", _ptr(D), B, Tn, int(kh), int(kp), float(power), float(mh), float(mp), _ptr(Mh), _ptr(Mp),
+          _ptr(H), _ptr(P))
     return (Mh, Mp, H, P) if medians else (Mh, Mp)
 
 
@@ -1929,14 +1872,12 @@ def hnr_rows(y_harm: torch.Tensor, y_perc: torch.Tensor, frame_length: int = 204
     if yh.stride(1) != 1 or yp.stride(1) != 1 or _ld(yh) != _ld(yp):
         yh, yp = yh.contiguous(), yp.contiguous()
     B, L = yh.shape
-    Tn = _at_least_one(1 + (L + 2 * (frame_length // 2) - frame_length) // hop if center else (
-        1 + (L - frame_length) // hop if L >= frame_length else 0))
+    Tn = _at_least_one(num_frames_padded(L, frame_length, hop, center))
     out = torch.empty((B, Tn), dtype=torch.float32, device=yh.device)
     rh = torch.empty_like(out) if rms else None
     rp = torch.empty_like(out) if rms else None
-    rc = lib().syg_hnr_rows_f32(_ptr(yh), _ptr(yp), B, L, _ld(yh), int(frame_length), hop, int(bool(center)), Tn,
-                                _ptr(out), _ptr(rh), _ptr(rp), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_hnr_rows_f32")
+    _call("syg_hnr_rows_f32", _ptr(yh), _ptr(yp), B, L, _ld(yh), int(frame_length), hop, int(bool(center)), Tn, _ptr(out),
+          _ptr(rh), _ptr(rp))
     return (out, rh, rp) if rms else out
 
 
@@ -1956,14 +1897,11 @@ def onset_strength(mel: torch.Tensor, lag: int = 1, max_size: int = 1, pad: int 
     mel = mel.contiguous()
     B, M, Tn = mel.shape
     T_out = int(pad) + Tn - int(lag) if T_out is None else int(T_out)
-    h = lib()
-    wb = h.syg_onset_strength_work_bytes(B, M, Tn)
+    wb = lib().syg_onset_strength_work_bytes(B, M, Tn)
     work = torch.empty((wb // 4,), dtype=torch.float32, device=mel.device) if wb > 0 else None
     env = torch.empty((B, max(T_out, 0)), dtype=torch.float32, device=mel.device)
-    rc = h.syg_onset_strength_f32(_ptr(mel), B, M, Tn, float(amin), float(top_db) if top_db is not None else -1.0,
-                                  int(lag), int(max_size), int(pad), T_out, int(bool(detrend)), _ptr(env), _ptr(work),
-                                  C.c_void_p(_stream_ptr()))
-    check(rc, "syg_onset_strength_f32")
+    _call("syg_onset_strength_f32", _ptr(mel), B, M, Tn, float(amin), float(top_db) if top_db is not None else -1.0,
+          int(lag), int(max_size), int(pad), T_out, int(bool(detrend)), _ptr(env), _ptr(work))
     return env
 
 
@@ -1981,10 +1919,8 @@ def onset_peaks(env: torch.Tensor, pre_max: int, post_max: int, pre_avg: int, po
             env, energy = env.contiguous(), energy.contiguous()
     frames = torch.empty((B, Tn), dtype=torch.int32, device=env.device)
     count = torch.empty((B,), dtype=torch.int32, device=env.device)
-    rc = lib().syg_onset_peaks_f32(_ptr(env), B, Tn, _ld(env), int(pre_max), int(post_max), int(pre_avg), int(post_avg),
-                                   float(delta), int(wait), int(bool(normalize)), int(bool(backtrack)), _ptr(energy),
-                                   _ptr(frames), _ptr(count), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_onset_peaks_f32")
+    _call("syg_onset_peaks_f32", _ptr(env), B, Tn, _ld(env), int(pre_max), int(post_max), int(pre_avg), int(post_avg),
+          float(delta), int(wait), int(bool(normalize)), int(bool(backtrack)), _ptr(energy), _ptr(frames), _ptr(count))
     return frames, count
 
 
@@ -1993,8 +1929,7 @@ def clip_metrics(y: torch.Tensor) -> torch.Tensor:
     y = _clips(y)
     B, L = y.shape
     out = torch.empty((B, 2), dtype=torch.float32, device=y.device)
-    rc = lib().syg_clip_metrics_f32(_ptr(y), B, L, _ld(y), _ptr(out), C.c_void_p(_stream_ptr()))
-    check(rc, "syg_clip_metrics_f32")
+    _call("syg_clip_metrics_f32", _ptr(y), B, L, _ld(y), _ptr(out))
     return out
 
 
@@ -2033,9 +1968,7 @@ def dwt(y: torch.Tensor, wavelet="db4", level: Optional[int] = None, mode: str =
     wb = h.syg_dwt_work_bytes(B, L, F, level)
     work = torch.empty((wb // 4,), dtype=torch.float32, device=y.device) if wb > 0 else None
     out = torch.empty((B, total), dtype=torch.float32, device=y.device)
-    rc = h.syg_dwt_f32(_ptr(y), B, L, _ld(y), _ptr(dec_lo), _ptr(dec_hi), F, code, level, _ptr(out), total, _ptr(work),
-                       C.c_void_p(_stream_ptr()))
-    check(rc, "syg_dwt_f32")
+    _call("syg_dwt_f32", _ptr(y), B, L, _ld(y), _ptr(dec_lo), _ptr(dec_hi), F, code, level, _ptr(out), total, _ptr(work))
     return out, [int(v) for v in lens_c]
 
 
@@ -2062,7 +1995,5 @@ def idwt(packed: torch.Tensor, lens, wavelet="db4", mode: str = "symmetric") -> 
         check(-1, "syg_idwt_work_bytes")
     work = torch.empty((wb // 4,), dtype=torch.float32, device=packed.device) if wb > 0 else None
     y = torch.empty((B, Lout), dtype=torch.float32, device=packed.device)
-    rc = h.syg_idwt_f32(_ptr(packed), B, _ld(packed), lp, levels, _ptr(rec_lo), _ptr(rec_hi), F, _ptr(y), Lout, _ptr(work),
-                        C.c_void_p(_stream_ptr()))
-    check(rc, "syg_idwt_f32")
+    _call("syg_idwt_f32", _ptr(packed), B, _ld(packed), lp, levels, _ptr(rec_lo), _ptr(rec_hi), F, _ptr(y), Lout, _ptr(work))
     return y
