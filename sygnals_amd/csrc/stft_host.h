@@ -1,6 +1,6 @@
 // Host side of the fused STFT front ends (stft_mel.hip, stft_mel_pow2.hip, stft_mel_w1024_seg.hip, stft_mel_w4096.hip,
-// stft_mel_wseg_small.hip) on top of host.h: the argument checks their entry points share and the contrast plan and row
-// arguments a rows entry point hands to its kernel.  No device code.  `who` names the entry point in the message; every
+// stft_mel_wseg_small.hip) on top of host.h: the argument checks their entry points share and the contrast plan, row
+// and MFCC arguments an entry point hands to its kernel.  No device code.  `who` names the entry point in the message; every
 // check returns SYG_OK or sets the last error and returns the code to pass on.
 #pragma once
 #include "host.h"
@@ -66,6 +66,24 @@ int fill_row_args(const char* who, int n_fft, int64_t T, float sr, float roll_pe
   rw.binhz = sr / (float)n_fft; rw.roll_percent = roll_percent; rw.bw_p = bw_p; rw.smask = stats_mask;
   rw.stats_out = stats_out; rw.contrast_out = contrast_out;
   return rc;
+}
+
+// The dB + DCT arguments of an MFCC entry point, checked, as the members the kernels' argument structs share (MfccArgs of
+// stft_mel.hip, Pow2Mfcc of stft_mel_pow2.hip; what else a struct holds -- padded frame count, row stride -- is the caller's).
+//   count_rule      the entry point's wording of the n_mfcc rule: a format that is given (who, n_mfcc, n_mels)
+//   rows_per_clip   rows between two clips of `out` (n_mfcc where the entry point has no such argument)
+//   frame_limit     T must stay below it (0: the entry point has no limit of its own)
+template <class Mfcc>
+int fill_mfcc_args(const char* who, const char* count_rule, int n_mels, const float* dct, int n_mfcc, int rows_per_clip,
+                   const float* lifter, float amin, float top_db, int ref_is_max, float ref_value, float* out, int64_t T,
+                   int64_t frame_limit, Mfcc& mf) {
+  SYG_REQUIRE(n_mfcc >= 1 && n_mfcc <= n_mels && rows_per_clip >= n_mfcc, count_rule, who, n_mfcc, n_mels);
+  SYG_REQUIRE(amin >= 1.17549435e-38f, "%s: amin must be strictly positive (a normal float)", who);
+  SYG_REQUIRE(ref_is_max == 0 || ref_is_max == 1, "%s: ref_is_max must be 0 or 1", who);
+  SYG_REQUIRE(frame_limit == 0 || T < frame_limit, "%s: clip too long", who);
+  mf.dct = dct; mf.lifter = lifter; mf.out = out; mf.n_mfcc = n_mfcc; mf.ref_is_max = ref_is_max;
+  mf.ref_value = ref_value; mf.amin = amin; mf.top_db = top_db;
+  return SYG_OK;
 }
 
 // piece table of the segment-sum projection (sygnals_amd._tables.pack_mel_segments / pack_mel_segments_rows) on the device

@@ -17,10 +17,25 @@
 //            16-byte load (pre-loaded behind barrier A); then the next frame is fetched LDS -> registers.
 //   barrier B
 //   reduce   the DMA of the tile after next is started; partial 16 x W tiles are combined in a fixed order
-//            (deterministic) into mel[b, m, t] (MODE 0/1) or the clip's LDS mel matrix (MODE 3).
-//   MODE 1   per-frame spectral statistics and contrast tail means from the same LDS rows (+ one barrier).
-//   MODE 3   at a clip's last tile: power_to_db + DCT-II from the LDS mel matrix inside the next tile's projection
-//            phase -- only MFCCs are written.   MODE 2: complex STFT output instead of the projection.
+//            (deterministic) into mel[b, m, t] or the clip's LDS mel matrix.
+// That is the matrix form of the projection.  What a launch does beyond the transform is its Mode (the enumeration and
+// its table of properties, mode_traits(), stand in front of the kernel; kernel and launcher read nothing else):
+//   MODE name          waves   entry point: what it does
+//    0   Mel           8 | 16  syg_stft2048_mel_f32: mel by weight matrix -> mel[b, m, t]
+//    1   MelRows       8 | 16  ... with stats_out / contrast_out: + per-frame statistics and contrast tail means from the
+//                              same LDS rows, behind barrier B (the "row functions", row_features.h)
+//    2   Complex       8       syg_stft2048_c2c_f32: complex STFT output, nothing projected
+//    3   ClipMatrix    16      syg_stft2048_mfcc_f32: MODE 0 into the clip's LDS mel matrix; at a clip's last tile
+//                              power_to_db + DCT-II inside the next tile's projection phase -- only MFCCs are written
+//    6   ClipSeg       16      syg_stft2048_mfcc_tri_f32: MODE 3 with the projection by segment sums, one wave per row
+//                              (tri_project: no weight matrix, no barrier A, no slab)
+//    7   ClipSegRows   16      syg_stft2048_features_tri_f32: MODE 6 + the row functions, MFCC, statistics and contrast
+//                              rows from one launch; syg_stft2048_stats_f32: the same without a table, row functions alone
+//    8   TileSeg4      8 | 16  syg_stft2048_mel_tri_f32, n_segtab = 2048: the tile form of MODE 6 with a FOUR-pass table (up
+//                              to 256 pieces) -- every frame's mel column straight to HBM, tiles shared out evenly over the
+//                              workgroups, no clip epilogue;   9 TileSeg4Rows: + the row functions
+//   10   TileSeg2      8 | 16  ... n_segtab = 1024: MODE 8 with the TWO-pass table of MODE 6;  11 TileSeg2Rows: + row functions
+// Every (waves, mode) is built for the three frame load paths (LOAD 0 / 1 / 2, see fetch_frame()).
 // Nothing but the input samples and the outputs touches HBM.
 //
 // Reference behaviour reproduced: librosa.stft (center zero padding, periodic window, rfft) -> np.abs ->
@@ -40,7 +55,6 @@
 namespace syg {
 namespace {
 
-constexpr bool X2_MEL = true;    // mel-only modes keep 4 |X|^2 in the power rows (see stft2048_kernel)
 constexpr int NFFT = 2048;
 constexpr int MC = 1024;         // complex points per frame
 constexpr int NBIN = 1025;
@@ -400,9 +414,7 @@ __device__ __forceinline__ MfccArgs uni(const MfccArgs& a) {
 // (v_log_f32, 1 ulp: ~6e-6 dB at -100 dB; inputs are >= amin, never denormal; exactly 0 when x == ref).
 // Out of line (inlined, its scalars push the tile loop's SGPRs into spills); uni() re-scalarises the arguments.
 typedef __attribute__((address_space(3))) float* lds_fptr;     // (a generic pointer would make every access a flat_*)
-// ----------------------------------------------------------------------------------
-// MODE 6 / 7: the mel projection of ONE power row by ONE wave, by segment sums: tri_project<2>() of mel_segments.h
-// ----------------------------------------------------------------------------------
+// MODE 6 ... 11: the mel projection of ONE power row by ONE wave, by segment sums: tri_project<NPASS>() of mel_segments.h
 #include "mel_segments.h"
 
 template <int WAVES>
@@ -464,7 +476,6 @@ __device__ __noinline__ void clip_dct(int clipmel_addr, int red_addr, int dct_ad
 }
 
 // ----------------------------------------------------------------------------------
-// MODE 0: mel only   MODE 1: mel + per-frame statistics / contrast   MODE 2: complex STFT output
 // LOAD 0 / 1: frames read straight from global memory   LOAD 2: tiles staged in LDS by LDS-DMA (hop <= 512)
 //
 // LDS map (floats):  Pbuf [TILE_T][P_STRIDE] + 16   power rows; a wave's exchange scratch aliases ITS OWN row
@@ -499,40 +510,70 @@ struct Lds {
   static_assert(O_TW2 % 4 == 0 && O_WIN % 4 == 0 && O_STAGE % 4 == 0 && O_CPL % 4 == 0, "16-byte aligned LDS sections");
 };
 
-template <int WAVES, int LOAD, int MODE>
+// What a launch does: one enumerator per mode (the numbers are the ones DESIGN.md, profiles/ and the tests speak of), one
+// row of properties per enumerator.  A new mode is an enumerator, a row of mode_traits() and an entry point.
+enum class Mode : int {    // (what each does, who launches it: the table at the top of the file)
+  Mel = 0, MelRows = 1, Complex = 2, ClipMatrix = 3, ClipSeg = 6, ClipSegRows = 7,
+  TileSeg4 = 8, TileSeg4Rows = 9, TileSeg2 = 10, TileSeg2Rows = 11,
+};
+enum class Proj { None, Matrix, Segments };   // nothing / MFMA against the packed weight matrix / tri_project per wave
+constexpr bool X2_MEL = true;    // (false: no mode keeps 4 |X|^2 in its power rows)
+
+struct ModeTraits {
+  Proj proj;
+  int npass;          // passes of the piece table (Segments; the other layouts are those of two passes)
+  bool clip;          // the clip's mel matrix lives in LDS (whole clips per workgroup); dB + DCT epilogue at clip end
+  bool rowfn;         // the per-frame row functions run
+  bool complex_out;
+  bool power4;        // the power rows hold 4 |X|^2: wave_rfft2048<.., X2> leaves its halvings out, the factor is taken back
+                      // -- exactly, a power of two -- where mel values leave the kernel (at the store; the dB conversion of
+                      // a clip works on 4 x mel with 4 x amin and 4 x ref).  The row functions need the true powers.
+  bool relc;          // lane constants re-made per frame (see the tile loop)
+  constexpr bool seg() const { return proj == Proj::Segments; }
+  constexpr bool seg_tile() const { return seg() && !clip; }      // the tile form: mel columns to HBM, tiles shared out evenly
+  constexpr bool x2() const { return X2_MEL && power4; }
+  // mel matrices of a clip-resident mode: the segment form fills one while the DCT of the clip before reads the other
+  constexpr int clip_matrices() const { return seg() ? 2 : 1; }
+};
+constexpr ModeTraits mode_traits(Mode m) {
+  switch (m) {                //     proj          npass  clip   rowfn  complex power4 relc
+    case Mode::Mel:          return {Proj::Matrix,   2, false, false, false, true,  false};
+    case Mode::MelRows:      return {Proj::Matrix,   2, false, true,  false, false, false};
+    case Mode::Complex:      return {Proj::None,     2, false, false, true,  false, false};
+    case Mode::ClipMatrix:   return {Proj::Matrix,   2, true,  false, false, true,  false};
+    case Mode::ClipSeg:      return {Proj::Segments, 2, true,  false, false, true,  false};
+    case Mode::ClipSegRows:  return {Proj::Segments, 2, true,  true,  false, false, true};
+    case Mode::TileSeg4:     return {Proj::Segments, 4, false, false, false, true,  false};
+    case Mode::TileSeg4Rows: return {Proj::Segments, 4, false, true,  false, false, false};
+    case Mode::TileSeg2:     return {Proj::Segments, 2, false, false, false, true,  false};
+    case Mode::TileSeg2Rows: return {Proj::Segments, 2, false, true,  false, false, false};
+  }
+  return {};
+}
+// the LDS map of a mode (the segment-sum projection has no partial tiles, so no slab)
+template <int WAVES, Mode MODE>
+using ModeLds = Lds<WAVES, !mode_traits(MODE).seg(), mode_traits(MODE).npass>;
+
+template <int WAVES, int LOAD, Mode MODE>
 __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
     const float* __restrict__ y, int64_t L, int64_t ldy, int hop, int pad, int64_t T, int tiles_per_clip,
     int64_t total_tiles, int tiles_per_wg, const float2* __restrict__ win2, const float2* __restrict__ twid,
     const float* __restrict__ wpacked, MelPlan plan, int n_mels, float* __restrict__ mel_out, float binhz,
     float roll_percent, float bw_p, int smask, float* __restrict__ stats_out, ContrastPlan cplan,
     float* __restrict__ contrast_out, float2* __restrict__ cout, int dma_wide, MfccArgs mf) {
-  // MODE 6: MODE 3 with the per-wave projection by segment sums (tri_project); MODE 7: MODE 6 + the per-frame row
-  // functions of MODE 1 (statistics / contrast): config C4's four features from one launch, no mel matrix in HBM
-  // MODE 8: the tile form of MODE 6 -- the per-wave projection with a FOUR-pass table (up to 256 pieces: the reference's
-  // default 128 bands, 64 bands at 44.1 / 48 kHz), every frame's mel column written straight to HBM (a 128-band clip
-  // matrix does not fit the LDS beside the rows; syg_logmel_dct_f32 is the second launch), tiles shared out evenly over
-  // the workgroups (no whole-clip chunks: one long clip fills the chip); MODE 9: MODE 8 + the row functions of MODE 7
-  // MODE 10 / 11: MODE 8 / 9 with a TWO-pass table (filterbanks of up to 128 pieces, e.g. 40 bands) -- the tile form of
-  // MODE 6 / 7 without the clip-resident epilogue; with 8 waves two workgroups share a CU and drift out of phase
-  constexpr bool TRIMEL = (MODE >= 8 && MODE <= 11);
-  constexpr bool TRI = (MODE == 6 || MODE == 7 || TRIMEL);
-  constexpr int NPASS = (MODE == 8 || MODE == 9) ? 4 : 2;
+  constexpr ModeTraits M = mode_traits(MODE);
+  constexpr bool TRI = M.seg(), TRIMEL = M.seg_tile();   // per-wave projection by segment sums (tri_project); its tile form
+  constexpr int NPASS = M.npass;
   constexpr int TRI_ROW_BASE = (NPASS == 4) ? TRI4_ROW_BASE : 0;
-  typedef Lds<WAVES, !TRI, NPASS> LM;
+  typedef ModeLds<WAVES, MODE> LM;
   constexpr int SEG_WORDS = LM::SEG_WORDS;
   constexpr int NTHREADS = WAVES * 64;
   constexpr int TILE_T = WAVES;                                    // one frame per wave per tile
-  constexpr bool COMPLEX_OUT = (MODE == 2);
-  constexpr bool ROWFN = (MODE == 1 || MODE == 7 || MODE == 9 || MODE == 11);   // per-frame row functions (MODE 1: behind barrier B)
-  constexpr bool CLIPM = (MODE == 3 || MODE == 6 || MODE == 7);      // the clip's mel matrix lives in LDS; epilogue at clip end
-  // MODE 0 / 3 (mel only): the power rows hold 4 |X|^2 (wave_rfft2048<.., X2>); the factor is taken back -- exactly, a
-  // power of two -- where mel values leave the kernel (MODE 0: at the store; MODE 3: the dB conversion works on 4 x mel
-  // with 4 x amin and 4 x ref, the optional mel copy is scaled at its store).  MODE 1's statistics need the true powers.
-  constexpr bool X2 = X2_MEL && (MODE == 0 || MODE == 3 || MODE == 6 || MODE == 8 || MODE == 10);
+  constexpr bool COMPLEX_OUT = M.complex_out, ROWFN = M.rowfn, CLIPM = M.clip, X2 = M.x2();
 #ifdef SYG_DEV_NO_RELC
   constexpr bool RELC = false;                                       // (timeline builds: round 3's form, for the before / after table)
 #else
-  constexpr bool RELC = (MODE == 7);                                 // lane constants re-made per frame (see the tile loop)
+  constexpr bool RELC = M.relc;
 #endif
   constexpr float MELSC = X2 ? 0.25f : 1.f;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1029,16 +1070,11 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
                       (int)(uintptr_t)(lds_fptr)(clipmel + n_mels * mf.tp + WAVES), mf, n_mels, (int)T, (int)pend_b, w, lane);
   }
 #if SYG_DEV
-  if (MODE == 3 && lane < 12)
+  if (CLIPM && !TRI && lane < 12)
     mel_out[((int64_t)blockIdx.x * WAVES + w) * 16 + lane] = (float)tacc[lane] / (float)(tile_end - tile_begin);
   if (ROWFN && stats_out != nullptr && lane < 12)
     stats_out[((int64_t)blockIdx.x * WAVES + w) * 16 + lane] = (float)tacc[lane] / (float)(tile_end - tile_begin);
 #endif
-}
-
-template <int WAVES, bool SLAB = true, int NPASS = 2>
-constexpr size_t lds_bytes() {
-  return (size_t)Lds<WAVES, SLAB, NPASS>::TOTAL * sizeof(float);
 }
 
 // Workgroups per CU: two of 8 waves or one of 16; each takes a contiguous chunk of tiles.
@@ -1064,85 +1100,120 @@ int load_mode() {
   return (v >= 0 && v <= 2) ? v : 2;
 }
 
-int check_common(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
-                 const float* window, const float* twiddle, int waves) {
-  const int rc = check_clips("stft2048", y, B, L, ldy, NFFT, hop, center, T, window, twiddle);
-  if (rc) return rc;
-  SYG_REQUIRE(B * ((T + waves - 1) / waves) < (int64_t)0x7fffffff, "stft2048: grid too large");
-  return SYG_OK;
+// LDS accounting: the fixed map of the mode (ModeLds), and behind it what a clip-resident launch adds, for the 16-wave
+// forms that have one: n_mat mel matrices [n_mels][tp] (tp: padded frames per clip), each with the per-wave maxima
+// red[waves] of its clip, then the DCT rows [n_mfcc][n_mels] and the lifter [n_mfcc]
+constexpr int64_t LDS_LIMIT = 160 * 1024;
+constexpr int64_t clip_lds_bytes(int n_mat, int n_mels, int64_t tp, int n_mfcc, int waves) {
+  return (n_mat * ((int64_t)n_mels * tp + waves) + (int64_t)n_mfcc * (n_mels + 1)) * (int64_t)sizeof(float);
+}
+// the same from the frame count of a clip, for the mode's 16 waves
+template <Mode MODE>
+int64_t clip_lds_bytes(int n_mels, int64_t T, int n_mfcc) {
+  return clip_lds_bytes(mode_traits(MODE).clip_matrices(), n_mels, ((T + MAXW - 1) / MAXW) * MAXW, n_mfcc, MAXW);
+}
+// 2: `extra` bytes fit beside the stage buffer; 1: in the stage buffer's place (the launch then loads its frames straight
+// from global memory); 0: not at all.  LM: the mode's fixed map
+template <class LM>
+constexpr int clip_lds_fit(int64_t extra) {
+  constexpr int64_t fixed = (int64_t)LM::TOTAL * sizeof(float), stage = (int64_t)LM::STAGE_FLOATS * sizeof(float);
+  return fixed + extra <= LDS_LIMIT ? 2 : fixed - stage + extra <= LDS_LIMIT ? 1 : 0;
 }
 
-constexpr size_t LDS_LIMIT = 160 * 1024;
+// What a launch reads and writes, in groups; value-initialised (LaunchArgs a = {}), an entry point sets what it uses.
+//   clip: y [B, L] (row stride ldy) -> T frames per clip   mel: the filterbank's device table (packed weights + plan, or
+//   the piece table) and the mel output   st: statistics / contrast rows   load: the frame load path asked for
+struct ClipArgs { const float* y; int64_t B, L, ldy; int hop, center; int64_t T; const float* window; const float* twiddle; };
+struct MelArgs { const float* table; MelPlan plan; int n_mels; float* mel_out; };
+struct StatArgs { float binhz, roll_percent, bw_p; int smask; float* stats_out; ContrastPlan cp; float* contrast_out; };
+struct LaunchArgs { ClipArgs clip; MelArgs mel; StatArgs st; float* cout; MfccArgs mf; int load; hipStream_t stream; };
+// the MfccArgs of a launch without a dB + DCT epilogue
+MfccArgs no_mfcc() { MfccArgs mf = {}; mf.amin = 1e-10f; mf.top_db = -1.f; return mf; }
 
-template <int WAVES, int MODE>
-int launch(int load, const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
-           const float* window, const float* twiddle, const float* wpacked, const MelPlan& plan, int n_mels,
-           float* mel_out, float binhz, float roll_percent, float bw_p, int smask, float* stats_out,
-           const ContrastPlan& cp,
-           float* contrast_out, float* cout, hipStream_t st, MfccArgs mf = MfccArgs()) {
-  const int pad = center ? NFFT / 2 : 0;
-  const int tiles = (int)((T + WAVES - 1) / WAVES);
-  const int64_t total_tiles = B * tiles;
+template <int WAVES, Mode MODE>
+int launch(const LaunchArgs& a) {
+  constexpr ModeTraits M = mode_traits(MODE);
+  typedef ModeLds<WAVES, MODE> LM;
+  const ClipArgs& c = a.clip;
+  MfccArgs mf = a.mf;
+  const int n_mels = a.mel.n_mels;
+  const int pad = c.center ? NFFT / 2 : 0;
+  const int tiles = (int)((c.T + WAVES - 1) / WAVES);
+  const int64_t total_tiles = c.B * tiles;
   int wgs = 0, per = 0;
   persistent_grid(total_tiles, WAVES, wgs, per);
-  constexpr bool TRIMEL = (MODE >= 8 && MODE <= 11);     // tile form of the segment-sum projection
-  constexpr int TRIMEL_NPASS = (MODE == 8 || MODE == 9) ? 4 : 2;
-  constexpr bool TRI = (MODE == 6 || MODE == 7);
-  size_t lds = TRIMEL ? lds_bytes<WAVES, false, TRIMEL_NPASS>() : lds_bytes<WAVES, !TRI>();
-  size_t clip_extra = 0;
-  if (TRIMEL) mf.tp = tiles * WAVES;
-  if (MODE == 3 || TRI) {
+  size_t lds = (size_t)LM::TOTAL * sizeof(float);
+  int64_t clip_extra = 0;
+  if (M.seg() || M.clip) mf.tp = tiles * WAVES;
+  if (M.clip) {
     // whole clips per workgroup; the clip's mel matrix [n_mels][tiles * WAVES] sits behind the fixed LDS map
-    int cw = 0, cper = 0;
-    persistent_grid(B, WAVES, cw, cper);
-    per = cper * tiles;
-    wgs = cw;
-    mf.tp = tiles * WAVES;
-    if (X2_MEL && (MODE == 3 || MODE == 6)) { mf.amin *= 4.f; mf.ref_value *= 4.f; }     // the clip's mel matrix holds 4 x mel (exact scaling)
-    clip_extra = ((size_t)(TRI ? 2 : 1) * ((size_t)n_mels * mf.tp + WAVES) + (size_t)mf.n_mfcc * (n_mels + 1)) * sizeof(float);
+    persistent_grid(c.B, WAVES, wgs, per);
+    per *= tiles;
+    if (M.x2()) { mf.amin *= 4.f; mf.ref_value *= 4.f; }     // the clip's mel matrix holds 4 x mel (exact scaling)
+    clip_extra = clip_lds_bytes(M.clip_matrices(), n_mels, mf.tp, mf.n_mfcc, WAVES);
   }
   // staged tiles (LDS-DMA) need the tile's sample run to fit the stage buffer and 32-bit byte offsets
-  bool can_stage = (MODE != 2) && hop <= 512 && L < ((int64_t)1 << 28);
+  bool can_stage = !M.complex_out && c.hop <= 512 && c.L < ((int64_t)1 << 28);
   // a clip matrix that does not fit behind the stage buffer takes the buffer's place: frames straight from global memory
-  constexpr size_t STAGE_BYTES = (size_t)Lds<WAVES, !TRI>::STAGE_FLOATS * sizeof(float);
-  if ((MODE == 3 || TRI) && !TRIMEL && lds + clip_extra > LDS_LIMIT) can_stage = false;
+  if (M.clip && clip_lds_fit<LM>(clip_extra) < 2) can_stage = false;
+  int load = a.load;
   if (load == 2 && !can_stage) load = 1;
-  const bool vec2 = (hop % 2 == 0) && (ldy % 2 == 0) && (((uintptr_t)y) % 8 == 0);
+  const bool vec2 = (c.hop % 2 == 0) && (c.ldy % 2 == 0) && (((uintptr_t)c.y) % 8 == 0);
   if (load == 1 && !vec2) load = 0;
-  if ((MODE == 3 || TRI) && !TRIMEL) {
-    lds = lds - (load != 2 ? STAGE_BYTES : 0) + clip_extra;
-    SYG_REQUIRE(lds <= LDS_LIMIT, "stft2048_mfcc: the clip's mel matrix (%d x %d) does not fit the LDS left over (%zu B > %zu B); "
-                "use syg_stft2048_mel_f32 + syg_logmel_dct_f32", n_mels, mf.tp, lds, LDS_LIMIT);
+  if (M.clip) {
+    lds = lds - (load != 2 ? (size_t)LM::STAGE_FLOATS * sizeof(float) : 0) + (size_t)clip_extra;
+    SYG_REQUIRE(lds <= (size_t)LDS_LIMIT, "stft2048_mfcc: the clip's mel matrix (%d x %d) does not fit the LDS left over (%zu B > %zu B); "
+                "use syg_stft2048_mel_f32 + syg_logmel_dct_f32", n_mels, mf.tp, lds, (size_t)LDS_LIMIT);
   }
-  const int dma_wide = (hop % 4 == 0) && (pad % 4 == 0) && (ldy % 4 == 0) && (L % 4 == 0) && (((uintptr_t)y) % 16 == 0);
+  const int dma_wide = (c.hop % 4 == 0) && (pad % 4 == 0) && (c.ldy % 4 == 0) && (c.L % 4 == 0) && (((uintptr_t)c.y) % 16 == 0);
   auto kern = load == 2 ? stft2048_kernel<WAVES, 2, MODE>
                         : load == 1 ? stft2048_kernel<WAVES, 1, MODE> : stft2048_kernel<WAVES, 0, MODE>;
-  const size_t cap = (MODE == 3 || TRI) ? LDS_LIMIT : TRIMEL ? lds_bytes<WAVES, false, TRIMEL_NPASS>() : lds_bytes<WAVES>();
-  const int rc = reserve_dynamic_lds("stft2048", (const void*)kern, cap);
-  if (rc) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(WAVES * 64), lds, st, y, L, ldy, hop, pad, T,
-                     tiles, total_tiles, per, (const float2*)window, (const float2*)twiddle, wpacked, plan, n_mels,
-                     mel_out, binhz, roll_percent, bw_p, smask, stats_out, cp, contrast_out, (float2*)cout, dma_wide, mf);
+  const size_t cap = M.clip ? (size_t)LDS_LIMIT : (size_t)LM::TOTAL * sizeof(float);
+  if (const int rc = reserve_dynamic_lds("stft2048", (const void*)kern, cap)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(WAVES * 64), lds, a.stream, c.y, c.L, c.ldy, c.hop, pad, c.T,
+                     tiles, total_tiles, per, (const float2*)c.window, (const float2*)c.twiddle, a.mel.table, a.mel.plan,
+                     n_mels, a.mel.mel_out, a.st.binhz, a.st.roll_percent, a.st.bw_p, a.st.smask, a.st.stats_out, a.st.cp,
+                     a.st.contrast_out, (float2*)a.cout, dma_wide, mf);
   SYG_CHECK_LAUNCH("stft2048");
   return SYG_OK;
 }
+// mel per tile (no clip residency): the mode of (projection, table passes, row functions), for 8 or 16 waves
+constexpr Mode tile_mode(Proj proj, int npass, bool rows) {
+  return proj == Proj::Matrix ? (rows ? Mode::MelRows : Mode::Mel)
+         : npass == 4 ? (rows ? Mode::TileSeg4Rows : Mode::TileSeg4) : (rows ? Mode::TileSeg2Rows : Mode::TileSeg2);
+}
+template <int WAVES, Proj PROJ, int NPASS>
+int launch_tile(bool rows, const LaunchArgs& a) {
+  return rows ? launch<WAVES, tile_mode(PROJ, NPASS, true)>(a) : launch<WAVES, tile_mode(PROJ, NPASS, false)>(a);
+}
 
-}  // namespace
-}  // namespace syg
+// checks shared by the seven entry points; fills the clip group and what every launch needs beside it
+int fill_clip_args(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T, const float* window,
+                   const float* twiddle, int waves, void* stream, LaunchArgs& a) {
+  if (const int rc = check_clips("stft2048", y, B, L, ldy, NFFT, hop, center, T, window, twiddle)) return rc;
+  SYG_REQUIRE(B * ((T + waves - 1) / waves) < (int64_t)0x7fffffff, "stft2048: grid too large");
+  a.clip = {y, B, L, ldy, hop, center, T, window, twiddle};
+  a.load = load_mode(); a.stream = (hipStream_t)stream;
+  return SYG_OK;
+}
 
-using namespace syg;
+// statistics / contrast group of the entry points with row functions (the parameters are looked at only with stats_out)
+int fill_stat_args(const char* who, float sr, float roll_percent, float bw_p, int stats_mask, float* stats_out,
+                   const int32_t* cplan_host, float* contrast_out, StatArgs& st) {
+  int rc = parse_contrast_plan("stft2048", NBIN, contrast_out, cplan_host, st.cp);
+  if (!rc && stats_out) rc = check_stats_args(who, sr, roll_percent, bw_p, stats_mask);
+  st.binhz = sr / (float)NFFT; st.roll_percent = roll_percent; st.bw_p = bw_p; st.smask = stats_mask;
+  st.stats_out = stats_out; st.contrast_out = contrast_out;
+  return rc;
+}
 
-namespace syg {
-namespace {
 int parse_mel_plan(const char* who, const int32_t* plan_host, int n_mels, MelPlan& plan) {
   // plan_host: {2 (layout version), waves, steps, n_groups, table_off}
   SYG_REQUIRE(plan_host[0] == 2, "%s: mel plan layout %d, this library needs layout 2 (sygnals_amd._tables.pack_mel_plan)",
               who, plan_host[0]);
   const int waves = plan_host[1];
   SYG_REQUIRE(waves == 8 || waves == 16, "%s: plan must be built for 8 or 16 waves (got %d)", who, waves);
-  plan.steps = plan_host[2];
-  plan.n_groups = plan_host[3];
-  plan.table_off = plan_host[4];
+  plan.steps = plan_host[2]; plan.n_groups = plan_host[3]; plan.table_off = plan_host[4];
   SYG_REQUIRE(n_mels >= 1 && plan.n_groups == (n_mels + 3) / 4 && plan.n_groups <= 64,
               "%s: plan has %d groups of four mel rows, n_mels=%d needs %d (at most 64)", who, plan.n_groups, n_mels,
               (n_mels + 3) / 4);
@@ -1151,47 +1222,37 @@ int parse_mel_plan(const char* who, const int32_t* plan_host, int n_mels, MelPla
   static_assert(P_STRIDE % 2 == 0, "slot reads are 8-byte words");
   return SYG_OK;
 }
+
+constexpr int64_t CLIP_FRAMES_LIMIT = (int64_t)1 << 24;     // frames per clip of the forms that keep frame indices in 24 bits
+
 }  // namespace
 }  // namespace syg
+
+using namespace syg;
 
 extern "C" int syg_stft2048_mel_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center,
                                     int64_t T, const float* window, const float* twiddle, const float* wpacked,
                                     const int32_t* plan_host, int n_mels, float* mel_out, float sr,
                                     float roll_percent, float bw_p, int stats_mask, float* stats_out,
-                                    const int32_t* cplan_host,
-                                    float* contrast_out, void* stream) {
+                                    const int32_t* cplan_host, float* contrast_out, void* stream) {
   SYG_REQUIRE(wpacked && plan_host && mel_out, "stft2048_mel: null pointer argument");
-  MelPlan plan;
-  int rc = parse_mel_plan("stft2048_mel", plan_host, n_mels, plan);
+  LaunchArgs a = {};
+  int rc = parse_mel_plan("stft2048_mel", plan_host, n_mels, a.mel.plan);
   if (rc) return rc;
   const int waves = plan_host[1];
-  rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, waves);
-  if (rc) return rc;
-  ContrastPlan cp = {};
-  if ((rc = parse_contrast_plan("stft2048", NBIN, contrast_out, cplan_host, cp))) return rc;
-  if (stats_out && ((rc = check_stats_args("stft2048_mel", sr, roll_percent, bw_p, stats_mask)) ||
-                    (rc = check_row_frames("stft2048_mel", T)))) return rc;
-  const bool extra = (stats_out != nullptr) || (contrast_out != nullptr);
-  const int load = load_mode();
-  const float binhz = sr / (float)NFFT;
-  hipStream_t st = (hipStream_t)stream;
-#define SYG_LAUNCH(W, M)                                                                                        \
-  launch<W, M>(load, y, B, L, ldy, hop, center, T, window, twiddle, wpacked, plan, n_mels, mel_out, binhz,      \
-               roll_percent, bw_p, stats_mask, stats_out, cp, contrast_out, nullptr, st)
-  if (waves == 8) return extra ? SYG_LAUNCH(8, 1) : SYG_LAUNCH(8, 0);
-  return extra ? SYG_LAUNCH(16, 1) : SYG_LAUNCH(16, 0);
-#undef SYG_LAUNCH
+  if ((rc = fill_clip_args(y, B, L, ldy, hop, center, T, window, twiddle, waves, stream, a))) return rc;
+  if ((rc = fill_stat_args("stft2048_mel", sr, roll_percent, bw_p, stats_mask, stats_out, cplan_host, contrast_out, a.st))) return rc;
+  if (stats_out && (rc = check_row_frames("stft2048_mel", T))) return rc;
+  a.mel.table = wpacked; a.mel.n_mels = n_mels; a.mel.mel_out = mel_out;
+  const bool rows = (stats_out != nullptr) || (contrast_out != nullptr);
+  return waves == 8 ? launch_tile<8, Proj::Matrix, 2>(rows, a) : launch_tile<16, Proj::Matrix, 2>(rows, a);
 }
 
-// 1 when the clip-resident form has room for the clip's mel matrix + DCT rows + lifter behind the fixed LDS map
+// (1, the stage buffer's place: 128 bands x 94 frames; measured 186 against 196 us for the two-launch form there, 176 against
+// 166 at 64 bands)
 extern "C" int syg_stft2048_mfcc_fits(int n_mels, int64_t T, int n_mfcc) {
   if (n_mels < 1 || n_mels > 16 * MAXW || T < 1 || n_mfcc < 1 || n_mfcc > n_mels) return 0;
-  const int64_t tp = ((T + MAXW - 1) / MAXW) * MAXW;
-  // 2: beside the stage buffer; 1: in the stage buffer's place (the launch then loads its frames straight from global
-  // memory: 128 bands x 94 frames; measured 186 against 196 us for the two-launch form there, 176 against 166 at 64 bands)
-  const int64_t extra = ((int64_t)n_mels * tp + 16 + (int64_t)n_mfcc * (n_mels + 1)) * 4;
-  if ((int64_t)lds_bytes<16>() + extra <= (int64_t)LDS_LIMIT) return 2;
-  return (int64_t)lds_bytes<16>() - (int64_t)Lds<16>::STAGE_FLOATS * 4 + extra <= (int64_t)LDS_LIMIT ? 1 : 0;
+  return clip_lds_fit<ModeLds<16, Mode::ClipMatrix>>(clip_lds_bytes<Mode::ClipMatrix>(n_mels, T, n_mfcc));
 }
 
 extern "C" int syg_stft2048_mfcc_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center,
@@ -1200,36 +1261,23 @@ extern "C" int syg_stft2048_mfcc_f32(const float* y, int64_t B, int64_t L, int64
                                      const float* lifter, float amin, float top_db, int ref_is_max, float ref_value,
                                      float* mel_out, float* mfcc_out, void* stream) {
   SYG_REQUIRE(wpacked && plan_host && dct && mfcc_out, "stft2048_mfcc: null pointer argument");
-  MelPlan plan;
-  int rc = parse_mel_plan("stft2048_mfcc", plan_host, n_mels, plan);
+  LaunchArgs a = {};
+  int rc = parse_mel_plan("stft2048_mfcc", plan_host, n_mels, a.mel.plan);
   if (rc) return rc;
   SYG_REQUIRE(plan_host[1] == 16, "stft2048_mfcc: needs a 16-wave plan (got %d)", plan_host[1]);
-  rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, 16);
-  if (rc) return rc;
-  SYG_REQUIRE(n_mfcc >= 1 && n_mfcc <= n_mels, "stft2048_mfcc: need 1 <= n_mfcc <= n_mels (n_mfcc=%d n_mels=%d)",
-              n_mfcc, n_mels);
-  SYG_REQUIRE(amin >= 1.17549435e-38f, "stft2048_mfcc: amin must be strictly positive (a normal float)");
-  SYG_REQUIRE(ref_is_max == 0 || ref_is_max == 1, "stft2048_mfcc: ref_is_max must be 0 or 1");
-  SYG_REQUIRE(T < ((int64_t)1 << 24), "stft2048_mfcc: clip too long");
-  ContrastPlan cp;
-  memset(&cp, 0, sizeof(cp));
-  MfccArgs mf;
-  mf.dct = dct; mf.lifter = lifter; mf.out = mfcc_out; mf.n_mfcc = n_mfcc; mf.ref_is_max = ref_is_max;
-  mf.ref_value = ref_value; mf.amin = amin; mf.top_db = top_db; mf.tp = 0; mf.rows_per_clip = n_mfcc;
-  return launch<16, 3>(load_mode(), y, B, L, ldy, hop, center, T, window, twiddle, wpacked, plan, n_mels, mel_out, 0.f,
-                       0.f, 0.f, 0, nullptr, cp, nullptr, nullptr, (hipStream_t)stream, mf);
+  if ((rc = fill_clip_args(y, B, L, ldy, hop, center, T, window, twiddle, 16, stream, a))) return rc;
+  if ((rc = fill_mfcc_args("stft2048_mfcc", "%s: need 1 <= n_mfcc <= n_mels (n_mfcc=%d n_mels=%d)", n_mels, dct, n_mfcc, n_mfcc,
+                           lifter, amin, top_db, ref_is_max, ref_value, mfcc_out, T, CLIP_FRAMES_LIMIT, a.mf))) return rc;
+  a.mel.table = wpacked; a.mel.n_mels = n_mels; a.mel.mel_out = mel_out; a.mf.rows_per_clip = n_mfcc;
+  return launch<16, Mode::ClipMatrix>(a);
 }
 
-// MODE 6: syg_stft2048_mfcc_f32 for TRIANGULAR filterbanks, the mel projection by segment sums inside each wave
-// (tri_project; no weight matrix, no workgroup barrier in the projection).  segtab: the piece table of
-// sygnals_amd._tables.pack_mel_segments ([2][2][64][4] words on the device, n_segtab = 1024).  Same results as
-// the matrix form to rounding (both sum in float32; the affine pieces reproduce the float32 weights to 1e-7 of the
-// largest -- checked on the host when the table is built).
+// syg_stft2048_mfcc_f32 for TRIANGULAR filterbanks (segtab: pack_mel_segments, [2][2][64][4] words).  Same results as the
+// matrix form to rounding (both sum in float32; the affine pieces reproduce the float32 weights to 1e-7 of the largest --
+// checked on the host when the table is built).  Fits: the two mel matrices have room beside the stage buffer
 extern "C" int syg_stft2048_mfcc_tri_fits(int n_mels, int64_t T, int n_mfcc) {
   if (n_mels < 1 || n_mels > 127 || T < 1 || n_mfcc < 1 || n_mfcc > n_mels) return 0;
-  const int64_t tp = ((T + MAXW - 1) / MAXW) * MAXW;
-  const int64_t bytes = (int64_t)lds_bytes<16, false>() + (2 * ((int64_t)n_mels * tp + 16) + (int64_t)n_mfcc * (n_mels + 1)) * 4;
-  return bytes <= (int64_t)LDS_LIMIT ? 1 : 0;
+  return clip_lds_fit<ModeLds<16, Mode::ClipSeg>>(clip_lds_bytes<Mode::ClipSeg>(n_mels, T, n_mfcc)) == 2;
 }
 
 extern "C" int syg_stft2048_mfcc_tri_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center,
@@ -1238,27 +1286,17 @@ extern "C" int syg_stft2048_mfcc_tri_f32(const float* y, int64_t B, int64_t L, i
                                          float amin, float top_db, int ref_is_max, float ref_value, float* mfcc_out,
                                          void* stream) {
   SYG_REQUIRE(segtab && dct && mfcc_out, "stft2048_mfcc_tri: null pointer argument");
+  LaunchArgs a = {};
   int rc = check_segtab("stft2048_mfcc_tri", segtab, n_segtab, SEGTAB_WORDS, n_mels, 127);
-  if (!rc) rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, 16);
+  if (!rc) rc = fill_clip_args(y, B, L, ldy, hop, center, T, window, twiddle, 16, stream, a);
   if (rc) return rc;
-  SYG_REQUIRE(n_mfcc >= 1 && n_mfcc <= n_mels, "stft2048_mfcc_tri: need 1 <= n_mfcc <= n_mels (n_mfcc=%d n_mels=%d)", n_mfcc, n_mels);
-  SYG_REQUIRE(amin >= 1.17549435e-38f, "stft2048_mfcc_tri: amin must be strictly positive (a normal float)");
-  SYG_REQUIRE(ref_is_max == 0 || ref_is_max == 1, "stft2048_mfcc_tri: ref_is_max must be 0 or 1");
-  SYG_REQUIRE(T < ((int64_t)1 << 24), "stft2048_mfcc_tri: clip too long");
-  ContrastPlan cp;
-  memset(&cp, 0, sizeof(cp));
-  MelPlan plan;
-  memset(&plan, 0, sizeof(plan));
-  MfccArgs mf;
-  mf.dct = dct; mf.lifter = lifter; mf.out = mfcc_out; mf.n_mfcc = n_mfcc; mf.ref_is_max = ref_is_max;
-  mf.ref_value = ref_value; mf.amin = amin; mf.top_db = top_db; mf.tp = 0; mf.rows_per_clip = n_mfcc;
-  return launch<16, 6>(load_mode(), y, B, L, ldy, hop, center, T, window, twiddle, segtab, plan, n_mels, nullptr, 0.f,
-                       0.f, 0.f, 0, nullptr, cp, nullptr, nullptr, (hipStream_t)stream, mf);
+  if ((rc = fill_mfcc_args("stft2048_mfcc_tri", "%s: need 1 <= n_mfcc <= n_mels (n_mfcc=%d n_mels=%d)", n_mels, dct, n_mfcc, n_mfcc,
+                           lifter, amin, top_db, ref_is_max, ref_value, mfcc_out, T, CLIP_FRAMES_LIMIT, a.mf))) return rc;
+  a.mel.table = segtab; a.mel.n_mels = n_mels; a.mf.rows_per_clip = n_mfcc;
+  return launch<16, Mode::ClipSeg>(a);
 }
 
-// MODE 7: MFCC rows + statistics rows + contrast tail means from ONE launch, with the
-// segment-sum projection of syg_stft2048_mfcc_tri_f32 -- BASELINE config C4 without a mel matrix in HBM and without
-// the projection's barriers; the clip epilogue runs on the waves that have no frame (see MODE 6).
+// BASELINE config C4 from one launch, without a mel matrix in HBM and without the projection's barriers
 extern "C" int syg_stft2048_features_tri_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
                                              const float* window, const float* twiddle, const float* segtab, int n_segtab,
                                              int n_mels, const float* dct, int n_mfcc, const float* lifter, float amin,
@@ -1267,37 +1305,22 @@ extern "C" int syg_stft2048_features_tri_f32(const float* y, int64_t B, int64_t 
                                              float* contrast_out, float* mfcc_out, int mfcc_rows_per_clip, void* stream) {
   SYG_REQUIRE(segtab && dct && mfcc_out, "stft2048_features_tri: null pointer argument");
   SYG_REQUIRE(stats_out || contrast_out, "stft2048_features_tri: no statistics requested (use syg_stft2048_mfcc_tri_f32)");
+  LaunchArgs a = {};
   int rc = check_segtab("stft2048_features_tri", segtab, n_segtab, SEGTAB_WORDS, n_mels, 127);
-  if (!rc) rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, 16);
+  if (!rc) rc = fill_clip_args(y, B, L, ldy, hop, center, T, window, twiddle, 16, stream, a);
   if (rc) return rc;
-  SYG_REQUIRE(n_mfcc >= 1 && n_mfcc <= n_mels && mfcc_rows_per_clip >= n_mfcc,
-              "stft2048_features_tri: need 1 <= n_mfcc <= n_mels and mfcc_rows_per_clip >= n_mfcc");
-  SYG_REQUIRE(amin >= 1.17549435e-38f, "stft2048_features_tri: amin must be strictly positive (a normal float)");
-  SYG_REQUIRE(ref_is_max == 0 || ref_is_max == 1, "stft2048_features_tri: ref_is_max must be 0 or 1");
-  SYG_REQUIRE(T < ((int64_t)1 << 24), "stft2048_features_tri: clip too long");
-  ContrastPlan cp = {};
-  if ((rc = parse_contrast_plan("stft2048", NBIN, contrast_out, cplan_host, cp))) return rc;
-  if (stats_out && (rc = check_stats_args("stft2048_features_tri", sr, roll_percent, bw_p, stats_mask))) return rc;
-  MelPlan plan;
-  memset(&plan, 0, sizeof(plan));
-  MfccArgs mf;
-  mf.dct = dct; mf.lifter = lifter; mf.out = mfcc_out; mf.n_mfcc = n_mfcc; mf.ref_is_max = ref_is_max;
-  mf.ref_value = ref_value; mf.amin = amin; mf.top_db = top_db; mf.tp = 0; mf.rows_per_clip = mfcc_rows_per_clip;
-  return launch<16, 7>(load_mode(), y, B, L, ldy, hop, center, T, window, twiddle, segtab, plan, n_mels, nullptr,
-                       sr / (float)NFFT, roll_percent, bw_p, stats_mask, stats_out, cp, contrast_out, nullptr,
-                       (hipStream_t)stream, mf);
+  if ((rc = fill_mfcc_args("stft2048_features_tri", "%s: need 1 <= n_mfcc <= n_mels and mfcc_rows_per_clip >= n_mfcc", n_mels, dct,
+                           n_mfcc, mfcc_rows_per_clip, lifter, amin, top_db, ref_is_max, ref_value, mfcc_out, T, CLIP_FRAMES_LIMIT,
+                           a.mf))) return rc;
+  if ((rc = fill_stat_args("stft2048_features_tri", sr, roll_percent, bw_p, stats_mask, stats_out, cplan_host, contrast_out, a.st))) return rc;
+  a.mel.table = segtab; a.mel.n_mels = n_mels; a.mf.rows_per_clip = mfcc_rows_per_clip;
+  return launch<16, Mode::ClipSegRows>(a);
 }
 
-// MODE 8 ... 11: the TILE form of the segment-sum projection -- samples in, mel POWER out [B, n_mels, T] (no weight matrix,
-// no projection barriers, every frame's column written by the wave that transformed it); syg_logmel_dct_f32 /
-// syg_feature_block_f32 is the second launch of an MFCC.  Optional statistics / contrast rows from the same launch (the row
-// functions of syg_stft2048_features_tri_f32).  Tiles are shared out evenly over the workgroups, so one long clip
-// (BASELINE config C1) fills the chip.
-//   segtab   n_segtab = 2048: pack_mel_segments(..., n_pass=4, row_base=4), [4][2][64][4] words -- up to 256 pieces: the
-//            reference's default filterbank of 128 bands (manager.py:214), 64 ... 200 bands at the usual sample rates;
-//            n_segtab = 1024: the two-pass table of syg_stft2048_mfcc_tri_f32 (up to 128 pieces, e.g. 40 bands)
-//   waves    16 (one workgroup per CU) or 8 (two per CU, each with its own tile barriers: they drift out of phase, so that
-//            one's transforms run beside the other's LDS exchanges)
+// The tile form: mel POWER out, syg_logmel_dct_f32 / syg_feature_block_f32 is the second launch of an MFCC; one long clip
+// (BASELINE config C1) fills the chip.  Four passes: the reference's default filterbank of 128 bands (manager.py:214).
+// waves = 8: two workgroups per CU, each with its own tile barriers -- they drift out of phase, so that one's transforms
+// run beside the other's LDS exchanges
 extern "C" int syg_stft2048_mel_tri_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
                                         const float* window, const float* twiddle, const float* segtab, int n_segtab,
                                         int n_mels, float* mel_out, float sr, float roll_percent, float bw_p, int stats_mask,
@@ -1308,67 +1331,42 @@ extern "C" int syg_stft2048_mel_tri_f32(const float* y, int64_t B, int64_t L, in
   int rc = check_segtab("stft2048_mel_tri", segtab, n_segtab, n_segtab == SEGTAB_WORDS ? SEGTAB_WORDS : SEGTAB4_WORDS, n_mels, 255);
   if (rc) return rc;
   SYG_REQUIRE(waves == 8 || waves == 16, "stft2048_mel_tri: waves must be 8 or 16 (got %d)", waves);
-  if ((rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, waves))) return rc;
+  LaunchArgs a = {};
+  if ((rc = fill_clip_args(y, B, L, ldy, hop, center, T, window, twiddle, waves, stream, a))) return rc;
   SYG_REQUIRE(T * (int64_t)n_mels < ((int64_t)1 << 29), "stft2048_mel_tri: clip too long (32-bit byte offsets inside a clip's mel block)");
-  ContrastPlan cp = {};
-  if ((rc = parse_contrast_plan("stft2048", NBIN, contrast_out, cplan_host, cp))) return rc;
-  if (stats_out && (rc = check_stats_args("stft2048_mel_tri", sr, roll_percent, bw_p, stats_mask))) return rc;
-  MelPlan plan;
-  memset(&plan, 0, sizeof(plan));
-  MfccArgs mf;
-  memset(&mf, 0, sizeof(mf));
-  mf.amin = 1e-10f; mf.top_db = -1.f;
-  const bool extra = stats_out != nullptr || contrast_out != nullptr;
+  const bool rows = stats_out != nullptr || contrast_out != nullptr;
+  if (rows && (rc = fill_stat_args("stft2048_mel_tri", sr, roll_percent, bw_p, stats_mask, stats_out, cplan_host, contrast_out, a.st)))
+    return rc;
+  a.mel.table = segtab; a.mel.n_mels = n_mels; a.mel.mel_out = mel_out; a.mf = no_mfcc();
   const bool four = n_segtab == SEGTAB4_WORDS;
-  const float binhz = extra ? sr / (float)NFFT : 0.f;
-  if (!extra) { roll_percent = 0.f; bw_p = 0.f; stats_mask = 0; }
-#define SYG_LAUNCH(W, M)                                                                                               \
-  launch<W, M>(load_mode(), y, B, L, ldy, hop, center, T, window, twiddle, segtab, plan, n_mels, mel_out, binhz, roll_percent, \
-               bw_p, stats_mask, stats_out, cp, contrast_out, nullptr, (hipStream_t)stream, mf)
-  if (waves == 16) {
-    if (four) return extra ? SYG_LAUNCH(16, 9) : SYG_LAUNCH(16, 8);
-    return extra ? SYG_LAUNCH(16, 11) : SYG_LAUNCH(16, 10);
-  }
-  if (four) return extra ? SYG_LAUNCH(8, 9) : SYG_LAUNCH(8, 8);
-  return extra ? SYG_LAUNCH(8, 11) : SYG_LAUNCH(8, 10);
-#undef SYG_LAUNCH
+  if (waves == 16) return four ? launch_tile<16, Proj::Segments, 4>(rows, a) : launch_tile<16, Proj::Segments, 2>(rows, a);
+  return four ? launch_tile<8, Proj::Segments, 4>(rows, a) : launch_tile<8, Proj::Segments, 2>(rows, a);
 }
 
-// MODE 7 without a filterbank: the per-frame statistics / contrast tail means alone (spectral_centroid / bandwidth /
-// flatness / rolloff / contrast of manager.py:289-343 need no mel spectrogram) -- transform + row functions, nothing is
-// projected, no clip epilogue; the waves only meet at the two stage hand-over barriers and run their row functions in two
-// staggered halves (see MODE 7).  hop <= 512 (staged tiles); other hops: syg_stft2048_mel_f32.
+// syg_stft2048_features_tri_f32's mode without a filterbank: nothing is projected, no clip epilogue; the waves only meet at
+// the two stage hand-over barriers.  hop <= 512 (staged tiles); other hops: syg_stft2048_mel_f32.
 extern "C" int syg_stft2048_stats_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
                                       const float* window, const float* twiddle, float sr, float roll_percent, float bw_p,
                                       int stats_mask, float* stats_out, const int32_t* cplan_host, float* contrast_out,
                                       void* stream) {
   SYG_REQUIRE(stats_out || contrast_out, "stft2048_stats: no statistics requested");
-  int rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, 16);
+  LaunchArgs a = {};
+  int rc = fill_clip_args(y, B, L, ldy, hop, center, T, window, twiddle, 16, stream, a);
   if (rc) return rc;
   SYG_REQUIRE(hop <= 512 && L < ((int64_t)1 << 28), "stft2048_stats: needs hop <= 512 (staged tiles); use syg_stft2048_mel_f32");
-  SYG_REQUIRE(T < ((int64_t)1 << 24), "stft2048_stats: clip too long");
-  ContrastPlan cp = {};
-  if ((rc = parse_contrast_plan("stft2048", NBIN, contrast_out, cplan_host, cp))) return rc;
-  if (stats_out && (rc = check_stats_args("stft2048_stats", sr, roll_percent, bw_p, stats_mask))) return rc;
-  MelPlan plan;
-  memset(&plan, 0, sizeof(plan));
-  MfccArgs mf;
-  memset(&mf, 0, sizeof(mf));
-  mf.amin = 1e-10f; mf.top_db = -1.f;
-  return launch<16, 7>(2, y, B, L, ldy, hop, center, T, window, twiddle, nullptr, plan, 0, nullptr, sr / (float)NFFT,
-                       roll_percent, bw_p, stats_mask, stats_out, cp, contrast_out, nullptr, (hipStream_t)stream, mf);
+  SYG_REQUIRE(T < CLIP_FRAMES_LIMIT, "stft2048_stats: clip too long");
+  if ((rc = fill_stat_args("stft2048_stats", sr, roll_percent, bw_p, stats_mask, stats_out, cplan_host, contrast_out, a.st))) return rc;
+  a.mf = no_mfcc(); a.load = 2;
+  return launch<16, Mode::ClipSegRows>(a);
 }
 
 extern "C" int syg_stft2048_c2c_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center,
                                     int64_t T, const float* window, const float* twiddle, float* out,
                                     void* stream) {
-  int rc = check_common(y, B, L, ldy, hop, center, T, window, twiddle, 8);
+  LaunchArgs a = {};
+  const int rc = fill_clip_args(y, B, L, ldy, hop, center, T, window, twiddle, 8, stream, a);
   if (rc) return rc;
   SYG_REQUIRE(out, "stft2048_c2c: null output");
-  MelPlan plan;
-  ContrastPlan cp;
-  memset(&plan, 0, sizeof(plan));
-  memset(&cp, 0, sizeof(cp));
-  return launch<8, 2>(1, y, B, L, ldy, hop, center, T, window, twiddle, nullptr, plan, 0, nullptr, 0.f, 0.f, 0.f, 0,
-                      nullptr, cp, nullptr, out, (hipStream_t)stream);
+  a.cout = out; a.load = 1;
+  return launch<8, Mode::Complex>(a);
 }

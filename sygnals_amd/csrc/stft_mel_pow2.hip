@@ -760,14 +760,12 @@ extern "C" int syg_stft_mfcc_pow2_f32(const float* y, int64_t B, int64_t L, int6
   int rc = check_args("stft_mfcc_pow2", y, B, L, ldy, n_fft, hop, center, T, window, twiddle, basis_p, Fp, n_mels, 2);
   if (rc) return rc;
   SYG_REQUIRE(dct && mfcc_out, "stft_mfcc_pow2: null pointer argument");
-  SYG_REQUIRE(n_mfcc >= 1 && n_mfcc <= n_mels, "stft_mfcc_pow2: need 1 <= n_mfcc <= n_mels");
-  SYG_REQUIRE(amin >= 1.17549435e-38f, "stft_mfcc_pow2: amin must be strictly positive (a normal float)");
-  SYG_REQUIRE(ref_is_max == 0 || ref_is_max == 1, "stft_mfcc_pow2: ref_is_max must be 0 or 1");
+  Pow2Mfcc mf;
+  if ((rc = fill_mfcc_args("stft_mfcc_pow2", "%s: need 1 <= n_mfcc <= n_mels", n_mels, dct, n_mfcc, n_mfcc, lifter, amin, top_db,
+                           ref_is_max, ref_value, mfcc_out, T, 0, mf))) return rc;
   SYG_REQUIRE(B <= 0x7fffffff, "stft_mfcc_pow2: too many clips");
   const int tiles = (int)((T + 15) / 16);
-  Pow2Mfcc mf;
-  mf.dct = dct; mf.lifter = lifter; mf.out = mfcc_out; mf.n_mfcc = n_mfcc; mf.ref_is_max = ref_is_max;
-  mf.ref_value = ref_value; mf.amin = amin; mf.top_db = top_db; mf.tp = tiles * 16;
+  mf.tp = tiles * 16;
   if (n_fft == 1024) {
     const size_t lds = w1024_lds_bytes(n_mels, mf.tp);
     SYG_REQUIRE(lds <= LDS_LIMIT, "stft_mfcc_pow2: the clip's mel matrix (%d x %d) does not fit the LDS (%zu B > %zu B); use "

@@ -1,7 +1,8 @@
 """The fifteen entry points of the fused STFT front ends (stft_mel.hip, stft_mel_pow2.hip, stft_mel_w1024_seg.hip,
 stft_mel_w4096.hip, stft_mel_wseg_small.hip) reject bad arguments before any device work: every case below is an otherwise
 valid call with ONE thing wrong, and pins the return code, the prefix that names the entry point (the 2048 file reports its
-clip checks as "stft2048") and a distinguishing part of syg_last_error().  No GPU is needed: nothing here reaches a device call."""
+clip checks as "stft2048") and a distinguishing part of syg_last_error().  The answers of the 2048 file's two `fits` functions
+are pinned at the end.  No GPU is needed: nothing here reaches a device call."""
 import ctypes as C
 import os
 
@@ -244,3 +245,31 @@ def test_other_family_rules(call):
     rejected(call("syg_stft_mel_pow2_f32", power=3), "stft_mel_pow2: ", "power must be 1 or 2")
     rejected(call("syg_stft_rows_w4096_f32", window=PMIS), "stft_rows_w4096: ", "16-byte aligned")
     rejected(call("syg_stft_mel_w4096_f32", window=PMIS), "stft_mel_w4096: ", "16-byte aligned")
+
+
+# (n_mels, n_mfcc) -> [(first T, value)]: the value holds from that frame count up to the next entry's (the last one up to 400)
+FITS = {
+    "syg_stft2048_mfcc_fits": {(40, 13): [(1, 2), (113, 1), (353, 0)], (64, 13): [(1, 2), (65, 1), (209, 0)],
+                               (128, 13): [(1, 2), (17, 1), (97, 0)], (127, 20): [(1, 2), (17, 1), (97, 0)], (1, 1): [(1, 2)]},
+    "syg_stft2048_mfcc_tri_fits": {(40, 13): [(1, 1), (97, 0)], (64, 13): [(1, 1), (49, 0)], (128, 13): [(1, 0)],
+                                   (127, 20): [(1, 1), (17, 0)], (1, 1): [(1, 1)]},
+}
+
+
+@pytest.mark.parametrize("name", sorted(FITS))
+def test_clip_resident_fits(h, name):
+    """syg_stft2048_mfcc_fits (2: the clip's mel matrix, DCT rows and lifter fit beside the stage buffer, 1: in its place, 0:
+    not at all) and syg_stft2048_mfcc_tri_fits (1: two mel matrices fit beside the stage buffer) for T = 1 ... 400: the frame
+    counts at which the answer changes (the padded frame count is a multiple of 16, so they are 16 k + 1) and the value on
+    each side, as the library gave them before the LDS accounting was moved into one place."""
+    fits = getattr(h, name)
+    for (n_mels, n_mfcc), steps in FITS[name].items():
+        want = []
+        for (t0, v), t1 in zip(steps, [t for t, _ in steps[1:]] + [401]):
+            want += [v] * (t1 - t0)
+        got = [fits(n_mels, T, n_mfcc) for T in range(1, 401)]
+        assert got == want, (n_mels, n_mfcc, [T for T in range(1, 401) if got[T - 1] != want[T - 1]][:8])
+    for bad in ((0, 94, 13), (40, 0, 13), (40, 94, 0), (40, 94, 41), (257 if name == "syg_stft2048_mfcc_fits" else 128, 94, 13)):
+        assert fits(*bad) == 0, bad
+    # what tests/test_gpu_fused.py relies on
+    assert [h.syg_stft2048_mfcc_fits(n, T, 13) for n, T in ((40, 94), (64, 94), (128, 94), (128, 120))] == [2, 1, 1, 0]
