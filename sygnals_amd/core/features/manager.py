@@ -41,22 +41,7 @@ class FeatureExtractionError(Exception):
 
 def mel_power_batch(y, sr, n_fft, hop, center, window, n_mels, fmin, fmax, power=2.0, win_length=None):
     """[B, L] device clips -> mel spectrogram [B, n_mels, T] of |STFT|^power."""
-    if power == 2.0 and ops.fused_mel_ok(sr, n_fft, n_mels, fmin, fmax):
-        mel, _, _ = ops.stft2048_mel(y, sr, hop, center, window, 2048 if win_length is None else win_length,
-                                     n_mels, fmin, fmax)
-        return mel
-    if power not in (1.0, 2.0):
-        raise SygnalsHipError("mel power must be 1.0 or 2.0 on the device")
-    if power == 2.0:
-        mel = ops.stft_mel_segments(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax)
-        if mel is not None:
-            return mel
-    if ops.fused_pow2_ok(n_fft, n_mels):
-        return ops.stft_mel_pow2(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax, int(power))
-    X = ops.stft_any(y, n_fft, hop, center, window, win_length)
-    P = ops.cabs_pow(X, int(power))
-    cfg = ops.mel_config(sr, n_fft, n_mels, fmin, fmax)
-    return ops.mel_dense(P, cfg.basis)
+    return ops.stft_front(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax, power)[0]
 
 
 def extract_features_batch(y, sr: int, features: List[str], frame_length: int = 2048, hop_length: int = 512,
@@ -160,64 +145,11 @@ def extract_features_batch(y, sr: int, features: List[str], frame_length: int = 
                   and ops.mfcc_fused_fits(n_mels, Tn, n_mfcc)):
                 cache["mfcc_dev"] = ops.stft2048_mfcc(yd, sr, hop_length, center, window, n_mels, n_mfcc, fmin, fmax, lifter)[0]
                 t_stft = Tn
-            elif (not want_mfcc and (want_stats or want_contrast) and frame_length == 2048 and ops.stft2048_stats_fits(hop_length, yd.shape[1])):
-                # no mel-based feature asked for: transform + row functions, nothing projected (syg_stft2048_stats_f32)
-                stats, cpv = ops.stft2048_stats(yd, sr, hop_length, center, window, 2048, want_stats, roll, bw_p, cplan)
-                t_stft = Tn
-            elif power == 2.0 and ops.fused_mel_ok(sr, frame_length, n_mels if want_mfcc else 16, fmin, fmax):
-                mel, stats, cpv = ops.stft2048_mel(yd, sr, hop_length, center, window, 2048, n_mels if want_mfcc else 16,
-                                                   fmin, fmax, want_stats, roll, bw_p, cplan)
-                t_stft = Tn
-            elif (frame_length == 1024 and (want_stats or want_contrast) and
-                  (not want_mfcc or (power in (1.0, 2.0) and ops.fused_pow2_ok(1024, n_mels)))):
-                # frame length 1024 with spectral features (the reference's own manager tests: tests/test_features_manager.py:
-                # 58-62, 167-174): the rows from the segment-sum kernel's launch, no spectrogram in HBM; the mel block from the
-                # same launch where the filterbank has a piece table (power 2), else from the dense-matrix kernel
-                seg_mel = want_mfcc and power == 2.0 and ops.w1024_segtab(sr, n_mels, fmin, fmax) is not None
-                mel, stats, cpv = ops.stft_rows_w1024(yd, sr, hop_length, center, window, None, n_mels if seg_mel else None,
-                                                      fmin, fmax, want_stats, roll, bw_p, cplan)
-                if want_mfcc and not seg_mel:
-                    mel = ops.stft_mel_pow2(yd, sr, 1024, hop_length, center, window, None, n_mels, fmin, fmax, int(power))
-                t_stft = Tn
-            elif (frame_length == 4096 and (want_stats or want_contrast) and
-                  (not want_mfcc or (power == 2.0 and ops.w4096_segtab(sr, n_mels, fmin, fmax) is not None))):
-                # frame length 4096: rows (and the mel block, power 2 with a piece table) from the one-wave-per-frame launch
-                mel, stats, cpv = ops.stft_rows_w4096(yd, sr, hop_length, center, window, None, n_mels if want_mfcc else None,
-                                                      fmin, fmax, want_stats, roll, bw_p, cplan)
-                t_stft = Tn
-            elif (frame_length in (512, 256) and (want_stats or want_contrast) and
-                  (not want_mfcc or (power in (1.0, 2.0) and ops.fused_pow2_ok(frame_length, n_mels)))):
-                # frame lengths 512 / 256 (256: the reference's short-signal tests): the rows from the segment-sum kernel's
-                # transform (one launch, no spectrogram in HBM); the mel block, if an MFCC is asked for too, from its own launch
-                stats, cpv = ops.stft_rows_wsmall(yd, sr, frame_length, hop_length, center, window, None, want_stats, roll, bw_p, cplan)
-                if want_mfcc:
-                    mel = ops.stft_mel_segments(yd, sr, frame_length, hop_length, center, window, None, n_mels, fmin, fmax) if power == 2.0 else None
-                    if mel is None:
-                        mel = ops.stft_mel_pow2(yd, sr, frame_length, hop_length, center, window, None, n_mels, fmin, fmax, int(power))
-                t_stft = Tn
-            elif (want_mfcc and not (want_stats or want_contrast) and power == 2.0 and
-                  (mel := ops.stft_mel_segments(yd, sr, frame_length, hop_length, center, window, None, n_mels, fmin, fmax)) is not None):
-                # only the mel spectrogram is needed: the segment-sum kernel of this frame length (1024 / 512 / 256 / 4096)
-                t_stft = mel.shape[2]
-            elif want_mfcc and not (want_stats or want_contrast) and power in (1.0, 2.0) and ops.fused_pow2_ok(frame_length, n_mels):
-                # ... or the dense-matrix kernel of the other power-of-two frame lengths
-                mel = ops.stft_mel_pow2(yd, sr, frame_length, hop_length, center, window, None, n_mels, fmin, fmax, int(power))
-                t_stft = mel.shape[2]
             else:
-                X = ops.stft_any(yd, frame_length, hop_length, center, window)
-                t_stft, F = X.shape[1], X.shape[2]
-                if want_stats or want_contrast:
-                    mag = ops.cabs_pow(X, 1).reshape(B * t_stft, F)
-                    if want_stats:
-                        stats = ops.spectral_stats(mag, ops.to_device_f32(freqs), roll, bw_p).reshape(8, B, t_stft).permute(1, 0, 2)
-                    if want_contrast:
-                        R = int(cplan[0])
-                        cpv = ops.contrast_pv(mag, cplan).reshape(2, R, B, t_stft).permute(2, 0, 1, 3).contiguous()
-                if want_mfcc:
-                    if power not in (1.0, 2.0):
-                        raise SygnalsHipError("mel power must be 1.0 or 2.0 on the device")
-                    P = ops.cabs_pow(X, int(power))
-                    mel = ops.mel_dense(P, ops.mel_config(sr, frame_length, n_mels, fmin, fmax).basis)
+                # every other request: the front-end kernels _front.front_route names for it
+                mel, stats, cpv = ops.stft_front(yd, sr, frame_length, hop_length, center, window, None,
+                                                 n_mels if want_mfcc else None, fmin, fmax, power, want_stats, roll, bw_p, cplan)
+                t_stft = next(v for v in (mel, stats, cpv) if v is not None).shape[-1]
         except Exception as e:  # mirrors manager.py:201-202, 225-226 (raised inside the per-feature try there too)
             cache["stft"] = FeatureExtractionError(f"Error calculating STFT: {e}")
             raise cache["stft"]
@@ -356,35 +288,14 @@ def extract_features(y, sr: int, features: List[str], frame_length: int = 2048, 
 
 def features_one_launch(y, sr, hop_length, center, window, n_mels, fmin, fmax, n_mfcc, smask, roll_percent, bw_p, cplan):
     """MFCC rows + statistics rows + contrast tail means of [B, L] device clips from ONE launch
-    (syg_stft2048_features_tri_f32: frame_length 2048, power 2, DCT-II ortho, no lifter, ref = max, top_db 80 -- the
+    (ops.stft2048_features_tri: frame_length 2048, power 2, DCT-II ortho, no lifter, ref = max, top_db 80 -- the
     defaults of manager.py:219-227 / cepstral.py:20-120), or None when the shape has no segment-sum form (the caller then
     takes the mel launch).  Returns (mfcc [B, n_mfcc, T], stats [B, 8, T] | None, contrast_pv [B, 2, R, T] | None)."""
-    import ctypes as C
-    from ..._lib import check, lib
-    B, L = y.shape
-    Tn = ops.num_frames(L, 2048, hop_length, center)
-    if not (hop_length <= 512 and ops.fused_waves() == 16 and 1 <= n_mfcc <= n_mels <= 127 and (smask or cplan is not None)):
+    if not (1 <= n_mfcc <= n_mels <= 127 and (smask or cplan is not None)):
         return None
-    cfg = ops.mel_config(sr, 2048, n_mels, fmin, fmax, waves=16)
-    if cfg.segtab is None or not lib().syg_stft2048_mfcc_tri_fits(int(n_mels), int(Tn), int(n_mfcc)):
-        return None
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    mf = torch.empty((B, n_mfcc, Tn), dtype=torch.float32, device=y.device)
-    stats = torch.zeros((B, 8, Tn), dtype=torch.float32, device=y.device) if smask else None
-    cpv = cph = None
-    if cplan is not None:
-        cph = np.ascontiguousarray(cplan, np.int32)
-        cpv = torch.empty((B, 2, int(cph[0]), Tn), dtype=torch.float32, device=y.device)
-    dct = ops._cached(("dct", n_mfcc, n_mels, 2, "ortho"), lambda: ops._dev(T.dct_matrix(n_mfcc, n_mels, 2, "ortho")))
-    rc = lib().syg_stft2048_features_tri_f32(
-        ops._ptr(y), B, L, y.stride(0), hop_length, int(center), Tn, ops._ptr(ops.window_dev(window, 2048, 2048)),
-        ops._ptr(ops.twiddle_dev(2048)), ops._ptr(cfg.segtab), int(cfg.segtab.numel()), n_mels, ops._ptr(dct), n_mfcc, None,
-        1e-10, 80.0, 1, 1.0, float(sr), float(roll_percent), float(bw_p), (smask | 32) if smask else 1, ops._ptr(stats),
-        cph.ctypes.data_as(C.c_void_p) if cph is not None else None, ops._ptr(cpv), ops._ptr(mf), n_mfcc,
-        C.c_void_p(ops._stream_ptr()))
-    check(rc, "syg_stft2048_features_tri_f32")
-    return mf, stats, cpv
+    launch = ops.stft2048_features_tri(y, sr, hop_length, center, window, n_mels, fmin, fmax, n_mfcc, smask, roll_percent,
+                                       bw_p, cplan)
+    return launch() if launch else None
 
 
 # ------------------------------------------------------------------ config C4: the packed per-clip feature block
@@ -409,80 +320,51 @@ def feature_block(y, sr: int, hop_length: int = 512, n_mels: int = 40, n_mfcc: i
     cplan = ops._cached(("cplan", float(sr), n_bands, float(fmin_contrast), float(quantile)),
                         lambda: T.contrast_plan(freqs, sr, n_bands, fmin_contrast, quantile))
     R = int(cplan[0])
-    rows = n_mfcc + 2 + R
     if out is None:
-        out = torch.empty((B, rows, Tn), dtype=torch.float32, device=y.device)
-    dct = ops._cached(("dct", n_mfcc, n_mels, 2, "ortho"), lambda: ops._dev(T.dct_matrix(n_mfcc, n_mels, 2, "ortho")))
-    import ctypes as C
-    from ..._lib import check, lib
-    st = C.c_void_p(ops._stream_ptr())
+        out = torch.empty((B, n_mfcc + 2 + R, Tn), dtype=torch.float32, device=y.device)
     # one_launch: everything from ONE fused launch -- samples in; MFCC rows straight into the head of the block,
     # statistics rows and contrast tail means out (the mel matrix stays in LDS) -- then the small kernel that turns those
-    # into the block's other rows: syg_stft2048_features_tri_f32 (each wave projects its own row by segment sums; the clip
+    # into the block's other rows: ops.stft2048_features_tri (each wave projects its own row by segment sums; the clip
     # epilogue runs on waves that have no frame).  Needs a two-pass piece table for the filterbank and the clip's mel
     # matrix in LDS (n_mels = 40: yes; 128: no).  one_launch=None picks it where it applies, True insists, False takes
     # the two launches below.  (Round 3's matrix form of the one launch lost to the two launches, 735 vs 724 us per 2048
     # clips, and is gone.)
-    cfg = ops.mel_config(sr, 2048, n_mels, 0.0, None, waves=16)
-    tri_ok = (cfg.segtab is not None and hop_length <= 512 and ops.fused_waves() == 16
-              and bool(lib().syg_stft2048_mfcc_tri_fits(int(n_mels), int(Tn), int(n_mfcc))))
     if one_launch not in (None, True, False, "segments"):
         raise ValueError("one_launch must be None, True, False or 'segments'")
-    if one_launch in (True, "segments") and not tri_ok:
-        raise SygnalsHipError("feature_block: no one-launch form for this shape (two-pass piece table + the clip's mel matrix in LDS)")
-    if one_launch is None:
-        one_launch = tri_ok and TRI_FEATURES_DEFAULT
-    if one_launch:
+    launch = None
+    if one_launch or (one_launch is None and TRI_FEATURES_DEFAULT):
         stats = torch.empty((B, 8, Tn), dtype=torch.float32, device=y.device)       # (only the rows read below are written)
-        cpv = torch.empty((B, 2, R, Tn), dtype=torch.float32, device=y.device)
-        rc = lib().syg_stft2048_features_tri_f32(
-            ops._ptr(y), B, L, y.stride(0), hop_length, 1, Tn, ops._ptr(ops.window_dev("hann", 2048, 2048)),
-            ops._ptr(ops.twiddle_dev(2048)), ops._ptr(cfg.segtab), int(cfg.segtab.numel()), n_mels, ops._ptr(dct), n_mfcc, None,
-            1e-10, 80.0, 1, 1.0, float(sr), float(roll_percent), 2.0, 1 | 8 | 32, ops._ptr(stats),
-            np.ascontiguousarray(cplan, np.int32).ctypes.data_as(C.c_void_p), ops._ptr(cpv), ops._ptr(out), rows, st)
-        check(rc, "syg_stft2048_features_tri_f32")
-        rc = lib().syg_feature_block_f32(None, B, n_mels, Tn, None, n_mfcc, 1e-10, 80.0, ops._ptr(stats), float(sr) / 2048.0,
-                                         ops._ptr(cpv), R, 1e-10, 80.0, ops._ptr(out), st)
-        check(rc, "syg_feature_block_f32")
-        return out
-    # two launches: mel + rows (matrix form, or -- projection="segments" -- the tile form of the segment-sum projection with
-    # `tri_waves` waves per workgroup), then the block kernel
-    mel, stats, cpv = ops.stft2048_mel(y, sr, hop_length, True, "hann", 2048, n_mels, 0.0, None, 1 | 8 | 32, roll_percent,
-                                       2.0, cplan, projection, tri_waves)
-    rc = lib().syg_feature_block_f32(ops._ptr(mel), B, n_mels, Tn, ops._ptr(dct), n_mfcc, 1e-10, 80.0, ops._ptr(stats),
-                                     float(sr) / 2048.0, ops._ptr(cpv), R, 1e-10, 80.0, ops._ptr(out), st)
-    check(rc, "syg_feature_block_f32")
+        launch = ops.stft2048_features_tri(y, sr, hop_length, True, "hann", n_mels, 0.0, None, n_mfcc, 1 | 8, roll_percent, 2.0,
+                                           cplan, out, stats)
+        if launch is None and one_launch:
+            raise SygnalsHipError("feature_block: no one-launch form for this shape (two-pass piece table + the clip's mel matrix in LDS)")
+    if launch:
+        _, stats, cpv = launch()
+        mel = dct = None
+    else:
+        # two launches: mel + rows (matrix form, or -- projection="segments" -- the tile form of the segment-sum projection
+        # with `tri_waves` waves per workgroup), then the block kernel
+        mel, stats, cpv = ops.stft2048_mel(y, sr, hop_length, True, "hann", 2048, n_mels, 0.0, None, 1 | 8 | 32, roll_percent,
+                                           2.0, cplan, projection, tri_waves)
+        dct = ops.dct_dev(n_mfcc, n_mels)
+    ops._call("syg_feature_block_f32", ops._ptr(mel), B, n_mels, Tn, ops._ptr(dct), n_mfcc, 1e-10, 80.0, ops._ptr(stats),
+              float(sr) / 2048.0, ops._ptr(cpv), R, 1e-10, 80.0, ops._ptr(out))
     return out
 
 
 def feature_block_dominant(y, sr, hop_length, n_mels, n_mfcc):
     """(name, callable, feature rows it carries) of the dominant kernel of feature_block (bench.py's roofline leg)."""
-    freqs = np.fft.rfftfreq(2048, 1.0 / sr)
-    cplan = T.contrast_plan(freqs, sr)
-    B, L = y.shape
-    Tn = ops.num_frames(L, 2048, hop_length, True)
-    cfg = ops.mel_config(sr, 2048, n_mels, 0.0, None, waves=16)
-    from ..._lib import check, lib
-    if (TRI_FEATURES_DEFAULT and cfg.segtab is not None and hop_length <= 512 and ops.fused_waves() == 16
-            and bool(lib().syg_stft2048_mfcc_tri_fits(int(n_mels), int(Tn), int(n_mfcc)))):
-        import ctypes as C
-        R = int(cplan[0])
-        rows = n_mfcc + 2 + R
-        out = torch.empty((B, rows, Tn), dtype=torch.float32, device=y.device)
-        stats = torch.empty((B, 8, Tn), dtype=torch.float32, device=y.device)
-        cpv = torch.empty((B, 2, R, Tn), dtype=torch.float32, device=y.device)
-        dct = ops._cached(("dct", n_mfcc, n_mels, 2, "ortho"), lambda: ops._dev(T.dct_matrix(n_mfcc, n_mels, 2, "ortho")))
-        cph = np.ascontiguousarray(cplan, np.int32)
-        args = (ops._ptr(y), B, L, y.stride(0), hop_length, 1, Tn, ops._ptr(ops.window_dev("hann", 2048, 2048)),
-                ops._ptr(ops.twiddle_dev(2048)), ops._ptr(cfg.segtab), int(cfg.segtab.numel()), n_mels, ops._ptr(dct), n_mfcc,
-                None, 1e-10, 80.0, 1, 1.0, float(sr), 0.85, 2.0, 1 | 8 | 32, ops._ptr(stats), cph.ctypes.data_as(C.c_void_p),
-                ops._ptr(cpv), ops._ptr(out), rows)
-
-        def run():
-            check(lib().syg_stft2048_features_tri_f32(*args, C.c_void_p(ops._stream_ptr())), "syg_stft2048_features_tri_f32")
-            return out, stats, cpv, cph
+    cplan = T.contrast_plan(np.fft.rfftfreq(2048, 1.0 / sr), sr)
+    R = int(cplan[0])
+    launch = None
+    if TRI_FEATURES_DEFAULT:
+        shape = (y.shape[0], n_mfcc + 2 + R, ops.num_frames(y.shape[1], 2048, hop_length, True))
+        launch = ops.stft2048_features_tri(y, sr, hop_length, True, "hann", n_mels, 0.0, None, n_mfcc, 1 | 8, 0.85, 2.0, cplan,
+                                           torch.empty(shape, dtype=torch.float32, device=y.device),
+                                           torch.empty((shape[0], 8, shape[2]), dtype=torch.float32, device=y.device))
+    if launch:
         return ("stft2048_kernel<16,2,7> (16 waves, staged tiles, per-wave mel projection by segment sums, clip-resident MFCC "
-                "+ centroid + rolloff + contrast tail means)", run, n_mfcc + 2 + 2 * R)
+                "+ centroid + rolloff + contrast tail means)", launch, n_mfcc + 2 + 2 * R)
     return ("stft2048_kernel<16,2,1> (16 waves, staged tiles, mel + centroid + rolloff + contrast tail means)",
             lambda: ops.stft2048_mel(y, sr, hop_length, True, "hann", 2048, n_mels, 0.0, None, 1 | 8, 0.85, 2.0, cplan),
-            n_mels + 3 + 2 * int(cplan[0]))
+            n_mels + 3 + 2 * R)

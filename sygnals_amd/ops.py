@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _tables as T
+from ._front import front_route, pow2_takes, stats2048_takes
 from ._lib import SygnalsHipError, check, lib
 
 
@@ -86,6 +87,10 @@ def window_dev(window, win_length, n_fft) -> torch.Tensor:
 
 def twiddle_dev(n) -> torch.Tensor:
     return _cached(("tw", n), lambda: _dev(T.twiddles(n)))
+
+
+def dct_dev(K, M, dct_type=2, norm="ortho") -> torch.Tensor:
+    return _cached(("dct", K, M, dct_type, norm), lambda: _dev(T.dct_matrix(K, M, dct_type, norm)))
 
 
 def num_frames(L: int, n_fft: int, hop: int, center: bool) -> int:
@@ -231,7 +236,7 @@ def fused_mel_ok(sr, n_fft, n_mels, fmin=0.0, fmax=None) -> bool:
 
 def fused_pow2_ok(n_fft, n_mels) -> bool:
     """True when the fused kernel for the other power-of-two frame lengths (stft_mel_pow2.hip) takes this shape."""
-    return is_pow2(n_fft) and 64 <= n_fft <= 1024 and 1 <= n_mels <= 256
+    return pow2_takes(n_fft, n_mels)
 
 
 def _basis_padded(cfg: "MelConfig", n_fft: int):
@@ -300,7 +305,7 @@ def stft_mel_pow2(y: torch.Tensor, sr: float, n_fft: int, hop: int, center: bool
     """Fused STFT(n_fft = 64 ... 1024) -> |X|^power -> mel [B, n_mels, T]: one launch, no spectrogram in HBM."""
     y, B, L, Tn, bp, Fp, win, tw = _pow2_front(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax)
     mel = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device)
-    _call("syg_stft_mel_pow2_f32", _ptr(y), B, L, y.stride(0), n_fft, hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(bp),
+    _call("syg_stft_mel_pow2_f32", _ptr(y), B, L, _ld(y), n_fft, hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(bp),
           Fp, n_mels, int(power), _ptr(mel))
     return mel
 
@@ -317,12 +322,12 @@ def stft_mfcc_pow2(y: torch.Tensor, sr: float, n_fft: int, hop: int, center: boo
     y, B, L, Tn, bp, Fp, win, tw = _pow2_front(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax)
     if not mfcc_pow2_fits(n_fft, n_mels, Tn, n_mfcc):
         raise SygnalsHipError("stft_mfcc_pow2: the clip's mel matrix does not fit the LDS; use stft_mel_pow2 + logmel_dct")
-    dct = _cached(("dct", n_mfcc, n_mels, 2, "ortho"), lambda: _dev(T.dct_matrix(n_mfcc, n_mels, 2, "ortho")))
+    dct = dct_dev(n_mfcc, n_mels)
     lw = T.lifter_weights(n_mfcc, lifter)
     lif = None if lw is None else _dev(lw)
     mf = torch.empty((B, n_mfcc, Tn), dtype=torch.float32, device=y.device)
     mel = torch.empty((B, n_mels, Tn), dtype=torch.float32, device=y.device) if keep_mel else None
-    _call("syg_stft_mfcc_pow2_f32", _ptr(y), B, L, y.stride(0), n_fft, hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(bp),
+    _call("syg_stft_mfcc_pow2_f32", _ptr(y), B, L, _ld(y), n_fft, hop, int(center), Tn, _ptr(win), _ptr(tw), _ptr(bp),
           Fp, n_mels, _ptr(dct), n_mfcc, None if lif is None else _ptr(lif), float(amin),
           -1.0 if top_db is None else float(top_db), 1, 1.0, None if mel is None else _ptr(mel), _ptr(mf))
     return mf, mel
@@ -466,36 +471,12 @@ def stft_rows_w4096(y: torch.Tensor, sr: float, hop: int = 1024, center: bool = 
     return _seg_rows(4096, y, sr, hop, center, window, win_length, n_mels, fmin, fmax, want_stats, roll_percent, bw_p, contrast)
 
 
-def stft_rows_seg(y, sr, n_fft, hop, center=True, window="hann", win_length=None, n_mels=None, fmin=0.0, fmax=None,
-                  want_stats=False, roll_percent=0.85, bw_p=2.0, contrast=None):
-    """Statistics / contrast rows (+ the mel power block when n_mels is given) from the segment-sum kernels of frame lengths
-    1024 / 4096 (one launch) and 512 / 256 (the rows from one launch, the mel block -- power 2 -- from the projection form's).
-    Returns (mel | None, stats | None, contrast_pv | None); raises SygnalsHipError for other frame lengths."""
-    if n_fft == 1024:
-        return stft_rows_w1024(y, sr, hop, center, window, win_length, n_mels, fmin, fmax, want_stats, roll_percent, bw_p, contrast)
-    if n_fft == 4096:
-        return stft_rows_w4096(y, sr, hop, center, window, win_length, n_mels, fmin, fmax, want_stats, roll_percent, bw_p, contrast)
-    if n_fft in (512, 256):
-        stats, cpv = stft_rows_wsmall(y, sr, n_fft, hop, center, window, win_length, want_stats, roll_percent, bw_p, contrast)
-        mel = None
-        if n_mels is not None:
-            mel = stft_mel_segments(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax)
-            if mel is None:
-                mel = stft_mel_pow2(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax)
-        return mel, stats, cpv
-    raise SygnalsHipError(f"stft_rows_seg: no row functions in the fused kernel of frame length {n_fft}")
-
-
 def stft_mel_segments(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax):
     """Mel power by one of the segment-sum kernels of the other frame lengths (1024, 512, 256, 4096), or None when the
     frame length / filterbank has none."""
-    if n_fft == 1024 and w1024_segtab(sr, n_mels, fmin, fmax) is not None:
-        return stft_mel_w1024_seg(y, sr, hop, center, window, win_length, n_mels, fmin, fmax)
-    if n_fft in (512, 256) and wsmall_segtab(sr, n_fft, n_mels, fmin, fmax) is not None:
-        return stft_mel_wseg_small(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax)
-    if n_fft == 4096 and w4096_segtab(sr, n_mels, fmin, fmax) is not None:
-        return stft_mel_w4096(y, sr, hop, center, window, win_length, n_mels, fmin, fmax)
-    return None
+    if n_fft not in _SEG or _segtab(n_fft, sr, n_mels, fmin, fmax) is None:
+        return None
+    return stft_front(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax)[0]
 
 
 def stft_mel_w4096(y: torch.Tensor, sr: float, hop: int = 1024, center: bool = True, window="hann", win_length=None,
@@ -549,9 +530,8 @@ def stft2048_mel(y: torch.Tensor, sr: float, hop: int = 512, center: bool = True
 
 
 def stft2048_stats_fits(hop: int, L: int = 0) -> bool:
-    """Whether stft2048_stats takes this call: the C side's conditions (syg_stft2048_stats_f32: staged tiles need
-    hop <= 512 and 32-bit byte offsets, L < 2^28; frame count below 2^24) and the 16-wave kernel."""
-    return hop <= 512 and L < (1 << 28) and 1 + L // max(hop, 1) < (1 << 24) and fused_waves() == 16
+    """Whether stft2048_stats takes this call (_front.stats2048_takes: the C side's conditions and the 16-wave kernel)."""
+    return stats2048_takes(hop, L, fused_waves())
 
 
 def stft2048_stats(y: torch.Tensor, sr: float, hop: int = 512, center: bool = True, window="hann", win_length: int = 2048,
@@ -571,6 +551,57 @@ def stft2048_stats(y: torch.Tensor, sr: float, hop: int = 512, center: bool = Tr
     return stats, cpv
 
 
+def front_caps(sr, n_fft, n_mels, fmin=0.0, fmax=None) -> dict:
+    """What _front.front_route needs to know about the tables, as plain values (n_mels None: no mel block is wanted)."""
+    return dict(waves=fused_waves(), plan2048=fused_mel_ok(sr, n_fft, n_mels or 16, fmin, fmax),
+                table=n_mels is not None and n_fft in _SEG and _segtab(n_fft, sr, n_mels, fmin, fmax) is not None)
+
+
+def stft_front(y, sr, n_fft, hop, center=True, window="hann", win_length=None, n_mels=None, fmin=0.0, fmax=None, power=2.0,
+               want_stats=False, roll_percent=0.85, bw_p=2.0, contrast=None, route=None):
+    """[B, L] clips -> (mel [B, n_mels, T] of |STFT|^power | None, stats [B, 8, T] | None, contrast_pv [B, 2, R, T] | None)
+    for any frame length, by the kernels _front.front_route names (route: an answer of it that the caller already has).
+    n_mels None: no mel block; want_stats / contrast: as stft2048_mel."""
+    smask = 31 if want_stats is True else int(want_stats or 0)
+    by_rows, by_mel = route or front_route(n_fft, hop, y.shape[1], power, n_mels, bool(smask) or contrast is not None,
+                                           front_caps(sr, n_fft, n_mels, fmin, fmax))
+    mel = stats = cpv = None
+    if "generic" in (by_rows, by_mel):
+        # the complex STFT of any frame length in HBM, then |X|, the row kernels and the dense mel matrix
+        X = stft_any(y, n_fft, hop, center, window, win_length)
+        B, Tn, F = X.shape[:3]
+        if smask or contrast is not None:
+            mag = cabs_pow(X, 1).reshape(B * Tn, F)
+            if smask:
+                freqs = to_device_f32(np.fft.rfftfreq(n_fft, 1.0 / sr))
+                stats = spectral_stats(mag, freqs, roll_percent, bw_p).reshape(8, B, Tn).permute(1, 0, 2)
+            if contrast is not None:
+                cpv = contrast_pv(mag, contrast).reshape(2, int(contrast[0]), B, Tn).permute(2, 0, 1, 3).contiguous()
+        if n_mels is not None:
+            if power not in (1.0, 2.0):
+                raise SygnalsHipError("mel power must be 1.0 or 2.0 on the device")
+            mel = mel_dense(cabs_pow(X, int(power)), mel_config(sr, n_fft, n_mels, fmin, fmax).basis)
+        return mel, stats, cpv
+
+    def call(name, *tail):
+        # the wrapper by name, looked up now: tests replace them with spies (those of 512 / 256 and the dense one take n_fft)
+        frame = (n_fft,) if name in ("stft_rows_wsmall", "stft_mel_wseg_small", "stft_mel_pow2") else ()
+        return globals()[name](y, sr, *frame, hop, center, window, win_length or n_fft, *tail)
+    rows_args = (smask, roll_percent, bw_p, contrast)
+    if by_rows in ("stft2048_stats", "stft_rows_wsmall"):
+        stats, cpv = call(by_rows, *rows_args)
+    elif by_rows:
+        # stft2048_mel (no mel wanted: 16 stand-in bands, discarded below); stft_rows_w1024 / w4096: the mel block too,
+        # unless it has a launch of its own
+        m = (n_mels or 16) if by_rows == "stft2048_mel" else (None if by_mel else n_mels)
+        mel, stats, cpv = call(by_rows, m, fmin, fmax, *rows_args)
+    if by_mel == "stft2048_mel":
+        mel = call(by_mel, n_mels, fmin, fmax)[0]
+    elif by_mel:
+        mel = call(by_mel, n_mels, fmin, fmax, *((int(power),) if by_mel == "stft_mel_pow2" else ()))
+    return (mel if n_mels is not None else None), stats, cpv
+
+
 def stft2048_c2c(y: torch.Tensor, hop: int = 512, center: bool = True, window="hann", win_length: int = 2048):
     """Complex STFT, frame-major [B, T, 1025, 2] float32."""
     y = _clips(y)
@@ -583,6 +614,22 @@ def stft2048_c2c(y: torch.Tensor, hop: int = 512, center: bool = True, window="h
     return out
 
 
+def _db_args(amin, top_db, ref, takes_db=False):
+    """The power_to_db arguments of the entry points, checked: (amin, top_db -- -1: none --, ref_is_max, ref_value).
+    ref: "max" / np.max (per-clip maximum), a scalar or, with takes_db, "db": the input is in dB already (DCT only)."""
+    if amin <= 0:
+        raise ValueError("amin must be strictly positive")
+    if top_db is not None and top_db < 0:
+        raise ValueError("top_db must be non-negative")
+    if takes_db and isinstance(ref, str) and ref == "db":
+        how = (2, 1.0)
+    elif (isinstance(ref, str) and ref == "max") or ref is np.max:
+        how = (1, 1.0)
+    else:
+        how = (0, float(ref))
+    return (float(amin), float(top_db) if top_db is not None else -1.0) + how
+
+
 def logmel_dct(mel: torch.Tensor, n_mfcc: Optional[int] = 13, dct_type: int = 2, norm="ortho", lifter: float = 0.0,
                amin: float = 1e-10, top_db: Optional[float] = 80.0, ref="max", keep_mel: bool = False):
     """power_to_db (ref = per-clip max or a scalar) then DCT.  Returns (logmel [B,M,T], mfcc [B,K,T] | None).
@@ -591,27 +638,17 @@ def logmel_dct(mel: torch.Tensor, n_mfcc: Optional[int] = 13, dct_type: int = 2,
     """
     require_gpu()
     B, M, Tn = mel.shape
-    if amin <= 0:
-        raise ValueError("amin must be strictly positive")
-    if top_db is not None and top_db < 0:
-        raise ValueError("top_db must be non-negative")
+    db = _db_args(amin, top_db, ref, takes_db=True)
     logmel = torch.empty_like(mel) if keep_mel else None
     mf = dct = lif = None
     K = 0
     if n_mfcc is not None:
         K = int(n_mfcc)
-        dct = _cached(("dct", K, M, dct_type, norm), lambda: _dev(T.dct_matrix(K, M, dct_type, norm)))
+        dct = dct_dev(K, M, dct_type, norm)
         lw = T.lifter_weights(K, float(lifter))
         lif = _dev(lw) if lw is not None else None
         mf = torch.empty((B, K, Tn), dtype=torch.float32, device=mel.device)
-    if isinstance(ref, str) and ref == "db":
-        ref_is_max, ref_value = 2, 1.0          # input already in dB: DCT only
-    elif (isinstance(ref, str) and ref == "max") or ref is np.max:
-        ref_is_max, ref_value = 1, 1.0
-    else:
-        ref_is_max, ref_value = 0, float(ref)
-    _call("syg_logmel_dct_f32", _ptr(mel), B, M, Tn, _ptr(dct), K, _ptr(lif), float(amin),
-          float(top_db) if top_db is not None else -1.0, ref_is_max, ref_value, _ptr(logmel), _ptr(mf))
+    _call("syg_logmel_dct_f32", _ptr(mel), B, M, Tn, _ptr(dct), K, _ptr(lif), *db, _ptr(logmel), _ptr(mf))
     return (logmel if keep_mel else mel), mf
 
 
@@ -621,21 +658,13 @@ def mel_mfcc(mel: torch.Tensor, n_mfcc: int = 13, dct_type: int = 2, norm="ortho
     DCT as logmel_dct, without writing the dB matrix to HBM."""
     require_gpu()
     B, M, Tn = mel.shape
-    if amin <= 0:
-        raise ValueError("amin must be strictly positive")
-    if top_db is not None and top_db < 0:
-        raise ValueError("top_db must be non-negative")
+    db = _db_args(amin, top_db, ref)
     K = int(n_mfcc)
-    dct = _cached(("dct", K, M, dct_type, norm), lambda: _dev(T.dct_matrix(K, M, dct_type, norm)))
+    dct = dct_dev(K, M, dct_type, norm)
     lw = T.lifter_weights(K, float(lifter))
     lif = _dev(lw) if lw is not None else None
     mf = torch.empty((B, K, Tn), dtype=torch.float32, device=mel.device)
-    if (isinstance(ref, str) and ref == "max") or ref is np.max:
-        ref_is_max, ref_value = 1, 1.0
-    else:
-        ref_is_max, ref_value = 0, float(ref)
-    _call("syg_mel_mfcc_f32", _ptr(mel), B, M, Tn, _ptr(dct), K, _ptr(lif), float(amin),
-          float(top_db) if top_db is not None else -1.0, ref_is_max, ref_value, _ptr(mf))
+    _call("syg_mel_mfcc_f32", _ptr(mel), B, M, Tn, _ptr(dct), K, _ptr(lif), *db, _ptr(mf))
     return mf
 
 
@@ -660,30 +689,22 @@ class _MfccCall:
 
     def __init__(self, B, L, ld, device, sr, hop, center, window, n_mels, n_mfcc, fmin, fmax, lifter, amin, top_db,
                  ref, dct_type, norm, keep_mel, projection="auto"):
-        if amin <= 0:
-            raise ValueError("amin must be strictly positive")
-        if top_db is not None and top_db < 0:
-            raise ValueError("top_db must be non-negative")
+        db = _db_args(amin, top_db, ref)
         Tn = num_frames(L, 2048, hop, center)
         if Tn <= 0:
             raise ValueError("signal too short for one frame")
         self.cfg = mel_config(sr, 2048, n_mels, fmin, fmax, waves=16)
         K = int(n_mfcc)
-        self.dct = _cached(("dct", K, n_mels, dct_type, norm), lambda: _dev(T.dct_matrix(K, n_mels, dct_type, norm)))
+        self.dct = dct_dev(K, n_mels, dct_type, norm)
         lw = T.lifter_weights(K, float(lifter))
         self.lif = _dev(lw) if lw is not None else None
-        if (isinstance(ref, str) and ref == "max") or ref is np.max:
-            ref_is_max, ref_value = 1, 1.0
-        else:
-            ref_is_max, ref_value = 0, float(ref)
         self.win = window_dev(window, 2048, 2048)
         self.tw = twiddle_dev(2048)
         self.shape = (B, L, ld)
         self.device = device
         self.mel_shape = (B, n_mels, Tn) if keep_mel else None
         self.out_shape = (B, K, Tn)
-        tail = (n_mels, _ptr(self.dct), K, _ptr(self.lif), float(amin), float(top_db) if top_db is not None else -1.0,
-                ref_is_max, ref_value)
+        tail = (n_mels, _ptr(self.dct), K, _ptr(self.lif)) + db
         # projection: "segments" = each wave projects its own power row by segment sums (no weight matrix, no workgroup
         # barrier in the projection: 133 against 149 us at config C2), "matrix" = block-sparse weights on the matrix
         # cores; "auto" takes the segment form when the filterbank has a piece table, the staged loads apply (hop <= 512),
@@ -751,6 +772,42 @@ def stft2048_mfcc(y: torch.Tensor, sr: float, hop: int = 512, center: bool = Tru
     return call(y)
 
 
+def stft2048_features_tri(y, sr, hop, center, window, n_mels, fmin, fmax, n_mfcc, smask, roll_percent, bw_p, cplan,
+                          out=None, stats=None):
+    """MFCC rows + statistics rows + contrast tail means of [B, L] device clips from ONE launch
+    (syg_stft2048_features_tri_f32: frame_length 2048, power 2, DCT-II ortho, no lifter, ref = max, top_db 80), prepared: a
+    callable whose every call is that one library call and returns (out, stats [B, 8, T] | None, contrast_pv [B, 2, R, T]
+    | None) -- or None when the shape has no one-launch form (two-pass piece table for the filterbank, staged loads:
+    hop <= 512, 16 waves, the clip's mel matrices in LDS).  smask: statistics rows wanted, cplan: the contrast plan or None.
+    out: a [B, rows >= n_mfcc, T] block whose first n_mfcc rows take the MFCC (default: a new [B, n_mfcc, T]); stats: the
+    caller's own buffer (default: zeros, so that rows not asked for read 0)."""
+    B, L = y.shape
+    Tn = num_frames(L, 2048, hop, center)
+    cfg = mel_config(sr, 2048, n_mels, fmin, fmax, waves=16)
+    if not (cfg.segtab is not None and hop <= 512 and fused_waves() == 16
+            and lib().syg_stft2048_mfcc_tri_fits(int(n_mels), int(Tn), int(n_mfcc))):
+        return None
+    if y.stride(1) != 1:
+        y = y.contiguous()
+    if out is None:
+        out = torch.empty((B, n_mfcc, Tn), dtype=torch.float32, device=y.device)
+    if stats is None and smask:
+        stats = torch.zeros((B, 8, Tn), dtype=torch.float32, device=y.device)
+    cph = cpv = None
+    if cplan is not None:
+        cph = np.ascontiguousarray(cplan, np.int32)
+        cpv = torch.empty((B, 2, int(cph[0]), Tn), dtype=torch.float32, device=y.device)
+    args = (_ptr(y), B, L, _ld(y), hop, int(center), Tn, _ptr(window_dev(window, 2048, 2048)), _ptr(twiddle_dev(2048)),
+            _ptr(cfg.segtab), int(cfg.segtab.numel()), n_mels, _ptr(dct_dev(n_mfcc, n_mels)), n_mfcc, None, 1e-10, 80.0, 1, 1.0,
+            float(sr), float(roll_percent), float(bw_p), (smask | 32) if smask else 1, _ptr(stats),
+            cph.ctypes.data_as(C.c_void_p) if cph is not None else None, _ptr(cpv), _ptr(out), out.shape[1])
+
+    def launch(_alive=(y, cph)):                     # (the arguments point into these)
+        _call("syg_stft2048_features_tri_f32", *args)
+        return out, stats, cpv
+    return launch
+
+
 def mfcc_batch(y: torch.Tensor, sr: float, n_fft: int = 2048, hop: int = 512, n_mels: int = 128, n_mfcc: int = 13,
                center: bool = True, window="hann", fmin: float = 0.0, fmax=None, lifter: float = 0.0, fused=None):
     """Config C2: [B, L] clips -> MFCC [B, n_mfcc, T] (manager path a1..a5), all on device.
@@ -758,33 +815,23 @@ def mfcc_batch(y: torch.Tensor, sr: float, n_fft: int = 2048, hop: int = 512, n_
     fused=None picks the one-launch clip-resident form when the clip's mel matrix fits in LDS and there are
     enough clips to fill the chip (a workgroup owns whole clips); True / False force either form.
     """
-    if n_fft != 2048 and fused_pow2_ok(n_fft, n_mels) and fused is not False:
-        # the other power-of-two frame lengths.  fused=True: ONE launch (a workgroup owns a clip, needs the clip's mel
-        # matrix to fit the LDS).  Default: the tile kernel + logmel_dct -- two launches, but more workgroups per CU
-        # (n_fft 1024: 266 us against 318 us per 1024 clips x 1 s; n_fft 512: 709 against 973 us)
-        fits = mfcc_pow2_fits(n_fft, n_mels, num_frames(y.shape[1], n_fft, hop, center), n_mfcc)
-        if fused and not fits:
-            raise SygnalsHipError("mfcc_batch: the clip's mel matrix does not fit the LDS of the one-launch form")
-        if fits and fused:
-            return stft_mfcc_pow2(y, sr, n_fft, hop, center, window, None, n_mels, n_mfcc, fmin, fmax, lifter)[0]
-        if n_fft == 1024 and w1024_segtab(sr, n_mels, fmin, fmax) is not None:
-            # free-running waves, mel by segment sums: 0.162 against 0.235 ms per 1024 clips x 1 s for the mel launch
-            mel = stft_mel_w1024_seg(y, sr, hop, center, window, None, n_mels, fmin, fmax)
-        elif wsmall_segtab(sr, n_fft, n_mels, fmin, fmax) is not None:
-            # the same for 512 / 256: 0.265 against 0.334 ms, 0.330 against 0.356 ms
-            mel = stft_mel_wseg_small(y, sr, n_fft, hop, center, window, None, n_mels, fmin, fmax)
-        else:
-            mel = stft_mel_pow2(y, sr, n_fft, hop, center, window, None, n_mels, fmin, fmax)
-        return mel_mfcc(mel, n_mfcc, lifter=lifter)
-    if n_fft == 4096 and fused is not False and w4096_segtab(sr, n_mels, fmin, fmax) is not None:
-        # frame length 4096: one launch samples -> mel (one wave per frame, mel by segment sums), then dB + DCT
-        return mel_mfcc(stft_mel_w4096(y, sr, hop, center, window, None, n_mels, fmin, fmax), n_mfcc, lifter=lifter)
     if not fused_mel_ok(sr, n_fft, n_mels, fmin, fmax):
-        # no fused kernel for this shape: complex STFT (any frame length) -> |X|^2 -> dense mel -> dB + DCT
-        if fused:
+        if fused and fused_pow2_ok(n_fft, n_mels):
+            # the other power-of-two frame lengths, fused=True: ONE launch (a workgroup owns a clip, needs the clip's mel
+            # matrix to fit the LDS).  The default is the mel launch + dB / DCT -- two launches, but more workgroups per CU
+            # (n_fft 1024: 266 us against 318 us per 1024 clips x 1 s; n_fft 512: 709 against 973 us)
+            if not mfcc_pow2_fits(n_fft, n_mels, num_frames(y.shape[1], n_fft, hop, center), n_mfcc):
+                raise SygnalsHipError("mfcc_batch: the clip's mel matrix does not fit the LDS of the one-launch form")
+            return stft_mfcc_pow2(y, sr, n_fft, hop, center, window, None, n_mels, n_mfcc, fmin, fmax, lifter)[0]
+        # the mel launch front_route names (segment sums at 1024 / 512 / 256 / 4096: 0.162 against 0.235 ms per 1024 clips
+        # x 1 s at 1024 for the dense kernel's; 0.265 against 0.334 ms, 0.330 against 0.356 ms), then dB + DCT; fused=False,
+        # or no fused kernel for the shape: complex STFT (any frame length) -> |X|^2 -> dense mel
+        route = (None, "generic")
+        if fused is not False:
+            route = front_route(n_fft, hop, y.shape[1], 2.0, n_mels, False, front_caps(sr, n_fft, n_mels, fmin, fmax))
+        if fused and route[1] == "generic":
             raise SygnalsHipError(f"mfcc_batch: no fused kernel for n_fft={n_fft}, n_mels={n_mels}")
-        P = cabs_pow(stft_any(y, n_fft, hop, center, window), 2)
-        mel = mel_dense(P, mel_config(sr, n_fft, n_mels, fmin, fmax).basis)
+        mel = stft_front(y, sr, n_fft, hop, center, window, None, n_mels, fmin, fmax, route=route)[0]
         return mel_mfcc(mel, n_mfcc, lifter=lifter)
     if fused is None:
         fused = mfcc_fused_pays(n_mels, num_frames(y.shape[1], 2048, hop, center), n_mfcc) and y.shape[0] >= 128

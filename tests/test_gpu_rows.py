@@ -31,7 +31,7 @@ def check_rows(ops, n_fft, hop, sr, L, center, n_mels, B=5, window="hann"):
     fr = O.fft_frequencies(sr, n_fft)
     F = n_fft // 2 + 1
     plan = T.contrast_plan(fr, sr)
-    mel, st, pv = ops.stft_rows_seg(y, sr, n_fft, hop, center, window, None, n_mels, 0.0, None, 31, 0.85, 2.0, plan)
+    mel, st, pv = ops.stft_front(y, sr, n_fft, hop, center, window, None, n_mels, 0.0, None, 2.0, 31, 0.85, 2.0, plan)
     st, pv = st.cpu().numpy(), pv.cpu().numpy()
     cdb = ops.contrast_db(torch.from_numpy(pv).cuda()).cpu().numpy()
     bands = O.contrast_bands(fr, sr)
@@ -70,9 +70,9 @@ def check_rows(ops, n_fft, hop, sr, L, center, n_mels, B=5, window="hann"):
             S = np.abs(O.stft(Y[i].astype(np.float64), n_fft, hop, window=window, center=center)) ** 2
             assert_parity(mel[i], O.melspectrogram(S, sr, n_fft, n_mels), TOL, f"mel clip {i}")
     # the rows alone (no filterbank) and single rows: the same bits
-    _, st1, _ = ops.stft_rows_seg(y, sr, n_fft, hop, center, window, None, None, 0.0, None, 1 | 8, 0.85, 2.0, None)
+    _, st1, _ = ops.stft_front(y, sr, n_fft, hop, center, window, None, None, 0.0, None, 2.0, 1 | 8, 0.85, 2.0, None)
     assert np.array_equal(st1.cpu().numpy()[:, [0, 3, 5, 6, 7]], st[:, [0, 3, 5, 6, 7]])
-    _, none, pv1 = ops.stft_rows_seg(y, sr, n_fft, hop, center, window, None, None, 0.0, None, 0, 0.85, 2.0, plan)
+    _, none, pv1 = ops.stft_front(y, sr, n_fft, hop, center, window, None, None, 0.0, None, 2.0, 0, 0.85, 2.0, plan)
     assert none is None and np.array_equal(pv1.cpu().numpy(), pv)
 
 

@@ -1,4 +1,5 @@
 """Host-side logic of the product (tables, plans, validation) -- CPU only, no GPU calls."""
+import functools
 import os
 import re
 
@@ -11,6 +12,7 @@ from numpy.testing import assert_allclose, assert_array_equal
 from oracle import cpu_ref as O
 from sygnals_amd import _tables as T
 from tests.cqt_cases import CASES as CQT_CASES
+from tests.front_cases import CASES as FRONT_CASES, EXPECT as FRONT_EXPECT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -341,6 +343,72 @@ def test_cqt_route_is_pinned(case):
             assert cqt_route(p, mode, fused=True) == (False, want), mode
     with pytest.raises(ValueError, match="cqt_mode"):
         cqt_route(p, "fp64")
+
+
+@functools.lru_cache(maxsize=None)
+def _front_caps_on_the_host(sr, n_fft, n_mels, waves=16):
+    """ops.front_caps without a device: the packers of sygnals_amd._tables raise ValueError for a filterbank they cannot
+    hold, which is how MelConfig (frame length 2048) and ops._segtab (1024 / 4096 / 512 / 256) find out before they upload."""
+    from sygnals_amd import ops
+
+    def packs(fn, *a, **kw):
+        try:
+            fn(*a, **kw)
+            return True
+        except ValueError:
+            return False
+    fb = (sr, n_fft, n_mels or 16, 0.0, sr / 2.0)
+    plan2048 = n_fft == 2048 and fb[2] <= 256 and (
+        packs(T.pack_mel_plan, T.mel_filterbank(*fb), waves) or
+        (fb[2] <= 255 and packs(T.pack_mel_segments, *fb, basis=T.mel_filterbank(*fb), n_pass=4, row_base=4)))
+    k = ops._SEG.get(n_fft)
+    table = bool(n_mels and k and n_mels <= k["max_mels"] and
+                 packs(k["pack"], *fb, basis=T.mel_filterbank(*fb), **k["pack_kw"]))
+    return dict(waves=waves, plan2048=plan2048, table=table)
+
+
+# (the rows whose request reaches front_route: not the MFCC rows straight from a launch, and not
+# mfcc_batch(fused=False), which takes the generic chain without asking)
+@pytest.mark.parametrize("case", sorted(k for k, (route, _) in FRONT_EXPECT.items() if route is not None and
+                                        not (FRONT_CASES[k].entry == "mfcc_batch" and FRONT_CASES[k].fused is False)))
+def test_front_route_is_pinned(case):
+    """Which wrappers of sygnals_amd.ops serve a request to the STFT front ends (sygnals_amd._front.front_route, the function
+    ops.stft_front launches from) for every row of tests/front_cases.py -- the route tests/test_gpu_front_route.py sees
+    taken on the device -- and the entry points recorded for the row are that route's."""
+    from sygnals_amd._front import front_route
+    from tests.front_cases import wants
+    c = FRONT_CASES[case]
+    route, calls = FRONT_EXPECT[case]
+    rows, mel = wants(c)
+    caps = _front_caps_on_the_host(c.sr, c.n_fft, c.n_mels if mel else None)
+    assert front_route(c.n_fft, c.hop, c.L, c.power, c.n_mels if mel else None, rows, caps) == route
+    for name in set(route) - {None}:
+        if name == "generic":
+            assert "syg_cabs_pow_f32" in calls
+        else:
+            assert f"syg_{name}_f32" in calls or (name == "stft2048_mel" and "syg_stft2048_mel_tri_f32" in calls), (name, calls)
+
+
+def test_front_route_beyond_what_a_test_can_run():
+    """The frame-length-2048 rows alone: stft2048_stats up to its entry point's limits (L < 2^28, fewer than 2^24 frames,
+    hop <= 512, 16 waves), beyond them the mel launch with stand-in bands at power 2, else the generic chain; a mel power
+    the device does not have is refused before anything runs."""
+    from sygnals_amd._front import front_route
+    from sygnals_amd._lib import SygnalsHipError
+    caps = dict(waves=16, plan2048=True, table=False)
+    assert front_route(2048, 512, (1 << 28) - 1, 2.0, None, True, caps) == ("stft2048_stats", None)
+    assert front_route(2048, 512, 1 << 28, 2.0, None, True, caps) == ("stft2048_mel", None)
+    assert front_route(2048, 512, 1 << 28, 1.0, None, True, caps) == ("generic", None)
+    assert front_route(2048, 1, (1 << 24) - 2, 2.0, None, True, caps) == ("stft2048_stats", None)
+    assert front_route(2048, 1, (1 << 24) - 1, 2.0, None, True, caps) == ("stft2048_mel", None)
+    assert front_route(2048, 513, 48000, 2.0, None, True, caps) == ("stft2048_mel", None)
+    assert front_route(2048, 512, 48000, 2.0, None, True, dict(caps, waves=8)) == ("stft2048_mel", None)
+    assert front_route(2048, 512, 48000, 2.0, None, True, dict(caps, waves=8, plan2048=False)) == ("generic", None)
+    assert front_route(2048, 512, 1 << 28, 2.0, 40, True, caps) == ("stft2048_mel", None)
+    assert front_route(2048, 512, 48000, 1.0, 40, True, caps) == ("generic", "generic")
+    for n_fft in (2048, 1024, 1000):
+        with pytest.raises(SygnalsHipError, match="mel power must be 1.0 or 2.0 on the device"):
+            front_route(n_fft, n_fft // 4, 48000, 3.0, 40, False, dict(caps, plan2048=n_fft == 2048))
 
 
 def test_cqt_route_covers_every_instantiation():

@@ -55,7 +55,7 @@ for it in range(N):
         Y2 = (rng.normal(0, 0.3, (B, L2)) * rng.random((B, 1))).astype(np.float32)
         y2 = ops.to_device_f32(Y2)
         fr = O.fft_frequencies(sr, nf)
-        _, st, _ = ops.stft_rows_seg(y2, sr, nf, hop2, center, "hann", None, None, 0.0, None, 31, 0.85, 2.0, None)
+        _, st, _ = ops.stft_front(y2, sr, nf, hop2, center, "hann", None, None, 0.0, None, 2.0, 31, 0.85, 2.0, None)
         st = st.cpu().numpy()
         Sm = np.abs(O.stft(Y2[0].astype(np.float64), nf, hop2, center=center))
         ref = O.spectral_stats_frames(Sm, fr)
