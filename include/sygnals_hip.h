@@ -52,13 +52,16 @@ const char* syg_last_error(void);
  *                         syg_cqt_octave_bf16x3_f32
  *   SYG_OPT_DWT_FORM      1 (default: the clip-resident kernels wherever a row fits) | 0: syg_dwt_f32 / syg_idwt_f32 run
  *                         one launch per level with the approximations through the workspace
+ *   SYG_OPT_FX_DELAY_FORM -1 (default: chunked chains where the plain form would leave the device mostly idle) | 0 (one
+ *                         lane per residue, always) | 1 (chunked, always): form of syg_fx_delay_f32
  * syg_set_option returns SYG_OK or SYG_E_INVALID (unknown key / value out of range); syg_get_option the current value. */
 #define SYG_OPT_RESERVED_CUS 0
 #define SYG_OPT_STFT_LOAD 1
 #define SYG_OPT_SOS_CLIP 2
 #define SYG_OPT_CQT_STAGED 3
 #define SYG_OPT_DWT_FORM 4
-#define SYG_OPT_COUNT 5
+#define SYG_OPT_FX_DELAY_FORM 5
+#define SYG_OPT_COUNT 6
 int syg_set_option(int key, int value);
 int syg_get_option(int key);
 
@@ -512,6 +515,56 @@ int syg_istft2048_f32(const float* D, int64_t B, int64_t T, int hop, int center,
 int syg_hnr_rows_f32(const float* y_harm, const float* y_perc, int64_t B, int64_t L, int64_t ldy, int frame_length,
                      int hop, int center, int64_t T, float* hnr_out, float* rms_harm_out, float* rms_perc_out,
                      void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Audio effects: sygnals/core/audio/effects/ (delay.py, tremolo.py, compression.py, reverb.py, utility.py).  Rows are
+ * [B, L] float32 with a row stride (ld*, in elements); `out` may alias `x` in every entry of this block.  No atomics: the
+ * results are bit-identical from run to run.  The float64 restatement of tests/effects_ref.py is the contract (the two
+ * spectral effects rest on librosa, which is not a dependency; the others are pinned to the reference's own output).
+ * syg_fx_delay_f32: apply_delay (delay.py:15-111) with D = delay_samples >= 1: w[n] = x[n] + feedback w[n - D],
+ *   out[n] = dry x[n] + wet w[n - D], w = 0 at negative indices; D >= L is legal (out = dry x).  0 <= feedback < 1 (also
+ *   after rounding to float32).  The output expression is __fadd_rn(__fmul_rn(dry, x), __fmul_rn(wet, w)), no FMA: at
+ *   feedback = 0 the result is exactly dry x[n] + wet x[n - D] in float32.  One lane per residue n mod D walks its chain;
+ *   where that would leave the device mostly idle (B min(D, L) under 256 lanes per CU) and a chain has at least
+ *   4 syg_fx_delay_chunk() steps, the chains are cut into chunks of syg_fx_delay_chunk() steps whose carries are scanned by
+ *   the same recurrence with feedback^chunk; that form needs `work`, syg_fx_delay_work_bytes(B, L, D) bytes (0 otherwise:
+ *   work may be NULL; -1 for a bad shape).  apply_chorus (chorus.py:24-156) computes this with
+ *   D = ceil((delay + depth) sr) + 2: its interpolation point lies left of its grid, so its LFO has no effect.
+ * syg_spectral_gate_f32: the gain of noise_reduction_spectral (utility.py:59-131) on the STFTs of syg_stft2048_c2c_f32:
+ *   D [B, T, 1025] complex of the clip, Dn [B, Tn, 1025] complex of its first noise_samples samples.
+ *   noise [B, 1025] float32 (always written) = mean over the Tn frames of re^2 + im^2, summed in float64;
+ *   gain [B, T, 1025] float32 = sqrt(max(0, 1 - (amount noise) / P)), P = __fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im))
+ *   of D; 0 where P == 0, never NaN.  gain D is the reference's sqrt(max(0, |D|^2 - amount noise)) exp(i angle D):
+ *   pass it to syg_istft2048_f32 as mask_a.  amount >= 0, finite.
+ * syg_fx_mix_f32: out[r, n] = a x[r, n] + b y[r, n], n < L; x reads as 0 from Lx on and y from Ly on; y may be NULL
+ *   (out = a x: adjust_gain, utility.py:22-55).  The dry / wet mix of apply_reverb over the longer wet signal, and
+ *   transient_shaping_hpss's harmonic + scale percussive.
+ * syg_fx_tremolo_f32: apply_tremolo (tremolo.py:55-111): out = x ((1 - depth) + depth lfo(n0 + n)), the LFO in float64
+ *   on the device, phase = ((2 pi) rate) ((n0 + n) / sr) in that order; SYG_LFO_SINE (sin + 1) / 2, SYG_LFO_TRIANGLE
+ *   (scipy.signal.sawtooth(phase, 0.5) + 1) / 2, SYG_LFO_SQUARE 1 where sin(phase) > 0, else 0.  The product is formed in
+ *   float64 and rounded once.  rate > 0, 0 <= depth <= 1, sr > 0, n0 >= 0 (the index of the row's first sample).
+ * syg_fx_compress_f32: simple_dynamic_range_compression (compression.py:14-64): where |x| > threshold,
+ *   x (threshold + (|x| - threshold) / ratio) / |x| (float64, rounded once), elsewhere x bit for bit.  ratio >= 1.
+ * syg_fx_midside_f32: stereo_widening_midside (utility.py:188-253) on x [B, 2, L] (row 2 b + c at (2 b + c) ldx):
+ *   mid = (l + r) / 2, side = width (l - r) / 2, out = (mid + side, mid - side).  width >= 0.
+ * ------------------------------------------------------------------------------- */
+#define SYG_LFO_SINE 0
+#define SYG_LFO_TRIANGLE 1
+#define SYG_LFO_SQUARE 2
+int syg_fx_delay_chunk(void);
+int64_t syg_fx_delay_work_bytes(int64_t B, int64_t L, int64_t delay_samples);
+int syg_fx_delay_f32(const float* x, int64_t B, int64_t L, int64_t ldx, int64_t delay_samples, double feedback, double dry,
+                     double wet, float* out, int64_t ldo, void* work, void* stream);
+int syg_spectral_gate_f32(const float* D, int64_t B, int64_t T, const float* Dn, int64_t Tn, double amount, float* gain,
+                          float* noise, void* stream);
+int syg_fx_mix_f32(const float* x, int64_t Lx, int64_t ldx, const float* y, int64_t Ly, int64_t ldy, int64_t B, int64_t L,
+                   double a, double b, float* out, int64_t ldo, void* stream);
+int syg_fx_tremolo_f32(const float* x, int64_t B, int64_t L, int64_t ldx, double sr, double rate, double depth, int shape,
+                       int64_t n0, float* out, int64_t ldo, void* stream);
+int syg_fx_compress_f32(const float* x, int64_t B, int64_t L, int64_t ldx, double threshold, double ratio, float* out,
+                        int64_t ldo, void* stream);
+int syg_fx_midside_f32(const float* x, int64_t B, int64_t L, int64_t ldx, double width, float* out, int64_t ldo,
+                       void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Onset detection: librosa 0.10 onset.onset_strength / util.peak_pick / onset.onset_detect as called by detect_onsets,

@@ -103,6 +103,14 @@ SIGNATURES = {
     "syg_idwt_length": (_l, [_p, _i, _i]),
     "syg_idwt_work_bytes": (_l, [_l, _p, _i, _i]),
     "syg_idwt_f32": (_i, [_p, _l, _l, _p, _i, _p, _p, _i, _p, _l, _p, _p]),
+    "syg_fx_delay_chunk": (_i, []),
+    "syg_fx_delay_work_bytes": (_l, [_l, _l, _l]),
+    "syg_fx_delay_f32": (_i, [_p, _l, _l, _l, _l, _d, _d, _d, _p, _l, _p, _p]),
+    "syg_spectral_gate_f32": (_i, [_p, _l, _l, _p, _l, _d, _p, _p, _p]),
+    "syg_fx_mix_f32": (_i, [_p, _l, _l, _p, _l, _l, _l, _l, _d, _d, _p, _l, _p]),
+    "syg_fx_tremolo_f32": (_i, [_p, _l, _l, _l, _d, _d, _d, _i, _l, _p, _l, _p]),
+    "syg_fx_compress_f32": (_i, [_p, _l, _l, _l, _d, _d, _p, _l, _p]),
+    "syg_fx_midside_f32": (_i, [_p, _l, _l, _l, _d, _p, _l, _p]),
 }
 
 _lib = None

@@ -1,1 +1,1 @@
-"""Device-backed mirror of sygnals/core/audio (features only)."""
+"""Device-backed mirror of sygnals/core/audio: features and the effects package."""

@@ -118,7 +118,8 @@ class _Settings:
       cqt_chain             True: up to three decimation levels per pass; False: one launch per level
       cqt_fused             True: the one-launch form (syg_cqt_fused_f32) where the plan has its shape; False: level by level
       one_launch_features   True: extract_features routes MFCC + statistics / contrast requests to the one-launch kernels
-    Options that live in the library (syg_set_option): reserved_cus, stft_load, sos_clip, cqt_staged, dwt_form."""
+    Options that live in the library (syg_set_option): reserved_cus, stft_load, sos_clip, cqt_staged, dwt_form,
+    fx_delay_form."""
     waves = T.WAVES
     cqt_mode = "bf16x3"
     cqt_streams = 1
@@ -128,11 +129,11 @@ class _Settings:
 
 
 settings = _Settings()
-_LIB_OPTIONS = {"reserved_cus": 0, "stft_load": 1, "sos_clip": 2, "cqt_staged": 3, "dwt_form": 4}      # SYG_OPT_* of include/sygnals_hip.h
+_LIB_OPTIONS = {"reserved_cus": 0, "stft_load": 1, "sos_clip": 2, "cqt_staged": 3, "dwt_form": 4, "fx_delay_form": 5}      # SYG_OPT_* of include/sygnals_hip.h
 
 
 def set_option(name: str, value: int) -> None:
-    """syg_set_option by name (reserved_cus | stft_load | sos_clip | cqt_staged | dwt_form)."""
+    """syg_set_option by name (reserved_cus | stft_load | sos_clip | cqt_staged | dwt_form | fx_delay_form)."""
     check(lib().syg_set_option(_LIB_OPTIONS[name], int(value)), "syg_set_option")
 
 
@@ -2044,3 +2045,138 @@ def idwt(packed: torch.Tensor, lens, wavelet="db4", mode: str = "symmetric") -> 
     y = torch.empty((B, Lout), dtype=torch.float32, device=packed.device)
     _call("syg_idwt_f32", _ptr(packed), B, _ld(packed), lp, levels, _ptr(rec_lo), _ptr(rec_hi), F, _ptr(y), Lout, _ptr(work))
     return y
+
+
+# ------------------------------------------------------------------ audio effects
+LFO_SHAPES = {"sine": 0, "triangle": 1, "square": 2}          # SYG_LFO_* of include/sygnals_hip.h
+
+
+def _fx_out(x: torch.Tensor, out: Optional[torch.Tensor], L: Optional[int] = None) -> torch.Tensor:
+    """The output rows of an effect: a new [B, L] tensor, or `out` checked (x itself for an in-place call)."""
+    shape = (x.shape[0], x.shape[1] if L is None else L)
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=x.device)
+    if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != x.device or out.stride(1) != 1:
+        raise ValueError(f"out must be a float32 tensor {shape} on x's device with unit stride along a row")
+    return out
+
+
+def fx_delay_chunk() -> int:
+    """Steps of a chain per chunk in the chunked form of syg_fx_delay_f32 (the library owns the figure)."""
+    return int(lib().syg_fx_delay_chunk())
+
+
+def fx_delay(x: torch.Tensor, delay_samples: int, feedback: float = 0.4, wet: float = 0.5, dry: float = 1.0,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Feedback delay of every row of x [B, L] (syg_fx_delay_f32): w[n] = x[n] + feedback w[n - D], out[n] = dry x[n] +
+    wet w[n - D] with D = delay_samples >= 1 (D >= L: out = dry x).  `out` may be x."""
+    x = _clips(x, "x")
+    B, L = x.shape
+    D = int(delay_samples)
+    if B < 1 or L < 1:
+        raise ValueError("fx_delay: empty input")
+    if D < 1:
+        raise ValueError("fx_delay: delay_samples must be >= 1")
+    if not 0.0 <= feedback < 1.0:
+        raise ValueError("fx_delay: feedback must be in [0, 1)")
+    out = _fx_out(x, out)
+    wb = lib().syg_fx_delay_work_bytes(B, L, D)
+    if wb < 0:
+        check(-1, "syg_fx_delay_work_bytes")
+    work = torch.empty((wb // 4,), dtype=torch.float32, device=x.device) if wb > 0 else None
+    _call("syg_fx_delay_f32", _ptr(x), B, L, _ld(x), D, float(feedback), float(dry), float(wet), _ptr(out), _ld(out),
+          _ptr(work))
+    return out
+
+
+def fx_mix(x: torch.Tensor, y: Optional[torch.Tensor] = None, a: float = 1.0, b: float = 1.0, length: Optional[int] = None,
+           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r, n] = a x[r, n] + b y[r, n] for n < length (syg_fx_mix_f32); x [B, Lx] and y [B, Ly] read as zero past
+    their own lengths, y may be None (a x); length defaults to the longer of the two.  `out` may be x."""
+    x = _clips(x, "x")
+    B, Lx = x.shape
+    Ly = 0
+    if y is not None:
+        y = _clips(y, "y")
+        if y.shape[0] != B:
+            raise ValueError("fx_mix: x and y must hold the same number of rows")
+        Ly = y.shape[1]
+    L = max(Lx, Ly) if length is None else int(length)
+    if B < 1 or L < 1 or Lx < 1 or (y is not None and Ly < 1):
+        raise ValueError("fx_mix: empty input")
+    out = _fx_out(x, out, L)
+    _call("syg_fx_mix_f32", _ptr(x), Lx, _ld(x), _ptr(y), Ly, _ld(y) if y is not None else 0, B, L, float(a), float(b),
+          _ptr(out), _ld(out))
+    return out
+
+
+def fx_tremolo(x: torch.Tensor, sr: float, rate: float = 5.0, depth: float = 0.5, shape: str = "sine", n0: int = 0,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x ((1 - depth) + depth lfo) on rows x [B, L] (syg_fx_tremolo_f32), the LFO in float64 on the device; n0 is the
+    index of the rows' first sample (a row that continues an earlier one).  `out` may be x."""
+    x = _clips(x, "x")
+    if shape not in LFO_SHAPES:
+        raise ValueError("LFO shape must be 'sine', 'triangle', or 'square'.")
+    if not 0.0 <= depth <= 1.0:
+        raise ValueError("fx_tremolo: depth must be in [0, 1]")
+    if not rate > 0 or not sr > 0:
+        raise ValueError("fx_tremolo: rate and sr must be positive")
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("fx_tremolo: empty input")
+    out = _fx_out(x, out)
+    _call("syg_fx_tremolo_f32", _ptr(x), x.shape[0], x.shape[1], _ld(x), float(sr), float(rate), float(depth),
+          LFO_SHAPES[shape], int(n0), _ptr(out), _ld(out))
+    return out
+
+
+def fx_compress(x: torch.Tensor, threshold: float = 0.8, ratio: float = 4.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Downward compression of rows x [B, L] (syg_fx_compress_f32): |x| > threshold -> threshold + (|x| - threshold) /
+    ratio with the sign kept; the other samples are copied bit for bit.  `out` may be x."""
+    x = _clips(x, "x")
+    if not threshold >= 0.0:
+        raise ValueError("fx_compress: threshold must be >= 0")
+    if not ratio >= 1.0:
+        raise ValueError("fx_compress: ratio must be >= 1")
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError("fx_compress: empty input")
+    out = _fx_out(x, out)
+    _call("syg_fx_compress_f32", _ptr(x), x.shape[0], x.shape[1], _ld(x), float(threshold), float(ratio), _ptr(out), _ld(out))
+    return out
+
+
+def fx_midside(x: torch.Tensor, width: float = 1.5) -> torch.Tensor:
+    """Mid / side widening of stereo clips x [B, 2, L] (syg_fx_midside_f32) -> [B, 2, L]: mid +- width side."""
+    require_gpu()
+    if x.dim() != 3 or x.shape[1] != 2 or x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError("x must be a float32 CUDA tensor of shape [B, 2, L]")
+    if not width >= 0.0:
+        raise ValueError("fx_midside: width must be >= 0")
+    B, _, L = x.shape
+    if B < 1 or L < 1:
+        raise ValueError("fx_midside: empty input")
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    _call("syg_fx_midside_f32", _ptr(x), B, L, L, float(width), _ptr(out), L)
+    return out
+
+
+def spectral_gate(D: torch.Tensor, Dn: torch.Tensor, amount: float = 1.0, profile: bool = False):
+    """The spectral-subtraction gain of noise_reduction_spectral (syg_spectral_gate_f32): D [B, T, 1025, 2] the clip's
+    STFT, Dn [B, Tn, 1025, 2] the STFT of its noise segment -> G [B, T, 1025] float32 = sqrt(max(0, 1 - amount N / |D|^2))
+    (0 where |D|^2 is 0), a mask for istft2048; with `profile` also N [B, 1025], the mean noise power per bin."""
+    require_gpu()
+    for name, t in (("D", D), ("Dn", Dn)):
+        if t.dim() != 4 or t.shape[2] != 1025 or t.shape[3] != 2 or t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError(f"{name} must be a float32 CUDA tensor [B, T, 1025, 2]")
+    if Dn.shape[0] != D.shape[0]:
+        raise ValueError("D and Dn must hold the same number of clips")
+    if not amount >= 0.0:
+        raise ValueError("reduction_amount must be non-negative.")
+    D, Dn = D.contiguous(), Dn.contiguous()
+    B, Tn = D.shape[0], D.shape[1]
+    if B < 1 or Tn < 1 or Dn.shape[1] < 1:
+        raise ValueError("spectral_gate: empty input")
+    G = torch.empty((B, Tn, 1025), dtype=torch.float32, device=D.device)
+    N = torch.empty((B, 1025), dtype=torch.float32, device=D.device)
+    _call("syg_spectral_gate_f32", _ptr(D), B, Tn, _ptr(Dn), Dn.shape[1], float(amount), _ptr(G), _ptr(N))
+    return (G, N) if profile else G
