@@ -761,6 +761,41 @@ int64_t syg_idwt_work_bytes(int64_t B, const int64_t* lens_host, int levels, int
 int syg_idwt_f32(const float* coeffs, int64_t B, int64_t ldc, const int64_t* lens_host, int levels, const float* rec_lo,
                  const float* rec_hi, int F, float* y, int64_t ldy, void* work, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Augmentation: the phase vocoder of librosa.effects.time_stretch (sygnals/core/audio/effects/time_stretch.py:15-48,
+ * sygnals/core/augment/effects_based.py:60-99) and add_noise (sygnals/core/augment/noise.py:19-101).
+ *
+ * syg_phase_vocoder_f32: librosa 0.10 core.phase_vocoder between syg_stft2048_c2c_f32 and syg_istft2048_f32.
+ *   D [B, T, 1025, 2] frame-major -> out [B, T_out, 1025, 2].  col [T_out] int32 and alpha [T_out] float64 are DEVICE
+ *   arrays, the step table of step = np.arange(0, T, rate): col[t] = int(step_t), alpha[t] = step_t mod 1
+ *   (sygnals_amd/_tables.vocoder_steps).  Per (clip, bin), in the order t = 0 .. T_out - 1:
+ *       out[t] = ((1 - alpha[t]) |D[col[t]]| + alpha[t] |D[col[t] + 1]|) p,   then p <- p u(D[col[t] + 1]) conj(u(D[col[t]])),
+ *   p = u(D[0]) at t = 0, u(z) = z / |z| formed in float64 (no magnitude of float32 parts under- or overflows) and
+ *   u(0) = (copysign(1, re), 0), which is exp(i np.angle(z)) for a bin stored as -0 + 0j as well; p is float64.  That is
+ *   librosa's phase accumulator modulo 2 pi without atan2 / sincos.  A column outside [0, T) reads as zero (librosa pads
+ *   two), so no table makes the kernel read outside D.
+ *   form: -1 the rule | 0 the chain form (one lane per (clip, bin) walks every step) | 1 the chunked form (steps cut into
+ *   chunks of syg_phase_vocoder_chunk(), the chunks' products scanned into chunk-start phasors; it reads D twice).  The
+ *   rule takes the chunked form where the chain form has fewer than eight waves a CU (17 B < 8 CUs) and T_out >= 4
+ *   chunks.  The chunked form needs `work`, syg_phase_vocoder_work_bytes(B, T_out, form) bytes, 16-byte aligned (0
+ *   otherwise: `work` may be NULL).  The two forms agree to the rounding of the float64 products.
+ *
+ * syg_fx_add_noise_f32: y [B, L], noise [B, L] (row strides ldy, ldn), snr_db [B] float64 DEVICE array -> out [B, L] (may
+ *   alias y).  Per row Ps = mean(y^2), Pn = mean(noise^2) in float64, sums in a fixed order; Ps or Pn below the float64
+ *   epsilon: the row is copied bit for bit; otherwise out = y + noise sqrt((Ps / 10^(snr_db / 10)) / Pn), formed in
+ *   float64 and rounded once.  L <= syg_fx_add_noise_resident_max(): one launch, a workgroup keeps its row in LDS between
+ *   the sums and the mix.  Longer rows: two launches (slice sums, then the mix) and `work` of
+ *   syg_fx_add_noise_work_bytes(B, L) bytes, 16-byte aligned.
+ * ------------------------------------------------------------------------------- */
+int syg_phase_vocoder_chunk(void);
+int64_t syg_phase_vocoder_work_bytes(int64_t B, int64_t T_out, int form);
+int syg_phase_vocoder_f32(const float* D, int64_t B, int64_t T, const int32_t* col, const double* alpha, int64_t T_out,
+                          float* out, void* work, int form, void* stream);
+int64_t syg_fx_add_noise_resident_max(void);
+int64_t syg_fx_add_noise_work_bytes(int64_t B, int64_t L);
+int syg_fx_add_noise_f32(const float* y, int64_t B, int64_t L, int64_t ldy, const float* noise, int64_t ldn,
+                         const double* snr_db, float* out, int64_t ldo, void* work, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

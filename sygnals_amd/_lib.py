@@ -111,6 +111,12 @@ SIGNATURES = {
     "syg_fx_tremolo_f32": (_i, [_p, _l, _l, _l, _d, _d, _d, _i, _l, _p, _l, _p]),
     "syg_fx_compress_f32": (_i, [_p, _l, _l, _l, _d, _d, _p, _l, _p]),
     "syg_fx_midside_f32": (_i, [_p, _l, _l, _l, _d, _p, _l, _p]),
+    "syg_phase_vocoder_chunk": (_i, []),
+    "syg_phase_vocoder_work_bytes": (_l, [_l, _l, _i]),
+    "syg_phase_vocoder_f32": (_i, [_p, _l, _l, _p, _p, _l, _p, _p, _i, _p]),
+    "syg_fx_add_noise_resident_max": (_l, []),
+    "syg_fx_add_noise_work_bytes": (_l, [_l, _l]),
+    "syg_fx_add_noise_f32": (_i, [_p, _l, _l, _l, _p, _l, _p, _p, _l, _p, _p]),
 }
 
 _lib = None

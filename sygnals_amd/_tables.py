@@ -540,3 +540,18 @@ def butter_padlen(sos: np.ndarray) -> int:
     ntaps = 2 * sos.shape[0] + 1
     ntaps -= min(int((sos[:, 2] == 0).sum()), int((sos[:, 5] == 0).sum()))
     return 3 * ntaps
+
+
+def vocoder_steps(n_frames: int, rate: float):
+    """The step table of librosa.phase_vocoder for an STFT of n_frames columns: step = np.arange(0, n_frames, rate) in
+    float64 -- numpy's own arange, so the device and the restatement cannot differ by a floor -- as
+    (col int32 [T'] = int(step), alpha float64 [T'] = step mod 1), T' = ceil(n_frames / rate)."""
+    n_frames, rate = int(n_frames), float(rate)
+    if n_frames < 1:
+        raise ValueError("vocoder_steps: n_frames must be >= 1")
+    if not rate > 0 or not np.isfinite(rate):
+        raise ValueError("vocoder_steps: rate must be positive and finite")
+    if n_frames / rate >= 2 ** 31:
+        raise ValueError("vocoder_steps: too many output frames")
+    steps = np.arange(0, n_frames, rate, dtype=np.float64)
+    return steps.astype(np.int64).astype(np.int32), np.mod(steps, 1.0)

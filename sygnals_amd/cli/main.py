@@ -5,8 +5,11 @@
 .csv -> DataFrame, .npz -> dict of arrays; ValueError -> click.UsageError).  The `dsp` and
 `filter` groups follow the surface documented in the reference's README.md:483-533, 704-900 --
 in the reference snapshot those groups are commented out (sygnals/cli/main.py:29-33, 115-119), so
-they are provided here rather than kept.  Run stand-alone as `python -m sygnals_amd.cli.main ...`
-or attach the groups to the reference CLI through the plugin (register_cli_commands).
+they are provided here rather than kept.  The `augment` group keeps the option names of
+sygnals/cli/augment_cmd.py (add-noise: --snr, --noise-type, --seed; time-stretch: --rate; -o/--output);
+pitch-shift is not offered.  Run stand-alone as `python -m sygnals_amd.cli.main ...`
+or attach the features / dsp / filter groups to the reference CLI through the plugin (register_cli_commands); `augment`
+is not attached there: the reference CLI already owns a group of that name.
 """
 from __future__ import annotations
 
@@ -293,9 +296,57 @@ def filter_apply(input_file, ftype, cutoff, fs, order, output):
     click.echo(f"Filtered signal saved to '{Path(output).name}'.")
 
 
+# ---------------------------------------------------------------- augment
+@click.group("augment")
+def augment_cmd():
+    """Apply data augmentation techniques to audio signals."""
+
+
+@augment_cmd.command("add-noise")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False, resolve_path=True))
+@click.option("-o", "--output", type=click.Path(resolve_path=True), required=True,
+              help="Output file path for the augmented audio.")
+@click.option("--snr", type=float, required=True, help="Target Signal-to-Noise Ratio (SNR) in dB.")
+@click.option("--noise-type", type=click.Choice(["gaussian", "white", "pink", "brown"], case_sensitive=False),
+              default="gaussian", show_default=True, help="Type of noise to add.")
+@click.option("--seed", type=int, default=None, help="Random seed for noise generation.")
+def augment_add_noise(input_file, output, snr, noise_type, seed):
+    """Add noise to the audio signal."""
+    from ..core.augment import add_noise
+    x, sr = _load_signal(input_file, None)
+    try:
+        y = add_noise(x, snr_db=snr, noise_type=noise_type.lower(), seed=seed)
+    except ValueError as e:
+        raise click.UsageError(f"Error during noise addition: {e}")
+    _save_series(y, sr, output)
+    click.echo(f"Successfully applied '{noise_type}' noise (SNR={snr} dB) to '{Path(input_file).name}', "
+               f"saved to '{Path(output).name}'.")
+
+
+@augment_cmd.command("time-stretch")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False, resolve_path=True))
+@click.option("-o", "--output", type=click.Path(resolve_path=True), required=True,
+              help="Output file path for the augmented audio.")
+@click.option("--rate", type=float, required=True, help="Factor to stretch time (>1 speeds up, <1 slows down).")
+def augment_time_stretch(input_file, output, rate):
+    """Stretch the time duration of the audio signal without changing pitch."""
+    from ..core.augment import time_stretch
+    if rate <= 0:
+        raise click.UsageError("Stretch rate must be positive.")
+    x, sr = _load_signal(input_file, None)
+    try:
+        y = time_stretch(x, rate=rate)
+    except ValueError as e:
+        raise click.UsageError(f"Error during time stretching: {e}")
+    _save_series(y, sr, output)
+    click.echo(f"Successfully applied time stretch (rate={rate}) to '{Path(input_file).name}', "
+               f"saved to '{Path(output).name}'.")
+
+
 cli.add_command(features_cmd)
 cli.add_command(dsp_cmd)
 cli.add_command(filter_cmd)
+cli.add_command(augment_cmd)
 
 if __name__ == "__main__":
     cli()

@@ -1,7 +1,8 @@
 // Audio effects of sygnals/core/audio/effects/: the feedback delay (delay.py:15-111, and what chorus.py computes), the
 // spectral-subtraction gate of noise_reduction_spectral (utility.py:59-131) as a real mask for syg_istft2048_f32, and the
-// pointwise effects (gain / mixes, tremolo.py, compression.py, mid/side widening).  The float64 restatement that is the
-// contract lives in tests/effects_ref.py.  No atomics anywhere: every result is bit-identical from run to run.
+// pointwise effects (gain / mixes, tremolo.py, compression.py, mid/side widening); and add_noise of
+// sygnals/core/augment/noise.py.  The float64 restatement that is the contract lives in tests/effects_ref.py (add_noise:
+// tests/vocoder_ref.py).  No atomics anywhere: every result is bit-identical from run to run.
 //
 // Delay.  w[n] = x[n] + fb w[n - D], out[n] = dry x[n] + wet w[n - D].  The recurrence is D independent chains, one per
 // residue n mod D, and neighbouring residues are neighbours in memory: a lane owns a residue and walks it in steps of D
@@ -20,6 +21,11 @@
 // Gate.  Two launches: gate_profile_kernel sums |Dn|^2 over the profile's frames per bin in float64 (four frame slices
 // per workgroup, combined in slice order); gate_mask_kernel is pointwise over D, lanes along the bins, four frames per
 // workgroup so that one long row fills the device.
+//
+// add_noise.  A row's two powers are needed before its first output sample.  A row of up to AN_RESIDENT samples is one
+// workgroup's: it sums while it copies y and noise into LDS and mixes from there (one launch, 12 bytes a sample).  A
+// longer row takes two launches: slice sums (so that one long row still fills the device), then the mix, which adds the
+// row's slices in slice order and reads y and noise again (20 bytes a sample).
 #include <float.h>
 #include <math.h>
 #include "host.h"
@@ -231,6 +237,116 @@ __global__ __launch_bounds__(FX_THREADS) void midside_kernel(const float* x, int
   }
 }
 
+// ------------------------------------------------------------------ add_noise
+// out = y + noise sqrt(Ps / (10^(snr / 10) Pn)) per row, Ps = mean(y^2) and Pn = mean(noise^2) in float64 (noise.py:75-99);
+// a row whose Ps or Pn is below the float64 epsilon is copied.  Every sum has a fixed order: no atomics.
+constexpr int AN_THREADS = 1024;           // the resident form: one workgroup a row
+constexpr int64_t AN_RESIDENT = 16384;     // samples of a row it keeps in LDS between the sums and the mix (y, noise: 128 KiB)
+constexpr int AN_SLICES = 64;              // most slices of a row in the two-launch form's power pass
+constexpr int AN_PER_THREAD = 16;          // samples per thread of its mix pass: the row's partial sums are read once per 16
+constexpr int64_t AN_SEG = (int64_t)FX_THREADS * AN_PER_THREAD;
+
+struct NoiseArgs {
+  const float* y; const float* noise; const double* snr; float* out; int64_t B, L, ldy, ldn, ldo; int S; int64_t slen; double2* part;
+};
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+  return v;
+}
+
+// sums of (a, c) over the workgroup, the waves' sums added in wave order; every thread gets the same pair
+template <int NT>
+__device__ __forceinline__ void block_sum2(double& a, double& c, double (*red)[NT / 64]) {
+  a = wave_sum_f64(a);
+  c = wave_sum_f64(c);
+  __syncthreads();                           // a second call reuses `red`
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = c; }
+  __syncthreads();
+  a = 0.0; c = 0.0;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) { a += red[0][w]; c += red[1][w]; }
+}
+
+// the reference's order: (Ps / 10^(snr / 10)) / Pn; false: the row is copied
+__device__ __forceinline__ bool noise_scale(double Ps, double Pn, double snr_db, double& s) {
+  constexpr double EPS = 2.220446049250313e-16;
+  if (Ps < EPS || Pn < EPS) return false;
+  s = sqrt((Ps / pow(10.0, snr_db / 10.0)) / Pn);
+  return true;
+}
+
+__device__ __forceinline__ float noise_mix(float y, float n, double s) { return (float)((double)y + (double)n * s); }
+
+__global__ __launch_bounds__(AN_THREADS) void noise_resident_kernel(NoiseArgs A) {
+  extern __shared__ float an_rows[];         // y [L] | noise [L]
+  __shared__ double red[2][AN_THREADS / 64];
+  float* sy = an_rows;
+  float* sn = an_rows + A.L;
+  for (int64_t b = blockIdx.x; b < A.B; b += gridDim.x) {
+    const float* y = A.y + b * A.ldy;
+    const float* nz = A.noise + b * A.ldn;
+    float* out = A.out + b * A.ldo;
+    double a = 0.0, c = 0.0;
+    for (int i = threadIdx.x; i < (int)A.L; i += AN_THREADS) {    // a thread re-reads only what it wrote itself
+      const float v = y[i], n = nz[i];
+      sy[i] = v; sn[i] = n;
+      a += (double)v * (double)v;
+      c += (double)n * (double)n;
+    }
+    block_sum2<AN_THREADS>(a, c, red);
+    double s = 0.0;
+    const bool mix = noise_scale(a / (double)A.L, c / (double)A.L, A.snr[b], s);
+    for (int i = threadIdx.x; i < (int)A.L; i += AN_THREADS) out[i] = mix ? noise_mix(sy[i], sn[i], s) : sy[i];
+  }
+}
+
+// part[b, sl] = (sum y^2, sum noise^2) over slice sl (slen samples) of row b; grid (S, rows)
+__global__ __launch_bounds__(FX_THREADS) void noise_power_kernel(NoiseArgs A) {
+  __shared__ double red[2][FX_THREADS / 64];
+  const int64_t n0 = (int64_t)blockIdx.x * A.slen, n1 = (A.L - n0 > A.slen) ? n0 + A.slen : A.L;
+  for (int64_t b = blockIdx.y; b < A.B; b += gridDim.y) {
+    const float* y = A.y + b * A.ldy;
+    const float* nz = A.noise + b * A.ldn;
+    double a = 0.0, c = 0.0;
+    for (int64_t i = n0 + threadIdx.x; i < n1; i += FX_THREADS) {
+      const float v = y[i], n = nz[i];
+      a += (double)v * (double)v;
+      c += (double)n * (double)n;
+    }
+    block_sum2<FX_THREADS>(a, c, red);
+    if (threadIdx.x == 0) A.part[b * A.S + blockIdx.x] = make_double2(a, c);
+  }
+}
+
+// grid (segments of AN_SEG samples, rows); the row's slices are summed in slice order by every thread (uniform loads)
+__global__ __launch_bounds__(FX_THREADS) void noise_mix_kernel(NoiseArgs A) {
+  const int64_t n0 = (int64_t)blockIdx.x * AN_SEG + threadIdx.x;
+  for (int64_t b = blockIdx.y; b < A.B; b += gridDim.y) {
+    double a = 0.0, c = 0.0;
+    for (int sl = 0; sl < A.S; ++sl) { const double2 p = A.part[b * A.S + sl]; a += p.x; c += p.y; }
+    double s = 0.0;
+    const bool mix = noise_scale(a / (double)A.L, c / (double)A.L, A.snr[b], s);
+    const float* y = A.y + b * A.ldy;
+    const float* nz = A.noise + b * A.ldn;
+    float* out = A.out + b * A.ldo;
+#pragma unroll
+    for (int j = 0; j < AN_PER_THREAD; ++j) {
+      const int64_t n = n0 + (int64_t)j * FX_THREADS;
+      if (n < A.L) out[n] = mix ? noise_mix(y[n], nz[n], s) : y[n];
+    }
+  }
+}
+
+// slices of a row in the power pass: enough workgroups to fill the device, none shorter than a mix segment
+inline int noise_slices(int64_t B, int64_t L) {
+  int64_t s = ceil_div(2048, B);
+  if (s > AN_SLICES) s = AN_SLICES;
+  const int64_t most = ceil_div(L, AN_SEG);
+  return (int)(s < most ? s : most);
+}
+
 inline dim3 rows_grid(int64_t L, int64_t rows) {
   return dim3((unsigned)ceil_div(L, FX_THREADS), (unsigned)(rows < FX_MAX_ROWS_Y ? rows : FX_MAX_ROWS_Y));
 }
@@ -383,5 +499,44 @@ extern "C" int syg_fx_midside_f32(const float* x, int64_t B, int64_t L, int64_t 
   hipLaunchKernelGGL(midside_kernel, rows_grid(L, B), dim3(FX_THREADS), 0, (hipStream_t)stream, x, B, L, ldx, (float)width,
                      out, ldo);
   SYG_CHECK_LAUNCH("fx_midside");
+  return SYG_OK;
+}
+
+extern "C" int64_t syg_fx_add_noise_resident_max(void) { return AN_RESIDENT; }
+
+extern "C" int64_t syg_fx_add_noise_work_bytes(int64_t B, int64_t L) {
+  if (B < 1 || L < 1 || L >= ((int64_t)1 << 39) || B >= ((int64_t)1 << 31)) {
+    set_error("fx_add_noise: bad B / L");
+    return -1;
+  }
+  return L <= AN_RESIDENT ? 0 : B * noise_slices(B, L) * (int64_t)sizeof(double2);
+}
+
+extern "C" int syg_fx_add_noise_f32(const float* y, int64_t B, int64_t L, int64_t ldy, const float* noise, int64_t ldn,
+                                    const double* snr_db, float* out, int64_t ldo, void* work, void* stream) {
+  SYG_REQUIRE(y && noise && snr_db && out, "fx_add_noise: null pointer argument (y / noise / snr_db / out)");
+  SYG_REQUIRE(B >= 1 && L >= 1 && L < ((int64_t)1 << 39) && B < ((int64_t)1 << 31), "fx_add_noise: bad B / L");
+  SYG_REQUIRE(ldy >= L && ldn >= L && ldo >= L, "fx_add_noise: bad ldy / ldn / ldo");
+  hipStream_t st = (hipStream_t)stream;
+  NoiseArgs A{y, noise, snr_db, out, B, L, ldy, ldn, ldo, 1, L, nullptr};
+  if (L <= AN_RESIDENT) {
+    const size_t lds = 2 * (size_t)L * sizeof(float);
+    if (const int rc = reserve_dynamic_lds("fx_add_noise", (const void*)noise_resident_kernel, lds)) return rc;
+    const int64_t cap = (int64_t)device_cu_count() * 8;
+    hipLaunchKernelGGL(noise_resident_kernel, dim3((unsigned)(B < cap ? B : cap)), dim3(AN_THREADS), lds, st, A);
+    SYG_CHECK_LAUNCH("fx_add_noise");
+    return SYG_OK;
+  }
+  SYG_REQUIRE(work, "fx_add_noise: a row past %lld samples takes two launches and needs `work` (syg_fx_add_noise_work_bytes)",
+              (long long)AN_RESIDENT);
+  SYG_REQUIRE(((uintptr_t)work & 15) == 0, "fx_add_noise: `work` must be 16-byte aligned");
+  A.S = noise_slices(B, L);
+  A.slen = ceil_div(L, A.S);
+  A.part = (double2*)work;
+  const unsigned gy = (unsigned)(B < FX_MAX_ROWS_Y ? B : FX_MAX_ROWS_Y);
+  hipLaunchKernelGGL(noise_power_kernel, dim3((unsigned)A.S, gy), dim3(FX_THREADS), 0, st, A);
+  SYG_CHECK_LAUNCH("fx_add_noise");
+  hipLaunchKernelGGL(noise_mix_kernel, dim3((unsigned)ceil_div(L, AN_SEG), gy), dim3(FX_THREADS), 0, st, A);
+  SYG_CHECK_LAUNCH("fx_add_noise");
   return SYG_OK;
 }

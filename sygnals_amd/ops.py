@@ -2180,3 +2180,83 @@ def spectral_gate(D: torch.Tensor, Dn: torch.Tensor, amount: float = 1.0, profil
     N = torch.empty((B, 1025), dtype=torch.float32, device=D.device)
     _call("syg_spectral_gate_f32", _ptr(D), B, Tn, _ptr(Dn), Dn.shape[1], float(amount), _ptr(G), _ptr(N))
     return (G, N) if profile else G
+
+
+# ------------------------------------------------------------------ augmentation
+VOCODER_FORMS = {None: -1, "chain": 0, "chunked": 1}
+
+
+def phase_vocoder_chunk() -> int:
+    """Steps per chunk in the chunked form of syg_phase_vocoder_f32 (the library owns the figure)."""
+    return int(lib().syg_phase_vocoder_chunk())
+
+
+def phase_vocoder(D: torch.Tensor, rate: float, form: Optional[str] = None) -> torch.Tensor:
+    """librosa.phase_vocoder (n_fft 2048, hop 512) on the frame-major STFT D [B, T, 1025, 2] -> [B, ceil(T / rate), 1025, 2]
+    (syg_phase_vocoder_f32).  form: None (the library's rule) | "chain" | "chunked", for tests and the benchmark."""
+    require_gpu()
+    if D.dim() != 4 or D.shape[2] != 1025 or D.shape[3] != 2 or D.dtype != torch.float32 or not D.is_cuda:
+        raise ValueError("D must be a float32 CUDA tensor [B, T, 1025, 2]")
+    if form not in VOCODER_FORMS:
+        raise ValueError("form must be None, 'chain' or 'chunked'")
+    if not rate > 0:
+        raise ValueError("Time stretch rate must be positive.")
+    D = D.contiguous()
+    B, Tn = D.shape[0], D.shape[1]
+    if B < 1 or Tn < 1:
+        raise ValueError("phase_vocoder: empty input")
+    col, alpha = (_dev(a) for a in T.vocoder_steps(Tn, rate))      # not cached: an augmenter draws a new rate per call
+    To, f = int(col.shape[0]), VOCODER_FORMS[form]
+    wb = lib().syg_phase_vocoder_work_bytes(B, To, f)
+    if wb < 0:
+        check(-1, "syg_phase_vocoder_work_bytes")
+    work = torch.empty((wb // 8,), dtype=torch.float64, device=D.device) if wb > 0 else None
+    out = torch.empty((B, To, 1025, 2), dtype=torch.float32, device=D.device)
+    _call("syg_phase_vocoder_f32", _ptr(D), B, Tn, _ptr(col), _ptr(alpha), To, _ptr(out), _ptr(work), f)
+    return out
+
+
+def time_stretch(y: torch.Tensor, rate: float) -> torch.Tensor:
+    """librosa.effects.time_stretch of clips y [B, L] -> [B, round(L / rate)] (Python's round, half to even, as librosa):
+    stft2048_c2c -> phase_vocoder -> istft2048(length=...), hann, hop 512, centred."""
+    y = _clips(y, "y")
+    if not rate > 0:
+        raise ValueError("Time stretch rate must be positive.")
+    if y.shape[0] < 1 or y.shape[1] < 1:
+        raise ValueError("time_stretch: empty input")
+    length = int(round(y.shape[1] / rate))
+    if length < 1:
+        raise ValueError(f"time_stretch: rate {rate} leaves no sample of a clip of {y.shape[1]}")
+    return istft2048(phase_vocoder(stft2048_c2c(y), rate), length=length)
+
+
+def fx_add_noise_resident_max() -> int:
+    """Longest row that syg_fx_add_noise_f32 serves in one launch (the library owns the figure)."""
+    return int(lib().syg_fx_add_noise_resident_max())
+
+
+def fx_add_noise(y: torch.Tensor, noise: torch.Tensor, snr_db, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y + noise scaled per row to the signal-to-noise ratio snr_db (a number, or one per row), powers in float64
+    (syg_fx_add_noise_f32); a row whose signal or noise power is below the float64 epsilon is copied.  `out` may be y."""
+    y, noise = _clips(y, "y"), _clips(noise, "noise")
+    if noise.shape != y.shape:
+        raise ValueError("fx_add_noise: y and noise must have the same shape")
+    B, L = y.shape
+    if B < 1 or L < 1:
+        raise ValueError("fx_add_noise: empty input")
+    if isinstance(snr_db, torch.Tensor) and snr_db.is_cuda:          # one per row, already on the device: no round trip
+        if snr_db.dtype != torch.float64 or tuple(snr_db.shape) != (B,):
+            raise ValueError("fx_add_noise: a device snr_db must be a float64 tensor [B]")
+        snr = snr_db.contiguous()
+    else:
+        snr = np.asarray(snr_db, dtype=np.float64)
+        if snr.ndim > 1 or (snr.ndim == 1 and snr.shape[0] != B) or not np.all(np.isfinite(snr)):
+            raise ValueError("fx_add_noise: snr_db must be a finite number or one per row")
+        snr = _dev(np.broadcast_to(snr, (B,)))
+    out = _fx_out(y, out)
+    wb = lib().syg_fx_add_noise_work_bytes(B, L)
+    if wb < 0:
+        check(-1, "syg_fx_add_noise_work_bytes")
+    work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device) if wb > 0 else None
+    _call("syg_fx_add_noise_f32", _ptr(y), B, L, _ld(y), _ptr(noise), _ld(noise), _ptr(snr), _ptr(out), _ld(out), _ptr(work))
+    return out
