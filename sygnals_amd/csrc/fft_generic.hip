@@ -1,5 +1,7 @@
 // Generic power-of-two FFT in LDS (Stockham autosort, radix 8 with a radix-4/2 tail: block_fft in common.h) and the
-// kernels built on it: batched c2c FFT/IFFT, framed STFT for any power-of-two n_fft, Welch PSD.
+// kernels built on it: batched c2c FFT/IFFT, framed STFT for any power-of-two n_fft, Welch PSD, and the power-of-two
+// engine (Pow2Fft) and entry points of the strided transform that four-step FFTs are composed from (kernels and launcher:
+// fft_strided.h).  Also the dense mel filterbank on the matrix cores and the small complex helpers (cmul, pack_real).
 //
 // Reference behaviour reproduced:
 //   scipy.fft.fft / ifft            (compute_fft / compute_ifft, sygnals/core/dsp.py:104, 151)
@@ -7,7 +9,7 @@
 //   scipy.signal.welch              (compute_psd_welch, sygnals/core/dsp.py:545-555)
 // One workgroup per transform; the two ping-pong buffers live in LDS (<= 128 KiB for
 // n = 8192), so every transform reads its input once and writes its output once.
-#include "host.h"
+#include "fft_strided.h"
 
 namespace syg {
 namespace {
@@ -320,104 +322,6 @@ __global__ __launch_bounds__(256) void welch_final2_kernel(const double* __restr
   psd[b * (int64_t)F + k] = (float)s;
 }
 
-// Strided variant used to compose large transforms (four-step) on the host side:
-// element e of transform (o, b) lives at in[o*in_os + b*in_bs + e*in_es]; the output may be
-// multiplied by the four-step twiddle W_bign^(b*k) (conjugated for the inverse).
-__global__ void fft_pow2_strided_kernel(const float2* __restrict__ in, float2* __restrict__ out, int n, int inverse,
-                                        const float2* __restrict__ tw, int64_t in_os, int64_t in_bs, int64_t in_es,
-                                        int64_t out_os, int64_t out_bs, int64_t out_es, int64_t bign, float scale,
-                                        int flags, int64_t mask_n, int64_t in_valid) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float2* x = reinterpret_cast<float2*>(lds);
-  float2* y = x + n;
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int64_t b = blockIdx.x, o = blockIdx.y;
-  const int64_t ibase = o * in_os, irow = b * in_bs, obase = o * out_os + b * out_bs;
-  for (int i = tid; i < n; i += nt) {
-    float2 v = fft_load(in, ibase, irow + (int64_t)i * in_es, flags, mask_n, in_valid);
-    if (inverse) v.y = -v.y;
-    x[i] = v;
-  }
-  __syncthreads();
-  float2* r = block_fft(x, y, n, tw, tid, nt);
-  for (int k = tid; k < n; k += nt) {
-    float2 v = r[k];
-    if (bign > 0) {
-      const int64_t e = (b * (int64_t)k) % bign;
-      double sn, cs;
-      sincospi(-2.0 * (double)e / (double)bign, &sn, &cs);
-      v = cmul(v, make_float2((float)cs, (float)sn));
-    }
-    v.x *= scale; v.y *= scale;
-    if (inverse) v.y = -v.y;
-    fft_store(out, obase + (int64_t)k * out_es, v, flags);
-  }
-}
-
-// Column-tiled form of the strided transform for the two passes of a four-step FFT.  The transforms of one pass
-// are the columns of a matrix whose rows are contiguous (in_bs == 1): a workgroup takes CB adjacent columns, so
-// every global access is a run of CB complex values (128 bytes at CB = 16) instead of one 8-byte element per line,
-// transposes them into LDS (one column = one natural-order array, pitch n + COLS_PAD), runs the CB transforms side
-// by side (256 / CB threads each; the trip counts and barriers of block_fft depend on n only) and stores either
-// k-fast (out_es == 1: the transposed layout pass A leaves for pass B) or column-fast (out_bs == 1: final order).
-constexpr int COLS_NT = 256;
-constexpr int COLS_PAD = 2;
-constexpr int COLS_MAXN = 1024;
-
-__device__ __forceinline__ float2 four_step_twiddle(int64_t e, int64_t bign) {
-  if (bign <= (1 << 24)) {                       // e < bign: exact in float, and bign is a power of two
-    float sn, cs;
-    sincospif(-2.0f * ((float)e / (float)bign), &sn, &cs);
-    return make_float2(cs, sn);
-  }
-  double sn, cs;
-  sincospi(-2.0 * (double)e / (double)bign, &sn, &cs);
-  return make_float2((float)cs, (float)sn);
-}
-
-template <bool KFAST>
-__global__ __launch_bounds__(COLS_NT) void fft_cols_kernel(const float2* __restrict__ in, float2* __restrict__ out,
-                                                           int n, int cb_log, int inverse,
-                                                           const float2* __restrict__ tw, int64_t in_os, int64_t in_es,
-                                                           int64_t out_os, int64_t out_bs, int64_t out_es,
-                                                           int64_t bign, float scale, int flags, int64_t mask_n, int64_t in_valid) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int CB = 1 << cb_log, LP = n + COLS_PAD;
-  float2* x = reinterpret_cast<float2*>(lds);
-  float2* y = x + CB * LP;
-  const int tid = threadIdx.x;
-  const int64_t c0 = (int64_t)blockIdx.x << cb_log, o = blockIdx.y;
-  const int64_t ibase = o * in_os, obase = o * out_os;
-  const int total = n << cb_log;
-  for (int idx = tid; idx < total; idx += COLS_NT) {
-    const int c = idx & (CB - 1), e = idx >> cb_log;
-    const int64_t pos = (int64_t)e * in_es + c0 + c;           // position inside the row (= the bin, for the analytic weights)
-    float2 v = fft_load(in, ibase, pos, flags, mask_n, in_valid);
-    if (inverse) v.y = -v.y;
-    x[c * LP + e] = v;
-  }
-  __syncthreads();
-  const int tpc_log = 8 - cb_log;                              // threads per column
-  const int g = tid >> tpc_log, lt = tid & ((1 << tpc_log) - 1);
-  const float2* r = block_fft(x + g * LP, y + g * LP, n, tw, lt, 1 << tpc_log) - g * LP;
-  int ln = 0;
-  while ((1 << ln) < n) ++ln;
-  for (int idx = tid; idx < total; idx += COLS_NT) {
-    int c, k;
-    if (KFAST) { k = idx & (n - 1); c = idx >> ln; }
-    else { c = idx & (CB - 1); k = idx >> cb_log; }
-    float2 v = r[c * LP + k];
-    if (bign > 0) {
-      int64_t e = (c0 + c) * (int64_t)k;
-      if (e >= bign) e %= bign;                                // (column * k < bign in a four-step split: never taken there)
-      v = cmul(v, four_step_twiddle(e, bign));
-    }
-    v.x *= scale; v.y *= scale;
-    if (inverse) v.y = -v.y;
-    fft_store(out, obase + (c0 + c) * out_bs + (int64_t)k * out_es, v, flags);
-  }
-}
-
 // out[i] = a[i] * b[i mod nb]   (conj_b: multiply by conj(b))
 __global__ void cmul_kernel(const float2* __restrict__ a, const float2* __restrict__ b, float2* __restrict__ out,
                             int64_t na, int64_t nb, int conj_b) {
@@ -439,6 +343,16 @@ __global__ void pack_real_kernel(const float* __restrict__ x, int64_t len, int64
 }
 
 int fft_threads(int n) { int t = n / 4; if (t < 64) t = 64; if (t > 1024) t = 1024; return t; }
+
+// The power-of-two engine of the strided transform (fft_strided.h): block_fft, nothing to prepare.
+struct Pow2Fft {
+  static constexpr bool POW2 = true;
+  bool plan(int) { return true; }
+  __device__ __forceinline__ float2* operator()(float2* x, float2* y, int n, const float2* __restrict__ tw, int tid,
+                                                int nt) const {
+    return block_fft(x, y, n, tw, tid, nt);
+  }
+};
 
 }  // namespace
 int welch_wave_launch(const float* x, int64_t B, int64_t ldx, int step, int64_t nseg, const float* window,
@@ -581,44 +495,9 @@ extern "C" int syg_fft_pow2_strided_ex_f32(const float* in, float* out, int64_t 
                                             int inverse, const float* twiddle, int64_t in_os, int64_t in_bs,
                                             int64_t in_es, int64_t out_os, int64_t out_bs, int64_t out_es,
                                             int64_t bign, float scale, int flags, int64_t mask_n, int64_t in_valid, void* stream) {
-  SYG_REQUIRE(in && out && twiddle, "fft_pow2_strided: null pointer argument");
-  SYG_REQUIRE(is_pow2(n) && n <= MAX_N, "fft_pow2_strided: n must be a power of two in [2, %d] (got %d)", MAX_N, n);
-  SYG_REQUIRE(batch >= 1 && batch < (int64_t)0x7fffffff && outer >= 1 && outer <= 65535,
-              "fft_pow2_strided: bad batch/outer");
-  SYG_REQUIRE(in != out, "fft_pow2_strided: in-place operation is not supported");
-  SYG_REQUIRE(flags >= 0 && flags <= 7 && (flags & 5) != 5 && mask_n >= 0 && in_valid >= 0, "fft_pow2_strided: bad flags / mask length");
-  if (in_bs == 1 && (out_es == 1 || out_bs == 1) && n <= COLS_MAXN && n >= 8) {
-    int cb_log = 4;                                            // 16 columns = 128-byte runs
-    while (cb_log > 2 && ((int64_t)n << cb_log) > 4096) --cb_log;
-    // (two workgroups per CU hide too little: above 40 KB of LDS take 8 columns, see fft_mixed.hip)
-    if (cb_log == 4 && (size_t)2 * ((size_t)(n + COLS_PAD) << 4) * sizeof(float2) > 40 * 1024) cb_log = 3;
-    if (batch % (1 << cb_log) == 0) {
-      const bool kfast = out_es == 1;
-      const void* fn = kfast ? (const void*)fft_cols_kernel<true> : (const void*)fft_cols_kernel<false>;
-      const size_t lds = (size_t)2 * ((size_t)(n + COLS_PAD) << cb_log) * sizeof(float2);
-      int rc = reserve_dynamic_lds("fft_pow2_strided(cols)", fn, lds);
-      if (rc) return rc;
-      const dim3 grid((unsigned)(batch >> cb_log), (unsigned)outer);
-      if (kfast)
-        hipLaunchKernelGGL(fft_cols_kernel<true>, grid, dim3(COLS_NT), lds, (hipStream_t)stream, (const float2*)in,
-                           (float2*)out, n, cb_log, inverse, (const float2*)twiddle, in_os, in_es, out_os, out_bs,
-                           out_es, bign, scale, flags, mask_n, in_valid);
-      else
-        hipLaunchKernelGGL(fft_cols_kernel<false>, grid, dim3(COLS_NT), lds, (hipStream_t)stream, (const float2*)in,
-                           (float2*)out, n, cb_log, inverse, (const float2*)twiddle, in_os, in_es, out_os, out_bs,
-                           out_es, bign, scale, flags, mask_n, in_valid);
-      SYG_CHECK_LAUNCH("fft_pow2_strided(cols)");
-      return SYG_OK;
-    }
-  }
-  const size_t lds = (size_t)n * 2 * sizeof(float2);
-  int rc = reserve_dynamic_lds("fft_pow2_strided", (const void*)fft_pow2_strided_kernel, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(fft_pow2_strided_kernel, dim3((unsigned)batch, (unsigned)outer), dim3(fft_threads(n)), lds,
-                     (hipStream_t)stream, (const float2*)in, (float2*)out, n, inverse, (const float2*)twiddle, in_os,
-                     in_bs, in_es, out_os, out_bs, out_es, bign, scale, flags, mask_n, in_valid);
-  SYG_CHECK_LAUNCH("fft_pow2_strided");
-  return SYG_OK;
+  // row kernel: fft_threads(n) threads; tile width by size alone (a batch it does not divide takes the row kernel)
+  return fft_strided_launch<Pow2Fft>("fft_pow2_strided", MAX_N, fft_threads, false, in, out, outer, batch, n, inverse, twiddle,
+                                     in_os, in_bs, in_es, out_os, out_bs, out_es, bign, scale, flags, mask_n, in_valid, stream);
 }
 
 extern "C" int syg_fft_pow2_strided_c2c_f32(const float* in, float* out, int64_t outer, int64_t batch, int n, int inverse,

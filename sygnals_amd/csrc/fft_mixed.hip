@@ -7,8 +7,9 @@
 // Stockham autosort with one pass per radix (8 / 4 / 2 for the power-of-two part, then 3, 5, 7): pass with radix R at
 // stride s (product of the radices done) reads a[j] = x[q + s (p + j m)], m = N / (s R), p = i / s, q = i mod s,
 // transforms the R points in registers and writes y[q + s (R p + j)] = a[j] W_N^(j p s); input and output in natural
-// order.  Same strided addressing and four-step twiddle as syg_fft_pow2_strided_c2c_f32.
-#include "host.h"
+// order.  This file holds the small DFTs, the passes, the radix plan and the mixed-radix engine (MixedFft) and entry points
+// of the strided transform; its kernels and launcher are the ones of the power-of-two engine (fft_strided.h).
+#include "fft_strided.h"
 
 namespace syg {
 namespace {
@@ -106,87 +107,18 @@ __device__ __forceinline__ float2* block_fft_mixed(float2* x, float2* y, int N, 
   return x;
 }
 
-// element e of transform (o, b) at in[o*in_os + b*in_bs + e*in_es]; output k of transform b times W_bign^(b k) when
-// bign > 0 (the four-step twiddle), times scale; inverse via conj(FFT(conj(x)))
-__global__ void fft_mixed_strided_kernel(const float2* __restrict__ in, float2* __restrict__ out, int n, Radices rd,
-                                         int inverse, const float2* __restrict__ tw, int64_t in_os, int64_t in_bs,
-                                         int64_t in_es, int64_t out_os, int64_t out_bs, int64_t out_es, int64_t bign,
-                                         float scale, int flags, int64_t mask_n, int64_t in_valid) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float2* x = reinterpret_cast<float2*>(lds);
-  float2* y = x + n;
-  const int tid = threadIdx.x, nt = blockDim.x;
-  const int64_t b = blockIdx.x, o = blockIdx.y;
-  const int64_t ibase = o * in_os, irow = b * in_bs, obase = o * out_os + b * out_bs;
-  for (int i = tid; i < n; i += nt) {
-    float2 v = fft_load(in, ibase, irow + (int64_t)i * in_es, flags, mask_n, in_valid);
-    if (inverse) v.y = -v.y;
-    x[i] = v;
+// The mixed-radix engine of the strided transform (fft_strided.h): block_fft_mixed with the pass radices of its length.
+struct MixedFft {
+  static constexpr bool POW2 = false;
+  Radices rd;
+  bool plan(int n);
+  __device__ __forceinline__ float2* operator()(float2* x, float2* y, int n, const float2* __restrict__ tw, int tid,
+                                                int nt) const {
+    return block_fft_mixed(x, y, n, rd, tw, tid, nt);
   }
-  __syncthreads();
-  float2* r = block_fft_mixed(x, y, n, rd, tw, tid, nt);
-  for (int k = tid; k < n; k += nt) {
-    float2 v = r[k];
-    if (bign > 0) {
-      const int64_t e = (b * (int64_t)k) % bign;
-      double sn, cs;
-      sincospi(-2.0 * (double)e / (double)bign, &sn, &cs);
-      v = cmul(v, make_float2((float)cs, (float)sn));
-    }
-    v.x *= scale; v.y *= scale;
-    if (inverse) v.y = -v.y;
-    fft_store(out, obase + (int64_t)k * out_es, v, flags);
-  }
-}
+};
 
-// Column-tiled form for the two passes of a four-step transform (see fft_cols_kernel in fft_generic.hip): the
-// transforms are columns of a row-major matrix (in_bs == 1); a workgroup takes CB adjacent columns, so global
-// accesses are runs of CB complex values, and runs the CB transforms side by side (256 / CB threads each).
-constexpr int MCOLS_NT = 256, MCOLS_PAD = 2;
-
-template <bool KFAST>
-__global__ __launch_bounds__(MCOLS_NT) void fft_mixed_cols_kernel(const float2* __restrict__ in, float2* __restrict__ out,
-                                                                  int n, Radices rd, int cb_log, int inverse,
-                                                                  const float2* __restrict__ tw, int64_t in_os,
-                                                                  int64_t in_es, int64_t out_os, int64_t out_bs,
-                                                                  int64_t out_es, int64_t bign, float scale, int flags,
-                                                                  int64_t mask_n, int64_t in_valid) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int CB = 1 << cb_log, LP = n + MCOLS_PAD;
-  float2* x = reinterpret_cast<float2*>(lds);
-  float2* y = x + CB * LP;
-  const int tid = threadIdx.x;
-  const int64_t c0 = (int64_t)blockIdx.x << cb_log, o = blockIdx.y;
-  const int64_t ibase = o * in_os, obase = o * out_os;
-  const int total = n << cb_log;
-  for (int idx = tid; idx < total; idx += MCOLS_NT) {
-    const int c = idx & (CB - 1), e = idx >> cb_log;
-    const int64_t pos = (int64_t)e * in_es + c0 + c;           // position inside the row (= the bin, for the analytic weights)
-    float2 v = fft_load(in, ibase, pos, flags, mask_n, in_valid);
-    if (inverse) v.y = -v.y;
-    x[c * LP + e] = v;
-  }
-  __syncthreads();
-  const int tpc_log = 8 - cb_log;
-  const int g = tid >> tpc_log, lt = tid & ((1 << tpc_log) - 1);
-  const float2* r = block_fft_mixed(x + g * LP, y + g * LP, n, rd, tw, lt, 1 << tpc_log) - g * LP;
-  for (int idx = tid; idx < total; idx += MCOLS_NT) {
-    int c, k;
-    if (KFAST) { c = idx / n; k = idx - c * n; }
-    else { c = idx & (CB - 1); k = idx >> cb_log; }
-    float2 v = r[c * LP + k];
-    if (bign > 0) {
-      int64_t e = (c0 + c) * (int64_t)k;
-      if (e >= bign) e %= bign;                                // (column * k < bign in a four-step split: never taken there)
-      double sn, cs;
-      sincospi(-2.0 * (double)e / (double)bign, &sn, &cs);
-      v = cmul(v, make_float2((float)cs, (float)sn));
-    }
-    v.x *= scale; v.y *= scale;
-    if (inverse) v.y = -v.y;
-    fft_store(out, obase + (c0 + c) * out_bs + (int64_t)k * out_es, v, flags);
-  }
-}
+int mixed_threads(int n) { const int nt = n / 8; return nt < 64 ? 64 : (nt > 1024 ? 1024 : ((nt + 63) / 64) * 64); }
 
 }  // namespace
 }  // namespace syg
@@ -208,53 +140,20 @@ extern "C" int syg_fft_mixed_plan(int64_t n, int32_t* radices_host, int max_pass
   return cnt;
 }
 
+bool MixedFft::plan(int n) {
+  int32_t rr[MAXPASS];
+  rd.n = syg_fft_mixed_plan(n, rr, MAXPASS);
+  for (int i = 0; i < MAXPASS; ++i) rd.r[i] = i < rd.n ? rr[i] : 1;
+  return rd.n >= 1;
+}
+
 extern "C" int syg_fft_mixed_strided_ex_f32(const float* in, float* out, int64_t outer, int64_t batch, int n,
                                              int inverse, const float* twiddle, int64_t in_os, int64_t in_bs,
                                              int64_t in_es, int64_t out_os, int64_t out_bs, int64_t out_es,
                                              int64_t bign, float scale, int flags, int64_t mask_n, int64_t in_valid, void* stream) {
-  SYG_REQUIRE(in && out && twiddle, "fft_mixed: null pointer argument");
-  SYG_REQUIRE(n >= 2 && n <= MIX_MAXN, "fft_mixed: n must be in [2, %d] (got %d)", MIX_MAXN, n);
-  SYG_REQUIRE(batch >= 1 && batch < (int64_t)0x7fffffff && outer >= 1 && outer <= 65535, "fft_mixed: bad batch/outer");
-  SYG_REQUIRE(in != out, "fft_mixed: in-place operation is not supported");
-  SYG_REQUIRE(flags >= 0 && flags <= 7 && (flags & 5) != 5 && mask_n >= 0 && in_valid >= 0, "fft_mixed: bad flags / mask length");
-  Radices rd;
-  int32_t rr[MAXPASS];
-  rd.n = syg_fft_mixed_plan(n, rr, MAXPASS);
-  SYG_REQUIRE(rd.n >= 1, "fft_mixed: n = %d has a prime factor other than 2, 3, 5, 7", n);
-  for (int i = 0; i < MAXPASS; ++i) rd.r[i] = i < rd.n ? rr[i] : 1;
-  if (in_bs == 1 && (out_es == 1 || out_bs == 1) && n <= 1024 && n >= 8) {
-    int cb_log = 4;                                            // 16 columns = 128-byte runs
-    while (cb_log > 2 && (((int64_t)n << cb_log) > 4096 || batch % (1 << cb_log) != 0)) --cb_log;
-    // two workgroups per CU hide too little: above 40 KB of LDS take 8 columns (64-byte runs) -- 758 -> 646 us for the two
-    // passes of 1024 x 48000 (200 x 240), 1145 -> 760 us for 1024 x 65536 (256 x 256); 4 columns are slower again
-    if (cb_log == 4 && (size_t)2 * ((size_t)(n + MCOLS_PAD) << 4) * sizeof(float2) > 40 * 1024) cb_log = 3;
-    if (((int64_t)n << cb_log) <= 4096 && batch % (1 << cb_log) == 0) {
-      const bool kfast = out_es == 1;
-      const void* fn = kfast ? (const void*)fft_mixed_cols_kernel<true> : (const void*)fft_mixed_cols_kernel<false>;
-      const size_t clds = (size_t)2 * ((size_t)(n + MCOLS_PAD) << cb_log) * sizeof(float2);
-      if (const int rc = reserve_dynamic_lds("fft_mixed(cols)", fn, clds)) return rc;
-      const dim3 grid((unsigned)(batch >> cb_log), (unsigned)outer);
-      if (kfast)
-        hipLaunchKernelGGL(fft_mixed_cols_kernel<true>, grid, dim3(MCOLS_NT), clds, (hipStream_t)stream,
-                           (const float2*)in, (float2*)out, n, rd, cb_log, inverse, (const float2*)twiddle, in_os,
-                           in_es, out_os, out_bs, out_es, bign, scale, flags, mask_n, in_valid);
-      else
-        hipLaunchKernelGGL(fft_mixed_cols_kernel<false>, grid, dim3(MCOLS_NT), clds, (hipStream_t)stream,
-                           (const float2*)in, (float2*)out, n, rd, cb_log, inverse, (const float2*)twiddle, in_os,
-                           in_es, out_os, out_bs, out_es, bign, scale, flags, mask_n, in_valid);
-      SYG_CHECK_LAUNCH("fft_mixed(cols)");
-      return SYG_OK;
-    }
-  }
-  const size_t lds = (size_t)n * 2 * sizeof(float2);
-  if (const int rc = reserve_dynamic_lds("fft_mixed", (const void*)fft_mixed_strided_kernel, lds)) return rc;
-  int nt = n / 8;
-  nt = nt < 64 ? 64 : (nt > 1024 ? 1024 : ((nt + 63) / 64) * 64);
-  hipLaunchKernelGGL(fft_mixed_strided_kernel, dim3((unsigned)batch, (unsigned)outer), dim3(nt), lds,
-                     (hipStream_t)stream, (const float2*)in, (float2*)out, n, rd, inverse, (const float2*)twiddle,
-                     in_os, in_bs, in_es, out_os, out_bs, out_es, bign, scale, flags, mask_n, in_valid);
-  SYG_CHECK_LAUNCH("fft_mixed");
-  return SYG_OK;
+  // row kernel: n / 8 threads in whole waves, 64 .. 1024; the tile narrows until its width divides `batch`
+  return fft_strided_launch<MixedFft>("fft_mixed", MIX_MAXN, mixed_threads, true, in, out, outer, batch, n, inverse, twiddle,
+                                      in_os, in_bs, in_es, out_os, out_bs, out_es, bign, scale, flags, mask_n, in_valid, stream);
 }
 
 extern "C" int syg_fft_mixed_strided_c2c_f32(const float* in, float* out, int64_t outer, int64_t batch, int n,

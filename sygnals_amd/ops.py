@@ -15,6 +15,8 @@ import numpy as np
 import torch
 
 from . import _tables as T
+from ._fftplan import (MAX_LDS_FFT, MAX_MIXED_FFT, MAX_ROWS, conv_fft_len, fft_plan, is_pow2,      # noqa: F401 (re-exported)
+                       next_direct_len, smooth_split)
 from ._front import front_route, pow2_takes, stats2048_takes
 from ._lib import SygnalsHipError, check, lib
 
@@ -843,10 +845,6 @@ def mfcc_batch(y: torch.Tensor, sr: float, n_fft: int = 2048, hop: int = 512, n_
 
 
 # ------------------------------------------------------------------ generic pow2 kernels
-def is_pow2(n: int) -> bool:
-    return n >= 2 and (n & (n - 1)) == 0
-
-
 def twiddle_rfft_dev(n_fft) -> torch.Tensor:
     """[n_fft + n_fft/2, 2]: W_nfft^k followed by W_{nfft/2}^k (layout of stft_pow2 / welch)."""
     return _cached(("twr", n_fft), lambda: _dev(np.concatenate([T.twiddles(n_fft), T.twiddles(n_fft // 2)], axis=0)))
@@ -886,9 +884,6 @@ def stft_any(y, n_fft, hop, center=True, window="hann", win_length=None):
     if is_pow2(n_fft) and 8 <= n_fft <= 16384:
         return stft_pow2(y, n_fft, hop, center, window, win_length)
     return stft_rows(y, n_fft, hop, center, window, win_length)
-
-
-MAX_ROWS = 65535
 
 
 def pack_frames(y: torch.Tensor, n_rows: int, length: int, step: int, first: int, n_out: int,
@@ -1101,35 +1096,58 @@ def contrast_db(pv: torch.Tensor, amin: float = 1e-10, top_db: Optional[float] =
 
 
 # ------------------------------------------------------------------ arbitrary-length FFT
-MAX_LDS_FFT = 8192
+FFT_REAL_IN, FFT_ABS_OUT, FFT_PAIR_IN = 1, 2, 4          # the fused ends: SYG_FFT_* of include/sygnals_hip.h
 
 
-def _fft_strided(x, out, outer, batch, n, inverse, strides, bign=0, scale=1.0):
-    in_os, in_bs, in_es, out_os, out_bs, out_es = strides
-    _call("syg_fft_pow2_strided_c2c_f32", _ptr(x), _ptr(out), outer, batch, n, int(inverse), _ptr(twiddle_dev(n)), in_os,
-          in_bs, in_es, out_os, out_bs, out_es, bign, float(scale))
+def _fft_strided(kind, x, out, outer, batch, n, inverse, strides, bign=0, scale=1.0, flags=0, mask_n=0, in_valid=0):
+    """One launch of the strided transform of engine `kind` ("pow2" / "mixed"): the _ex_ entry where a fused end is asked
+    for, the _c2c_ entry otherwise."""
+    args = (_ptr(x), _ptr(out), outer, batch, n, int(inverse), _ptr(twiddle_dev(n)), *strides, bign, float(scale))
+    if flags or mask_n or in_valid:
+        _call("syg_fft_%s_strided_ex_f32" % kind, *args, int(flags), int(mask_n), int(in_valid))
+    else:
+        _call("syg_fft_%s_strided_c2c_f32" % kind, *args)
+
+
+def _run_plan(plan, x, out, rows, inverse, scale=1.0, ld=None, flags=0, mask_n=0, in_valid=0):
+    """Runs fft_plan's (kind, n1, n2) on `rows` rows of x into out: one launch, or the four-step passes A and B through a
+    temporary.  The fused ends: FFT_REAL_IN / FFT_PAIR_IN (with in_valid) and mask_n act where x is loaded, FFT_ABS_OUT
+    where out is stored; ld is the row stride of x (default n; in floats for a pair input)."""
+    kind, n1, n2 = plan
+    n = n1 * n2
+    ld = n if ld is None else ld
+    if n2 == 1 and not (flags or mask_n or in_valid):
+        _fft_strided(kind, x, out, 1, rows, n, inverse, (0, n, 1, 0, n, 1), scale=scale)
+    elif n2 == 1:
+        # (one transform per row: the ROW is the outer index, so that an element's position inside the row is its bin)
+        _fft_strided(kind, x, out, rows, 1, n, inverse, (ld, 0, 1, n, 0, 1), scale=scale, flags=flags, mask_n=mask_n,
+                     in_valid=in_valid)
+    else:
+        tmp = torch.empty((rows, n, 2), dtype=torch.float32, device=x.device)
+        # pass A: n2 transforms of length n1 over the slow index (input stride n2), twiddle W_n^(i2 k1), stored [i2][k1];
+        # pass B: n1 transforms of length n2 over i2 (input stride n1), output X[k1 + n1 k2]
+        _fft_strided(kind, x, tmp, rows, n2, n1, inverse, (ld, 1, n2, n, n1, 1), bign=n, flags=flags & ~FFT_ABS_OUT,
+                     mask_n=mask_n, in_valid=in_valid)
+        _fft_strided(kind, tmp, out, rows, n1, n2, inverse, (n, 1, n1, n, 1, n1), scale=scale, flags=flags & FFT_ABS_OUT)
+    return out
+
+
+def _fft_direct(x: torch.Tensor, inverse: bool, plan) -> torch.Tensor:
+    """The plain complex transform of the rows of x [rows, n, 2] by its plan."""
+    rows, n, _ = x.shape
+    if plan is None:
+        raise SygnalsHipError(f"FFT length {n} exceeds the supported maximum 2^26")
+    if plan[2] == 1 and plan[0] == "pow2":
+        return fft_pow2(x, inverse)                 # (contiguous rows: the kernel without strides)
+    if plan[2] > 1 and rows > MAX_ROWS:
+        raise SygnalsHipError("too many rows for the four-step FFT")
+    x = x.contiguous()
+    return _run_plan(plan, x, torch.empty_like(x), rows, inverse, scale=(1.0 / n if inverse else 1.0))
 
 
 def fft_pow2_any(x: torch.Tensor, inverse: bool = False) -> torch.Tensor:
     """Complex FFT of rows of x [rows, n, 2], n any power of two up to 2^26 (four-step above 8192)."""
-    rows, n, _ = x.shape
-    if n <= MAX_LDS_FFT:
-        return fft_pow2(x, inverse)
-    lg = n.bit_length() - 1
-    n1 = 1 << (lg // 2)
-    n2 = n // n1
-    if n2 > MAX_LDS_FFT:
-        raise SygnalsHipError(f"FFT length {n} exceeds the supported maximum 2^26")
-    if rows > 65535:
-        raise SygnalsHipError("too many rows for the four-step FFT")
-    x = x.contiguous()
-    tmp = torch.empty_like(x)
-    out = torch.empty_like(x)
-    # step A: N2 transforms of length N1 over n1 (input stride N2), twiddle W_N^(n2*k1), stored [n2][k1]
-    _fft_strided(x, tmp, rows, n2, n1, inverse, (n, 1, n2, n, n1, 1), bign=n)
-    # step B: N1 transforms of length N2 over n2 (input stride N1), output X[k1 + N1*k2]
-    _fft_strided(tmp, out, rows, n1, n2, inverse, (n, 1, n1, n, 1, n1), scale=(1.0 / n if inverse else 1.0))
-    return out
+    return _fft_direct(x, inverse, fft_plan(x.shape[1]))
 
 
 def cmul(a: torch.Tensor, b: torch.Tensor, conj_b: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1156,9 +1174,7 @@ def _bluestein_tables(n: int):
     w[k] = exp(-i*pi*k^2/n); forward: X = w * IFFT_M(FFT_M(x*w) * FFT_M(wrap(conj w)));
     the inverse uses the conjugate chirp and folds the 1/n into the final multiply.
     """
-    m = max(2, 2 * n - 1)                      # any length the FFT kernels take directly will do for the chirp
-    while not (is_pow2(m) or (_is_smooth(m) and smooth_split(m) is not None)):   # convolution: the next 7-smooth one
-        m += 1
+    m = next_direct_len(max(2, 2 * n - 1))     # any length the FFT kernels take directly will do for the chirp convolution
     k = np.arange(n, dtype=np.int64)
     w = np.exp(-1j * np.pi * ((k * k) % (2 * n)).astype(np.float64) / n)
 
@@ -1174,59 +1190,13 @@ def _bluestein_tables(n: int):
     return m, fwd, inv
 
 
-MAX_MIXED_FFT = 8192
-
-
-def smooth_split(n: int):
-    """None when n has a prime factor other than 2, 3, 5, 7 (or is too long); (n, 1) when one mixed-radix launch
-    takes it; else the most balanced (n1, n2), n1 * n2 = n, both <= 8192 -- the four-step factors."""
-    if n < 2 or not _is_smooth(n):
-        return None
-    if n <= MAX_MIXED_FFT:
-        return n, 1
-    best = None
-    d = 1
-    while d * d <= n:
-        if n % d == 0 and n // d <= MAX_MIXED_FFT:
-            best = (d, n // d)                       # d <= sqrt(n): the largest such d is the most balanced split
-        d += 1
-    return best
-
-
-def _is_smooth(n: int) -> bool:
-    for p in (2, 3, 5, 7):
-        while n % p == 0:
-            n //= p
-    return n == 1
-
-
-def _fft_mixed_strided(x, out, outer, batch, n, inverse, strides, bign=0, scale=1.0):
-    in_os, in_bs, in_es, out_os, out_bs, out_es = strides
-    _call("syg_fft_mixed_strided_c2c_f32", _ptr(x), _ptr(out), outer, batch, n, int(inverse), _ptr(twiddle_dev(n)), in_os,
-          in_bs, in_es, out_os, out_bs, out_es, bign, float(scale))
-
-
 def fft_smooth(x: torch.Tensor, inverse: bool = False) -> torch.Tensor:
     """Complex FFT of rows of x [rows, n, 2] for n = 2^a 3^b 5^c 7^d: one mixed-radix launch up to 8192 points,
     four-step (two passes of mixed-radix transforms) above."""
-    rows, n, _ = x.shape
-    split = smooth_split(n)
+    split = smooth_split(x.shape[1])
     if split is None:
-        raise SygnalsHipError(f"fft_smooth: n = {n} is not a product of 2, 3, 5, 7 that splits into factors <= 8192")
-    x = x.contiguous()
-    out = torch.empty_like(x)
-    n1, n2 = split
-    if n2 == 1:
-        _fft_mixed_strided(x, out, 1, rows, n, inverse, (0, n, 1, 0, n, 1), scale=(1.0 / n if inverse else 1.0))
-        return out
-    if rows > MAX_ROWS:
-        raise SygnalsHipError("too many rows for the four-step FFT")
-    tmp = torch.empty_like(x)
-    # step A: n2 transforms of length n1 over the slow index (stride n2), twiddle W_n^(i2 k1), stored [i2][k1];
-    # step B: n1 transforms of length n2 over i2 (stride n1), output X[k1 + n1 k2]
-    _fft_mixed_strided(x, tmp, rows, n2, n1, inverse, (n, 1, n2, n, n1, 1), bign=n)
-    _fft_mixed_strided(tmp, out, rows, n1, n2, inverse, (n, 1, n1, n, 1, n1), scale=(1.0 / n if inverse else 1.0))
-    return out
+        raise SygnalsHipError(f"fft_smooth: n = {x.shape[1]} is not a product of 2, 3, 5, 7 that splits into factors <= 8192")
+    return _fft_direct(x, inverse, ("mixed",) + split)
 
 
 def fft_any(x: torch.Tensor, inverse: bool = False) -> torch.Tensor:
@@ -1243,10 +1213,9 @@ def fft_any(x: torch.Tensor, inverse: bool = False) -> torch.Tensor:
         for r0 in range(0, rows, MAX_ROWS):
             out[r0:r0 + MAX_ROWS] = fft_any(x[r0:r0 + MAX_ROWS], inverse)
         return out
-    if is_pow2(n):
-        return fft_pow2_any(x, inverse)
-    if _is_smooth(n) and smooth_split(n) is not None:
-        return fft_smooth(x, inverse)
+    plan = fft_plan(n)
+    if plan is not None or is_pow2(n):           # (a power of two without a plan is too long: _fft_direct says so)
+        return _fft_direct(x, inverse, plan)
     m, fwd, inv = _cached(("blue", n), lambda: _bluestein_tables(n))
     w_in, bf, w_out = inv if inverse else fwd
     a = torch.zeros((rows, m, 2), dtype=torch.float32, device=x.device)
@@ -1352,18 +1321,6 @@ def pack_rows(x: torch.Tensor, n: int, window: Optional[torch.Tensor] = None, de
     return out
 
 
-def conv_fft_len(n_out: int) -> int:
-    """Transform length (in real samples, even) for a linear convolution with n_out output samples: the smallest
-    M >= n_out, M >= 16, whose half M/2 is a product of 2, 3, 5, 7 that the FFT kernels take directly -- what
-    scipy.fft.next_fast_len does for fftconvolve.  (A power of two can be up to twice the needed length.)"""
-    m = max(16, n_out + (n_out & 1))
-    while True:
-        h = m // 2
-        if is_pow2(h) or (_is_smooth(h) and smooth_split(h) is not None):
-            return m
-        m += 2
-
-
 def rfft_conv(x: torch.Tensor, k: torch.Tensor, reverse_k: bool = False) -> torch.Tensor:
     """Full linear convolution of the rows of x [B, n] with k [1 or B, m] -> [B, n + m - 1] (a view of the
     transform buffer).  reverse_k convolves with the time-reversed k, i.e. cross-correlates."""
@@ -1381,77 +1338,34 @@ def rfft_conv(x: torch.Tensor, k: torch.Tensor, reverse_k: bool = False) -> torc
     return fft_any(za, True).view(B, M)[:, : n + m - 1]
 
 
-FFT_REAL_IN, FFT_ABS_OUT, FFT_PAIR_IN = 1, 2, 4
-
-
-def _two_kernel_plan(n: int):
-    """(kind, n1, n2) of the one- or two-launch plan of a length-n complex transform, or None (Bluestein lengths)."""
-    if n < 2:
-        return None
-    if is_pow2(n):
-        if n <= MAX_LDS_FFT:
-            return "pow2", n, 1
-        n1 = 1 << ((n.bit_length() - 1) // 2)
-        return ("pow2", n1, n // n1) if n // n1 <= MAX_LDS_FFT else None
-    if _is_smooth(n) and smooth_split(n) is not None:
-        n1, n2 = smooth_split(n)
-        return "mixed", n1, n2
-    return None
-
-
 def fft_pair_rows(x: torch.Tensor, H: int):
     """Forward transform of length H of the rows of the REAL tensor x [B, n] read as the complex sequences
     (x[2 p], x[2 p + 1]), zero beyond n -- pack_rows(x, 2 H) folded into the first pass's load.  None without a plan."""
     B, n = x.shape
-    plan = _two_kernel_plan(H)
+    plan = fft_plan(H)
     if plan is None or B > MAX_ROWS or x.dtype != torch.float32 or not x.is_cuda or n > 2 * H:
         return None
     if x.stride(1) != 1:
         x = x.contiguous()
-    kind, n1, n2 = plan
-    ld = x.stride(0)
     out = torch.empty((B, H, 2), dtype=torch.float32, device=x.device)
-    if n2 == 1:
-        _strided_ex(kind, x, out, B, 1, H, False, (ld, 0, 1, H, 0, 1), flags=FFT_PAIR_IN, in_valid=n)
-        return out
-    tmp = torch.empty_like(out)
-    _strided_ex(kind, x, tmp, B, n2, n1, False, (ld, 1, n2, H, n1, 1), bign=H, flags=FFT_PAIR_IN, in_valid=n)
-    _strided_ex(kind, tmp, out, B, n1, n2, False, (H, 1, n1, H, 1, n1))
-    return out
-
-
-def _strided_ex(kind, x, out, outer, batch, n, inverse, strides, bign=0, scale=1.0, flags=0, mask_n=0, in_valid=0):
-    in_os, in_bs, in_es, out_os, out_bs, out_es = strides
-    _call("syg_fft_%s_strided_ex_f32" % kind, _ptr(x), _ptr(out), outer, batch, n, int(inverse), _ptr(twiddle_dev(n)), in_os,
-          in_bs, in_es, out_os, out_bs, out_es, bign, float(scale), int(flags), int(mask_n), int(in_valid))
+    return _run_plan(plan, x, out, B, False, ld=x.stride(0), flags=FFT_PAIR_IN, in_valid=n)
 
 
 def analytic_fused(x: torch.Tensor, magnitude: bool):
     """scipy.signal.hilbert of the rows of x [B, n] (float32, contiguous) with the packing, masking and |.| passes folded
     into the transforms' loads and stores: complex [B, n, 2], or the envelope [B, n] when magnitude.  Returns None where
-    the length has no two-kernel plan (powers of two up to 2^26 and 7-smooth lengths that split into two factors <= 8192;
+    the length has no plan (powers of two up to 2^26 and 7-smooth lengths that split into two factors <= 8192 have one;
     other lengths go through Bluestein in analytic_signal)."""
     B, n = x.shape
-    plan = _two_kernel_plan(n)
+    plan = fft_plan(n)
     if plan is None or B > MAX_ROWS:
         return None
-    kind, n1, n2 = plan
     x = x.contiguous()
     X = torch.empty((B, n, 2), dtype=torch.float32, device=x.device)
     out = torch.empty((B, n) if magnitude else (B, n, 2), dtype=torch.float32, device=x.device)
-    oflag = FFT_ABS_OUT if magnitude else 0
-    if n2 == 1:
-        # (one transform per row: the ROW is the outer index, so that an element's position inside the row is its bin)
-        _strided_ex(kind, x, X, B, 1, n, False, (n, 0, 1, n, 0, 1), flags=FFT_REAL_IN)
-        _strided_ex(kind, X, out, B, 1, n, True, (n, 0, 1, n, 0, 1), scale=1.0 / n, flags=oflag, mask_n=n)
-        return out
-    tmp = torch.empty_like(X)
-    # forward: step A reads the REAL rows; inverse: step A weights the spectrum as it loads it, step B stores |.|
-    _strided_ex(kind, x, tmp, B, n2, n1, False, (n, 1, n2, n, n1, 1), bign=n, flags=FFT_REAL_IN)
-    _strided_ex(kind, tmp, X, B, n1, n2, False, (n, 1, n1, n, 1, n1))
-    _strided_ex(kind, X, tmp, B, n2, n1, True, (n, 1, n2, n, n1, 1), bign=n, mask_n=n)
-    _strided_ex(kind, tmp, out, B, n1, n2, True, (n, 1, n1, n, 1, n1), scale=1.0 / n, flags=oflag)
-    return out
+    # forward: the load reads the REAL rows; inverse: the load weights the spectrum, the store takes |.|
+    _run_plan(plan, x, X, B, False, flags=FFT_REAL_IN)
+    return _run_plan(plan, X, out, B, True, scale=1.0 / n, flags=FFT_ABS_OUT if magnitude else 0, mask_n=n)
 
 
 def analytic_signal(x: torch.Tensor) -> torch.Tensor:

@@ -411,6 +411,24 @@ def test_front_route_beyond_what_a_test_can_run():
             front_route(n_fft, n_fft // 4, 48000, 3.0, 40, False, dict(caps, plan2048=n_fft == 2048))
 
 
+FFT_PLANS = {1: None, 2: ("pow2", 2, 1), 250: ("mixed", 250, 1), 2025: ("mixed", 2025, 1), 6000: ("mixed", 6000, 1),
+             8192: ("pow2", 8192, 1), 8193: None, 11: None, 1009: None, 16384: ("pow2", 128, 128), 32768: ("pow2", 128, 256),
+             65536: ("pow2", 256, 256), 1 << 19: ("pow2", 512, 1024), 1 << 21: ("pow2", 1024, 2048),
+             1 << 25: ("pow2", 4096, 8192), 1 << 26: ("pow2", 8192, 8192), 1 << 27: None, 24000: ("mixed", 150, 160),
+             44100: ("mixed", 210, 210), 48000: ("mixed", 200, 240), 3 << 20: ("mixed", 1536, 2048), 528000: None,
+             7 ** 9: None, 3 << 25: None}
+
+
+def test_fft_plan_is_pinned():
+    """Which launches serve a transform length (sygnals_amd._fftplan.fft_plan, the one place that is decided), and the
+    convolution lengths found through it; evaluated from the code before the plan had one home."""
+    from sygnals_amd._fftplan import conv_fft_len, fft_plan
+    for n, plan in FFT_PLANS.items():
+        assert fft_plan(n) == plan, n
+    for n_out, m in {1: 16, 15: 16, 17: 18, 1000: 1000, 2018: 2048, 44100: 44100, 48511: 48600, 1052672: 1053696}.items():
+        assert conv_fft_len(n_out) == m, n_out
+
+
 def test_cqt_route_covers_every_instantiation():
     """The table reaches every instantiation of the three octave kernels that the entry points can launch: frame length x
     (one | paired row tiles), odd tile counts, row groups of the rfft form, and the one-launch form at 8, 12 and 16 filters."""

@@ -1,6 +1,6 @@
 """A/B timing of library variants on one box: alternates the variants (subprocess per run, SYGNALS_AMD_LIB) so that
 clock drift and box-to-box differences cancel; prints min / median per variant.
-    python3 tools/ab_bench.py [--what mfcc|c4|mel] [--rounds 3] name=path.so [name=path.so ...]
+    python3 tools/ab_bench.py [--what mfcc|c4|mel|fft48k|fft64k|fftenv48k] [--rounds 3] name=path.so [name=path.so ...]
 (`product` as a path means the in-tree product library)"""
 import os, subprocess, sys, statistics
 what, rounds, libs = "mfcc", 3, []
@@ -28,6 +28,7 @@ if what == "cqt":
     stream = (torch.randn(48000 * 3600, device="cuda", generator=g, dtype=torch.float32) * 0.05).reshape(1, -1)
 y2 = ops.to_device_f32(np.tile(Y, (2048 // 64, 1))) if what.startswith("c4blk") else None
 XC = torch.randn((1024, 48000 if what == "fft48k" else 65536, 2), dtype=torch.float32, device="cuda") if what.startswith("fft") else None
+XR = torch.randn((1024, 48000), dtype=torch.float32, device="cuda") if what == "fftenv48k" else None
 fn = {"mfcc": lambda: ops.stft2048_mfcc(y, 48000, 512, True, "hann", 40, 13),
       "mfcc441": lambda: ops.stft2048_mfcc(y, 44100, 512, True, "hann", 40, 13),       # (a 3-step scan layout of the segment projection)
       "mfccmat": lambda: ops.stft2048_mfcc(y, 48000, 512, True, "hann", 40, 13, projection="matrix"),
@@ -47,6 +48,7 @@ fn = {"mfcc": lambda: ops.stft2048_mfcc(y, 48000, 512, True, "hann", 40, 13),
       "cqt": lambda: ops.cqt(stream, 48000),
       "fft48k": lambda: ops.fft_any(XC),                      # 1024 x 48000 complex, mixed radix 200 x 240
       "fft64k": lambda: ops.fft_pow2_any(XC),                 # 1024 x 65536 complex, four-step 256 x 256
+      "fftenv48k": lambda: ops.analytic_fused(XR, True),      # envelope of 1024 x 48000 real rows: the fused ends, four launches
       "stats5": lambda: ops.stft2048_mel(y, 48000, n_mels=40, want_stats=31),       # the a6-a9 row: all five statistics + mel (MODE 1)
       "stats5only": lambda: ops.stft2048_stats(y, 48000, want_stats=31),           # the same rows without the mel spectrogram
       "efb_c4": lambda: EFB(y, 48000, ["mfcc", "spectral_centroid", "spectral_rolloff", "spectral_contrast"], feature_params={"mfcc": {"n_mels": 40}}, to_host=False),   # the reference-API path of C4's features, 1024 clips
@@ -74,7 +76,7 @@ for r in range(rounds):
         out = subprocess.run([sys.executable, "-c", CHILD, what], env=env, capture_output=True, text=True)
         us = [float(l.split()[1]) for l in out.stdout.splitlines() if l.startswith("US")]
         if not us:
-            print(n, "FAILED", out.stderr[-400:]); continue
+            sys.exit("%s FAILED (rc %d): nothing more is started\n%s" % (n, out.returncode, out.stderr[-400:]))
         res[n].append(us[0])
 for n, v in res.items():
     if v: print(f"{what:5s} {n:14s} min {min(v):7.1f}  median {statistics.median(v):7.1f}  runs {['%.1f' % x for x in v]}")
