@@ -796,6 +796,46 @@ int64_t syg_fx_add_noise_work_bytes(int64_t B, int64_t L);
 int syg_fx_add_noise_f32(const float* y, int64_t B, int64_t L, int64_t ldy, const float* noise, int64_t ldn,
                          const double* snr_db, float* out, int64_t ldo, void* work, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Numerical Laplace transform (sygnals/core/transforms.py:159-199), an arbitrary-point z-transform:
+ *     out[b, i] = t_step sum_{n < L} x[b, n] exp(-s_i n t_step),   x [B, L] float32 (row stride ldx) -> out [B, S, 2] float64.
+ * Gate: |out - float64 formula| <= 1e-5 |t_step| sum_n |x[b, n]| exp(-Re(s_i) n t_step).  Same call, same bits (no atomics).
+ *
+ * The s-values reach the library as DEVICE tables built on the host in float64 (sygnals_amd/_laplace.plan builds them;
+ * the kernels trust them, so these are preconditions).  With C = syg_laplace_chunk(), a = Re(s) t_step, a column is
+ *   forward   if a >= 0: z = exp(-s t_step), anchor = 1;
+ *   reversed  if a <  0: z = exp(+s t_step), anchor = exp(-s (L - 1) t_step)  (the transform of the reversed row);
+ *   steep     if |a| (C - 1) > 40, in either direction; steep columns need |a| syg_laplace_steep() >= 746, which that
+ *             threshold implies: the kernel reads only the first (reversed: last) syg_laplace_steep() samples for them.
+ * Every |z| <= 1, and -a (L - 1) <= 700 keeps every anchor finite (the reference's own exp overflows beyond that).
+ * Columns are ordered [forward, padded to a multiple of syg_laplace_tile_cols() | reversed, padded likewise | steep
+ * forward | steep reversed]: S_fwd and S_rev are the PADDED counts, S16 = S_fwd + S_rev, Sc = S16 + S_steep_fwd +
+ * S_steep_rev.
+ *   table  [C, 2, S16] float32: table[i][0 / 1][c] = Re / Im of z_c^i (forward) or z_c^(C - 1 - i) (reversed), each
+ *          formed in float64 and rounded once; zero in padding columns.  May be NULL when S16 = 0.
+ *   fac    [Sc, syg_laplace_fac_stride()] float64: (re, im) of Z^r for r = 0 .. 15 | Z^16 | Z^(segment / C) | z, with
+ *          Z = z^C; every power formed by one exp, not by repeated products.  Zero in padding columns.
+ *   anchor [Sc, 2] float64, as above (it alone depends on L).
+ *   col    [Sc] int32: the index in [0, S) that column writes, -1 for padding (any value outside [0, S) writes nothing,
+ *          so no table makes the kernel write outside `out`; an index no column names is left unwritten).
+ * Launch forms: -1 the rule | 0 whole-row (one wave per (clip, column tile) walks the row) | 1 segmented (the row is cut
+ * into segments of syg_laplace_segment() samples whose float64 sums go to `work`; a second launch adds them in a fixed
+ * order).  The rule takes the segmented form for rows longer than one segment where the whole-row form has fewer than
+ * eight waves a CU (B S16 / 16 < 8 CUs).  It needs `work`, syg_laplace_work_bytes(B, L, S16, form) bytes (0 otherwise:
+ * `work` may be NULL); `out` and `work` are 16-byte aligned.  A tile is syg_laplace_tile_rows() chunks of one clip: a
+ * clip with fewer chunks pads the tile with zero chunks.
+ * ------------------------------------------------------------------------------- */
+int syg_laplace_chunk(void);
+int syg_laplace_tile_rows(void);
+int syg_laplace_tile_cols(void);
+int64_t syg_laplace_segment(void);
+int syg_laplace_steep(void);
+int syg_laplace_fac_stride(void);
+int64_t syg_laplace_work_bytes(int64_t B, int64_t L, int64_t S16, int form);
+int syg_laplace_f32(const float* x, int64_t B, int64_t L, int64_t ldx, const float* table, const double* fac,
+                    const double* anchor, const int32_t* col, int64_t S_fwd, int64_t S_rev, int64_t S_steep_fwd,
+                    int64_t S_steep_rev, int64_t S, double t_step, double* out, void* work, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

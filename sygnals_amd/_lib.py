@@ -117,6 +117,14 @@ SIGNATURES = {
     "syg_fx_add_noise_resident_max": (_l, []),
     "syg_fx_add_noise_work_bytes": (_l, [_l, _l]),
     "syg_fx_add_noise_f32": (_i, [_p, _l, _l, _l, _p, _l, _p, _p, _l, _p, _p]),
+    "syg_laplace_chunk": (_i, []),
+    "syg_laplace_tile_rows": (_i, []),
+    "syg_laplace_tile_cols": (_i, []),
+    "syg_laplace_segment": (_l, []),
+    "syg_laplace_steep": (_i, []),
+    "syg_laplace_fac_stride": (_i, []),
+    "syg_laplace_work_bytes": (_l, [_l, _l, _l, _i]),
+    "syg_laplace_f32": (_i, [_p, _l, _l, _l, _p, _p, _p, _p, _l, _l, _l, _l, _l, _d, _p, _p, _i, _p]),
 }
 
 _lib = None

@@ -246,6 +246,44 @@ def dsp_hilbert(input_file, output):
     click.echo(f"Analytic signal saved to '{Path(output).name}'.")
 
 
+def parse_s_values(text: str) -> np.ndarray:
+    """'1.0,0.5+0.2j' -> complex128 array; each token goes through complex().  A bad or empty token is a usage error."""
+    out = []
+    for tok in text.split(","):
+        try:
+            out.append(complex(tok.strip()))
+        except ValueError:
+            raise click.UsageError(f"--s-values: cannot read '{tok.strip()}' as a complex number (write sigma+omegaj, e.g. 0.5+0.2j).")
+    return np.asarray(out, dtype=np.complex128)
+
+
+@dsp_cmd.command("laplace")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--s-values", "s_values", required=True,
+              help="Comma-separated list of complex 's' values (sigma+j*omega), e.g. '0.1+0.5j,1.0'.")
+@click.option("--t-step", type=float, default=None, help="Time step between samples (1/fs). Required if the input carries no rate.")
+def dsp_laplace(input_file, output, s_values, t_step):
+    """Compute the Numerical Laplace Transform for specified s-values."""
+    from ..core.transforms import laplace_transform_numerical
+    s = parse_s_values(s_values)
+    x, sr = _load_signal(input_file, None)
+    if t_step is None:
+        if not sr:
+            raise click.UsageError("--t-step is required: the input file carries no sampling rate.")
+        t_step = 1.0 / float(sr)
+    try:
+        F = laplace_transform_numerical(x, s, t_step)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    if Path(output).suffix.lower() == ".npz":
+        sio.save_data({"s_values": s, "laplace": F, "t_step": np.array(t_step)}, output)
+    else:
+        sio.save_data(pd.DataFrame({"s_real": s.real, "s_imag": s.imag, "Real": F.real, "Imag": F.imag, "Magnitude": np.abs(F)}),
+                      output)
+    click.echo(f"Laplace transform saved to '{Path(output).name}'.")
+
+
 @dsp_cmd.command("stft")
 @click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
 @click.option("-o", "--output", required=True, type=click.Path())

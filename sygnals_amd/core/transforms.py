@@ -1,9 +1,10 @@
 """Device-backed mirror of sygnals/core/transforms.py: discrete_wavelet_transform :22-79,
 inverse_discrete_wavelet_transform :81-115 (pywt.wavedec / waverec: the Daubechies family haar, db1 ... db10 and the modes
-symmetric, reflect, periodic, constant and zero; sygnals_amd/_wavelets.py, csrc/dwt.hip) and hilbert_transform :119-151.
+symmetric, reflect, periodic, constant and zero; sygnals_amd/_wavelets.py, csrc/dwt.hip), hilbert_transform :119-151 and
+laplace_transform_numerical :159-199 (sygnals_amd/_laplace.py, csrc/laplace.hip).
 
-`dwt_batch` / `idwt_batch` are the batched forms that keep the coefficients on the device.  The numerical-Laplace
-function of that module is outside the hot path.
+`dwt_batch` / `idwt_batch` are the batched forms that keep the coefficients on the device, `laplace_batch` the one that
+keeps the transform there.
 """
 from __future__ import annotations
 
@@ -12,7 +13,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .. import _wavelets, ops
+from .. import _laplace, _wavelets, ops
 from .dsp import _c128, analytic_batch
 
 
@@ -68,3 +69,24 @@ def inverse_discrete_wavelet_transform(coeffs, wavelet: str, mode: str = "symmet
     _wavelets.waverec_length(lens, _wavelets.filter_length(wavelet))         # refuses mismatched lengths before a copy
     y = ops.idwt(ops.to_device_f32(np.concatenate(arrs)[None, :]), lens, wavelet, mode)
     return y[0].cpu().numpy().astype(np.float64)
+
+
+def laplace_batch(y: torch.Tensor, s_values, t_step: float = 1.0) -> torch.Tensor:
+    """Numerical Laplace transform of every clip of y [B, L] (float32, on the device) at the complex s_values [S] ->
+    [B, S] complex128 on the device: F[b, i] = t_step sum_n y[b, n] exp(-s_i n t_step) (ops.laplace)."""
+    return ops.laplace(y, s_values, t_step)
+
+
+def laplace_transform_numerical(data, s_values, t_step: float = 1.0) -> np.ndarray:
+    """sum_n data[n] exp(-s n t_step) t_step for each s in s_values, complex128.  Served: finite t_step and s-values with
+    -Re(s) t_step (len(data) - 1) <= 700 (beyond that the reference's own exp overflows); the data is rounded to float32."""
+    data, s_values = np.asarray(data), np.asarray(s_values)
+    if data.ndim != 1:
+        raise ValueError("Input data must be 1D.")
+    if s_values.ndim != 1:
+        raise ValueError("s_values must be 1D.")
+    s = _laplace.check_s_values(s_values, t_step)
+    if s.size == 0 or data.size == 0:                                # an empty list gives an empty result, no data zeros
+        return np.zeros(s.size, dtype=np.complex128)
+    _laplace.check_domain(s, t_step, data.size)
+    return ops.laplace(ops.to_device_f32(data[None, :]), s, t_step)[0].cpu().numpy()

@@ -14,6 +14,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import _laplace as LP
 from . import _tables as T
 from ._fftplan import (MAX_LDS_FFT, MAX_MIXED_FFT, MAX_ROWS, conv_fft_len, fft_plan, is_pow2,      # noqa: F401 (re-exported)
                        next_direct_len, smooth_split)
@@ -2173,4 +2174,72 @@ def fx_add_noise(y: torch.Tensor, noise: torch.Tensor, snr_db, out: Optional[tor
         check(-1, "syg_fx_add_noise_work_bytes")
     work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device) if wb > 0 else None
     _call("syg_fx_add_noise_f32", _ptr(y), B, L, _ld(y), _ptr(noise), _ld(noise), _ptr(snr), _ptr(out), _ld(out), _ptr(work))
+    return out
+
+
+# ------------------------------------------------------------------ numerical Laplace transform
+LAPLACE_FORMS = {None: -1, "whole": 0, "segmented": 1}
+
+
+def laplace_constants() -> dict:
+    """The figures syg_laplace_f32 rests on (the library owns them): samples per chunk, the tile's chunk rows and s-value
+    columns, samples per segment of the segmented form, samples a steep column reads, float64 factors per column."""
+    h = lib()
+    return dict(C=int(h.syg_laplace_chunk()), tile_rows=int(h.syg_laplace_tile_rows()), tile_cols=int(h.syg_laplace_tile_cols()),
+                segment=int(h.syg_laplace_segment()), steep=int(h.syg_laplace_steep()), fac_stride=int(h.syg_laplace_fac_stride()))
+
+
+@functools.lru_cache(maxsize=16)
+def _laplace_plan_dev(dev: int, s_bytes: bytes, t_step: float):
+    k = laplace_constants()
+    p = LP.plan(np.frombuffer(s_bytes, dtype=np.complex128), t_step, k["C"], k["tile_cols"], k["segment"], k["steep"],
+                k["fac_stride"])
+    return p, _dev(p.table), _dev(p.fac), _dev(p.col)
+
+
+@functools.lru_cache(maxsize=64)
+def _laplace_anchor_dev(dev: int, s_bytes: bytes, t_step: float, L: int):
+    return _dev(LP.anchors(_laplace_plan_dev(dev, s_bytes, t_step)[0], L))
+
+
+def laplace_plan(s_values, t_step: float = 1.0):
+    """(plan, table, fac, col): the host plan (sygnals_amd/_laplace.LaplacePlan) of a list of s-values and its device
+    tables, cached on the s-values' bytes and t_step."""
+    require_gpu()
+    s = LP.check_s_values(s_values, t_step)
+    return _laplace_plan_dev(torch.cuda.current_device(), s.tobytes(), float(t_step))
+
+
+def laplace(y: torch.Tensor, s_values, t_step: float = 1.0, out: Optional[torch.Tensor] = None,
+            form: Optional[str] = None) -> torch.Tensor:
+    """Numerical Laplace transform of every clip of y [B, L] at the complex s_values [S]:
+    F[b, i] = t_step sum_n y[b, n] exp(-s_i n t_step) -> [B, S] complex128 on the device (syg_laplace_f32).  Served:
+    finite t_step and s with -Re(s) t_step (L - 1) <= 700.  form: None (the library's rule) | "whole" | "segmented", for
+    tests and the benchmark."""
+    require_gpu()
+    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
+        raise ValueError("y must be a float32 CUDA tensor [B, L]")
+    if form not in LAPLACE_FORMS:
+        raise ValueError("form must be None, 'whole' or 'segmented'")
+    if y.stride(1) != 1:
+        y = y.contiguous()
+    B, L = y.shape
+    s = LP.check_s_values(s_values, t_step)
+    S = s.size
+    if B < 1 or L < 1 or S < 1:
+        raise ValueError("laplace: empty input")
+    LP.check_domain(s, t_step, L)
+    if out is None:
+        out = torch.empty((B, S), dtype=torch.complex128, device=y.device)
+    elif out.shape != (B, S) or out.dtype != torch.complex128 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("out must be a contiguous complex128 CUDA tensor [B, S]")
+    dev, key, f = torch.cuda.current_device(), s.tobytes(), LAPLACE_FORMS[form]
+    p, table, fac, col = _laplace_plan_dev(dev, key, float(t_step))
+    anchor = _laplace_anchor_dev(dev, key, float(t_step), int(L))
+    wb = lib().syg_laplace_work_bytes(B, L, p.S16, f)
+    if wb < 0:
+        check(-1, "syg_laplace_work_bytes")
+    work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device) if wb > 0 else None
+    _call("syg_laplace_f32", _ptr(y), B, L, _ld(y), _ptr(table), _ptr(fac), _ptr(anchor), _ptr(col), p.S_fwd, p.S_rev,
+          p.S_steep_fwd, p.S_steep_rev, S, float(t_step), _ptr(out), _ptr(work), f)
     return out
