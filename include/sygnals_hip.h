@@ -836,6 +836,36 @@ int syg_laplace_f32(const float* x, int64_t B, int64_t L, int64_t ldx, const flo
                     const double* anchor, const int32_t* col, int64_t S_fwd, int64_t S_rev, int64_t S_steep_fwd,
                     int64_t S_steep_rev, int64_t S, double t_step, double* out, void* work, int form, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Polyphase resampling, scipy.signal.resample_poly in index form (the plan is host work: sygnals_amd/_resample.py):
+ *     t = (n + n_pre_remove) down,  p = t mod up,  q = t div up,
+ *     y[b, n] = sum_{j < Kp} table[p][j] x~[b, q - j],     n < n_out = ceil(L up / down),
+ * x [B, L] float32 (row stride ldx) -> y [B, n_out] float32 (row stride ldy); x~ is x inside [0, L) and the pad rule
+ * outside.  Gate: |y - scipy.signal.resample_poly in float64| <= 1e-5 of the row's peak.  float32 accumulation in a
+ * fixed order, no atomics: the same call gives the same bits and a batch equals its rows.
+ *   up, down  reduced by their gcd by the caller, each in [1, syg_resample_rate_max()]
+ *   table     DEVICE [up, Kp] float32, dense: table[p][j] = hp[p + j up] of the padded, up-scaled filter hp, zero past
+ *             its end (a precondition: the kernel reads up Kp floats)
+ *   pad       0 constant (cval) | 1 edge | 2 wrap | 3 symmetric | 4 reflect (L >= 2); scipy's mean / minimum / maximum
+ *             are the constant rule with 0 on the row minus its statistic and are formed by the caller
+ *   form      -1 the rule | 0 table in LDS | 1 table read from global memory.  The rule: LDS where up Kp 4 bytes <=
+ *             syg_resample_table_lds_rule(), global memory beyond (measured the faster place for a large table).  Form 0
+ *             serves up (Kp | 1) 4 bytes <= syg_resample_table_lds_max() (rows are stored with an odd stride) and is
+ *             an error beyond.  A table of more than syg_resample_table_max() bytes is refused.
+ * A block takes tiles of syg_resample_tile() consecutive outputs of one row and stages their input span in LDS; where
+ * a full tile reads more than syg_resample_span_max() input samples (strong decimation) the taps read global memory.
+ * B <= 65535 a call.
+ * ------------------------------------------------------------------------------- */
+int syg_resample_tile(void);
+int64_t syg_resample_table_lds_rule(void);
+int64_t syg_resample_table_lds_max(void);
+int64_t syg_resample_table_max(void);
+int syg_resample_span_max(void);
+int syg_resample_rate_max(void);
+int syg_resample_poly_f32(const float* x, int64_t B, int64_t L, int64_t ldx, int up, int down, int64_t n_pre_remove, int Kp,
+                          const float* table, int pad, float cval, int form, int64_t n_out, float* y, int64_t ldy,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,13 @@ SIGNATURES = {
     "syg_laplace_fac_stride": (_i, []),
     "syg_laplace_work_bytes": (_l, [_l, _l, _l, _i]),
     "syg_laplace_f32": (_i, [_p, _l, _l, _l, _p, _p, _p, _p, _l, _l, _l, _l, _l, _d, _p, _p, _i, _p]),
+    "syg_resample_tile": (_i, []),
+    "syg_resample_table_lds_rule": (_l, []),
+    "syg_resample_table_lds_max": (_l, []),
+    "syg_resample_table_max": (_l, []),
+    "syg_resample_span_max": (_i, []),
+    "syg_resample_rate_max": (_i, []),
+    "syg_resample_poly_f32": (_i, [_p, _l, _l, _l, _i, _i, _l, _i, _p, _i, _f, _i, _l, _p, _l, _p]),
 }
 
 _lib = None

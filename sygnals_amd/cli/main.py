@@ -284,6 +284,43 @@ def dsp_laplace(input_file, output, s_values, t_step):
     click.echo(f"Laplace transform saved to '{Path(output).name}'.")
 
 
+def parse_window_spec(text: str):
+    """'kaiser:5.0' -> ('kaiser', 5.0); 'hann' -> 'hann' (firwin's window specification)."""
+    name, *params = [t.strip() for t in text.split(":")]
+    if not name:
+        raise click.UsageError("--window: empty window name (write e.g. kaiser:5.0 or hann).")
+    try:
+        return (name, *[float(v) for v in params]) if params else name
+    except ValueError:
+        raise click.UsageError(f"--window: cannot read the parameters of '{text}' as numbers (write e.g. kaiser:5.0).")
+
+
+@dsp_cmd.command("resample")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--target-sr", "target_sr", type=int, required=True, help="Sampling rate of the output (Hz).")
+@click.option("--fs", type=int, default=None, help="Sampling rate of the input (Hz). Required if the input carries no rate.")
+@click.option("--window", default="kaiser:5.0", show_default=True, help="Window of the anti-aliasing filter design, name[:param].")
+@click.option("--padtype", default="constant", show_default=True, help="How the signal is extended past its ends.")
+def dsp_resample(input_file, output, target_sr, fs, window, padtype):
+    """Resample a signal to another sampling rate (polyphase, scipy.signal.resample_poly)."""
+    from ..core.dsp import resample
+    if target_sr <= 0:
+        raise click.UsageError("--target-sr must be a positive sampling rate.")
+    if fs is not None and fs <= 0:
+        raise click.UsageError("--fs must be a positive sampling rate.")
+    w = parse_window_spec(window)
+    x, sr = _load_signal(input_file, fs)
+    if not sr:
+        raise click.UsageError("--fs is required: the input file carries no sampling rate.")
+    try:
+        y = resample(x, sr, target_sr, window=w, padtype=padtype)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    _save_series(y, target_sr, output)
+    click.echo(f"Resampled signal ({sr} Hz -> {target_sr} Hz, {y.size} samples) saved to '{Path(output).name}'.")
+
+
 @dsp_cmd.command("stft")
 @click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
 @click.option("-o", "--output", required=True, type=click.Path())

@@ -3,7 +3,8 @@
 Same signatures, dtypes (float64 / complex128 out) and error behaviour as the reference:
 compute_fft :40-112, compute_ifft :114-162, compute_stft :167-229, apply_convolution :294-337,
 compute_correlation :342-394, compute_autocorrelation :396-433, compute_psd_periodogram :438-498,
-compute_psd_welch :495-560, amplitude_envelope :565-636, apply_window :641-691.  Arithmetic runs in fp32 on the device (parity gate 1e-5, peak-relative).
+compute_psd_welch :495-560, amplitude_envelope :565-636, apply_window :641-691; `resample` is the `scipy` resampling
+method of the reference's pipeline (scipy.signal.resample_poly) on the device.  Arithmetic runs in fp32 on the device (parity gate 1e-5, peak-relative).
 """
 from __future__ import annotations
 
@@ -13,7 +14,7 @@ from typing import Optional, Tuple, Union
 import numpy as np
 from scipy.signal import get_window
 
-from .. import ops
+from .. import _resample, ops
 from .._lib import SygnalsHipError
 
 logger = logging.getLogger(__name__)
@@ -320,3 +321,32 @@ def amplitude_envelope(y, method: str = "hilbert", frame_length: Optional[int] =
         from .audio.features import rms_energy
         return rms_energy(y, frame_length=frame_length, hop_length=hop_length, center=True)
     raise ValueError(f"Unsupported envelope method: {method}. Choose 'hilbert' or 'rms'.")
+
+
+# ------------------------------------------------------------------ resampling (scipy.signal.resample_poly)
+def resample_poly_batch(y, up, down, window=("kaiser", 5.0), padtype: str = "constant", cval=None):
+    """Rows of the device tensor y [B, L] (float32) resampled by up / down -> device tensor [B, ceil(L up / down)]
+    (ops.resample_poly: scipy.signal.resample_poly's filter, alignment and pad types constant, mean, minimum, maximum,
+    edge, wrap, symmetric and reflect)."""
+    return ops.resample_poly(y, up, down, window, padtype, cval)
+
+
+def resample_batch(y, orig_sr, target_sr, window=("kaiser", 5.0), padtype: str = "constant", cval=None):
+    """Rows of the device tensor y [B, L] from orig_sr to target_sr (positive, integer-valued rates): up / down is
+    target_sr / orig_sr reduced."""
+    up, down = _resample.ratio_of_rates(orig_sr, target_sr)
+    return ops.resample_poly(y, up, down, window, padtype, cval)
+
+
+def resample(data, orig_sr, target_sr, window=("kaiser", 5.0), padtype: str = "constant", cval=None) -> np.ndarray:
+    """1-D data from orig_sr to target_sr, float64 out: scipy.signal.resample_poly(data, up, down) with up / down =
+    target_sr / orig_sr reduced; the data is rounded to float32 and the arithmetic is float32 on the device."""
+    data = np.asarray(data)
+    if data.ndim != 1:
+        raise ValueError("Input data must be a 1D array.")
+    up, down = _resample.ratio_of_rates(orig_sr, target_sr)
+    _resample.check_padtype(padtype, data.size if data.size else None)
+    if data.size == 0:
+        return np.array([], dtype=np.float64)
+    out = ops.resample_poly(ops.to_device_f32(data[None, :]), up, down, window, padtype, cval)
+    return out[0].cpu().numpy().astype(np.float64)

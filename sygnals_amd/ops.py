@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _laplace as LP
+from . import _resample as RS
 from . import _tables as T
 from ._fftplan import (MAX_LDS_FFT, MAX_MIXED_FFT, MAX_ROWS, conv_fft_len, fft_plan, is_pow2,      # noqa: F401 (re-exported)
                        next_direct_len, smooth_split)
@@ -2242,4 +2243,115 @@ def laplace(y: torch.Tensor, s_values, t_step: float = 1.0, out: Optional[torch.
     work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device) if wb > 0 else None
     _call("syg_laplace_f32", _ptr(y), B, L, _ld(y), _ptr(table), _ptr(fac), _ptr(anchor), _ptr(col), p.S_fwd, p.S_rev,
           p.S_steep_fwd, p.S_steep_rev, S, float(t_step), _ptr(out), _ptr(work), f)
+    return out
+
+
+# ------------------------------------------------------------------ polyphase resampling
+RESAMPLE_FORMS = {None: -1, "lds": 0, "global": 1}
+
+
+def resample_constants() -> dict:
+    """The figures syg_resample_poly_f32 rests on (the library owns them): outputs per tile, the table size (up * Kp * 4
+    bytes) up to which the rule puts the table in LDS, the size up to which form='lds' may (on up * (Kp | 1) * 4: rows
+    are stored with an odd stride), the size of a served table (up * Kp * 4), the input samples a tile stages at most,
+    the largest up / down."""
+    h = lib()
+    return dict(tile=int(h.syg_resample_tile()), table_lds_rule=int(h.syg_resample_table_lds_rule()),
+                table_lds_max=int(h.syg_resample_table_lds_max()),
+                table_max=int(h.syg_resample_table_max()), span_max=int(h.syg_resample_span_max()),
+                rate_max=int(h.syg_resample_rate_max()))
+
+
+def resample_table_in_lds(up: int, Kp: int) -> bool:
+    """The library's placement rule: True where the table of up phases x Kp taps sits in LDS when form is None."""
+    return up * Kp * 4 <= resample_constants()["table_lds_rule"]
+
+
+def resample_table_fits_lds(up: int, Kp: int) -> bool:
+    """True where form='lds' is served for a table of up phases x Kp taps."""
+    return up * (Kp | 1) * 4 <= resample_constants()["table_lds_max"]
+
+
+def _resample_check_size(up: int, down: int, nbytes: int) -> None:
+    k = resample_constants()
+    if up > k["rate_max"] or down > k["rate_max"]:
+        raise ValueError(f"resample_poly: up={up}, down={down} exceed the served bound of {k['rate_max']}")
+    if nbytes > k["table_max"]:
+        raise ValueError(f"resample_poly: the filter table of up={up}, down={down} takes {nbytes} bytes, above the bound of "
+                         f"{k['table_max']} bytes")
+
+
+@functools.lru_cache(maxsize=64)
+def _resample_table_dev(dev: int, up: int, down: int, wkey, L: int):
+    p = RS._plan(up, down, wkey, L)
+    return p, _dev(p.table)
+
+
+def resample_plan(up, down, L, window=RS.DEFAULT_WINDOW):
+    """(plan, table): the host plan (sygnals_amd/_resample.ResamplePlan) of rows of L samples at up / down and its device
+    table [up, Kp] float32, cached per (up, down, window, L).  up == down after reduction has no table: (plan, None)."""
+    up, down = RS.reduce_ratio(up, down)
+    if up == 1 and down == 1:
+        return RS.resample_plan(1, 1, L), None
+    wkey = RS.window_key(window)
+    _resample_check_size(up, down, RS.table_bytes(up, down, window))
+    require_gpu()
+    if int(L) != L or L < 1:
+        raise ValueError(f"L must be a positive integer, got {L}")
+    return _resample_table_dev(torch.cuda.current_device(), up, down, wkey, int(L))
+
+
+def resample_poly(y: torch.Tensor, up, down, window=RS.DEFAULT_WINDOW, padtype: str = "constant", cval=None,
+                  form: Optional[str] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """scipy.signal.resample_poly along the rows of y [B, L] (float32, on the device; rows may be strided) ->
+    [B, ceil(L up / down)] float32 (syg_resample_poly_f32).  window: firwin's window specification or a 1-D array of
+    taps.  padtype: constant (cval, default 0), mean, minimum, maximum, edge, wrap, symmetric, reflect.  form: None (the
+    library's rule) | "lds" | "global", the table's placement, for tests and the benchmark.  up == down after reduction
+    returns a copy without a launch."""
+    up, down = RS.reduce_ratio(up, down)
+    if form not in RESAMPLE_FORMS:
+        raise ValueError("form must be None, 'lds' or 'global'")
+    if not isinstance(y, torch.Tensor) or y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError("y must be a float32 CUDA tensor [B, L]")
+    B, L = y.shape
+    if B < 1 or L < 1:
+        raise ValueError("resample_poly: empty input")
+    RS.check_padtype(padtype, L)
+    if cval is not None and padtype != "constant":
+        raise ValueError("cval has no effect unless padtype is 'constant'")
+    same = up == 1 and down == 1
+    if not same:
+        _resample_check_size(up, down, RS.table_bytes(up, down, window))
+    require_gpu()
+    if not y.is_cuda:
+        raise ValueError("y must be a float32 CUDA tensor [B, L]")
+    if same:
+        if out is None:
+            return y.clone(memory_format=torch.contiguous_format)
+        out.copy_(y)
+        return out
+    p, table = resample_plan(up, down, L, window)
+    _resample_check_size(up, down, p.table.nbytes)
+    if form == "lds" and not resample_table_fits_lds(p.up, p.Kp):
+        raise ValueError(f"resample_poly: form='lds' needs up * (Kp | 1) * 4 <= {resample_constants()['table_lds_max']} bytes "
+                         f"(up={p.up}, Kp={p.Kp})")
+    if y.stride(1) != 1:
+        y = y.contiguous()
+    if out is None:
+        out = torch.empty((B, p.n_out), dtype=torch.float32, device=y.device)
+    elif out.shape != (B, p.n_out) or out.dtype != torch.float32 or not out.is_cuda or out.stride(1) != 1:
+        raise ValueError(f"out must be a float32 CUDA tensor [B, {p.n_out}] with unit column stride")
+    stat = None
+    if padtype in RS.STAT_PADS:                                  # the row minus its statistic, zeros outside, added back
+        stat = {"mean": lambda t: t.mean(dim=1, keepdim=True), "minimum": lambda t: t.amin(dim=1, keepdim=True),
+                "maximum": lambda t: t.amax(dim=1, keepdim=True)}[padtype](y)
+        y = y - stat
+    pad = RS.PAD_CODES.get(padtype, 0)
+    fill = float(cval) if (cval is not None and stat is None) else 0.0
+    for lo in range(0, B, 65535):                                # grid rows of one launch
+        yb, ob = y[lo:lo + 65535], out[lo:lo + 65535]
+        _call("syg_resample_poly_f32", _ptr(yb), yb.shape[0], L, _ld(yb), p.up, p.down, p.n_pre_remove, p.Kp, _ptr(table), pad,
+              fill, RESAMPLE_FORMS[form], p.n_out, _ptr(ob), _ld(ob))
+    if stat is not None:
+        out += stat
     return out

@@ -184,10 +184,18 @@ def wav_batches(paths: Sequence, batch_clips: int, length: Optional[int] = None,
 
 
 def mfcc_from_files(paths: Sequence, sr: float, batch_clips: int = 1024, length: Optional[int] = None,
-                    workers: int = 8, depth: int = 2, **mfcc_kw) -> np.ndarray:
+                    workers: int = 8, depth: int = 2, target_sr: Optional[float] = None, **mfcc_kw) -> np.ndarray:
     """MFCCs of a list of equally long WAV clips -> float32 [N, n_mfcc, T] (ops.mfcc_batch per batch; keyword
-    arguments as ops.mfcc_batch: n_fft, hop, n_mels, n_mfcc, ...)."""
-    pipe = DevicePipeline(lambda x: ops.mfcc_batch(x, sr, **mfcc_kw), depth=depth)
+    arguments as ops.mfcc_batch: n_fft, hop, n_mels, n_mfcc, ...).  With target_sr each batch is resampled on the device
+    from sr to target_sr (ops.resample_poly, scipy.signal.resample_poly's defaults) and the MFCCs are taken at target_sr;
+    `length` counts samples at the files' rate."""
+    if target_sr is None:
+        compute = lambda x: ops.mfcc_batch(x, sr, **mfcc_kw)                      # noqa: E731
+    else:
+        from ._resample import ratio_of_rates
+        up, down = ratio_of_rates(sr, target_sr)
+        compute = lambda x: ops.mfcc_batch(ops.resample_poly(x, up, down), target_sr, **mfcc_kw)   # noqa: E731
+    pipe = DevicePipeline(compute, depth=depth)
     out = [r for _, r in pipe.run(wav_batches(paths, batch_clips, length, workers))]
     if not out:
         raise ValueError("mfcc_from_files: no input files")
