@@ -866,6 +866,63 @@ int syg_resample_poly_f32(const float* x, int64_t B, int64_t L, int64_t ldx, int
                           const float* table, int pad, float cval, int form, int64_t n_out, float* y, int64_t ldy,
                           void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Dynamic time warping, librosa.sequence.dtw with its default step set [[1,1],[0,1],[1,0]] (the float64 restatement
+ * that is the contract: tests/dtw_ref.py).  Three stages, each usable alone:
+ *
+ * syg_dtw_cost_f32: C[b, n, m] = metric(X[b, :, n], Y[b, :, m]).
+ *   X [B, K, N], Y [B, K, M] float32, row strides ldx >= N, ldy >= M, batch strides bsx, bsy >= 0 in elements (0: every
+ *   pair shares that sequence) -> C [B, N, M] float32, dense.  metric: 0 euclidean | 1 sqeuclidean | 2 cityblock |
+ *   3 cosine.  The first three are sums over k, in ascending order, of f(x_k - y_k), never the norm-and-dot form: a
+ *   frame against itself costs exactly 0.  cosine is 1 - x.y / (|x| |y|); a zero-norm frame gives NaN as SciPy's
+ *   cdist does, and what the recurrence does with a NaN is unspecified.  Gate: |C - C in float64| <= 1e-5 max C.
+ *   A block takes a tile of syg_dtw_cost_tile() frames of X by as many of Y and stages them in LDS.
+ *
+ * syg_dtw_f32: the accumulated cost, the step codes, the end value and the warping path of every pair of C
+ *   [B, N, M] float32 (row stride ldc >= M, batch stride bsc >= 0 elements).
+ *     D[n, m] = min_k ( D[n - s0_k, m - s1_k] + (w_mul_k C[n, m] + w_add_k) ),  D[0, 0] = C[0, 0], under subseq
+ *     D[0, :] = C[0, :]; a later step replaces an earlier one only if strictly smaller (the diagonal wins ties).
+ *   The accumulators are float64 and every operation is rounded on its own (t = w_mul C; t = t + w_add; t = D + t):
+ *   D depends on nothing but C and, with the default weights, equals a float64 NumPy evaluation bit for bit.
+ *   weights_mul_host, weights_add_host: HOST [3] float64, finite, or NULL for 1 and 0.
+ *   Outputs, all DEVICE; the optional ones are skipped when NULL:
+ *     D        optional [B, N, M] float64
+ *     steps    optional [B, N, M] uint8, the index of the step taken into each cell, one byte a cell (lanes and
+ *              tiles that border each other never share a byte, so no store is a read-modify-write)
+ *     cost     [B] float64: D[N - 1, M - 1], under subseq the least value of the last row
+ *     end_col  [B] int32: M - 1, under subseq the first arg-min column of the last row (np.argmin's tie rule)
+ *     path     optional [B, N + M - 1, 2] int32, from the end cell to (0, 0) (to row 0 under subseq) as librosa
+ *              returns it, (-1, -1) past path_len; path_len [B] int32 goes with it; both need `steps`.  The walk runs
+ *              on the device.
+ *   With neither D nor steps nothing of size N M is written: the distance-only path.
+ *   form  -1 the rule | 0 pair-resident | 1 tiled (syg_dtw_form() tells which one the rule takes).
+ *     Pair-resident: one wave owns a pair, a lane a run of up to syg_dtw_run_max() columns; serves
+ *     M <= syg_dtw_resident_max_cols() and needs no workspace.  Tiled: tiles of `tile` x `tile` cells (0: the product
+ *     tile syg_dtw_tile(); at most syg_dtw_tile_max()), one launch per block anti-diagonal, no waiting between
+ *     workgroups inside a launch; needs `work`, syg_dtw_work_bytes(B, N, M, form, tile) bytes (8-byte aligned).  The
+ *     rule: pair-resident wherever M fits it, tiled beyond.
+ *
+ * Ragged batches (both entries): x_len, y_len DEVICE [B] int32 or NULL, with their HOST copies x_len_host, y_len_host
+ * (both or neither; the library checks the host copy, the kernels read the device one and hold it inside [1, N] /
+ * [1, M]).  Pair b is the top left x_len[b] x y_len[b] corner of its matrix; nothing outside it is read by syg_dtw_f32
+ * or written by it, and syg_dtw_cost_f32 writes zeros there.
+ * No atomics: the same call gives the same bits and a batch equals its pairs.  B <= 65535 a call.
+ * ------------------------------------------------------------------------------- */
+int syg_dtw_tile(void);
+int syg_dtw_tile_max(void);
+int syg_dtw_resident_max_cols(void);
+int syg_dtw_run_max(void);
+int syg_dtw_cost_tile(void);
+int syg_dtw_form(int64_t B, int64_t N, int64_t M, int form);
+int64_t syg_dtw_work_bytes(int64_t B, int64_t N, int64_t M, int form, int tile);
+int syg_dtw_cost_f32(const float* X, const float* Y, int64_t B, int64_t K, int64_t N, int64_t M, int64_t ldx, int64_t ldy,
+                     int64_t bsx, int64_t bsy, const int32_t* x_len, const int32_t* y_len, const int32_t* x_len_host,
+                     const int32_t* y_len_host, int metric, float* C, void* stream);
+int syg_dtw_f32(const float* C, int64_t B, int64_t N, int64_t M, int64_t ldc, int64_t bsc, const int32_t* x_len,
+                const int32_t* y_len, const int32_t* x_len_host, const int32_t* y_len_host, const double* weights_mul_host,
+                const double* weights_add_host, int subseq, int form, int tile, double* D, uint8_t* steps, double* cost,
+                int32_t* end_col, int32_t* path, int32_t* path_len, void* work, int64_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,15 @@ SIGNATURES = {
     "syg_resample_span_max": (_i, []),
     "syg_resample_rate_max": (_i, []),
     "syg_resample_poly_f32": (_i, [_p, _l, _l, _l, _i, _i, _l, _i, _p, _i, _f, _i, _l, _p, _l, _p]),
+    "syg_dtw_tile": (_i, []),
+    "syg_dtw_tile_max": (_i, []),
+    "syg_dtw_resident_max_cols": (_i, []),
+    "syg_dtw_run_max": (_i, []),
+    "syg_dtw_cost_tile": (_i, []),
+    "syg_dtw_form": (_i, [_l, _l, _l, _i]),
+    "syg_dtw_work_bytes": (_l, [_l, _l, _l, _i, _i]),
+    "syg_dtw_cost_f32": (_i, [_p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _p, _p, _p, _p, _i, _p, _p]),
+    "syg_dtw_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _l, _p]),
 }
 
 _lib = None

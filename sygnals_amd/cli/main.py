@@ -228,6 +228,55 @@ def dsp_correlation(input_file_1, input_file_2, output, mode, method):
     click.echo(f"{'Auto' if input_file_2 is None else 'Cross-'}correlation saved to '{Path(output).name}'.")
 
 
+DTW_FRAME, DTW_HOP, DTW_MFCC = 2048, 512, 13
+
+
+@dsp_cmd.command("dtw")
+@click.argument("input_file_1", type=click.Path(exists=True, dir_okay=False))
+@click.argument("input_file_2", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--metric", type=click.Choice(["euclidean", "sqeuclidean", "cityblock", "cosine"]), default="euclidean",
+              show_default=True)
+@click.option("--subseq", is_flag=True, help="Align the first input to a part of the second.")
+@click.option("--on", "on", type=click.Choice(["mfcc", "samples"]), default=None,
+              help="What is aligned: the MFCC sequences (13 coefficients, frame 2048, hop 512; the default for audio) or the "
+                   "raw samples (the default for CSV / NPZ series).")
+def dsp_dtw(input_file_1, input_file_2, output, metric, subseq, on):
+    """Align two signals by dynamic time warping (librosa.sequence.dtw's default steps)."""
+    from .. import ops
+    from ..core.alignment import dtw
+    x, sr_x = _load_signal(input_file_1, None)
+    y, sr_y = _load_signal(input_file_2, None)
+    if on is None:
+        on = "mfcc" if (sr_x and sr_y) else "samples"
+    hop = 1
+    try:
+        if on == "mfcc":
+            if not sr_x or not sr_y:
+                raise click.UsageError("--on mfcc needs inputs that carry a sampling rate (audio); use --on samples for a series.")
+            if sr_x != sr_y:
+                raise click.UsageError(f"The inputs have different sampling rates ({sr_x} Hz and {sr_y} Hz): bring them to one "
+                                       "rate with `dsp resample` first.")
+            hop = DTW_HOP
+            X, Y = (ops.mfcc_batch(ops.to_device_f32(v[None, :]), sr_x, DTW_FRAME, DTW_HOP, n_mfcc=DTW_MFCC)[0] for v in (x, y))
+        else:
+            X, Y = x, y
+        D, wp = dtw(X, Y, metric=metric, subseq=subseq)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    cost = float(D[wp[0, 0], wp[0, 1]])
+    if Path(output).suffix.lower() == ".npz":                        # the path as librosa returns it: end first
+        sio.save_data({"path": wp, "cost": np.array(cost), "metric": np.array(metric), "hop_length": np.array(hop)}, output)
+    else:                                                            # the table runs in time order
+        wp = wp[::-1]
+        tx, ty = (wp[:, i] * hop / float(sr) if sr else wp[:, i].astype(np.float64) for i, sr in ((0, sr_x), (1, sr_y)))
+        try:
+            sio.save_data(pd.DataFrame({"index_x": wp[:, 0], "index_y": wp[:, 1], "time_x": tx, "time_y": ty}), output)
+        except ValueError as e:
+            raise click.UsageError(str(e))
+    click.echo(f"DTW path ({len(wp)} steps) saved to '{Path(output).name}'.")
+
+
 @dsp_cmd.command("hilbert")
 @click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
 @click.option("-o", "--output", required=True, type=click.Path())

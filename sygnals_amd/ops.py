@@ -2355,3 +2355,138 @@ def resample_poly(y: torch.Tensor, up, down, window=RS.DEFAULT_WINDOW, padtype: 
     if stat is not None:
         out += stat
     return out
+
+
+# ------------------------------------------------------------------ dynamic time warping
+DTW_FORMS = {None: -1, "resident": 0, "tiled": 1}
+DTW_METRICS = {"euclidean": 0, "sqeuclidean": 1, "cityblock": 2, "cosine": 3}
+
+
+def dtw_constants() -> dict:
+    """The figures syg_dtw_f32 / syg_dtw_cost_f32 rest on (the library owns them): the tiled form's product tile edge and
+    the largest edge it takes, the widest matrix of the pair-resident form, the longest column run of a lane, the cost
+    kernel's tile edge."""
+    h = lib()
+    return dict(tile=int(h.syg_dtw_tile()), tile_max=int(h.syg_dtw_tile_max()),
+                resident_max_cols=int(h.syg_dtw_resident_max_cols()), run_max=int(h.syg_dtw_run_max()),
+                cost_tile=int(h.syg_dtw_cost_tile()))
+
+
+def dtw_plan(B: int, N: int, M: int, want_steps: bool = True, form: Optional[str] = None, tile: int = 0) -> dict:
+    """What a call of dtw() on B pairs of N x M takes: form ('resident' | 'tiled', the library's rule unless `form` names
+    one), work_bytes (the tiled form's float64 seam workspace) and steps_bytes (one byte a cell when the step codes are
+    wanted, which the path needs).  No device work."""
+    if form not in DTW_FORMS:
+        raise ValueError("form must be None, 'resident' or 'tiled'")
+    h = lib()
+    f = h.syg_dtw_form(int(B), int(N), int(M), DTW_FORMS[form])
+    wb = h.syg_dtw_work_bytes(int(B), int(N), int(M), DTW_FORMS[form], int(tile))
+    if f < 0 or wb < 0:
+        check(-1, "syg_dtw_work_bytes")
+    return dict(form="tiled" if f == 1 else "resident", work_bytes=int(wb),
+                steps_bytes=int(B) * int(N) * int(M) if want_steps else 0)
+
+
+def _dtw_lens(v, B: int, device, name: str):
+    """(device int32 [B], host ctypes pointer, keep-alive) of a per-pair length list, or (None, None, None)."""
+    if v is None:
+        return None, None, None
+    host = np.ascontiguousarray((v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.int32))
+    if host.shape != (B,):
+        raise ValueError(f"{name} must hold one length per pair ([{B}]), got shape {host.shape}")
+    dev = v if (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.int32 and v.is_contiguous()) \
+        else torch.from_numpy(host).to(device)
+    return dev, host.ctypes.data_as(C.c_void_p), host
+
+
+def _dtw_seq(t, name):
+    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda:
+        raise ValueError(f"{name} must be a float32 CUDA tensor [B, K, length]")
+    if t.shape[2] > 1 and t.stride(2) != 1:
+        t = t.contiguous()
+    B, K, L = t.shape
+    ld = int(t.stride(1)) if K > 1 else L
+    bs = int(t.stride(0)) if B > 1 else 0
+    if ld < L or bs < 0:
+        t = t.contiguous()
+        ld, bs = L, (K * L if B > 1 else 0)
+    return t, ld, bs
+
+
+def dtw_cost(X: torch.Tensor, Y: torch.Tensor, metric: str = "euclidean", x_len=None, y_len=None) -> torch.Tensor:
+    """Pairwise frame costs C[b, n, m] = metric(X[b, :, n], Y[b, :, m]) of X [B, K, N] and Y [B, K, M] (float32, on the
+    device; rows may be strided, a batch stride of 0 shares one sequence) -> [B, N, M] float32 (syg_dtw_cost_f32).
+    metric: euclidean | sqeuclidean | cityblock | cosine.  x_len / y_len [B]: ragged batches; cells outside a pair's
+    x_len x y_len corner are written as 0 and nothing outside it is read."""
+    require_gpu()
+    if metric not in DTW_METRICS:
+        raise ValueError(f"metric must be one of {sorted(DTW_METRICS)}, got {metric!r}")
+    X, ldx, bsx = _dtw_seq(X, "X")
+    Y, ldy, bsy = _dtw_seq(Y, "Y")
+    B, K, N = X.shape
+    if Y.shape[0] != B or Y.shape[1] != K:
+        raise ValueError(f"X {tuple(X.shape)} and Y {tuple(Y.shape)} must agree in B and K")
+    xd, xh, _kx = _dtw_lens(x_len, B, X.device, "x_len")
+    yd, yh, _ky = _dtw_lens(y_len, B, X.device, "y_len")
+    M = Y.shape[2]
+    out = torch.empty((B, N, M), dtype=torch.float32, device=X.device)
+    _call("syg_dtw_cost_f32", _ptr(X), _ptr(Y), B, K, N, M, ldx, ldy, bsx, bsy, _ptr(xd), _ptr(yd), xh, yh,
+          DTW_METRICS[metric], _ptr(out))
+    return out
+
+
+def dtw(C_: torch.Tensor, x_len=None, y_len=None, weights_mul=None, weights_add=None, subseq: bool = False,
+        want_D: bool = False, want_steps: bool = False, want_path: bool = True, form: Optional[str] = None,
+        tile: int = 0) -> dict:
+    """The DTW recurrence (librosa's default step set) and the backtrack on every pair of the cost tensor C_ [B, N, M]
+    (float32, on the device; rows may be strided) -> dict of device tensors (syg_dtw_f32):
+      cost [B] float64, end_col [B] int32 always; D [B, N, M] float64 (want_D); steps [B, N, M] uint8 (want_steps or
+      want_path); path [B, N + M - 1, 2] int32, end first, (-1, -1) past path_len [B] int32 (want_path).
+    With none of the three wanted nothing of size N M is written (the distance-only path).  weights_mul / weights_add:
+    three finite values each (default 1 and 0).  x_len / y_len [B]: ragged batches; cells of D and steps outside a pair's
+    corner are 0.  form: None (the library's rule) | 'resident' | 'tiled'; tile: the tiled form's tile edge (0: the
+    product tile), for tests and the benchmark."""
+    require_gpu()
+    if not isinstance(C_, torch.Tensor) or C_.dim() != 3 or C_.dtype != torch.float32 or not C_.is_cuda:
+        raise ValueError("C must be a float32 CUDA tensor [B, N, M]")
+    if form not in DTW_FORMS:
+        raise ValueError("form must be None, 'resident' or 'tiled'")
+    if C_.shape[2] > 1 and C_.stride(2) != 1:
+        C_ = C_.contiguous()
+    B, N, M = C_.shape
+    ldc = int(C_.stride(1)) if N > 1 else M
+    bsc = int(C_.stride(0)) if B > 1 else 0
+    if ldc < M or bsc < 0:
+        C_ = C_.contiguous()
+        ldc, bsc = M, (N * M if B > 1 else 0)
+    w = []
+    for v, name in ((weights_mul, "weights_mul"), (weights_add, "weights_add")):
+        if v is None:
+            w.append(None)
+            continue
+        a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+        if a.shape != (3,) or not np.isfinite(a).all():
+            raise ValueError(f"{name} must hold three finite values (one per step of [[1,1],[0,1],[1,0]])")
+        w.append(a)
+    dev = C_.device
+    xd, xh, _kx = _dtw_lens(x_len, B, dev, "x_len")
+    yd, yh, _ky = _dtw_lens(y_len, B, dev, "y_len")
+    ragged = xd is not None or yd is not None
+    alloc = torch.zeros if ragged else torch.empty
+    f = DTW_FORMS[form]
+    wb = lib().syg_dtw_work_bytes(B, N, M, f, int(tile))
+    if wb < 0:
+        check(-1, "syg_dtw_work_bytes")
+    work = torch.empty((wb // 8,), dtype=torch.float64, device=dev) if wb > 0 else None
+    D = alloc((B, N, M), dtype=torch.float64, device=dev) if want_D else None
+    steps = alloc((B, N, M), dtype=torch.uint8, device=dev) if (want_steps or want_path) else None
+    cost = torch.empty((B,), dtype=torch.float64, device=dev)
+    end_col = torch.empty((B,), dtype=torch.int32, device=dev)
+    path = torch.empty((B, N + M - 1, 2), dtype=torch.int32, device=dev) if want_path else None
+    path_len = torch.empty((B,), dtype=torch.int32, device=dev) if want_path else None
+    _call("syg_dtw_f32", _ptr(C_), B, N, M, ldc, bsc, _ptr(xd), _ptr(yd), xh, yh,
+          w[0].ctypes.data_as(C.c_void_p) if w[0] is not None else None,
+          w[1].ctypes.data_as(C.c_void_p) if w[1] is not None else None,
+          1 if subseq else 0, f, int(tile), _ptr(D), _ptr(steps), _ptr(cost), _ptr(end_col), _ptr(path), _ptr(path_len),
+          _ptr(work), wb)
+    return dict(cost=cost, end_col=end_col, D=D, steps=steps, path=path, path_len=path_len)
