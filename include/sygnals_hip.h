@@ -923,6 +923,48 @@ int syg_dtw_f32(const float* C, int64_t B, int64_t N, int64_t M, int64_t ldc, in
                 const double* weights_add_host, int subseq, int form, int tile, double* D, uint8_t* steps, double* cost,
                 int32_t* end_col, int32_t* path, int32_t* path_len, void* work, int64_t work_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Continuous wavelet transform, pywt.cwt as a bank of FIR filters (the float64 restatement that is the contract:
+ * tests/cwt_ref.py; the plan is host work: sygnals_amd/_cwt.py):
+ *     W[b, s, t] = sum_{j < taps_s} h_s[j] x~[b, t + shift_s - j],     t = c stride,  c < n_out = ceil(L / stride),
+ * x [B, L] float32 (row stride ldx), x~ = x inside [0, L) and 0 outside.  h_s = -sqrt(s) d(k_s): pywt.cwt's
+ * diff(convolve(x, k_s)) with the difference taken on the filter, in float64, by the plan; shift_s = floor(d_s) + 1 is
+ * pywt.cwt's crop.  Gate: |W - W in float64| <= 1e-5 A_s per clip and scale, A_s = ||h_s||_1 max|x|.
+ *   table   DEVICE float32: the taps of every filter; a complex wavelet's filter is a re plane of `taps` floats followed
+ *           by its im plane
+ *   meta    DEVICE [S][4] int32: {offset of the filter in table, taps, shift, index of the scale in y}.  A precondition:
+ *           the kernel reads table[offset .. offset + taps) (twice that for cplx); an entry whose index is outside
+ *           [0, S_out) or whose taps < 1 is skipped
+ *   cplx    0 real wavelet | 1 complex wavelet
+ *   output  0 coef: y [B, S_out, n_out] float32 ([B, S_out, n_out, 2], re and im interleaved, for cplx)
+ *           1 magnitude |W|, 2 power |W|^2: y [B, S_out, n_out] float32
+ *   y       dense; only the rows that meta names are written
+ * syg_cwt_f32 is the direct form: a block takes syg_cwt_tile() output columns of one clip and up to
+ * syg_cwt_scales_per_group() consecutive entries of meta, stages their input span in LDS (`reach`: the widest span of a
+ * group at one column, max shift - min (shift - taps + 1) + 1; it sizes the staged words only) and reuses it for each of
+ * them; a span of more than syg_cwt_span_max() samples is read from global memory instead.  float32 accumulation, taps
+ * ascending, no atomics: the same call gives the same bits, a batch equals its rows, a strided call equals the columns
+ * it keeps.  Filters of at most syg_cwt_direct_taps_max() taps are the ones the caller's rule sends here.
+ * The spectral form is three steps around the strided transforms of length M >= L + taps - 1:
+ *   syg_cwt_spectrum_c64  Z[b, r, :] = X[b, :] H[r, :] (complex64, [B, M] by [R, M] -> [B, R, M]), one launch
+ *   the inverse transform of every row of Z
+ *   syg_cwt_crop_f32      row r of Z [B, R, M] read at m = shift + c stride -> y in the requested form.
+ *                         rmeta DEVICE [R][4] int32: {shift_a, index_a, shift_b, index_b}.  Real wavelet: the real part
+ *                         is scale a, the imaginary part scale b (index_b = -1: none).  cplx: {shift, index, 0, -1}.
+ * syg_cwt_work_bytes(B, R, M): the bytes the spectral form holds for B clips (padded rows, their transform, the
+ * products, the inverse's result and the four-step temporary), -1 on bad arguments.  B <= 65535 a call.
+ * ------------------------------------------------------------------------------- */
+int syg_cwt_tile(void);
+int syg_cwt_direct_taps_max(void);
+int syg_cwt_scales_per_group(void);
+int syg_cwt_span_max(void);
+int64_t syg_cwt_work_bytes(int64_t B, int64_t R, int64_t M);
+int syg_cwt_f32(const float* x, int64_t B, int64_t L, int64_t ldx, const float* table, const int32_t* meta, int64_t S,
+                int64_t S_out, int cplx, int64_t reach, int output, int64_t stride, int64_t n_out, float* y, void* stream);
+int syg_cwt_spectrum_c64(const float* X, const float* H, int64_t B, int64_t R, int64_t M, float* Z, void* stream);
+int syg_cwt_crop_f32(const float* Z, int64_t B, int64_t R, int64_t M, const int32_t* rmeta, int64_t L, int64_t S_out, int cplx,
+                     int output, int64_t stride, int64_t n_out, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,14 @@ SIGNATURES = {
     "syg_dtw_work_bytes": (_l, [_l, _l, _l, _i, _i]),
     "syg_dtw_cost_f32": (_i, [_p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _p, _p, _p, _p, _i, _p, _p]),
     "syg_dtw_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _l, _p]),
+    "syg_cwt_tile": (_i, []),
+    "syg_cwt_direct_taps_max": (_i, []),
+    "syg_cwt_scales_per_group": (_i, []),
+    "syg_cwt_span_max": (_i, []),
+    "syg_cwt_work_bytes": (_l, [_l, _l, _l]),
+    "syg_cwt_f32": (_i, [_p, _l, _l, _l, _p, _p, _l, _l, _i, _l, _i, _l, _l, _p, _p]),
+    "syg_cwt_spectrum_c64": (_i, [_p, _p, _l, _l, _l, _p, _p]),
+    "syg_cwt_crop_f32": (_i, [_p, _l, _l, _l, _p, _l, _l, _i, _i, _l, _l, _p, _p]),
 }
 
 _lib = None

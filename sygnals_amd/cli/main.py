@@ -333,6 +333,63 @@ def dsp_laplace(input_file, output, s_values, t_step):
     click.echo(f"Laplace transform saved to '{Path(output).name}'.")
 
 
+def parse_scale_values(text: str) -> np.ndarray:
+    """'1,2.5,8' -> float64 array.  A bad or empty token is a usage error."""
+    out = []
+    for tok in text.split(","):
+        try:
+            out.append(float(tok.strip()))
+        except ValueError:
+            raise click.UsageError(f"--scale-values: cannot read '{tok.strip()}' as a number (write e.g. 1,2.5,8).")
+    return np.asarray(out, dtype=np.float64)
+
+
+@dsp_cmd.command("cwt")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--scales", "num_scales", type=int, default=None,
+              help="Number of scales, spaced geometrically from 1 to max(2, length / 8).")
+@click.option("--scale-values", "scale_values", default=None, help="Comma-separated list of scales, e.g. '1,2,4,8'.")
+@click.option("--wavelet", default="morl", show_default=True, help="morl, mexh, gaus1 or cmorB-C (e.g. cmor1.5-1.0).")
+@click.option("--magnitude", is_flag=True, help="Save |W| instead of the coefficients.")
+@click.option("--stride", type=int, default=1, show_default=True, help="Keep every H-th column of the time axis.")
+def dsp_cwt(input_file, output, num_scales, scale_values, wavelet, magnitude, stride):
+    """Compute the Continuous Wavelet Transform (a scalogram) over a list of scales."""
+    from ..core import transforms as TR
+    if (num_scales is None) == (scale_values is None):
+        raise click.UsageError("Give exactly one of --scales N and --scale-values 'a,b,...'.")
+    if num_scales is not None and num_scales < 1:
+        raise click.UsageError("--scales must be at least 1.")
+    if stride < 1:
+        raise click.UsageError("--stride must be at least 1.")
+    x, sr = _load_signal(input_file, None)
+    period = 1.0 / float(sr) if sr else 1.0
+    try:
+        scales = TR.scalogram_scales(num_scales, x.size) if num_scales is not None else parse_scale_values(scale_values)
+        W, freqs = TR.continuous_wavelet_transform(x, scales, wavelet, sampling_period=period)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    W = W[:, ::stride]
+    if magnitude:
+        W = np.abs(W)
+    if Path(output).suffix.lower() == ".npz":
+        sio.save_data({"scales": np.asarray(scales, dtype=np.float64), "frequencies": freqs, "coefficients": W,
+                       "wavelet": np.array(wavelet)}, output)
+    else:
+        S, n = W.shape
+        cols = {"scale": np.repeat(scales, n), "frequency": np.repeat(freqs, n),
+                "time": np.tile(np.arange(n) * stride * period, S)}
+        if np.iscomplexobj(W):
+            cols.update(real=W.real.ravel(), imag=W.imag.ravel())
+        else:
+            cols["value"] = W.ravel()
+        try:
+            sio.save_data(pd.DataFrame(cols), output)
+        except ValueError as e:
+            raise click.UsageError(str(e))
+    click.echo(f"CWT ({W.shape[0]} scales x {W.shape[1]} columns, {wavelet}) saved to '{Path(output).name}'.")
+
+
 def parse_window_spec(text: str):
     """'kaiser:5.0' -> ('kaiser', 5.0); 'hann' -> 'hann' (firwin's window specification)."""
     name, *params = [t.strip() for t in text.split(":")]

@@ -1,10 +1,12 @@
 """Device-backed mirror of sygnals/core/transforms.py: discrete_wavelet_transform :22-79,
 inverse_discrete_wavelet_transform :81-115 (pywt.wavedec / waverec: the Daubechies family haar, db1 ... db10 and the modes
 symmetric, reflect, periodic, constant and zero; sygnals_amd/_wavelets.py, csrc/dwt.hip), hilbert_transform :119-151 and
-laplace_transform_numerical :159-199 (sygnals_amd/_laplace.py, csrc/laplace.hip).
+laplace_transform_numerical :159-199 (sygnals_amd/_laplace.py, csrc/laplace.hip).  continuous_wavelet_transform is the
+pywt.cwt call of sygnals/utils/visualizations.py plot_scalogram (morl, mexh, gaus1 and cmorB-C; sygnals_amd/_cwt.py,
+csrc/cwt.hip).
 
 `dwt_batch` / `idwt_batch` are the batched forms that keep the coefficients on the device, `laplace_batch` the one that
-keeps the transform there.
+keeps the transform there, `cwt_batch` the one that keeps the scalogram there.
 """
 from __future__ import annotations
 
@@ -13,7 +15,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from .. import _laplace, _wavelets, ops
+from .. import _cwt, _laplace, _wavelets, ops
 from .dsp import _c128, analytic_batch
 
 
@@ -90,3 +92,45 @@ def laplace_transform_numerical(data, s_values, t_step: float = 1.0) -> np.ndarr
         return np.zeros(s.size, dtype=np.complex128)
     _laplace.check_domain(s, t_step, data.size)
     return ops.laplace(ops.to_device_f32(data[None, :]), s, t_step)[0].cpu().numpy()
+
+
+def scalogram_scales(num, L) -> np.ndarray:
+    """The scale grid plot_scalogram makes from a count: geomspace(1, max(2, L / 8), max(1, num))."""
+    return _cwt.scalogram_scales(num, L)
+
+
+def central_frequency(wavelet, precision: int = 8) -> float:
+    """pywt.central_frequency of a served wavelet, in cycles per unit of its own axis."""
+    return _cwt.central_frequency(wavelet, precision)
+
+
+def scale2frequency(wavelet, scales, precision: int = 8) -> np.ndarray:
+    """pywt.scale2frequency: central_frequency(wavelet) / scales."""
+    return _cwt.scale2frequency(wavelet, _cwt.check_scales(scales), precision)
+
+
+def cwt_batch(y: torch.Tensor, scales, wavelet: str = "morl", output: str = "magnitude", stride: int = 1) -> torch.Tensor:
+    """Scalograms of every clip of y [B, L] (float32, on the device) -> [B, S, ceil(L / stride)] float32 on the device
+    ([..., 2] for the `coef` of a complex wavelet): the image-like feature format_features_as_image / image_device take
+    (ops.cwt)."""
+    return ops.cwt(y, scales, wavelet, output, stride)
+
+
+def continuous_wavelet_transform(data, scales, wavelet: str = "morl", sampling_period: float = 1.0, method: str = "conv"):
+    """pywt.cwt without `axis`: (coefs [S, L], frequencies [S]); coefs float64 for a real wavelet, complex128 for a complex
+    one.  method: 'conv' (the library's rule picks the path per scale) | 'fft' (every scale through the transforms).  The
+    data is rounded to float32."""
+    data = np.asarray(data)
+    if data.ndim != 1:
+        raise ValueError("Input data must be a 1D array.")
+    if data.size == 0:
+        raise ValueError("Input data must hold at least one sample.")
+    if method not in ("conv", "fft"):
+        raise ValueError("method must be 'conv' or 'fft'.")
+    w = _cwt.parse_wavelet(wavelet)
+    s = _cwt.check_scales(scales)
+    _cwt.cwt_plan(s, wavelet)                                        # a scale too small is refused before a copy
+    W = ops.cwt(ops.to_device_f32(data[None, :]), s, wavelet, "coef", 1, form="spectral" if method == "fft" else None)[0]
+    W = W.cpu().numpy().astype(np.float64)
+    coefs = W[..., 0] + 1j * W[..., 1] if w.complex else W
+    return coefs, _cwt.scale2frequency(wavelet, s) / sampling_period

@@ -14,6 +14,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import _cwt as CW
 from . import _laplace as LP
 from . import _resample as RS
 from . import _tables as T
@@ -2357,8 +2358,144 @@ def resample_poly(y: torch.Tensor, up, down, window=RS.DEFAULT_WINDOW, padtype: 
     return out
 
 
+# ------------------------------------------------------------------ continuous wavelet transform
+CWT_FORMS = (None, "direct", "spectral")
+CWT_WORK_BYTES = 1 << 30            # the spectral form takes the clips in blocks whose work buffers stay below this
+CWT_MAX_ELEMS = 1 << 31             # B S ceil(L / stride) at most
+
+
+def cwt_constants() -> dict:
+    """The figures syg_cwt_f32 rests on (the library owns them): output columns per tile, the tap count up to which the
+    rule runs a filter direct, the scales a block serves from one staged span, the input samples a block stages at most."""
+    h = lib()
+    return dict(tile=int(h.syg_cwt_tile()), direct_taps_max=int(h.syg_cwt_direct_taps_max()),
+                scales_per_group=int(h.syg_cwt_scales_per_group()), span_max=int(h.syg_cwt_span_max()))
+
+
+@functools.lru_cache(maxsize=32)
+def _cwt_table_dev(dev: int, name: str, s_bytes: bytes):
+    p = CW._plan(name, s_bytes)
+    return p, _dev(p.table)
+
+
+@functools.lru_cache(maxsize=64)
+def _cwt_direct_dev(dev: int, name: str, s_bytes: bytes, idx_bytes: bytes):
+    p = CW._plan(name, s_bytes)
+    idx = np.frombuffer(idx_bytes, dtype=np.int64)
+    idx = idx[np.argsort(p.taps[idx], kind="stable")]              # filters of like length share a group's span
+    return _dev(p.meta(idx)), p.reach(idx, cwt_constants()["scales_per_group"])
+
+
+def cwt_fft_len(L: int, taps_max: int) -> int:
+    """Transform length of the spectral form: conv_fft_len of the full convolution's length, which must itself have a plan."""
+    M = conv_fft_len(L + taps_max - 1)
+    if fft_plan(M) is None:
+        M = next_direct_len(M)
+    if fft_plan(M) is None:
+        raise ValueError(f"cwt: rows of {L} samples under a filter of {taps_max} taps need a transform of {M} points, above the "
+                         "longest plan (2^26)")
+    return M
+
+
+@functools.lru_cache(maxsize=8)
+def _cwt_spectral_dev(dev: int, name: str, s_bytes: bytes, idx_bytes: bytes, L: int):
+    """(M, R, H [R, M, 2] the filter rows' transforms, rmeta): per wavelet, scale list, spectral subset and row length."""
+    p = CW._plan(name, s_bytes)
+    idx = np.frombuffer(idx_bytes, dtype=np.int64)
+    rows = CW.spectral_rows(p, idx)
+    M = cwt_fft_len(L, int(p.taps[idx].max()))
+    h, rmeta = CW.spectral_tables(p, rows, M)
+    return M, len(rows), fft_any(_dev(h)), _dev(rmeta)
+
+
+def cwt_plan(scales, wavelet="morl", L=None):
+    """(plan, table): the host plan (sygnals_amd/_cwt.CwtPlan: one differenced filter per scale, its tap count, crop
+    offset and l1 norm) and its device table, cached per wavelet and scale list.  With L, the transforms of the spectral
+    form's filter rows for rows of L samples are made and cached as well."""
+    p = CW.cwt_plan(scales, wavelet)
+    require_gpu()
+    dev, key = torch.cuda.current_device(), p.scales.tobytes()
+    if L is not None:
+        if int(L) != L or L < 1:
+            raise ValueError(f"L must be a positive integer, got {L}")
+        _, spec = CW.split_forms(p, cwt_constants()["direct_taps_max"], None)
+        if spec.size:
+            _cwt_spectral_dev(dev, p.wavelet.name, key, spec.astype(np.int64).tobytes(), int(L))
+    return _cwt_table_dev(dev, p.wavelet.name, key)
+
+
+def cwt_out_shape(B: int, S: int, L: int, stride: int, cplx: bool, output: str):
+    n_out = -(-L // stride)
+    return (B, S, n_out, 2) if (cplx and output == "coef") else (B, S, n_out)
+
+
+def cwt(y: torch.Tensor, scales, wavelet="morl", output: str = "coef", stride: int = 1, form: Optional[str] = None,
+        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Continuous wavelet transform (pywt.cwt's arithmetic; tests/cwt_ref.py) of every clip of y [B, L] (float32, on the
+    device; rows may be strided) at the scales [S] -> [B, S, ceil(L / stride)] float32, or [..., 2] (re, im) for the `coef`
+    of a complex wavelet.  wavelet: morl | mexh | gaus1 | cmorB-C.  output: coef | magnitude |W| | power |W|^2.  stride
+    keeps the columns 0, stride, 2 stride ...: exactly W[..., ::stride].  form: None (the rule: filters of at most
+    cwt_constants()['direct_taps_max'] taps run direct, the longer ones through the transforms) | "direct" | "spectral",
+    for tests and the benchmark."""
+    w = CW.parse_wavelet(wavelet)
+    if output not in CW.OUTPUTS:
+        raise ValueError("output must be 'coef', 'magnitude' or 'power'")
+    if form not in CWT_FORMS:
+        raise ValueError("form must be None, 'direct' or 'spectral'")
+    if isinstance(stride, bool) or int(stride) != stride or stride < 1:
+        raise ValueError(f"stride must be an integer >= 1, got {stride}")
+    stride = int(stride)
+    if not isinstance(y, torch.Tensor) or y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError("y must be a float32 CUDA tensor [B, L]")
+    B, L = y.shape
+    if B < 1 or L < 1:
+        raise ValueError("cwt: empty input")
+    p = CW.cwt_plan(scales, wavelet)
+    S = p.S
+    shape = cwt_out_shape(B, S, L, stride, w.complex, output)
+    n_out = shape[2]
+    if B * S * n_out > CWT_MAX_ELEMS:
+        raise ValueError(f"cwt: the result of {B} clips x {S} scales x {n_out} columns has {B * S * n_out} elements, above the "
+                         f"bound of 2^31; take fewer clips a call or a larger stride")
+    require_gpu()
+    if not y.is_cuda:
+        raise ValueError("y must be a float32 CUDA tensor [B, L]")
+    if y.stride(1) != 1:
+        y = y.contiguous()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=y.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 CUDA tensor {list(shape)}")
+    dev, key, code, cplx = torch.cuda.current_device(), p.scales.tobytes(), CW.OUTPUTS[output], int(w.complex)
+    _, table = _cwt_table_dev(dev, w.name, key)
+    direct, spec = CW.split_forms(p, cwt_constants()["direct_taps_max"], form)
+    if direct.size:
+        meta, reach = _cwt_direct_dev(dev, w.name, key, direct.astype(np.int64).tobytes())
+        for lo in range(0, B, 65535):                                # grid rows of one launch
+            yb, ob = y[lo:lo + 65535], out[lo:lo + 65535]
+            _call("syg_cwt_f32", _ptr(yb), yb.shape[0], L, _ld(yb), _ptr(table), _ptr(meta), int(direct.size), S, cplx, reach,
+                  code, stride, n_out, _ptr(ob))
+    if spec.size:
+        M, R, H, rmeta = _cwt_spectral_dev(dev, w.name, key, spec.astype(np.int64).tobytes(), int(L))
+        plan = fft_plan(M)
+        per_clip = lib().syg_cwt_work_bytes(1, R, M)
+        if per_clip < 0:
+            check(-1, "syg_cwt_work_bytes")
+        bb = int(max(1, min(B, MAX_ROWS // R, CWT_WORK_BYTES // per_clip)))
+        for lo in range(0, B, bb):
+            yb, ob = y[lo:lo + bb], out[lo:lo + bb]
+            nb = yb.shape[0]
+            X = torch.empty((nb, M, 2), dtype=torch.float32, device=y.device)
+            _run_plan(plan, pack_rows(yb, M), X, nb, False, flags=FFT_REAL_IN)      # once for all scales
+            Z = torch.empty((nb * R, M, 2), dtype=torch.float32, device=y.device)
+            _call("syg_cwt_spectrum_c64", _ptr(X), _ptr(H), nb, R, M, _ptr(Z))
+            Wz = _run_plan(plan, Z, torch.empty_like(Z), nb * R, True, scale=1.0 / M)
+            _call("syg_cwt_crop_f32", _ptr(Wz), nb, R, M, _ptr(rmeta), L, S, cplx, code, stride, n_out, _ptr(ob))
+    return out
+
+
 # ------------------------------------------------------------------ dynamic time warping
-DTW_FORMS = {None: -1, "resident": 0, "tiled": 1}
+DTW_FORMS ={None: -1, "resident": 0, "tiled": 1}
 DTW_METRICS = {"euclidean": 0, "sqeuclidean": 1, "cityblock": 2, "cosine": 3}
 
 
