@@ -944,7 +944,9 @@ int syg_dtw_f32(const float* C, int64_t B, int64_t N, int64_t M, int64_t ldc, in
  * group at one column, max shift - min (shift - taps + 1) + 1; it sizes the staged words only) and reuses it for each of
  * them; a span of more than syg_cwt_span_max() samples is read from global memory instead.  float32 accumulation, taps
  * ascending, no atomics: the same call gives the same bits, a batch equals its rows, a strided call equals the columns
- * it keeps.  Filters of at most syg_cwt_direct_taps_max() taps are the ones the caller's rule sends here.
+ * it keeps.  Filters of at most syg_cwt_direct_taps_max() taps are the ones the caller's rule sends here.  At stride 1 a
+ * block also stages the taps of the scale at hand, in at most syg_cwt_taps_lds_max() words (both planes of a complex
+ * filter, each padded by six); a longer filter reads its taps from global memory.
  * The spectral form is three steps around the strided transforms of length M >= L + taps - 1:
  *   syg_cwt_spectrum_c64  Z[b, r, :] = X[b, :] H[r, :] (complex64, [B, M] by [R, M] -> [B, R, M]), one launch
  *   the inverse transform of every row of Z
@@ -958,6 +960,7 @@ int syg_cwt_tile(void);
 int syg_cwt_direct_taps_max(void);
 int syg_cwt_scales_per_group(void);
 int syg_cwt_span_max(void);
+int syg_cwt_taps_lds_max(void);
 int64_t syg_cwt_work_bytes(int64_t B, int64_t R, int64_t M);
 int syg_cwt_f32(const float* x, int64_t B, int64_t L, int64_t ldx, const float* table, const int32_t* meta, int64_t S,
                 int64_t S_out, int cplx, int64_t reach, int output, int64_t stride, int64_t n_out, float* y, void* stream);

@@ -145,6 +145,7 @@ SIGNATURES = {
     "syg_cwt_direct_taps_max": (_i, []),
     "syg_cwt_scales_per_group": (_i, []),
     "syg_cwt_span_max": (_i, []),
+    "syg_cwt_taps_lds_max": (_i, []),
     "syg_cwt_work_bytes": (_l, [_l, _l, _l]),
     "syg_cwt_f32": (_i, [_p, _l, _l, _l, _p, _p, _l, _l, _i, _l, _i, _l, _l, _p, _p]),
     "syg_cwt_spectrum_c64": (_i, [_p, _p, _l, _l, _l, _p, _p]),

@@ -246,6 +246,7 @@ extern "C" int syg_cwt_tile(void) { return CW_TILE; }
 extern "C" int syg_cwt_direct_taps_max(void) { return CW_DIRECT_TAPS_MAX; }
 extern "C" int syg_cwt_scales_per_group(void) { return CW_SPG; }
 extern "C" int syg_cwt_span_max(void) { return CW_SPAN_MAX; }
+extern "C" int syg_cwt_taps_lds_max(void) { return CW_TAPS_LDS_MAX; }
 
 extern "C" int64_t syg_cwt_work_bytes(int64_t B, int64_t R, int64_t M) {
   if (B < 1 || R < 1 || M < 2 || B > 65535 || R > 65535 || M > ((int64_t)1 << 27)) {

@@ -2366,10 +2366,12 @@ CWT_MAX_ELEMS = 1 << 31             # B S ceil(L / stride) at most
 
 def cwt_constants() -> dict:
     """The figures syg_cwt_f32 rests on (the library owns them): output columns per tile, the tap count up to which the
-    rule runs a filter direct, the scales a block serves from one staged span, the input samples a block stages at most."""
+    rule runs a filter direct, the scales a block serves from one staged span, the input samples a block stages at most,
+    the words of taps a block stages at most (the stride-1 form)."""
     h = lib()
     return dict(tile=int(h.syg_cwt_tile()), direct_taps_max=int(h.syg_cwt_direct_taps_max()),
-                scales_per_group=int(h.syg_cwt_scales_per_group()), span_max=int(h.syg_cwt_span_max()))
+                scales_per_group=int(h.syg_cwt_scales_per_group()), span_max=int(h.syg_cwt_span_max()),
+                taps_lds_max=int(h.syg_cwt_taps_lds_max()))
 
 
 @functools.lru_cache(maxsize=32)
@@ -2432,7 +2434,7 @@ def cwt_out_shape(B: int, S: int, L: int, stride: int, cplx: bool, output: str):
 def cwt(y: torch.Tensor, scales, wavelet="morl", output: str = "coef", stride: int = 1, form: Optional[str] = None,
         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Continuous wavelet transform (pywt.cwt's arithmetic; tests/cwt_ref.py) of every clip of y [B, L] (float32, on the
-    device; rows may be strided) at the scales [S] -> [B, S, ceil(L / stride)] float32, or [..., 2] (re, im) for the `coef`
+    device; rows may be strided, rows less than L apart are copied) at the scales [S] -> [B, S, ceil(L / stride)] float32, or [..., 2] (re, im) for the `coef`
     of a complex wavelet.  wavelet: morl | mexh | gaus1 | cmorB-C.  output: coef | magnitude |W| | power |W|^2.  stride
     keeps the columns 0, stride, 2 stride ...: exactly W[..., ::stride].  form: None (the rule: filters of at most
     cwt_constants()['direct_taps_max'] taps run direct, the longer ones through the transforms) | "direct" | "spectral",
@@ -2460,7 +2462,7 @@ def cwt(y: torch.Tensor, scales, wavelet="morl", output: str = "coef", stride: i
     require_gpu()
     if not y.is_cuda:
         raise ValueError("y must be a float32 CUDA tensor [B, L]")
-    if y.stride(1) != 1:
+    if y.stride(1) != 1 or _ld(y) < L:                               # (rows that overlap, an expanded row: a copy)
         y = y.contiguous()
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=y.device)

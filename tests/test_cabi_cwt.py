@@ -13,8 +13,8 @@ from sygnals_amd import _cwt as CW
 from tests import cwt_ref as R
 from tests.test_cabi_symbols import declared_functions
 
-NEW = ["syg_cwt_tile", "syg_cwt_direct_taps_max", "syg_cwt_scales_per_group", "syg_cwt_span_max", "syg_cwt_work_bytes",
-       "syg_cwt_f32", "syg_cwt_spectrum_c64", "syg_cwt_crop_f32"]
+NEW = ["syg_cwt_tile", "syg_cwt_direct_taps_max", "syg_cwt_scales_per_group", "syg_cwt_span_max", "syg_cwt_taps_lds_max",
+       "syg_cwt_work_bytes", "syg_cwt_f32", "syg_cwt_spectrum_c64", "syg_cwt_crop_f32"]
 WAVELETS = ("morl", "mexh", "gaus1", "cmor1.5-1.0")
 REFUSED = ("gaus2", "gaus8", "cgau1", "shan1.5-1.0", "fbsp2-1.5-1.0", "db4", "haar", "cmor", "cmor0-1.0", "cmor1.5", "cmor-1-1", "", 7)
 
@@ -46,7 +46,8 @@ def test_constants(h):
     from sygnals_amd import ops
     k = ops.cwt_constants()
     assert k == dict(tile=h.syg_cwt_tile(), direct_taps_max=h.syg_cwt_direct_taps_max(),
-                     scales_per_group=h.syg_cwt_scales_per_group(), span_max=h.syg_cwt_span_max())
+                     scales_per_group=h.syg_cwt_scales_per_group(), span_max=h.syg_cwt_span_max(),
+                     taps_lds_max=h.syg_cwt_taps_lds_max())
     assert k["tile"] % 256 == 0 and 256 <= k["tile"] <= 4096
     assert 1 <= k["scales_per_group"] <= 64
     assert 4 * k["span_max"] <= 160 * 1024                                # the staged span fits the 160 KiB of LDS
