@@ -968,6 +968,65 @@ int syg_cwt_spectrum_c64(const float* X, const float* H, int64_t B, int64_t R, i
 int syg_cwt_crop_f32(const float* Z, int64_t B, int64_t R, int64_t M, const int32_t* rmeta, int64_t L, int64_t S_out, int cplx,
                      int output, int64_t stride, int64_t n_out, float* y, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Cepstral analysis (the float64 restatement that is the contract: tests/cepstrum_ref.py).
+ *     real cepstrum      c = ifft(log(max(|X|, amin))).real,  X = fft(x, n)
+ *     complex cepstrum   c = ifft(log(max(|X|, amin)) + i phi_u).real, phi_u the unwrapped phase with its linear term
+ *                        pi ndelay k / center taken out (center = (n + 1) / 2, ndelay = rint(phi_u[center] / pi))
+ * amin must be finite and >= 0 everywhere (at 0 a zero bin gives -inf and the result is unspecified).
+ * Gate: |c - c in float64| <= 1e-5 K per frame or row, K = mean_k ||x w||_1 / max(|X_k|, amin).
+ *
+ * syg_cepstrogram2048_f32: the fused kernel, frames of 2048 samples only (another frame_length: SYG_E_UNSUPPORTED).
+ *   y [B, L] float32 (row stride ldy), framed, zero-padded and counted as syg_stft2048_c2c_f32 does (T by its rule);
+ *   window [2048] float32 (the padded analysis window), twiddle [2048][2] = exp(-2 pi i k / 2048);
+ *   out [B, n_ceps, T] float32, quefrencies 0 .. n_ceps - 1, 1 <= n_ceps <= 2048.  One wave per frame, a workgroup of
+ *   syg_cepstrum_constants(SYG_CEPS_WAVES) waves per tile of SYG_CEPS_TILE_FRAMES consecutive frames, staged in LDS and
+ *   stored with the frame index fastest.  float32 in one fixed order, no atomics: the same call gives the same bits, a
+ *   batch equals its rows, n_ceps = Q equals the first Q rows of the full result.
+ * The chain form, for every length (the transforms between the steps are the caller's: the strided FFT entries):
+ *   syg_cepstrum_logmag_c64  X [rows, in_bins][2] complex64, in_bins = n (a whole spectrum) or n / 2 + 1 (a one-sided one,
+ *                            extended evenly) -> Z [rows, n][2] = (log(max(|X|, amin)) - log(amin), 0); for amin = 0
+ *                            nothing is subtracted.  In place (Z == X) only for in_bins == n.
+ *   syg_cepstrum_gather_f32  Z [rows, n][2], the inverse transform of the above -> out[(b n_ceps + q) T + t] = Re Z[b T + t, q]
+ *                            (+ log(amin) at q = 0; pass amin = 0 to add nothing), q < n_ceps; T = 1: out [rows, n_ceps].
+ *                            rows is a multiple of T (whole clips) or less than T (a run of one clip's frames, `out`
+ *                            pointing at its first frame).
+ * Complex cepstrum of rows:
+ *   syg_cepstrum_unwrap_c64  X [B, n][2] -> Z [B, n][2] = (log(max(|X|, amin)) - log(amin), phi_u) and ndelay [B] int32.
+ *                            phi = atan2f, except bin 0: 0 for Re X[0] >= 0, else +pi.  np.unwrap's rule as integer wrap
+ *                            counts, their prefix sum exact, phi_u formed in float64 and stored as float32.  work:
+ *                            syg_cepstrum_unwrap_work_bytes(B, n) bytes, 4-byte aligned (-1 on bad arguments).  Blocks of
+ *                            SYG_CEPS_SCAN bins, block sums and a second pass; no workgroup waits on another.  n >= 2.
+ *   syg_cepstrum_exp_c64     Xh [B, n][2] -> Z = exp(Re Xh) (cos, sin)(Im Xh + pi ndelay[b] k / center): the middle of the
+ *                            inverse complex cepstrum (exact for even n; for odd n only at ndelay = 0).
+ * syg_cepstrum_peaks_f32: over ceps [B, Q, T] float32, per frame q* = the first maximum of c[qmin .. qmax]
+ *   (1 <= qmin <= qmax < Q), the parabolic shift d = (c[q*-1] - c[q*+1]) / (2 (c[q*-1] - 2 c[q*] + c[q*+1])) where
+ *   qmin < q* < qmax and the denominator is negative (else 0), in float64 from the float32 values;
+ *   f0 [B, T] float64 = sr / (q* + d), NaN where strength < threshold; strength [B, T] float32 = c[q*]; qstar [B, T] int32;
+ *   voiced [B, T] uint8.
+ * syg_cepstrum_constants(key): the figures above (SYG_CEPS_*), -1 for an unknown key.
+ * ------------------------------------------------------------------------------- */
+enum {
+  SYG_CEPS_FRAME = 0,        /* frame length of the fused kernel */
+  SYG_CEPS_TILE_FRAMES = 1,  /* consecutive frames a workgroup stages and stores together */
+  SYG_CEPS_WAVES = 2,        /* waves of a workgroup */
+  SYG_CEPS_SCAN = 3,         /* bins a block of the unwrap scans */
+  SYG_CEPS_LDS_FIXED = 4,    /* bytes of LDS a workgroup of the fused kernel holds beside its stage */
+  SYG_CEPS_LDS_MAX = 5       /* bytes of LDS at n_ceps = 2048 */
+};
+int64_t syg_cepstrum_constants(int key);
+int syg_cepstrogram2048_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int frame_length, int hop, int center, int64_t T,
+                            const float* window, const float* twiddle, int n_ceps, double amin, float* out, void* stream);
+int syg_cepstrum_logmag_c64(const float* X, int64_t rows, int64_t in_bins, int64_t n, double amin, float* Z, void* stream);
+int syg_cepstrum_gather_f32(const float* Z, int64_t rows, int64_t n, int64_t n_ceps, int64_t T, double amin, float* out,
+                            void* stream);
+int64_t syg_cepstrum_unwrap_work_bytes(int64_t B, int64_t n);
+int syg_cepstrum_unwrap_c64(const float* X, int64_t B, int64_t n, double amin, void* work, int64_t work_bytes, float* Z,
+                            int32_t* ndelay, void* stream);
+int syg_cepstrum_exp_c64(const float* Xh, int64_t B, int64_t n, const int32_t* ndelay, float* Z, void* stream);
+int syg_cepstrum_peaks_f32(const float* ceps, int64_t B, int64_t Q, int64_t T, int qmin, int qmax, double sr, double threshold,
+                           double* f0, float* strength, int32_t* qstar, uint8_t* voiced, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

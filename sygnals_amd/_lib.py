@@ -150,6 +150,14 @@ SIGNATURES = {
     "syg_cwt_f32": (_i, [_p, _l, _l, _l, _p, _p, _l, _l, _i, _l, _i, _l, _l, _p, _p]),
     "syg_cwt_spectrum_c64": (_i, [_p, _p, _l, _l, _l, _p, _p]),
     "syg_cwt_crop_f32": (_i, [_p, _l, _l, _l, _p, _l, _l, _i, _i, _l, _l, _p, _p]),
+    "syg_cepstrum_constants": (_l, [_i]),
+    "syg_cepstrogram2048_f32": (_i, [_p, _l, _l, _l, _i, _i, _i, _l, _p, _p, _i, _d, _p, _p]),
+    "syg_cepstrum_logmag_c64": (_i, [_p, _l, _l, _l, _d, _p, _p]),
+    "syg_cepstrum_gather_f32": (_i, [_p, _l, _l, _l, _l, _d, _p, _p]),
+    "syg_cepstrum_unwrap_work_bytes": (_l, [_l, _l]),
+    "syg_cepstrum_unwrap_c64": (_i, [_p, _l, _l, _d, _p, _l, _p, _p, _p]),
+    "syg_cepstrum_exp_c64": (_i, [_p, _l, _l, _p, _p, _p]),
+    "syg_cepstrum_peaks_f32": (_i, [_p, _l, _l, _l, _i, _i, _d, _d, _p, _p, _p, _p, _p]),
 }
 
 _lib = None

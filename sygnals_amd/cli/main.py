@@ -390,6 +390,63 @@ def dsp_cwt(input_file, output, num_scales, scale_values, wavelet, magnitude, st
     click.echo(f"CWT ({W.shape[0]} scales x {W.shape[1]} columns, {wavelet}) saved to '{Path(output).name}'.")
 
 
+@dsp_cmd.command("cepstrum")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--kind", type=click.Choice(["real", "complex"]), default="real", show_default=True)
+@click.option("--n", "n", type=int, default=None, help="Transform length (the input is zero-padded or cut); default: its length.")
+@click.option("--frames", is_flag=True, help="The real cepstrum of every frame (a cepstrogram) instead of the whole signal.")
+@click.option("--n-fft", "n_fft", type=int, default=2048, show_default=True, help="Frame length (with --frames).")
+@click.option("--hop", type=int, default=512, show_default=True, help="Hop between frames (with --frames).")
+@click.option("--n-ceps", "n_ceps", type=int, default=None, help="Quefrencies kept per frame (with --frames); default n_fft / 2 + 1.")
+def dsp_cepstrum(input_file, output, kind, n, frames, n_fft, hop, n_ceps):
+    """Compute the real or complex cepstrum of a signal, or the cepstrogram of its frames."""
+    from .. import _cepstrum, ops
+    from ..core import dsp as D
+    if frames and kind == "complex":
+        raise click.UsageError("--frames gives the real cepstrum of every frame: it cannot be combined with --kind complex.")
+    if frames and n is not None:
+        raise click.UsageError("--n is the whole signal's transform length: with --frames give --n-fft.")
+    if n is not None and n < (2 if kind == "complex" else 1):
+        raise click.UsageError(f"--n must be at least {2 if kind == 'complex' else 1}.")
+    if frames and (n_fft < 2 or hop < 1):
+        raise click.UsageError("--n-fft must be at least 2 and --hop at least 1.")
+    x, sr = _load_signal(input_file, None)
+    unit = 1.0 / float(sr) if sr else 1.0
+    cols = {}
+    try:
+        if frames:
+            _cepstrum.check_n_ceps(n_ceps, n_fft)                    # refused before a copy
+            c = ops.cepstrogram(ops.to_device_f32(x[None, :]), n_fft, hop, n_ceps=n_ceps)[0].cpu().numpy().astype(np.float64)
+        elif kind == "real":
+            c = D.real_cepstrum(x, n)
+        else:
+            c, ndelay = D.complex_cepstrum(x, n)
+            cols["ndelay"] = np.array(ndelay)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    quef = np.arange(c.shape[0]) * unit
+    if Path(output).suffix.lower() == ".npz":
+        data = {"cepstrum": c, "quefrency": quef, **cols}
+        if frames:
+            data.update(n_fft=np.array(n_fft), hop_length=np.array(hop))
+        sio.save_data(data, output)
+    else:
+        if frames:
+            Q, T = c.shape
+            table = {"quefrency": np.repeat(quef, T), "time": np.tile(np.arange(T) * hop * unit, Q), "value": c.ravel()}
+        else:
+            table = {"quefrency": quef, "value": c}
+            if cols:
+                table["ndelay"] = np.full(c.shape[0], int(cols["ndelay"]))
+        try:
+            sio.save_data(pd.DataFrame(table), output)
+        except ValueError as e:
+            raise click.UsageError(str(e))
+    what = f"Cepstrogram ({c.shape[0]} quefrencies x {c.shape[1]} frames)" if frames else f"{kind.capitalize()} cepstrum ({c.shape[0]} points)"
+    click.echo(f"{what} saved to '{Path(output).name}'.")
+
+
 def parse_window_spec(text: str):
     """'kaiser:5.0' -> ('kaiser', 5.0); 'hann' -> 'hann' (firwin's window specification)."""
     name, *params = [t.strip() for t in text.split(":")]

@@ -74,10 +74,22 @@ def _pitch_defaults(fmin, fmax, hop_length):
 
 def fundamental_frequency_batch(y, sr: int, fmin: Optional[float] = None, fmax: Optional[float] = None,
                                 method: str = "pyin", hop_length: Optional[int] = None, frame_length: int = 2048,
-                                win_length: Optional[int] = None, center: bool = True):
+                                win_length: Optional[int] = None, center: bool = True, threshold: Optional[float] = None):
     """Batched fundamental_frequency of clips y [B, L] (a float32 device tensor or an array): device tensors
-    (times [T] float64 on the host, f0 [B, T] with NaN unvoiced, voiced_flag [B, T] float32 0 / 1, voiced_probs [B, T])."""
+    (times [T] float64 on the host, f0 [B, T] with NaN unvoiced, voiced_flag [B, T] float32 0 / 1, voiced_probs [B, T]).
+    method 'cepstrum' (not in the reference; tests/cepstrum_ref.py is its contract) takes the peak of the real cepstrum of
+    every hann frame between the quefrencies sr / fmax and sr / fmin; a frame is voiced when the peak reaches `threshold`
+    (default 0.13), and voiced_probs equals voiced_flag.  Any frame length is served (2048 by the fused kernel)."""
     fmin, fmax, hop = _pitch_defaults(fmin, fmax, hop_length)
+    if method not in ("pyin", "yin", "cepstrum"):
+        raise ValueError(f"Unsupported pitch estimation method: {method}. Choose 'pyin', 'yin' or 'cepstrum'.")
+    if threshold is not None and method != "cepstrum":
+        raise TypeError("fundamental_frequency: threshold belongs to method='cepstrum'")
+    if method == "cepstrum":
+        from ... import _cepstrum as CP
+        if win_length is not None:
+            raise TypeError("fundamental_frequency: method='cepstrum' windows the whole frame (no win_length)")
+        CP.quefrency_range(sr, fmin, fmax, int(frame_length))         # refused before a copy
     y = y if hasattr(y, "is_cuda") else ops.to_device_f32(np.atleast_2d(np.asarray(y)))
     if y.dim() != 2:
         raise ValueError("Input audio batch must be a 2D array [B, L].")
@@ -89,7 +101,10 @@ def fundamental_frequency_batch(y, sr: int, fmin: Optional[float] = None, fmax: 
         vf = _finite01(f0)
         vp = vf
     else:
-        raise ValueError(f"Unsupported pitch estimation method: {method}. Choose 'pyin' or 'yin'.")
+        f0, voiced, _ = ops.pitch_cepstrum(y, sr, fmin, fmax, frame_length, hop if hop is not None else 512, center,
+                                           threshold=CP.THRESHOLD if threshold is None else float(threshold))
+        vf = voiced.float()
+        vp = vf
     hop_calc = hop if hop is not None else 512
     times = np.arange(f0.shape[1], dtype=np.float64) * hop_calc / sr
     return times, f0, vf, vp
@@ -105,12 +120,12 @@ def fundamental_frequency(y, sr: int, fmin: Optional[float] = None, fmax: Option
     if y.ndim != 1:
         raise ValueError("Input audio data must be a 1D array.")
     logger.debug(f"Estimating Fundamental Frequency (Pitch) using {method}: fmin={fmin}, fmax={fmax}, hop={hop_length}")
-    allowed = {"frame_length", "win_length", "center"}
+    allowed = {"frame_length", "win_length", "center", "threshold"}
     if set(kwargs) - allowed:
         raise TypeError(f"fundamental_frequency: unsupported librosa arguments on the device backend: "
                         f"{sorted(set(kwargs) - allowed)}")
-    if method not in ("pyin", "yin"):
-        raise ValueError(f"Unsupported pitch estimation method: {method}. Choose 'pyin' or 'yin'.")
+    if method not in ("pyin", "yin", "cepstrum"):
+        raise ValueError(f"Unsupported pitch estimation method: {method}. Choose 'pyin', 'yin' or 'cepstrum'.")
     times, f0, vf, vp = fundamental_frequency_batch(y[None, :], sr, fmin, fmax, method, hop_length, **kwargs)
     return (times, f0[0].cpu().numpy().astype(np.float64), vf[0].cpu().numpy().astype(np.float64),
             vp[0].cpu().numpy().astype(np.float64))

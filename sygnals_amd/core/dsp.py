@@ -14,7 +14,7 @@ from typing import Optional, Tuple, Union
 import numpy as np
 from scipy.signal import get_window
 
-from .. import _resample, ops
+from .. import _cepstrum, _resample, ops
 from .._lib import SygnalsHipError
 
 logger = logging.getLogger(__name__)
@@ -350,3 +350,66 @@ def resample(data, orig_sr, target_sr, window=("kaiser", 5.0), padtype: str = "c
         return np.array([], dtype=np.float64)
     out = ops.resample_poly(ops.to_device_f32(data[None, :]), up, down, window, padtype, cval)
     return out[0].cpu().numpy().astype(np.float64)
+
+
+# ------------------------------------------------------------------ cepstral analysis (not in the reference's code: its
+# specification lists it, docs/dev_spec_v1.0.0.md 3.5; the float64 restatement tests/cepstrum_ref.py is the contract)
+def real_cepstrum_batch(x, n: Optional[int] = None, amin: float = _cepstrum.AMIN):
+    """Rows of the device tensor x [B, L] (float32) -> their real cepstra [B, n] (ops.real_cepstrum)."""
+    return ops.real_cepstrum(x, n, amin)
+
+
+def complex_cepstrum_batch(x, n: Optional[int] = None, amin: float = _cepstrum.AMIN):
+    """Rows of the device tensor x [B, L] (float32) -> (complex cepstra [B, n], ndelay [B] int32) (ops.complex_cepstrum)."""
+    return ops.complex_cepstrum(x, n, amin)
+
+
+def inverse_complex_cepstrum_batch(ceps, ndelay):
+    """(complex cepstra [B, n] on the device, ndelay [B]) -> the rows [B, n] (ops.inverse_complex_cepstrum)."""
+    return ops.inverse_complex_cepstrum(ceps, ndelay)
+
+
+def cepstrogram_batch(y, n_fft: int = 2048, hop_length: int = 512, center: bool = True, window="hann",
+                      win_length: Optional[int] = None, n_ceps: Optional[int] = None, amin: float = _cepstrum.AMIN):
+    """Clips y [B, L] on the device (float32) -> the real cepstrum of every frame, [B, Q, T] (ops.cepstrogram): compute_stft's
+    framing, Q = n_ceps or n_fft // 2 + 1 quefrencies."""
+    return ops.cepstrogram(y, n_fft, hop_length, center, window, win_length, n_ceps, amin)
+
+
+def _cepstrum_row(data, n, n_min: int = 1):
+    data = np.asarray(data)
+    if data.ndim != 1:
+        raise ValueError("Input data must be a 1D array.")
+    if data.size == 0:
+        raise ValueError("Input data must hold at least one sample.")
+    return data, _cepstrum.row_length(n, data.shape[0], n_min)
+
+
+def real_cepstrum(data, n: Optional[int] = None, amin: float = _cepstrum.AMIN) -> np.ndarray:
+    """ifft(log(max(|fft(data, n)|, amin))).real, float64 [n]; data is rounded to float32 and the arithmetic is float32 on
+    the device.  amin must be finite and >= 0 (at 0 a zero bin gives -inf)."""
+    data, n = _cepstrum_row(data, n)
+    amin = _cepstrum.check_amin(amin)
+    return ops.real_cepstrum(ops.to_device_f32(data[None, :]), n, amin)[0].cpu().numpy().astype(np.float64)
+
+
+def complex_cepstrum(data, n: Optional[int] = None, amin: float = _cepstrum.AMIN) -> Tuple[np.ndarray, int]:
+    """(c float64 [n], ndelay): ifft(log(max(|X|, amin)) + i phi).real with phi the unwrapped phase of X = fft(data, n)
+    (np.unwrap's rule; bin 0 counts as 0 or +pi by the sign of Re X[0]) less its linear term pi ndelay k / center,
+    center = (n + 1) // 2, ndelay = rint(phi[center] / pi).  A right shift of a minimum-phase row by d samples gives
+    ndelay = -d."""
+    data, n = _cepstrum_row(data, n, 2)
+    amin = _cepstrum.check_amin(amin)
+    c, nd = ops.complex_cepstrum(ops.to_device_f32(data[None, :]), n, amin)
+    return c[0].cpu().numpy().astype(np.float64), int(nd[0].item())
+
+
+def inverse_complex_cepstrum(ceps, ndelay: int) -> np.ndarray:
+    """The row whose complex cepstrum is (ceps, ndelay), float64.  Exact for even n at any ndelay; for odd n only at
+    ndelay = 0 (the linear term is then no circular shift: errors of 1e-2 at n = 255 and ndelay = -31).  The sign of the
+    row's sum is not part of (ceps, ndelay): a row with a negative sum comes back with its sum's sign turned, x - 2 mean(x)."""
+    ceps, _ = _cepstrum_row(ceps, None, 2)
+    if isinstance(ndelay, bool) or int(ndelay) != ndelay:
+        raise ValueError(f"ndelay must be an integer, got {ndelay}")
+    x = ops.inverse_complex_cepstrum(ops.to_device_f32(ceps[None, :]), [int(ndelay)])
+    return x[0].cpu().numpy().astype(np.float64)

@@ -14,6 +14,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from . import _cepstrum as CP
 from . import _cwt as CW
 from . import _laplace as LP
 from . import _resample as RS
@@ -2629,3 +2630,197 @@ def dtw(C_: torch.Tensor, x_len=None, y_len=None, weights_mul=None, weights_add=
           1 if subseq else 0, f, int(tile), _ptr(D), _ptr(steps), _ptr(cost), _ptr(end_col), _ptr(path), _ptr(path_len),
           _ptr(work), wb)
     return dict(cost=cost, end_col=end_col, D=D, steps=steps, path=path, path_len=path_len)
+
+
+# ------------------------------------------------------------------ cepstral analysis
+CEPSTRUM_FORMS = (None, "fused", "chain")
+CEPS_SLAB_ELEMS = 1 << 26          # complex points a buffer of the chain form holds at most (512 MiB)
+_CEPS_KEYS = {"frame": 0, "tile_frames": 1, "waves": 2, "scan": 3, "lds_fixed": 4, "lds_max": 5}      # SYG_CEPS_* of include/sygnals_hip.h
+
+
+def cepstrum_constants() -> dict:
+    """The figures csrc/cepstrum.hip rests on (the library owns them): the fused kernel's frame length, the frames a
+    workgroup stages and stores together, its waves, the bins a block of the phase unwrap scans, and the bytes of LDS a
+    workgroup holds beside its stage and at n_ceps = 2048."""
+    h = lib()
+    return {k: int(h.syg_cepstrum_constants(v)) for k, v in _CEPS_KEYS.items()}
+
+
+def _ceps_tensor(x, what: str, dims: int = 2):
+    if not isinstance(x, torch.Tensor) or x.dim() != dims or x.dtype != torch.float32:
+        raise ValueError(f"{what} must be a float32 CUDA tensor of {dims} dimensions")
+    if min(x.shape) < 1:
+        raise ValueError(f"{what}: empty input")
+
+
+def _ceps_on_device(x, what: str):
+    require_gpu()
+    if not x.is_cuda:
+        raise ValueError(f"{what} must be a float32 CUDA tensor")
+    if x.stride(-1) != 1 or (x.dim() == 2 and _ld(x) < x.shape[1]):
+        x = x.contiguous()
+    return x
+
+
+def cepstrogram_frames(L: int, n_fft: int, hop: int, center: bool) -> int:
+    """The frame count of stft_any (compute_stft) for clips of L samples."""
+    if n_fft == 2048 or (is_pow2(n_fft) and 8 <= n_fft <= 16384):
+        return _frames(L, n_fft, hop, center)
+    return _at_least_one(num_frames_padded(L, n_fft, hop, center))
+
+
+def _ceps_chain_rows(X, n: int, Q: int, T: int, amin: float, out_ptr) -> None:
+    """One-sided spectra X [rows, n // 2 + 1, 2] of frames -> their first Q quefrencies at out_ptr (laid out [.., Q, T])."""
+    rows = X.shape[0]
+    Z = torch.empty((rows, n, 2), dtype=torch.float32, device=X.device)
+    _call("syg_cepstrum_logmag_c64", _ptr(X), rows, n // 2 + 1, n, amin, _ptr(Z))
+    Cz = fft_any(Z, inverse=True)
+    _call("syg_cepstrum_gather_f32", _ptr(Cz), rows, n, Q, T, amin, out_ptr)
+
+
+def cepstrogram(y: torch.Tensor, n_fft: int = 2048, hop: int = 512, center: bool = True, window="hann", win_length=None,
+                n_ceps=None, amin: float = CP.AMIN, form: Optional[str] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Real cepstrum of every windowed frame of the clips y [B, L] (float32, on the device; rows may be strided) ->
+    [B, Q, T] float32, quefrencies 0 .. Q - 1, Q = n_ceps or n_fft // 2 + 1: c = ifft(log(max(|X|, amin))).real
+    (tests/cepstrum_ref.py).  Framing, zero centre padding, frame count, window and win_length are stft_any's.
+    form: None (the rule: the fused kernel at n_fft = 2048, the chain stft_any -> log|X| -> inverse transform elsewhere)
+    | "fused" (n_fft = 2048 only) | "chain"."""
+    if form not in CEPSTRUM_FORMS:
+        raise ValueError("form must be None, 'fused' or 'chain'")
+    if isinstance(n_fft, bool) or int(n_fft) != n_fft or n_fft < 2 or n_fft > CP.MAX_N:
+        raise ValueError(f"n_fft must be an integer in [2, 2^26], got {n_fft}")
+    if isinstance(hop, bool) or int(hop) != hop or hop < 1:
+        raise ValueError(f"hop must be an integer >= 1, got {hop}")
+    n_fft, hop = int(n_fft), int(hop)
+    Q = CP.check_n_ceps(n_ceps, n_fft)
+    amin = CP.check_amin(amin)
+    if form == "fused" and n_fft != 2048:
+        raise ValueError(f"cepstrogram: the fused form serves n_fft = 2048 only (got {n_fft}); other lengths take form='chain'")
+    _ceps_tensor(y, "y")
+    B, L = y.shape
+    T = cepstrogram_frames(L, n_fft, hop, bool(center))
+    CP.check_size("cepstrogram", (B, Q, T), ("clips", "quefrencies", "frames"))
+    y = _ceps_on_device(y, "y")
+    shape = (B, Q, T)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=y.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 CUDA tensor {list(shape)}")
+    if n_fft == 2048 and form != "chain":
+        win = window_dev(window, 2048 if win_length is None else win_length, 2048)
+        _call("syg_cepstrogram2048_f32", _ptr(y), B, L, _ld(y), 2048, hop, int(bool(center)), T, _ptr(win), _ptr(twiddle_dev(2048)),
+              Q, amin, _ptr(out))
+        return out
+    F = n_fft // 2 + 1
+    rows_max = max(1, min(MAX_ROWS, CEPS_SLAB_ELEMS // n_fft))
+    if T <= rows_max:                                           # whole clips a pass
+        per = rows_max // T
+        for b0 in range(0, B, per):
+            X = stft_any(y[b0:b0 + per], n_fft, hop, center, window, win_length)
+            _ceps_chain_rows(X.view(-1, F, 2), n_fft, Q, T, amin, _ptr(out[b0:b0 + per]))
+        return out
+    for b in range(B):                                          # long clips: runs of frames of one clip
+        X = stft_any(y[b:b + 1], n_fft, hop, center, window, win_length).view(T, F, 2)
+        for t0 in range(0, T, rows_max):
+            _ceps_chain_rows(X[t0:t0 + rows_max], n_fft, Q, T, amin, C.c_void_p(out[b].data_ptr() + 4 * t0))
+    return out
+
+
+def _ceps_rows(x, n, who: str, n_min: int = 1):
+    _ceps_tensor(x, "x")
+    B, L = x.shape
+    n = CP.row_length(n, L, n_min)
+    CP.check_size(who, (B, n), ("rows", "points"))
+    return _ceps_on_device(x, "x"), B, n
+
+
+def _ceps_slabs(B: int, n: int):
+    per = max(1, min(B, MAX_ROWS, CEPS_SLAB_ELEMS // n))
+    return [(b0, min(per, B - b0)) for b0 in range(0, B, per)]
+
+
+def real_cepstrum(x: torch.Tensor, n=None, amin: float = CP.AMIN) -> torch.Tensor:
+    """Real cepstrum of every row of x [B, L] -> [B, n] float32: ifft(log(max(|fft(x, n)|, amin))).real; x is zero-padded
+    or cut to n (default L)."""
+    amin = CP.check_amin(amin)
+    x, B, n = _ceps_rows(x, n, "real_cepstrum")
+    out = torch.empty((B, n), dtype=torch.float32, device=x.device)
+    for b0, bc in _ceps_slabs(B, n):
+        X = fft_any(pack_real(x[b0:b0 + bc], n))
+        _call("syg_cepstrum_logmag_c64", _ptr(X), bc, n, n, amin, _ptr(X))
+        _call("syg_cepstrum_gather_f32", _ptr(fft_any(X, inverse=True)), bc, n, n, 1, amin, _ptr(out[b0:b0 + bc]))
+    return out
+
+
+def complex_cepstrum(x: torch.Tensor, n=None, amin: float = CP.AMIN):
+    """Complex cepstrum of every row of x [B, L] -> (c [B, n] float32, ndelay [B] int32): the phase is unwrapped by
+    np.unwrap's rule (bin 0: 0 or +pi by the sign of Re X[0]) and its linear term pi ndelay k / center is taken out.  A right
+    shift of a minimum-phase row by d samples gives ndelay = -d.  n >= 2."""
+    amin = CP.check_amin(amin)
+    x, B, n = _ceps_rows(x, n, "complex_cepstrum", 2)
+    out = torch.empty((B, n), dtype=torch.float32, device=x.device)
+    nd = torch.empty((B,), dtype=torch.int32, device=x.device)
+    for b0, bc in _ceps_slabs(B, n):
+        X = fft_any(pack_real(x[b0:b0 + bc], n))
+        wb = lib().syg_cepstrum_unwrap_work_bytes(bc, n)
+        if wb < 0:
+            check(-1, "syg_cepstrum_unwrap_work_bytes")
+        work = torch.empty((wb // 4,), dtype=torch.int32, device=x.device)
+        Z = torch.empty_like(X)
+        _call("syg_cepstrum_unwrap_c64", _ptr(X), bc, n, amin, _ptr(work), wb, _ptr(Z), _ptr(nd[b0:b0 + bc]))
+        _call("syg_cepstrum_gather_f32", _ptr(fft_any(Z, inverse=True)), bc, n, n, 1, amin, _ptr(out[b0:b0 + bc]))
+    return out, nd
+
+
+def inverse_complex_cepstrum(c: torch.Tensor, ndelay) -> torch.Tensor:
+    """The rows x [B, n] whose complex cepstrum is (c [B, n], ndelay [B]):
+    ifft(exp(Re Xh + i (Im Xh + pi ndelay k / center))).real, Xh = fft(c).  Exact for even n at any ndelay; for odd n only
+    at ndelay = 0 (the linear term is then no circular shift: errors of 1e-2 at n = 255, ndelay = -31)."""
+    x, B, n = _ceps_rows(c, None, "inverse_complex_cepstrum", 2)
+    nd = ndelay if isinstance(ndelay, torch.Tensor) else torch.as_tensor(np.asarray(ndelay, dtype=np.int32).reshape(-1))
+    if nd.dim() != 1 or nd.shape[0] != B or nd.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"ndelay must hold one integer per row ({B})")
+    nd = nd.to(device=x.device, dtype=torch.int32).contiguous()
+    out = torch.empty((B, n), dtype=torch.float32, device=x.device)
+    for b0, bc in _ceps_slabs(B, n):
+        Xh = fft_any(pack_real(x[b0:b0 + bc], n))
+        _call("syg_cepstrum_exp_c64", _ptr(Xh), bc, n, _ptr(nd[b0:b0 + bc]), _ptr(Xh))
+        _call("syg_cepstrum_gather_f32", _ptr(fft_any(Xh, inverse=True)), bc, n, n, 1, 0.0, _ptr(out[b0:b0 + bc]))
+    return out
+
+
+def cepstrum_peaks(ceps: torch.Tensor, qmin: int, qmax: int, sr: float, threshold: float = CP.THRESHOLD):
+    """The cepstral peak of every frame of ceps [B, Q, T] (float32, on the device): q* = the first maximum of
+    c[qmin .. qmax], a parabolic shift where the peak is interior and the parabola opens downwards (float64, from the float32
+    values) -> (f0 [B, T] float64 = sr / (q* + shift), NaN where the peak is below threshold; strength [B, T] float32 =
+    c[q*]; qstar [B, T] int32; voiced [B, T] bool)."""
+    _ceps_tensor(ceps, "ceps", 3)
+    B, Q, Tn = ceps.shape
+    if any(isinstance(v, bool) or int(v) != v for v in (qmin, qmax)) or not 1 <= qmin <= qmax < Q:
+        raise ValueError(f"cepstrum_peaks: need 1 <= qmin <= qmax < Q (got qmin={qmin}, qmax={qmax}, Q={Q})")
+    if not (float(sr) > 0 and np.isfinite(float(sr))) or np.isnan(float(threshold)):
+        raise ValueError(f"cepstrum_peaks: bad sr={sr} / threshold={threshold}")
+    require_gpu()
+    if not ceps.is_cuda:
+        raise ValueError("ceps must be a float32 CUDA tensor of 3 dimensions")
+    ceps = ceps.contiguous()
+    dev = ceps.device
+    f0 = torch.empty((B, Tn), dtype=torch.float64, device=dev)
+    strength = torch.empty((B, Tn), dtype=torch.float32, device=dev)
+    qstar = torch.empty((B, Tn), dtype=torch.int32, device=dev)
+    voiced = torch.empty((B, Tn), dtype=torch.uint8, device=dev)
+    _call("syg_cepstrum_peaks_f32", _ptr(ceps), B, Q, Tn, int(qmin), int(qmax), float(sr), float(threshold), _ptr(f0), _ptr(strength),
+          _ptr(qstar), _ptr(voiced))
+    return f0, strength, qstar, voiced.bool()
+
+
+def pitch_cepstrum(y: torch.Tensor, sr: float, fmin: float, fmax: float, frame_length: int = 2048, hop: Optional[int] = None,
+                   center: bool = True, window="hann", threshold: float = CP.THRESHOLD, amin: float = CP.AMIN):
+    """Cepstral pitch of clips y [B, L] -> (f0 [B, T] float32 with NaN unvoiced, voiced [B, T] bool, strength [B, T]
+    float32): the peak of the real cepstrum of every frame between the quefrencies ceil(sr / fmax) and
+    min(floor(sr / fmin), frame_length // 2 - 1).  Any frame length (2048: the fused kernel)."""
+    qmin, qmax = CP.quefrency_range(sr, fmin, fmax, int(frame_length))
+    hop = int(hop) if hop is not None else int(frame_length) // 4
+    ceps = cepstrogram(y, int(frame_length), hop, center, window, None, qmax + 1, amin)
+    f0, strength, _, voiced = cepstrum_peaks(ceps, qmin, qmax, sr, threshold)
+    return f0.float(), voiced, strength

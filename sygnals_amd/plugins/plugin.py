@@ -82,7 +82,8 @@ class SygnalsAmdPlugin(_Base):
         from ..core import transforms as TR
         for fn in (D.compute_fft, D.compute_ifft, D.compute_stft, D.compute_cqt, D.compute_psd_welch, D.apply_window,
                    D.apply_convolution, D.compute_correlation, D.compute_autocorrelation, D.compute_psd_periodogram,
-                   D.amplitude_envelope, D.resample, TR.hilbert_transform, TR.continuous_wavelet_transform,
+                   D.amplitude_envelope, D.resample, D.real_cepstrum, D.complex_cepstrum,
+                   D.inverse_complex_cepstrum, TR.hilbert_transform, TR.continuous_wavelet_transform,
                    TR.laplace_transform_numerical,
                    TR.discrete_wavelet_transform, TR.inverse_discrete_wavelet_transform):
             registry.add_transform(fn.__name__, fn)
