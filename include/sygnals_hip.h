@@ -54,6 +54,10 @@ const char* syg_last_error(void);
  *                         one launch per level with the approximations through the workspace
  *   SYG_OPT_FX_DELAY_FORM -1 (default: chunked chains where the plain form would leave the device mostly idle) | 0 (one
  *                         lane per residue, always) | 1 (chunked, always): form of syg_fx_delay_f32
+ *   SYG_OPT_STFT_FREERUN  -1 (default: the library decides) | 0 (off) | 1 (on where syg_stft2048_mfcc_tri_freerun() holds):
+ *                         free-running form of syg_stft2048_mfcc_tri_f32 -- no stage buffer, every wave loads its next frame
+ *                         under its projection, one workgroup barrier per clip.  An explicit SYG_OPT_STFT_LOAD >= 0 turns
+ *                         the -1 default off
  * syg_set_option returns SYG_OK or SYG_E_INVALID (unknown key / value out of range); syg_get_option the current value. */
 #define SYG_OPT_RESERVED_CUS 0
 #define SYG_OPT_STFT_LOAD 1
@@ -61,7 +65,8 @@ const char* syg_last_error(void);
 #define SYG_OPT_CQT_STAGED 3
 #define SYG_OPT_DWT_FORM 4
 #define SYG_OPT_FX_DELAY_FORM 5
-#define SYG_OPT_COUNT 6
+#define SYG_OPT_STFT_FREERUN 6
+#define SYG_OPT_COUNT 7
 int syg_set_option(int key, int value);
 int syg_get_option(int key);
 
@@ -152,6 +157,9 @@ int syg_stft2048_mfcc_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int
  * Needs TWO mel matrices in LDS (the dB + DCT of a clip runs beside the next clip's first tile):
  * syg_stft2048_mfcc_tri_fits() says whether a shape fits. */
 int syg_stft2048_mfcc_tri_fits(int n_mels, int64_t T, int n_mfcc);
+/* 1: the free-running form of syg_stft2048_mfcc_tri_f32 (SYG_OPT_STFT_FREERUN) can load these clips: hop, L and ldy even,
+ * y 8-byte aligned, L < 2^28.  Host-side arithmetic only (y is not dereferenced); the launch uses it itself. */
+int syg_stft2048_mfcc_tri_freerun(int hop, int64_t L, int64_t ldy, const float* y);
 int syg_stft2048_mfcc_tri_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center,
                               int64_t T, const float* window, const float* twiddle, const float* segtab,
                               int n_segtab, int n_mels, const float* dct, int n_mfcc, const float* lifter,

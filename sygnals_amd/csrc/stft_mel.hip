@@ -35,7 +35,9 @@
 //                              to 256 pieces) -- every frame's mel column straight to HBM, tiles shared out evenly over the
 //                              workgroups, no clip epilogue;   9 TileSeg4Rows: + the row functions
 //   10   TileSeg2      8 | 16  ... n_segtab = 1024: MODE 8 with the TWO-pass table of MODE 6;  11 TileSeg2Rows: + row functions
-// Every (waves, mode) is built for the three frame load paths (LOAD 0 / 1 / 2, see fetch_frame()).
+// Every (waves, mode) is built for the three frame load paths (LOAD 0 / 1 / 2, see fetch_frame()); MODE 6 also has the
+// free-running form LOAD 3: no stage buffer, every wave prefetches its next frame from global memory under its own
+// projection and the workgroup meets once per clip (syg_stft2048_mfcc_tri_freerun() says where it is used).
 // Nothing but the input samples and the outputs touches HBM.
 //
 // Reference behaviour reproduced: librosa.stft (center zero padding, periodic window, rfft) -> np.abs ->
@@ -51,6 +53,11 @@
 // -DSYG_DEV=1: per-phase cycle stamps (tools/timeline.py; a development build -- syg_build_variant() != 0 -- whose
 // statistics output carries the counters)
 #include "stft_dev.h"
+
+// (buffer_load_dwordx2 by the compiler's own intrinsic, so that it counts the loads in its waits; the 8-byte builtin of
+// this toolchain, __builtin_amdgcn_raw_buffer_load_b64, compiles to a 4-byte load)
+typedef float syg_v2f __attribute__((ext_vector_type(2)));
+__device__ syg_v2f syg_raw_buffer_load_v2f(__amdgpu_buffer_rsrc_t rs, int voffset, int soffset, int aux) __asm("llvm.amdgcn.raw.ptr.buffer.load.v2f32");
 
 namespace syg {
 namespace {
@@ -338,10 +345,27 @@ __device__ __forceinline__ void wave_rfft2048(float2 (&v)[16], const LaneConst& 
 // the analysis window (LDS copy) is applied by apply_window() when the frame is consumed.
 //   LOAD 0 / 1: straight from global memory (scalar / 8-byte loads)
 //   LOAD 2    : from the tile's staged sample run in LDS (filled by LDS-DMA, stage_tile())
+//   LOAD 3    : 8-byte buffer loads through the clip's descriptor, whose range check returns the zero padding (as in
+//               stage_tile()): one path for every frame.  hop, L and the clip's first sample are even, so a pair of samples
+//               is inside or outside as a whole.  Each load's whole byte offset is formed in its address register, where a
+//               negative one is a huge unsigned one (an immediate offset added by the hardware could bring it back in range
+//               or not, depending on the width of that sum: not relied on).
 template <int LOAD>
 __device__ __forceinline__ void fetch_frame(float2 (&v)[16], const float* __restrict__ yb, int64_t L, int64_t s0,
                                             const float* __restrict__ stage_frame, int lane) {
   const int col = p1col(lane);
+  if (LOAD == 3) {
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(yb), 0, (int)(L * 4), 0x00020000);
+    const int base = ((int)s0 + 2 * col) * 4;
+#pragma unroll
+    for (int a = 0; a < 16; ++a) {
+      int off = base + 512 * a;
+      asm volatile("" : "+v"(off));
+      const syg_v2f r = syg_raw_buffer_load_v2f(rs, off, 0, 0);
+      v[a] = make_float2(r.x, r.y);
+    }
+    return;
+  }
   if (LOAD == 2) {
     const float2* sf = reinterpret_cast<const float2*>(stage_frame);
 #pragma unroll
@@ -529,6 +553,7 @@ struct ModeTraits {
                       // -- exactly, a power of two -- where mel values leave the kernel (at the store; the dB conversion of
                       // a clip works on 4 x mel with 4 x amin and 4 x ref).  The row functions need the true powers.
   bool relc;          // lane constants re-made per frame (see the tile loop)
+  bool freerun;       // the 16-wave launch has the free-running form (LOAD 3)
   constexpr bool seg() const { return proj == Proj::Segments; }
   constexpr bool seg_tile() const { return seg() && !clip; }      // the tile form: mel columns to HBM, tiles shared out evenly
   constexpr bool x2() const { return X2_MEL && power4; }
@@ -536,17 +561,17 @@ struct ModeTraits {
   constexpr int clip_matrices() const { return seg() ? 2 : 1; }
 };
 constexpr ModeTraits mode_traits(Mode m) {
-  switch (m) {                //     proj          npass  clip   rowfn  complex power4 relc
-    case Mode::Mel:          return {Proj::Matrix,   2, false, false, false, true,  false};
-    case Mode::MelRows:      return {Proj::Matrix,   2, false, true,  false, false, false};
-    case Mode::Complex:      return {Proj::None,     2, false, false, true,  false, false};
-    case Mode::ClipMatrix:   return {Proj::Matrix,   2, true,  false, false, true,  false};
-    case Mode::ClipSeg:      return {Proj::Segments, 2, true,  false, false, true,  false};
-    case Mode::ClipSegRows:  return {Proj::Segments, 2, true,  true,  false, false, true};
-    case Mode::TileSeg4:     return {Proj::Segments, 4, false, false, false, true,  false};
-    case Mode::TileSeg4Rows: return {Proj::Segments, 4, false, true,  false, false, false};
-    case Mode::TileSeg2:     return {Proj::Segments, 2, false, false, false, true,  false};
-    case Mode::TileSeg2Rows: return {Proj::Segments, 2, false, true,  false, false, false};
+  switch (m) {                //     proj          npass  clip   rowfn  complex power4 relc   freerun
+    case Mode::Mel:          return {Proj::Matrix,   2, false, false, false, true,  false, false};
+    case Mode::MelRows:      return {Proj::Matrix,   2, false, true,  false, false, false, false};
+    case Mode::Complex:      return {Proj::None,     2, false, false, true,  false, false, false};
+    case Mode::ClipMatrix:   return {Proj::Matrix,   2, true,  false, false, true,  false, false};
+    case Mode::ClipSeg:      return {Proj::Segments, 2, true,  false, false, true,  false,  true};
+    case Mode::ClipSegRows:  return {Proj::Segments, 2, true,  true,  false, false, true, false};
+    case Mode::TileSeg4:     return {Proj::Segments, 4, false, false, false, true,  false, false};
+    case Mode::TileSeg4Rows: return {Proj::Segments, 4, false, true,  false, false, false, false};
+    case Mode::TileSeg2:     return {Proj::Segments, 2, false, false, false, true,  false, false};
+    case Mode::TileSeg2Rows: return {Proj::Segments, 2, false, true,  false, false, false, false};
   }
   return {};
 }
@@ -570,6 +595,10 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
   constexpr int NTHREADS = WAVES * 64;
   constexpr int TILE_T = WAVES;                                    // one frame per wave per tile
   constexpr bool COMPLEX_OUT = M.complex_out, ROWFN = M.rowfn, CLIPM = M.clip, X2 = M.x2();
+  // free-running waves: no stage buffer; a wave holds its next frame in registers across its projection (loaded from
+  // global memory) and the workgroup meets once per clip
+  constexpr bool FREERUN = (LOAD == 3);
+  static_assert(!FREERUN || (M.freerun && WAVES == 16 && TRI && CLIPM && !ROWFN), "LOAD 3: the free-running form of the mode");
 #ifdef SYG_DEV_NO_RELC
   constexpr bool RELC = false;                                       // (timeline builds: round 3's form, for the before / after table)
 #else
@@ -689,6 +718,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
     __syncthreads();                                  // every wave holds its frame: the stage may be refilled
     if (tile_begin + 1 < tile_end) dma(tile_begin + 1);
   }
+  if (FREERUN) fetch(tile_begin);
 
 #if SYG_DEV
   unsigned long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev;
@@ -700,7 +730,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
     const int64_t b = cq;
     const int64_t t0 = t0_of(tile, cq);
     const int64_t t = t0 + w;
-    if (LOAD != 2) fetch(tile);
+    if (LOAD < 2) fetch(tile);
     // MODE 1: the row functions behind barrier B are chains of dependent wave-level steps that hide their latency only
     // behind each other; a wave that is through starts its next transform, whose dense vector work would take the
     // issue slots from the waves still in their row functions (oldest wave first at equal priority) and stretch the
@@ -802,6 +832,15 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
       int tdep = lane;
       TICK(5, tdep);                   // (split + row store)
 #endif
+      // LOAD 3: the wave's power row is stored; the loads of the frame it transforms next (of the next clip, behind a clip's
+      // last tile) are issued here and land under the projection, whose ~190 vector instructions need few registers.  A wave
+      // that runs clip_dct issues them behind it: the entry of an out-of-line function waits for every outstanding load.
+      auto prefetch = [&]() {
+        have = false;
+        if (tile + 1 < tile_end) fetch(tile + 1);
+      };
+      const bool dct_behind = FREERUN && clip_done && !tri_defer && w < tri_ndct;   // clip_dct behind the clip barrier
+      if (FREERUN && mine && !dct_behind) prefetch();
       if (mine) {
         if (tri_proj) project();
       } else if (tri_defer && pend_b >= 0) {
@@ -809,6 +848,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
         clip_dct<WAVES>((int)(uintptr_t)(lds_fptr)cmp, (int)(uintptr_t)(lds_fptr)(tri_red + (cur ^ 1) * WAVES),
                         (int)(uintptr_t)(lds_fptr)tri_dct, mf, n_mels, (int)T, (int)pend_b, w - (WAVES - tri_idle), lane, tri_idle);
       }
+      if (FREERUN && !mine && !dct_behind) prefetch();
       // MODE 7: statistics / contrast of this wave's own row.  Out-of-line: the entry of such a function waits for every
       // outstanding memory operation, so the results wait in lanes of three registers and are stored -- and the stage
       // refill is issued -- behind the barriers.  Statistics first (a wide contrast band may park its lists in the row's
@@ -840,8 +880,22 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
       }
       if (CLIPM && clip_done) publish_max();
       TICK(7, tdep);                   // row functions of the early half
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();                                  // X1: the clip's columns of this tile are written too
+      if (FREERUN) {
+        // The clip barrier, the only one of the tile loop: nothing inside a clip is shared -- a wave reads its own power
+        // row, writes its own column of the clip's mel matrix and keeps its own maximum.  What hangs on this barrier:
+        //   - clip c's matrix and its maxima red[cur][] (publish_max above) are complete behind it: clip_dct of clip c runs
+        //     behind it -- at once on the first waves, or (deferred) on the idle waves of clip c + 1's last tile, which have
+        //     passed this barrier in clip c's last tile and run it IN FRONT of clip c + 1's barrier;
+        //   - clip c's matrix and red[cur][] are next written in clip c + 2, that is behind clip c + 1's barrier, which a
+        //     wave running clip_dct of clip c reaches only when it is through with it (both placements above);
+        //   - behind the loop the pending epilogue of the last clip follows that clip's barrier (a chunk is whole clips).
+        // clip_done depends on the tile alone (t0, T): every wave of the workgroup, with or without a frame, walks the
+        // same tiles and so executes this barrier once per clip.
+        if (clip_done) __syncthreads();
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                // X1: the clip's columns of this tile are written too
+      }
       TICK(8, tdep);                   // wait at X1
       if (LOAD == 2) {
         have = false;
@@ -857,6 +911,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
                           (int)(uintptr_t)(lds_fptr)tri_dct, mf, n_mels, (int)T, (int)b, w, lane);
         cur ^= 1;
       }
+      if (dct_behind) prefetch();
       if (ROWFN && mine) {
         if (!row_early) row_compute();
         else { row_sres = prow[lane]; row_pv = make_float2(prow[64 + lane], prow[128 + lane]); }
@@ -1100,6 +1155,15 @@ int load_mode() {
   return (v >= 0 && v <= 2) ? v : 2;
 }
 
+// Default of SYG_OPT_STFT_FREERUN = -1: on -- at C2 every run of it was faster than every run of the staged form, by several times
+// the run-to-run spread
+constexpr bool FREERUN_DEFAULT = true;
+// Where the free-running form can run (syg_stft2048_mfcc_tri_freerun): 8-byte loads of sample pairs that the descriptor's
+// range check takes or leaves as a whole (hop, L, ldy even, y 8-byte aligned), byte offsets inside a clip in 32 bits
+bool freerun_ok(int hop, int64_t L, int64_t ldy, const float* y) {
+  return hop % 2 == 0 && L % 2 == 0 && ldy % 2 == 0 && ((uintptr_t)y) % 8 == 0 && L < ((int64_t)1 << 28);
+}
+
 // LDS accounting: the fixed map of the mode (ModeLds), and behind it what a clip-resident launch adds, for the 16-wave
 // forms that have one: n_mat mel matrices [n_mels][tp] (tp: padded frames per clip), each with the per-wave maxima
 // red[waves] of its clip, then the DCT rows [n_mfcc][n_mels] and the lifter [n_mfcc]
@@ -1160,7 +1224,14 @@ int launch(const LaunchArgs& a) {
   if (load == 2 && !can_stage) load = 1;
   const bool vec2 = (c.hop % 2 == 0) && (c.ldy % 2 == 0) && (((uintptr_t)c.y) % 8 == 0);
   if (load == 1 && !vec2) load = 0;
-  if (M.clip) {
+  // the free-running form where the mode has one and its loads are possible; an explicit load path (the three are
+  // compared by the tests) is kept unless the form is asked for
+  if (M.freerun && WAVES == 16) {
+    const int fr = option(SYG_OPT_STFT_FREERUN);
+    const bool want = fr == 1 || (fr < 0 && FREERUN_DEFAULT && option(SYG_OPT_STFT_LOAD) < 0);
+    if (want && freerun_ok(c.hop, c.L, c.ldy, c.y)) load = 3;
+  }
+  if (M.clip) {       // (no stage buffer unless the tiles are staged)
     lds = lds - (load != 2 ? (size_t)LM::STAGE_FLOATS * sizeof(float) : 0) + (size_t)clip_extra;
     SYG_REQUIRE(lds <= (size_t)LDS_LIMIT, "stft2048_mfcc: the clip's mel matrix (%d x %d) does not fit the LDS left over (%zu B > %zu B); "
                 "use syg_stft2048_mel_f32 + syg_logmel_dct_f32", n_mels, mf.tp, lds, (size_t)LDS_LIMIT);
@@ -1168,6 +1239,8 @@ int launch(const LaunchArgs& a) {
   const int dma_wide = (c.hop % 4 == 0) && (pad % 4 == 0) && (c.ldy % 4 == 0) && (c.L % 4 == 0) && (((uintptr_t)c.y) % 16 == 0);
   auto kern = load == 2 ? stft2048_kernel<WAVES, 2, MODE>
                         : load == 1 ? stft2048_kernel<WAVES, 1, MODE> : stft2048_kernel<WAVES, 0, MODE>;
+  if constexpr (M.freerun && WAVES == 16)
+    if (load == 3) kern = stft2048_kernel<WAVES, 3, MODE>;
   const size_t cap = M.clip ? (size_t)LDS_LIMIT : (size_t)LM::TOTAL * sizeof(float);
   if (const int rc = reserve_dynamic_lds("stft2048", (const void*)kern, cap)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(WAVES * 64), lds, a.stream, c.y, c.L, c.ldy, c.hop, pad, c.T,
@@ -1278,6 +1351,10 @@ extern "C" int syg_stft2048_mfcc_f32(const float* y, int64_t B, int64_t L, int64
 extern "C" int syg_stft2048_mfcc_tri_fits(int n_mels, int64_t T, int n_mfcc) {
   if (n_mels < 1 || n_mels > 127 || T < 1 || n_mfcc < 1 || n_mfcc > n_mels) return 0;
   return clip_lds_fit<ModeLds<16, Mode::ClipSeg>>(clip_lds_bytes<Mode::ClipSeg>(n_mels, T, n_mfcc)) == 2;
+}
+
+extern "C" int syg_stft2048_mfcc_tri_freerun(int hop, int64_t L, int64_t ldy, const float* y) {
+  return freerun_ok(hop, L, ldy, y) ? 1 : 0;
 }
 
 extern "C" int syg_stft2048_mfcc_tri_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center,
