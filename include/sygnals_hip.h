@@ -1035,6 +1035,51 @@ int syg_cepstrum_exp_c64(const float* Xh, int64_t B, int64_t n, const int32_t* n
 int syg_cepstrum_peaks_f32(const float* ceps, int64_t B, int64_t Q, int64_t T, int qmin, int qmax, double sr, double threshold,
                            double* f0, float* strength, int32_t* qstar, uint8_t* voiced, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Linear prediction (the float64 restatement that is the contract: tests/lpc_ref.py).  order p, 1 <= p <= min(64, N - 2).
+ *     SYG_LPC_BURG      librosa.lpc's recurrence on f = x[1:], b = x[:-1]: k_i = -2 sum f b / (sum (f^2 + b^2) + DBL_MIN),
+ *                       a <- a + k_i reversed(a), err = sum (f^2 + b^2) / (2 (N - 1 - p)) over the last f and b
+ *     SYG_LPC_AUTOCORR  r[l] = sum_n xw[n] xw[n + l] (biased, not normalised), Levinson-Durbin in float64,
+ *                       err = (r[0] + sum_j a[j] r[j]) / N;  r[0] = 0 gives a = [1, 0, ...], err = 0
+ * Samples are float32, promoted to float64 and multiplied by the float32 window table where one is given (NULL: none);
+ * everything after that is float64.  Gates: |a - a_ref| <= 1e-5 max|a_ref|, |k - k_ref| <= 1e-5, |err - err_ref| <= 1e-5 err_ref.
+ * One fixed summation order, no atomics: the same call gives the same bits and a batch equals its rows.
+ *
+ * syg_lpc_frames_f32: y [B, L] float32 (row stride ldy), frames of frame_length N in [p + 2, 2048] (longer:
+ *   SYG_E_UNSUPPORTED), any hop >= 1; centred frames start at t hop - N / 2, samples outside the clip are 0; T by
+ *   frames_expected for N a power of two >= 8 and by the padded rule otherwise (ops.cepstrogram_frames).  window [N] or NULL.
+ *   a [B, p + 1, T] (a[0] = 1), k [B, p, T] or NULL (reflection coefficients), err [B, T] or NULL; the frame index is fastest.
+ *   One wave per frame, sample n in lane n % 64 and register n / 64 (ceil(N / 64) registers); a workgroup of SYG_LPC_WAVES waves takes
+ *   SYG_LPC_TILE_FRAMES consecutive frames and reads their span once into LDS where it is at most SYG_LPC_SPAN_MAX floats.
+ * syg_lpc_rows_f32: whole rows y [B, L] of any length L in [p + 2, 2^26] -> a [B, p + 1], k [B, p] or NULL, err [B] or NULL.
+ *   window [L] or NULL.  Burg: p + 1 launches over a float64 workspace f, b [B, L] (each applies k_{i-1} to chunks of
+ *   SYG_LPC_STAGE_CHUNK samples and leaves the partial sums of k_i, which the next launch adds in a fixed order), then a
+ *   one-wave step-up.  Autocorr: partial lag sums over chunks of SYG_LPC_ACORR_CHUNK samples, then a one-wave Levinson.
+ *   work: syg_lpc_rows_work_bytes(B, L, order, method) bytes, 8-byte aligned (-1 on bad arguments).
+ * syg_lpc_envelope_f32: a [B, p + 1, T], err [B, T] -> out [B, n_fft / 2 + 1, T] = P[k] = err / |A(e^{-2 pi i k / n_fft})|^2,
+ *   A(z) = sum_j a[j] z^-j by Horner's rule in float64; phasor [n_fft / 2 + 1][2] float64 = (cos, -sin)(2 pi k / n_fft);
+ *   db = 1: 10 log10(max(P, amin)).  n_fft even.
+ * syg_lpc_constants(key): the figures above (SYG_LPC_*), -1 for an unknown key.
+ * ------------------------------------------------------------------------------- */
+enum { SYG_LPC_BURG = 0, SYG_LPC_AUTOCORR = 1 };
+enum {
+  SYG_LPC_MAX_FRAME = 0,     /* longest frame of the frame kernel */
+  SYG_LPC_MAX_ORDER = 1,     /* highest order */
+  SYG_LPC_WAVES = 2,         /* waves of a workgroup of the frame kernel */
+  SYG_LPC_TILE_FRAMES = 3,   /* consecutive frames a workgroup takes and stores together */
+  SYG_LPC_SPAN_MAX = 4,      /* floats of a tile's span that are read once into LDS */
+  SYG_LPC_STAGE_CHUNK = 5,   /* samples a workgroup of a Burg stage over whole rows owns */
+  SYG_LPC_ACORR_CHUNK = 6    /* samples a workgroup of the row autocorrelation owns */
+};
+int64_t syg_lpc_constants(int key);
+int syg_lpc_frames_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int frame_length, int hop, int center, int64_t T,
+                       const float* window, int order, int method, float* a, float* k, float* err, void* stream);
+int64_t syg_lpc_rows_work_bytes(int64_t B, int64_t L, int order, int method);
+int syg_lpc_rows_f32(const float* y, int64_t B, int64_t L, int64_t ldy, const float* window, int order, int method, void* work,
+                     int64_t work_bytes, float* a, float* k, float* err, void* stream);
+int syg_lpc_envelope_f32(const float* a, const float* err, int64_t B, int order, int64_t T, int n_fft, const double* phasor, int db,
+                         double amin, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

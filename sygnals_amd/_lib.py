@@ -159,6 +159,11 @@ SIGNATURES = {
     "syg_cepstrum_unwrap_c64": (_i, [_p, _l, _l, _d, _p, _l, _p, _p, _p]),
     "syg_cepstrum_exp_c64": (_i, [_p, _l, _l, _p, _p, _p]),
     "syg_cepstrum_peaks_f32": (_i, [_p, _l, _l, _l, _i, _i, _d, _d, _p, _p, _p, _p, _p]),
+    "syg_lpc_constants": (_l, [_i]),
+    "syg_lpc_frames_f32": (_i, [_p, _l, _l, _l, _i, _i, _i, _l, _p, _i, _i, _p, _p, _p, _p]),
+    "syg_lpc_rows_work_bytes": (_l, [_l, _l, _i, _i]),
+    "syg_lpc_rows_f32": (_i, [_p, _l, _l, _l, _p, _i, _i, _p, _l, _p, _p, _p, _p]),
+    "syg_lpc_envelope_f32": (_i, [_p, _p, _l, _i, _l, _i, _p, _i, _d, _p, _p]),
 }
 
 _lib = None

@@ -447,6 +447,63 @@ def dsp_cepstrum(input_file, output, kind, n, frames, n_fft, hop, n_ceps):
     click.echo(f"{what} saved to '{Path(output).name}'.")
 
 
+@dsp_cmd.command("lpc")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--order", type=int, required=True, help="Prediction order, 1 ... min(64, N - 2) for N samples (a frame's with --frames).")
+@click.option("--method", type=click.Choice(["burg", "autocorr"]), default="burg", show_default=True)
+@click.option("--frames", is_flag=True, help="The coefficients of every frame instead of the whole signal.")
+@click.option("--frame-length", "frame_length", type=int, default=2048, show_default=True, help="Frame length (with --frames), at most 2048.")
+@click.option("--hop", type=int, default=512, show_default=True, help="Hop between frames (with --frames).")
+@click.option("--envelope", is_flag=True, help="Also save the all-pole spectral envelope in dB.")
+@click.option("--n-fft", "n_fft", type=int, default=2048, show_default=True, help="Points of the envelope's frequency grid (with --envelope).")
+def dsp_lpc(input_file, output, order, method, frames, frame_length, hop, envelope, n_fft):
+    """Compute linear prediction coefficients (LPC) of a signal or of its frames, and their spectral envelope."""
+    from .. import _lpc, ops
+    try:
+        if frames:
+            N, hop = _lpc.check_frame(frame_length, hop)
+            _lpc.check_order(order, N)                           # refused before the file is read
+        if envelope:
+            _lpc.check_n_fft(n_fft)
+        x, sr = _load_signal(input_file, None)
+        if not frames:
+            _lpc.check_row(x.size)
+            _lpc.check_order(order, x.size)
+        y = ops.to_device_f32(np.asarray(x)[None, :])
+        if frames:
+            a, k, err = ops.lpc_frames(y, order, N, hop, True, method, None, True, True)
+        else:
+            a, k, err = ops.lpc_rows(y, order, method, None, None, True, True)
+            a, k, err = a[:, :, None], k[:, :, None], err[:, None]
+        env = ops.lpc_envelope(a, err, n_fft, db=True)[0].cpu().numpy().astype(np.float64) if envelope else None
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    a, k, err = (t[0].cpu().numpy().astype(np.float64) for t in (a, k, err))
+    freqs = np.arange(n_fft // 2 + 1) * ((float(sr) if sr else 1.0) / n_fft)
+    if not frames:
+        a, k, err = a[:, 0], k[:, 0], err[0]
+        env = env[:, 0] if envelope else None
+    if Path(output).suffix.lower() == ".npz":
+        data = {"a": a, "k": k, "err": np.asarray(err), "order": np.array(order), "method": np.array(method)}
+        if frames:
+            data.update(frame_length=np.array(N), hop_length=np.array(hop))
+        if envelope:
+            data.update(envelope=env, frequencies=freqs)
+        sio.save_data(data, output)
+    else:
+        T = a.shape[1] if frames else 1
+        A2, K2 = a.reshape(order + 1, T), k.reshape(order, T)
+        table = {"frame": np.tile(np.arange(T), order + 1), "index": np.repeat(np.arange(order + 1), T), "a": A2.ravel(),
+                 "k": np.concatenate([np.full(T, np.nan), K2.ravel()]), "err": np.tile(np.reshape(err, T), order + 1)}
+        try:
+            sio.save_data(pd.DataFrame(table), output)
+        except ValueError as e:
+            raise click.UsageError(str(e))
+    what = f"LPC (order {order}, {method}, {a.shape[1]} frames)" if frames else f"LPC (order {order}, {method})"
+    click.echo(f"{what} saved to '{Path(output).name}'.")
+
+
 def parse_window_spec(text: str):
     """'kaiser:5.0' -> ('kaiser', 5.0); 'hann' -> 'hann' (firwin's window specification)."""
     name, *params = [t.strip() for t in text.split(":")]

@@ -1,4 +1,5 @@
-"""Device-backed mirror of sygnals/core/features/cepstral.py (mfcc :20-120)."""
+"""Device-backed mirror of sygnals/core/features/cepstral.py (mfcc :20-120), and linear prediction (LPC), which that file's
+feature table names as the next cepstral-family feature."""
 from __future__ import annotations
 
 import logging
@@ -6,7 +7,7 @@ from typing import Any, Dict, Optional
 
 import numpy as np
 
-from ... import ops
+from ... import _lpc, ops
 
 logger = logging.getLogger(__name__)
 
@@ -46,4 +47,56 @@ def mfcc(y=None, sr: Optional[int] = None, S=None, n_mfcc: int = 13, dct_type: i
     return mf[0].cpu().numpy().astype(np.float64)
 
 
-CEPSTRAL_FEATURES: Dict[str, Any] = {"mfcc": mfcc}
+def _lpc_clips(y):
+    """[B, L] on the device from a device tensor or a NumPy array; argument errors come first and need no device."""
+    import torch
+    if isinstance(y, torch.Tensor):
+        if y.dim() != 2 or y.dtype != torch.float32:
+            raise ValueError("y must be a float32 tensor [B, L] or a NumPy array [B, L]")
+        return y
+    y = np.asarray(y)
+    if y.ndim != 2:
+        raise ValueError("y must be [B, L]")
+    if y.size == 0:
+        raise ValueError("y: empty input")
+    return y
+
+
+def lpc(y, order: int, method: str = "burg", window=None) -> np.ndarray:
+    """Linear prediction coefficients a[0 .. order] (a[0] = 1) of a 1-D signal, float64: librosa.lpc(y, order=order) for
+    method='burg' (Burg's recurrence, float64 on the device; no window unless one is given); method='autocorr' is the
+    autocorrelation method (hann unless another window is given) with a Levinson-Durbin recursion.
+    1 <= order <= min(64, len(y) - 2)."""
+    _lpc.check_method(method)
+    y = np.asarray(y)
+    if y.ndim != 1:
+        raise ValueError("Input signal 'y' must be a 1D array.")
+    if y.size == 0:
+        raise ValueError("y: empty input")
+    _lpc.check_row(y.shape[0])
+    _lpc.check_order(order, y.shape[0])
+    a = ops.lpc_rows(ops.to_device_f32(y[None, :]), order, method, window)
+    return a[0].cpu().numpy().astype(np.float64)
+
+
+def lpc_batch(y, order: int, frame_length: int = 2048, hop_length: int = 512, center: bool = True, method: str = "burg",
+              window=None, return_reflection: bool = False, return_error: bool = False):
+    """LPC of every frame of the clips y [B, L] (a device tensor or a NumPy array) -> a [B, order + 1, T] float32 on the
+    device, with the reflection coefficients [B, order, T] and the prediction error [B, T] when asked for
+    (ops.lpc_frames)."""
+    _lpc.check_method(method)
+    N, hop = _lpc.check_frame(frame_length, hop_length)
+    _lpc.check_order(order, N)
+    y = _lpc_clips(y)
+    if not hasattr(y, "is_cuda"):
+        y = ops.to_device_f32(y)
+    return ops.lpc_frames(y, order, N, hop, center, method, window, return_reflection, return_error)
+
+
+def lpc_envelope_batch(a, err, n_fft: int = 2048, db: bool = False, amin: float = _lpc.AMIN):
+    """The all-pole envelope err / |A|^2 of coefficients a [B, order + 1, T] and errors err [B, T] on the device ->
+    [B, n_fft / 2 + 1, T] float32, in dB when db=True (ops.lpc_envelope)."""
+    return ops.lpc_envelope(a, err, n_fft, db, amin)
+
+
+CEPSTRAL_FEATURES: Dict[str, Any] = {"mfcc": mfcc, "lpc": lpc}

@@ -17,6 +17,7 @@ import torch
 from . import _cepstrum as CP
 from . import _cwt as CW
 from . import _laplace as LP
+from . import _lpc
 from . import _resample as RS
 from . import _tables as T
 from ._fftplan import (MAX_LDS_FFT, MAX_MIXED_FFT, MAX_ROWS, conv_fft_len, fft_plan, is_pow2,      # noqa: F401 (re-exported)
@@ -2825,3 +2826,137 @@ def pitch_cepstrum(y: torch.Tensor, sr: float, fmin: float, fmax: float, frame_l
     ceps = cepstrogram(y, int(frame_length), hop, center, window, None, qmax + 1, amin)
     f0, strength, _, voiced = cepstrum_peaks(ceps, qmin, qmax, sr, threshold)
     return f0.float(), voiced, strength
+
+
+# ------------------------------------------------------------------ linear prediction
+_LPC_KEYS = {"max_frame": 0, "max_order": 1, "waves": 2, "tile_frames": 3, "span_max": 4, "stage_chunk": 5,
+             "acorr_chunk": 6}                 # SYG_LPC_* of include/sygnals_hip.h
+
+
+def lpc_constants() -> dict:
+    """The figures csrc/lpc.hip rests on (the library owns them): the longest frame of the frame kernel, the highest
+    order, the waves of its workgroup, the frames a workgroup takes together, the floats of a tile's span that are read
+    once into LDS, and the samples a workgroup of the two whole-row forms owns."""
+    h = lib()
+    return {k: int(h.syg_lpc_constants(v)) for k, v in _LPC_KEYS.items()}
+
+
+def lpc_window_table(window, N: int):
+    """The float32 window table of N points, float64 on the host (None: no window; 'ones': all ones; else stft_any's)."""
+    if window is None:
+        return None
+    if isinstance(window, str) and window == "ones":
+        return np.ones(N, dtype=np.float32)
+    return T.analysis_window(window, N, N).astype(np.float32)
+
+
+def _lpc_window_dev(window, N: int):
+    if window is None:
+        return None
+    if isinstance(window, str) and window == "ones":
+        return _cached(("lpc_ones", N), lambda: _dev(np.ones(N, dtype=np.float32)))
+    return window_dev(window, N, N)
+
+
+def _lpc_out(t, shape, what: str, device):
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 CUDA tensor {list(shape)}")
+    return t
+
+
+def _lpc_result(a, k, err, return_reflection, return_error):
+    if not (return_reflection or return_error):
+        return a
+    return (a,) + ((k,) if return_reflection else ()) + ((err,) if return_error else ())
+
+
+def lpc_frames(y: torch.Tensor, order: int, frame_length: int = 2048, hop: int = 512, center: bool = True, method: str = "burg",
+               window=None, return_reflection: bool = False, return_error: bool = False, out: Optional[torch.Tensor] = None,
+               out_k: Optional[torch.Tensor] = None, out_err: Optional[torch.Tensor] = None):
+    """Linear prediction of every frame of the clips y [B, L] (float32, on the device; rows may be strided) ->
+    a [B, order + 1, T] float32 with a[:, 0] = 1 (and the reflection coefficients k [B, order, T] and the prediction error
+    err [B, T] when asked for), the frame index fastest.  method: 'burg' (librosa.lpc's recurrence; no window unless one is
+    given) | 'autocorr' (biased autocorrelation and Levinson-Durbin; hann unless another is given; 'ones' for none).
+    Framing, zero centre padding and frame count are cepstrogram_frames'.  frame_length in [order + 2, 2048]; float64 past
+    the load (tests/lpc_ref.py is the contract)."""
+    m = _lpc.check_method(method)
+    N, hop = _lpc.check_frame(frame_length, hop)
+    p = _lpc.check_order(order, N)
+    _ceps_tensor(y, "y")
+    B, L = y.shape
+    Tn = cepstrogram_frames(L, N, hop, bool(center))
+    _lpc.check_size("lpc_frames", (B, p + 1, Tn), ("clips", "coefficients", "frames"))
+    y = _ceps_on_device(y, "y")
+    win = _lpc_window_dev(_lpc.default_window(method, window), N)
+    a = _lpc_out(out, (B, p + 1, Tn), "out", y.device)
+    k = _lpc_out(out_k, (B, p, Tn), "out_k", y.device) if (return_reflection or out_k is not None) else None
+    err = _lpc_out(out_err, (B, Tn), "out_err", y.device) if (return_error or out_err is not None) else None
+    _call("syg_lpc_frames_f32", _ptr(y), B, L, _ld(y), N, hop, int(bool(center)), Tn, _ptr(win), p, m, _ptr(a), _ptr(k), _ptr(err))
+    return _lpc_result(a, k, err, return_reflection, return_error)
+
+
+def lpc_rows(y: torch.Tensor, order: int, method: str = "burg", window=None, form: Optional[str] = None,
+             return_reflection: bool = False, return_error: bool = False, out: Optional[torch.Tensor] = None,
+             out_k: Optional[torch.Tensor] = None, out_err: Optional[torch.Tensor] = None):
+    """Linear prediction of every whole row of y [B, L] -> a [B, order + 1] float32 (and k [B, order], err [B]): librosa.lpc(y,
+    order) on every row for method='burg'.  form: None (the rule: rows of at most 2048 samples are one frame of the frame
+    kernel, longer rows take the stage form: one launch per stage over a float64 workspace) | 'frame' (L <= 2048 only) |
+    'stage'."""
+    if form not in _lpc.FORMS:
+        raise ValueError("form must be None, 'frame' or 'stage'")
+    m = _lpc.check_method(method)
+    _ceps_tensor(y, "y")
+    B, L = y.shape
+    _lpc.check_row(L)
+    p = _lpc.check_order(order, L)
+    if form == "frame" and L > _lpc.MAX_FRAME:
+        raise ValueError(f"lpc_rows: the frame form serves rows of at most {_lpc.MAX_FRAME} samples (got {L}); longer rows take form='stage'")
+    _lpc.check_size("lpc_rows", (B, L), ("rows", "samples"))
+    y = _ceps_on_device(y, "y")
+    win = _lpc_window_dev(_lpc.default_window(method, window), L)
+    a = _lpc_out(out, (B, p + 1), "out", y.device)
+    k = _lpc_out(out_k, (B, p), "out_k", y.device) if (return_reflection or out_k is not None) else None
+    err = _lpc_out(out_err, (B,), "out_err", y.device) if (return_error or out_err is not None) else None
+    if form == "frame" or (form is None and L <= _lpc.MAX_FRAME):
+        _call("syg_lpc_frames_f32", _ptr(y), B, L, _ld(y), L, L, 0, 1, _ptr(win), p, m, _ptr(a), _ptr(k), _ptr(err))
+    else:
+        wb = lib().syg_lpc_rows_work_bytes(B, L, p, m)
+        if wb < 0:
+            check(-1, "syg_lpc_rows_work_bytes")
+        work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device)
+        _call("syg_lpc_rows_f32", _ptr(y), B, L, _ld(y), _ptr(win), p, m, _ptr(work), wb, _ptr(a), _ptr(k), _ptr(err))
+    return _lpc_result(a, k, err, return_reflection, return_error)
+
+
+def lpc_phasor_table(n_fft: int) -> np.ndarray:
+    """e^{-2 pi i k / n_fft}, k = 0 .. n_fft / 2, float64 [n_fft / 2 + 1, 2]."""
+    ang = -2.0 * np.pi * np.arange(n_fft // 2 + 1, dtype=np.float64) / n_fft
+    return np.stack([np.cos(ang), np.sin(ang)], axis=1)
+
+
+def lpc_envelope(a: torch.Tensor, err: torch.Tensor, n_fft: int = 2048, db: bool = False, amin: float = _lpc.AMIN,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The all-pole spectral envelope of a [B, order + 1, T] and err [B, T] (float32, on the device) ->
+    [B, n_fft / 2 + 1, T] float32: P[k] = err / |A(e^{-2 pi i k / n_fft})|^2, A(z) = sum_j a[j] z^-j, Horner's rule in float64;
+    db=True: 10 log10(max(P, amin))."""
+    n_fft = _lpc.check_n_fft(n_fft)
+    amin = _lpc.check_amin(amin)
+    _ceps_tensor(a, "a", 3)
+    _ceps_tensor(err, "err", 2)
+    B, p1, Tn = a.shape
+    if not 2 <= p1 <= _lpc.MAX_ORDER + 1:
+        raise ValueError(f"a must hold order + 1 coefficients a frame, order in 1 ... {_lpc.MAX_ORDER} (got {p1})")
+    if tuple(err.shape) != (B, Tn):
+        raise ValueError(f"err must be [B, T] = [{B}, {Tn}], got {list(err.shape)}")
+    K = n_fft // 2 + 1
+    _lpc.check_size("lpc_envelope", (B, K, Tn), ("clips", "bins", "frames"))
+    require_gpu()
+    if not (a.is_cuda and err.is_cuda):
+        raise ValueError("a and err must be float32 CUDA tensors")
+    a, err = a.contiguous(), err.contiguous()
+    out = _lpc_out(out, (B, K, Tn), "out", a.device)
+    ph = _cached(("lpc_phasor", n_fft), lambda: _dev(lpc_phasor_table(n_fft)))
+    _call("syg_lpc_envelope_f32", _ptr(a), _ptr(err), B, p1 - 1, Tn, n_fft, _ptr(ph), int(bool(db)), amin, _ptr(out))
+    return out

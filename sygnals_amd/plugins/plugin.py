@@ -80,10 +80,11 @@ class SygnalsAmdPlugin(_Base):
     def register_transforms(self, registry):
         from ..core import dsp as D
         from ..core import transforms as TR
+        from ..core.features import cepstral as CF
         for fn in (D.compute_fft, D.compute_ifft, D.compute_stft, D.compute_cqt, D.compute_psd_welch, D.apply_window,
                    D.apply_convolution, D.compute_correlation, D.compute_autocorrelation, D.compute_psd_periodogram,
                    D.amplitude_envelope, D.resample, D.real_cepstrum, D.complex_cepstrum,
-                   D.inverse_complex_cepstrum, TR.hilbert_transform, TR.continuous_wavelet_transform,
+                   D.inverse_complex_cepstrum, CF.lpc, TR.hilbert_transform, TR.continuous_wavelet_transform,
                    TR.laplace_transform_numerical,
                    TR.discrete_wavelet_transform, TR.inverse_discrete_wavelet_transform):
             registry.add_transform(fn.__name__, fn)
