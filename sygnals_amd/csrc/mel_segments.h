@@ -1,5 +1,6 @@
-// Mel projection of one LDS power row by one wave, by SEGMENT SUMS (shared by stft_mel.hip MODE 6 / 7 and
-// stft_mel_w4096.hip).  Included inside namespace syg { namespace { ... } } after common.h.
+// Mel projection of one LDS power row by one wave, by SEGMENT SUMS (shared by stft_mel.hip MODE 6 ... 11,
+// stft_mel_w1024_seg.hip, stft_mel_wseg_small.hip and stft_mel_w4096.hip).  Included inside namespace syg { namespace {
+// ... } } after common.h.
 #pragma once
 // The projection (sygnals_amd/_tables.py: pack_mel_segments builds the table):
 // A triangular filterbank is piecewise affine in the bin index, so a run of bins inside one segment (between two band
@@ -62,6 +63,26 @@ __device__ __forceinline__ void tri_piece_sums(const float (&pw)[9], int lead, i
 #undef SYG_TRI_STEP
 #undef SYG_TRI_HEAD
 static_assert(TRI_LEAD_MAX == 4, "tri_piece_sums unrolls four entry steps");
+
+// The piece table's way into LDS for kernels that read it as the host packed it (the free-running kernels of frame
+// lengths 1024 / 512 / 256 / 4096): copies segtab (16-byte aligned) to segl, ends the workgroup's table set-up with ITS
+// BARRIER -- which also publishes whatever else the caller has staged in front of the call -- and returns tri_project's
+// scan8.  project false (a kernel-uniform choice: no filterbank): nothing is copied, the barrier stays, false.
+template <int NPASS>
+__device__ __forceinline__ bool tri_stage_table(float4* segl, const float4* __restrict__ segtab, bool project, int tid,
+                                                int nthreads) {
+  if (project)
+    for (int i = tid; i < NPASS * 2 * 64; i += nthreads) segl[i] = segtab[i];
+  __syncthreads();
+  unsigned lk = 0;
+  if (project) {
+    const int* si = reinterpret_cast<const int*>(segl);
+    const int lane = tid & 63;
+#pragma unroll
+    for (int p = 0; p < NPASS; ++p) lk |= (unsigned)(si[4 * (128 * p + lane) + 2] | si[4 * (128 * p + lane) + 3]);
+  }
+  return __builtin_amdgcn_ballot_w64((lk >> 24) != 0) != 0;
+}
 
 // segl: the piece table in LDS, [NPASS][2][64 lanes] 16-byte words (layout: pack_mel_segments); store(word, value) is
 // called in the lanes that hold a band, with the table's band word (the caller decides what it carries: MODE 6 / 7 turn

@@ -5,6 +5,7 @@
 // 513; stft_mel_wseg_small.hip: 257 / 129; stft_mel_w4096.hip: 2049): NBIN = bins per row (16 NL + 1), PS: the row holds 4^PS |X|^2 (the kernels that
 // pack 2 / 4 / 8 real frames into one complex transform leave the halvings of the split out; the factor -- a power of two
 // -- is taken back here, exactly).
+// At the end of the file: what the free-running kernels (1024 / 512 / 256 / 4096) share around the row functions.
 // Rows are skewed: bin k sits at word ppos(k) = k + k / 16.  Included inside namespace syg { namespace { ... } } after common.h.
 #pragma once
 
@@ -778,3 +779,46 @@ struct RowArgs {
   int n_rows, ascending;                              // contrast plan: see parse_contrast_plan
   int lo[SYG_MAX_BANDS], hi[SYG_MAX_BANDS], k[SYG_MAX_BANDS];
 };
+
+// The contrast plan's copy in LDS (cpl: 3 SYG_MAX_BANDS words, lo / hi / k), which the row functions read with lane =
+// band; the caller's workgroup barrier publishes it.
+__device__ __forceinline__ void stage_contrast_plan(int* cpl, const RowArgs& rw, int tid) {
+  if (tid < SYG_MAX_BANDS) {
+    int lo = 0, hi = 0, k = 0;                        // (selects on scalar values: no branch, no load, per band)
+#pragma unroll
+    for (int r = 0; r < SYG_MAX_BANDS; ++r)
+      if (tid == r) { lo = rw.lo[r]; hi = rw.hi[r]; k = rw.k[r]; }
+    cpl[tid] = lo; cpl[SYG_MAX_BANDS + tid] = hi; cpl[2 * SYG_MAX_BANDS + tid] = k;
+  }
+}
+
+// What rw asks for of one row (statistics, contrast or both: one out-of-line call) -- x: the statistics register of
+// row_stats, y / z: peak / valley of row_contrast_all; what is not asked for is 0.  WIDE: see band_contrast.  The two null
+// tests are taken once, up front: in a trial with them inside each branch the 1024 kernel spilled 7 more scalar registers.
+template <int NBIN, int PS, bool WIDE = false>
+__device__ __forceinline__ float3 row_results(lds_row row, int lane, const RowArgs& rw, lds_iptr cpl) {
+  const bool stats = rw.stats_out != nullptr, contrast = rw.contrast_out != nullptr;
+  float3 f = make_float3(0.f, 0.f, 0.f);
+  if (stats && contrast) {
+    f = row_features<NBIN, PS>(row, lane, rw.binhz, rw.roll_percent, rw.bw_p, rw.smask, cpl, rw.n_rows, rw.ascending);
+  } else if (stats) {
+    f.x = row_stats<NBIN, PS>(row, lane, rw.binhz, rw.roll_percent, rw.bw_p, rw.smask);
+  } else {
+    const float2 pv = row_contrast_all<PS, WIDE>(row, lane, cpl, rw.n_rows, rw.ascending);
+    f.y = pv.x; f.z = pv.y;
+  }
+  return f;
+}
+
+// The global stores of one row's results (frame t of clip b, T frames per clip): lane r writes band r's peak (sy) and
+// valley (sz) and the statistics row r (sx) where stats_row_mask() has it.  Called behind the LAST out-of-line call of
+// a unit of work (see row_stats_body).
+__device__ __forceinline__ void store_row_results(const RowArgs& rw, int64_t b, int64_t t, int64_t T, int lane, float sx,
+                                                  float sy, float sz) {
+  if (rw.contrast_out != nullptr && lane < rw.n_rows) {
+    rw.contrast_out[((b * 2 + 0) * rw.n_rows + lane) * T + t] = sy;
+    rw.contrast_out[((b * 2 + 1) * rw.n_rows + lane) * T + t] = sz;
+  }
+  if (rw.stats_out != nullptr && lane < SYG_NSTAT && ((stats_row_mask(rw.smask) >> lane) & 1))
+    rw.stats_out[(b * SYG_NSTAT + lane) * T + t] = sx;
+}

@@ -1,7 +1,8 @@
 // Host side of the fused STFT front ends (stft_mel.hip, stft_mel_pow2.hip, stft_mel_w1024_seg.hip, stft_mel_w4096.hip,
 // stft_mel_wseg_small.hip) on top of host.h: the argument checks their entry points share and the contrast plan, row
-// and MFCC arguments an entry point hands to its kernel.  No device code.  `who` names the entry point in the message; every
-// check returns SYG_OK or sets the last error and returns the code to pass on.
+// and MFCC arguments an entry point hands to its kernel, and the launch tail of the free-running front ends.  No device
+// code.  `who` names the entry point in the message; every check returns SYG_OK or sets the last error and returns the
+// code to pass on.
 #pragma once
 #include "host.h"
 #include <string.h>
@@ -92,6 +93,25 @@ inline int check_segtab(const char* who, const float* segtab, int n_segtab, int 
               "(sygnals_amd._tables.pack_mel_segments / pack_mel_segments_rows)", who, n_segtab, expect_words);
   SYG_REQUIRE(((uintptr_t)segtab) % 16 == 0, "%s: the piece table must be 16-byte aligned", who);
   SYG_REQUIRE(n_mels >= 1 && n_mels <= max_mels, "%s: n_mels must be in [1, %d] (got %d)", who, max_mels, n_mels);
+  return SYG_OK;
+}
+
+// The launch of a free-running front end (frame lengths 1024 / 512 / 256 / 4096): `kern` -- the caller's choice between
+// its <ROWS> instantiations -- on `threads` threads per workgroup with lds_bytes of dynamic LDS, on at most wgs_per_cu
+// workgroups per CU (what is resident times the rounds the kernel's loop is good for).  The kernel takes args..., then
+// the rows argument by value: *rows, or all zero (no rows) for a null pointer.
+template <class Rows, class Kern, class... Args>
+int launch_front(const char* who, Kern kern, int64_t wgs, int wgs_per_cu, int threads, size_t lds_bytes, hipStream_t st,
+                 const Rows* rows, Args... args) {
+  const int64_t cap = (int64_t)device_cu_count() * wgs_per_cu;
+  if (wgs > cap) wgs = cap;
+  Rows rw;
+  memset(&rw, 0, sizeof(rw));
+  if (rows) rw = *rows;
+  const int rc = reserve_dynamic_lds(who, (const void*)kern, lds_bytes);
+  if (rc) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(threads), lds_bytes, st, args..., rw);
+  SYG_CHECK_LAUNCH(who);
   return SYG_OK;
 }
 

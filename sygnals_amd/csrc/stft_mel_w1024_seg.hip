@@ -27,6 +27,23 @@ constexpr int S1_SCW = 2 * S1_ROW + 16;              // per-wave scratch = its t
 constexpr int S1_SEG_WORDS = 4 * 2 * 64 * 4;
 static_assert(S1_SCW >= 2 * wfft::SC_COMPLEX, "the exchange scratch must fit inside the two rows");
 
+// dynamic LDS in words, read by the kernel and its launcher
+template <bool ROWS> struct S1Lds {
+  static constexpr int O_ROW = 0;                                       // [wave][2 rows]
+  static constexpr int O_TW2 = O_ROW + S1_WAVES * S1_SCW;
+  static constexpr int O_TW1 = O_TW2 + wfft::TW2_COMPLEX * 2;
+  static constexpr int O_SEG = O_TW1 + wfft::TW1_COMPLEX * 2;
+  // the window sits in LDS, not in 16 registers per lane: with it in registers the kernel spilled, and every reload of a
+  // spilled register waits for ALL outstanding memory operations -- the next pair's samples included
+  static constexpr int O_WIN = O_SEG + S1_SEG_WORDS;
+  static constexpr int O_CPL = O_WIN + 1024;                            // ROWS: the contrast plan (lo / hi / k per band), lane = band
+  // ROWS: the results of the pair's row functions wait here ([2 rows][3 registers][64 lanes] per wave) until the pair's
+  // stores are issued behind the last call -- held in registers across the calls they were spilled
+  static constexpr int O_RES = O_CPL + 3 * SYG_MAX_BANDS;
+  static constexpr int TOTAL = ROWS ? O_RES + S1_WAVES * 2 * 3 * 64 : O_CPL;
+  static_assert(O_SEG % 4 == 0, "16-byte piece-table words");
+};
+
 __device__ __forceinline__ int s1_pos(int k) { return S1_BASE + k + (k >> 4); }      // == _tables.row_pos + row_base
 
 #ifndef SYG_S1_WAVES_PER_SIMD
@@ -40,43 +57,28 @@ __global__ __launch_bounds__(S1_WAVES * 64, SYG_S1_WAVES_PER_SIMD) void stft_mel
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* rowa = lds + w * S1_SCW;
+  typedef S1Lds<ROWS> LY;
+  float* rowa = lds + LY::O_ROW + w * S1_SCW;
   float* rowb = rowa + S1_ROW;
   float2* sc = reinterpret_cast<float2*>(rowa);
-  float2* tw2l = reinterpret_cast<float2*>(lds + S1_WAVES * S1_SCW);
-  float2* tw1l = tw2l + wfft::TW2_COMPLEX;
-  float4* segl = reinterpret_cast<float4*>(tw1l + wfft::TW1_COMPLEX);
+  float2* tw2l = reinterpret_cast<float2*>(lds + LY::O_TW2);
+  float2* tw1l = reinterpret_cast<float2*>(lds + LY::O_TW1);
+  float4* segl = reinterpret_cast<float4*>(lds + LY::O_SEG);
+  float* winl = lds + LY::O_WIN;
+  int* cpl = reinterpret_cast<int*>(lds + LY::O_CPL);
+  float* resl = lds + LY::O_RES + w * (2 * 3 * 64);
   wfft::Lane lc;
   wfft::init_lane(lc, lane);
-  if (tid < 64) tw2l[(tid >> 4) * wfft::TW2_STRIDE + (tid & 15)] = tw1024[(16 * (tid >> 4) * (tid & 15)) & 1023];
-  for (int i = tid; i < wfft::TW1_COMPLEX; i += S1_WAVES * 64) tw1l[i] = tw1024[(i & 63) * ((i >> 6) + 1)];
-  const bool project = !ROWS || segtab != nullptr;
-  if (project)
-    for (int i = tid; i < S1_SEG_WORDS / 4; i += S1_WAVES * 64) segl[i] = segtab[i];
-  // the window sits in LDS, not in 16 registers per lane: with it in registers the kernel spilled, and every reload of a
-  // spilled register waits for ALL outstanding memory operations -- the next pair's samples included
-  float* winl = reinterpret_cast<float*>(segl) + S1_SEG_WORDS;
+  wfft::init_tables(tw2l, tw1l, tw1024, 1024, tid, S1_WAVES * 64);
   for (int i = tid; i < 1024; i += S1_WAVES * 64) winl[i] = win[i];
-  int* cpl = reinterpret_cast<int*>(winl + 1024);     // ROWS: the contrast plan (lo / hi / k per band), lane = band
-  // ROWS: the results of the pair's row functions wait here ([2 rows][3 registers][64 lanes] per wave) until the pair's
-  // stores are issued behind the last call -- held in registers across the calls they were spilled
-  float* resl = reinterpret_cast<float*>(cpl + 3 * SYG_MAX_BANDS) + w * (2 * 3 * 64);
   if (ROWS) {
-#pragma unroll
-    for (int r = 0; r < SYG_MAX_BANDS; ++r)
-      if (tid == r) { cpl[r] = rw.lo[r]; cpl[SYG_MAX_BANDS + r] = rw.hi[r]; cpl[2 * SYG_MAX_BANDS + r] = rw.k[r]; }
+    stage_contrast_plan(cpl, rw, tid);
     // (words of the rows that no bin is stored to -- the pad words, the base and the tail -- are read by the row
     // functions' masked lanes and by the projection's masked window words: cleared once, so that they hold numbers)
     for (int i = tid; i < S1_WAVES * S1_SCW; i += S1_WAVES * 64) lds[i] = 0.f;
   }
-  __syncthreads();
-  unsigned lk = 0;
-  if (project) {
-    const int* si = reinterpret_cast<const int*>(segl);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) lk |= (unsigned)(si[4 * (128 * p + lane) + 2] | si[4 * (128 * p + lane) + 3]);
-  }
-  const bool scan8 = __builtin_amdgcn_ballot_w64((lk >> 24) != 0) != 0;
+  const bool project = !ROWS || segtab != nullptr;
+  const bool scan8 = tri_stage_table<4>(segl, segtab, project, tid, S1_WAVES * 64);
 
   // raw samples of the wave's two frames (x: frame ta, y: frame ta + 1; zero outside the clip: center=True's padding)
   float2 raw[16];
@@ -147,15 +149,7 @@ __global__ __launch_bounds__(S1_WAVES * 64, SYG_S1_WAVES_PER_SIMD) void stft_mel
       for (int r = 0; r < 2; ++r) {
         if (r == 1 && !hasb) break;
         lds_row pr = (lds_row)((r == 0 ? rowa : rowb) + S1_BASE);
-        float3 f = make_float3(0.f, 0.f, 0.f);
-        if (rw.stats_out != nullptr && rw.contrast_out != nullptr) {
-          f = row_features<513, 1>(pr, lane, rw.binhz, rw.roll_percent, rw.bw_p, rw.smask, (lds_iptr)cpl, rw.n_rows, rw.ascending);
-        } else if (rw.stats_out != nullptr) {
-          f.x = row_stats<513, 1>(pr, lane, rw.binhz, rw.roll_percent, rw.bw_p, rw.smask);
-        } else {
-          const float2 pv = row_contrast_all<1>(pr, lane, (lds_iptr)cpl, rw.n_rows, rw.ascending);
-          f.y = pv.x; f.z = pv.y;
-        }
+        const float3 f = row_results<513, 1>(pr, lane, rw, (lds_iptr)cpl);
         int lr = lane;
         asm volatile("" : "+v"(lr));
         resl[(3 * r + 0) * 64 + lr] = f.x; resl[(3 * r + 1) * 64 + lr] = f.y; resl[(3 * r + 2) * 64 + lr] = f.z;
@@ -172,26 +166,14 @@ __global__ __launch_bounds__(S1_WAVES * 64, SYG_S1_WAVES_PER_SIMD) void stft_mel
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         if (r == 1 && !hasb) break;
-        const int64_t t = ta + r;
-        if (rw.contrast_out != nullptr && lq < rw.n_rows) {
-          rw.contrast_out[((b * 2 + 0) * rw.n_rows + lq) * T + t] = resl[(3 * r + 1) * 64 + lq];
-          rw.contrast_out[((b * 2 + 1) * rw.n_rows + lq) * T + t] = resl[(3 * r + 2) * 64 + lq];
-        }
-        if (rw.stats_out != nullptr && lq < SYG_NSTAT && ((stats_row_mask(rw.smask) >> lq) & 1))
-          rw.stats_out[(b * SYG_NSTAT + lq) * T + t] = resl[(3 * r + 0) * 64 + lq];
+        const float* res = resl + 3 * r * 64 + lq;
+        store_row_results(rw, b, ta + r, T, lq, res[0], res[64], res[128]);
       }
     }
     wave_lds_sync();                                   // the rows are read: the next transform may use the scratch
   }
 }
 
-}  // namespace
-}  // namespace syg
-
-using namespace syg;
-
-namespace syg {
-namespace {
 int w1024_launch(const char* who, const float* y, int64_t B, int64_t L, int64_t ldy, int hop, int center, int64_t T,
                  const float* window, const float* twiddle, const float* segtab, int n_segtab, int n_mels, float* mel_out,
                  const RowArgs* rows, void* stream) {
@@ -204,23 +186,17 @@ int w1024_launch(const char* who, const float* y, int64_t B, int64_t L, int64_t 
   const int64_t ppc = (T + 1) / 2, n_pairs = B * ppc;
   SYG_REQUIRE(n_pairs < ((int64_t)1 << 40), "%s: too many frames", who);
   const int pad = center ? 512 : 0;
-  const size_t lds = ((size_t)S1_WAVES * S1_SCW + 2 * (wfft::TW2_COMPLEX + wfft::TW1_COMPLEX) + S1_SEG_WORDS + 1024 +
-                      (rows ? 3 * SYG_MAX_BANDS + S1_WAVES * 2 * 3 * 64 : 0)) * sizeof(float);
-  int64_t wgs = (n_pairs + S1_WAVES - 1) / S1_WAVES;
-  const int64_t cap = (int64_t)device_cu_count() * 2 * 2;   // two workgroups per CU resident (60 KiB of LDS each), two rounds
-  if (wgs > cap) wgs = cap;
-  RowArgs rw;
-  memset(&rw, 0, sizeof(rw));
-  if (rows) rw = *rows;
-  auto kern = rows ? stft_mel_w1024_seg_kernel<true> : stft_mel_w1024_seg_kernel<false>;
-  if ((rc = reserve_dynamic_lds(who, (const void*)kern, lds))) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(S1_WAVES * 64), lds, (hipStream_t)stream, y, L, ldy, hop, pad, T, ppc,
-                     n_pairs, window, (const float2*)twiddle, (const float4*)segtab, n_mels, mel_out, rw);
-  SYG_CHECK_LAUNCH(who);
-  return SYG_OK;
+  // two workgroups per CU resident (60 KiB of LDS each), two rounds
+  return launch_front(who, rows ? stft_mel_w1024_seg_kernel<true> : stft_mel_w1024_seg_kernel<false>,
+                      (n_pairs + S1_WAVES - 1) / S1_WAVES, 2 * 2, S1_WAVES * 64,
+                      (rows ? S1Lds<true>::TOTAL : S1Lds<false>::TOTAL) * sizeof(float), (hipStream_t)stream, rows, y, L, ldy,
+                      hop, pad, T, ppc, n_pairs, window, (const float2*)twiddle, (const float4*)segtab, n_mels, mel_out);
 }
+
 }  // namespace
 }  // namespace syg
+
+using namespace syg;
 
 // y [B, L] (row stride ldy) -> mel_out [B, n_mels, T], power 2; segtab: the two-row table of
 // sygnals_amd._tables.pack_mel_segments_rows(sr, 1024, n_mels, fmin, fmax, rows=2, row_words=568, row_base=4) (2048 words on the

@@ -32,6 +32,23 @@ template <int NF> struct SmallCfg;
 template <> struct SmallCfg<4> { static constexpr int NFFT = 512, ROW = 296, LOGSEQ = 1, WINDOW = 17; static constexpr float SCALE = 0.0625f; };
 template <> struct SmallCfg<8> { static constexpr int NFFT = 256, ROW = 160, LOGSEQ = 2, WINDOW = 9; static constexpr float SCALE = 0.015625f; };
 
+// dynamic LDS in words, read by the kernel and its launcher
+template <int NF, bool ROWS> struct SmallLds {
+  static constexpr int SCW = NF * SmallCfg<NF>::ROW;                    // a wave's rows (the exchange scratch aliases them)
+  static constexpr int O_ROW = 0;
+  static constexpr int O_TW2 = O_ROW + SS_WAVES * SCW;
+  static constexpr int O_TW1 = O_TW2 + wfft::TW2_COMPLEX * 2;
+  static constexpr int O_SEG = O_TW1 + wfft::TW1_COMPLEX * 2;
+  static constexpr int O_STG = O_SEG + SS_SEG_WORDS;                    // [wave]: its [band][16 frames] tile
+  // the window sits in LDS, not in 16 registers per lane: with it in registers the kernel spilled (11 registers at NF = 8),
+  // and every reload of a spilled register waits for ALL outstanding memory operations -- the next group's samples included
+  static constexpr int O_WIN = O_STG + SS_WAVES * SS_MAX_MELS * SS_GP;
+  static constexpr int O_CPL = O_WIN + SmallCfg<NF>::NFFT;              // ROWS: the contrast plan (lo / hi / k per band), lane = band
+  static constexpr int TOTAL = O_CPL + (ROWS ? 3 * SYG_MAX_BANDS : 0);
+  static_assert(SCW >= 2 * wfft::SC_COMPLEX, "the exchange scratch must fit inside the rows");
+  static_assert(O_SEG % 4 == 0, "16-byte piece-table words");
+};
+
 __device__ __forceinline__ int ss_pos(int k) { return SS_BASE + k + (k >> 4); }      // == _tables.row_pos + row_base
 
 template <int NF, bool ROWS>
@@ -42,46 +59,31 @@ __global__ __launch_bounds__(SS_WAVES * 64, 4) void stft_mel_wseg_small_kernel(
   typedef SmallCfg<NF> CF;
   constexpr int NBIN = CF::NFFT / 2 + 1, PS = (NF == 4) ? 2 : 3;      // the rows hold 16 |X|^2 / 64 |X|^2 = 4^PS |X|^2
   constexpr int ROW = CF::ROW, NSEQ = NF / 2, SPA = 64 / NSEQ;       // samples of a sequence per 64 elements of z
-  constexpr int SCW = NF * ROW;
-  static_assert(SCW >= 2 * wfft::SC_COMPLEX, "the exchange scratch must fit inside the rows");
+  typedef SmallLds<NF, ROWS> LY;
+  constexpr int SCW = LY::SCW;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* row0 = lds + w * SCW;
+  float* row0 = lds + LY::O_ROW + w * SCW;
   float2* sc = reinterpret_cast<float2*>(row0);
-  float2* tw2l = reinterpret_cast<float2*>(lds + SS_WAVES * SCW);
-  float2* tw1l = tw2l + wfft::TW2_COMPLEX;
-  float4* segl = reinterpret_cast<float4*>(tw1l + wfft::TW1_COMPLEX);
-  float* stg0 = reinterpret_cast<float*>(segl) + SS_SEG_WORDS;
-  float* stg = stg0 + w * (SS_MAX_MELS * SS_GP);                                         // this wave's [band][16 frames] tile
+  float2* tw2l = reinterpret_cast<float2*>(lds + LY::O_TW2);
+  float2* tw1l = reinterpret_cast<float2*>(lds + LY::O_TW1);
+  float4* segl = reinterpret_cast<float4*>(lds + LY::O_SEG);
+  float* stg = lds + LY::O_STG + w * (SS_MAX_MELS * SS_GP);
+  float* winl = lds + LY::O_WIN;
+  int* cpl = reinterpret_cast<int*>(lds + LY::O_CPL);
   wfft::Lane lc;
   wfft::init_lane(lc, lane);
-  if (tid < 64) tw2l[(tid >> 4) * wfft::TW2_STRIDE + (tid & 15)] = tw1024[(16 * (tid >> 4) * (tid & 15)) & 1023];
-  for (int i = tid; i < wfft::TW1_COMPLEX; i += SS_WAVES * 64) tw1l[i] = tw1024[(i & 63) * ((i >> 6) + 1)];
-  if (!ROWS)
-    for (int i = tid; i < SS_SEG_WORDS / 4; i += SS_WAVES * 64) segl[i] = segtab[i];
+  wfft::init_tables(tw2l, tw1l, tw1024, 1024, tid, SS_WAVES * 64);
   // element 64 a + lane of z: sequence r = lane % NSEQ = frames (first + 2 r, first + 2 r + 1), sample SPA a + lane / NSEQ
   const int rs = lane & (NSEQ - 1), nl = lane >> CF::LOGSEQ;
-  // the window sits in LDS, not in 16 registers per lane: with it in registers the kernel spilled (11 registers at NF = 8),
-  // and every reload of a spilled register waits for ALL outstanding memory operations -- the next group's samples included
-  float* winl = stg0 + SS_WAVES * (SS_MAX_MELS * SS_GP);
   for (int i = tid; i < CF::NFFT; i += SS_WAVES * 64) winl[i] = win[i];
-  int* cpl = reinterpret_cast<int*>(winl + CF::NFFT);     // ROWS: the contrast plan (lo / hi / k per band), lane = band
   if (ROWS) {
-#pragma unroll
-    for (int r = 0; r < SYG_MAX_BANDS; ++r)
-      if (tid == r) { cpl[r] = rw.lo[r]; cpl[SYG_MAX_BANDS + r] = rw.hi[r]; cpl[2 * SYG_MAX_BANDS + r] = rw.k[r]; }
+    stage_contrast_plan(cpl, rw, tid);
     // (row words that no bin is stored to -- pads, base, tail -- are read under masks: cleared once)
     for (int i = tid; i < SS_WAVES * SCW; i += SS_WAVES * 64) lds[i] = 0.f;
   }
-  __syncthreads();
-  unsigned lk = 0;
-  if (!ROWS) {
-    const int* si = reinterpret_cast<const int*>(segl);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) lk |= (unsigned)(si[4 * (128 * p + lane) + 2] | si[4 * (128 * p + lane) + 3]);
-  }
-  const bool scan8 = __builtin_amdgcn_ballot_w64((lk >> 24) != 0) != 0;
+  const bool scan8 = tri_stage_table<4>(segl, segtab, !ROWS, tid, SS_WAVES * 64);
 
   float2 raw[16];
   auto fetch = [&](int64_t bq, int64_t tfirst) {
@@ -203,15 +205,7 @@ __global__ __launch_bounds__(SS_WAVES * 64, 4) void stft_mel_wseg_small_kernel(
       for (int r = 0; r < NF; ++r) {
         if (tfirst + r >= T) break;
         lds_row pr = (lds_row)(row0 + r * ROW + SS_BASE);
-        float3 f = make_float3(0.f, 0.f, 0.f);
-        if (rw.stats_out != nullptr && rw.contrast_out != nullptr) {
-          f = row_features<NBIN, PS>(pr, lane, rw.binhz, rw.roll_percent, rw.bw_p, rw.smask, (lds_iptr)cpl, rw.n_rows, rw.ascending);
-        } else if (rw.stats_out != nullptr) {
-          f.x = row_stats<NBIN, PS>(pr, lane, rw.binhz, rw.roll_percent, rw.bw_p, rw.smask);
-        } else {
-          const float2 pv = row_contrast_all<PS>(pr, lane, (lds_iptr)cpl, rw.n_rows, rw.ascending);
-          f.y = pv.x; f.z = pv.y;
-        }
+        const float3 f = row_results<NBIN, PS>(pr, lane, rw, (lds_iptr)cpl);
         int lr = lane;
         asm volatile("" : "+v"(lr));
         if (lr < 16) { stg[(3 * r + 0) * 16 + lr] = f.x; stg[(3 * r + 1) * 16 + lr] = f.y; stg[(3 * r + 2) * 16 + lr] = f.z; }
@@ -221,12 +215,8 @@ __global__ __launch_bounds__(SS_WAVES * 64, 4) void stft_mel_wseg_small_kernel(
       for (int r = 0; r < NF; ++r) {
         const int64_t t = tfirst + r;
         if (t >= T) break;
-        if (rw.contrast_out != nullptr && lq < rw.n_rows) {
-          rw.contrast_out[((b * 2 + 0) * rw.n_rows + lq) * T + t] = stg[(3 * r + 1) * 16 + lq];
-          rw.contrast_out[((b * 2 + 1) * rw.n_rows + lq) * T + t] = stg[(3 * r + 2) * 16 + lq];
-        }
-        if (rw.stats_out != nullptr && lq < SYG_NSTAT && ((stats_row_mask(rw.smask) >> lq) & 1))
-          rw.stats_out[(b * SYG_NSTAT + lq) * T + t] = stg[(3 * r + 0) * 16 + lq];
+        const float* res = stg + 3 * r * 16 + lq;
+        store_row_results(rw, b, t, T, lq, res[0], res[16], res[32]);
       }
       wave_lds_sync();                                 // the rows and the tile area are read: the next transform may run
       if (live2) fetch(b2, tf2);
@@ -273,21 +263,11 @@ int launch_small(const char* who, const float* y, int64_t B, int64_t L, int64_t 
   const int64_t gpc = (T + SS_GF - 1) / SS_GF, n_groups = B * gpc;
   SYG_REQUIRE(n_groups < ((int64_t)1 << 40), "%s: too many frames", who);
   const int pad = center ? CF::NFFT / 2 : 0;
-  const size_t lds = ((size_t)SS_WAVES * NF * CF::ROW + 2 * (wfft::TW2_COMPLEX + wfft::TW1_COMPLEX) + SS_SEG_WORDS +
-                      (size_t)SS_WAVES * SS_MAX_MELS * SS_GP + CF::NFFT + (rows ? 3 * SYG_MAX_BANDS : 0)) * sizeof(float);
-  int64_t wgs = (n_groups + SS_WAVES - 1) / SS_WAVES;
-  const int64_t cap = (int64_t)device_cu_count() * 2;  // one workgroup per CU resident (141 / 148 KiB of LDS), two rounds
-  if (wgs > cap) wgs = cap;
-  RowArgs rw;
-  memset(&rw, 0, sizeof(rw));
-  if (rows) rw = *rows;
-  auto kern = rows ? stft_mel_wseg_small_kernel<NF, true> : stft_mel_wseg_small_kernel<NF, false>;
-  const int rc = reserve_dynamic_lds(who, (const void*)kern, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(SS_WAVES * 64), lds, st, y, L, ldy, hop, pad, T, gpc, n_groups, window,
-                     (const float2*)twiddle, (const float4*)segtab, n_mels, mel_out, rw);
-  SYG_CHECK_LAUNCH(who);
-  return SYG_OK;
+  // one workgroup per CU resident (141 / 148 KiB of LDS), two rounds
+  return launch_front(who, rows ? stft_mel_wseg_small_kernel<NF, true> : stft_mel_wseg_small_kernel<NF, false>,
+                      (n_groups + SS_WAVES - 1) / SS_WAVES, 2, SS_WAVES * 64,
+                      (rows ? SmallLds<NF, true>::TOTAL : SmallLds<NF, false>::TOTAL) * sizeof(float), st, rows, y, L, ldy, hop,
+                      pad, T, gpc, n_groups, window, (const float2*)twiddle, (const float4*)segtab, n_mels, mel_out);
 }
 
 }  // namespace

@@ -1,8 +1,9 @@
 // One-wave 1024-point complex FFT held 16 points per lane (radix 16 x 16 x 4), for kernels whose unit of work is a
 // single wavefront: two lane exchanges through a 4.1 KiB per-wave LDS scratch, everything else in registers.
 // The same transform as the FFT phase of stft_mel.hip (index maps validated by tools/wave_fft_model_v4.py); kept in a
-// header of its own so that kernels with a relaxed register budget (welch_wave.hip) can use it without touching the
-// register-starved headline kernel.
+// header of its own so that kernels with a relaxed register budget can use it without touching the register-starved
+// headline kernel.  On top of it, at the end of the file, the power spectrum of a 4096-sample REAL sequence from two of
+// these transforms (rfft4096_pow: welch_wave.hip accumulates the powers, stft_mel_w4096.hip stores them to its row).
 //
 // Layout on exit: unit u = lane + 64 j (j = 0, 1) owns the bins k = kb_j + 256 d (d = 0..3), kb = (u >> 3) + 16 (u & 7),
 // and their mirrors 1024 - k; lane 0 / unit 0 owns k = {0, 256, 128, 384} instead (mirrors {0, 768, 896, 640}) and
@@ -48,13 +49,14 @@ __device__ __forceinline__ int bin_of(int lane, int j, int d) {
   return (u >> 3) + 16 * (u & 7) + 256 * d;
 }
 
-// LDS tables shared by the waves of a workgroup, built from tw[m] = exp(-2 pi i m / n_tw), n_tw a multiple of 2048:
+// LDS tables shared by the waves of a workgroup, built from tw[m] = exp(-2 pi i m / n_tw), n_tw a multiple of 1024:
 //   tw2l[b' * TW2_STRIDE + c'] = W_64^(b' c'),   tw1l[(c - 1) * 64 + b] = W_1024^(b c)
+// (the largest exponents, 16 * 3 * 15 and 63 * 15, stay below 1024: no index wraps)
 __device__ __forceinline__ void init_tables(float2* tw2l, float2* tw1l, const float2* __restrict__ tw, int n_tw, int tid,
                                             int nthreads) {
-  const int s = n_tw / 2048;
-  if (tid < 64) tw2l[(tid >> 4) * TW2_STRIDE + (tid & 15)] = tw[s * 32 * (tid >> 4) * (tid & 15)];
-  for (int i = tid; i < TW1_COMPLEX; i += nthreads) tw1l[i] = tw[s * 2 * (i & 63) * ((i >> 6) + 1)];
+  const int s = n_tw / 1024;
+  if (tid < 64) tw2l[(tid >> 4) * TW2_STRIDE + (tid & 15)] = tw[s * 16 * (tid >> 4) * (tid & 15)];
+  for (int i = tid; i < TW1_COMPLEX; i += nthreads) tw1l[i] = tw[s * (i & 63) * ((i >> 6) + 1)];
 }
 
 // Forward transform of z[64 a + lane] = v[a].  On exit zk[j][d] = Z[k], zm[j][d] = Z[1024 - k] for the bins of the header
@@ -133,6 +135,73 @@ __device__ __forceinline__ void cfft1024(float2 (&v)[16], const Lane& lc, float2
   zm[0][1] = sp ? G[0][3] : zm[0][1];
   zm[0][2] = sp ? H[0][3] : zm[0][2];
   zm[0][3] = sp ? H[0][2] : zm[0][3];
+}
+
+// ---- 4096-point real-input power spectrum: x[0 .. 4095] is the 2048-point complex sequence z[m] = x[2m] + i x[2m+1];
+// its transform is the radix-2 combine of two cfft1024 -- E of the even, O of the odd elements of z -- and the real-input
+// split on mirror pairs.  The lane that owns bin k of E and O also owns bin 1024 - k, which is everything the bins
+// {k, 2048 - k, 1024 - k, 1024 + k} of x need: all in registers.
+constexpr int RFFT4096_TW = 8 * 64;      // complex entries of each of the two twiddle tables below
+
+// t2048[q * 64 + lane] = W_2048^k, t4096[q * 64 + lane] = W_4096^k for k = bin_of(lane, q >> 2, q & 3); tw4096[m] = W_4096^m
+__device__ __forceinline__ void init_rfft4096_tables(float2* t2048, float2* t4096, const float2* __restrict__ tw4096, int tid,
+                                                     int nthreads) {
+  for (int i = tid; i < RFFT4096_TW; i += nthreads) {
+    const int q = i >> 6, l = i & 63;
+    const int k = bin_of(l, q >> 2, q & 3);
+    t2048[q * 64 + l] = tw4096[2 * k];
+    t4096[q * 64 + l] = tw4096[k];
+  }
+}
+
+// E = zk + conj(zm), O = -i (zk - conj(zm));  X[k] = (E + w O) / 2,  X[N/2 - k] = conj(E - w O) / 2; returns 4 |X|^2
+__device__ __forceinline__ void split_pow(float2 zk, float2 zm, float2 w, float& pk, float& pm) {
+  const float2 E = make_float2(zk.x + zm.x, zk.y - zm.y);
+  const float2 O = make_float2(zk.y + zm.y, zm.x - zk.x);
+  const float2 wO = cmul(w, O);
+  const float ax = E.x + wO.x, ay = E.y + wO.y, bx = E.x - wO.x, by = E.y - wO.y;
+  pk = fmaf(ax, ax, ay * ay);
+  pm = fmaf(bx, bx, by * by);
+}
+
+// (ek, em, e512) / (ok, om, o512): what cfft1024 returned for E / O.  put(slot, bin, 4 |X[bin]|^2) is called 34 times in
+// EVERY lane, slot a compile-time constant at each call (a caller may keep a register per slot):
+//   slot 4 (4 j + d) + {0, 1, 2, 3}: the bins {k, 2048 - k, 1024 - k, 1024 + k} of k = bin_of(lane, j, d); at k = 0
+//                                    (lane 0) the last one repeats bin 1024 and is to be dropped,
+//   slots 32 / 33:                   the bins 512 / 1536, meaningful in lane 0 only (as z512 of cfft1024 is).
+// (No branch in here on purpose: with the last pair under `lane == 0` welch_wave_kernel needs 7 to 24 registers more.)
+template <typename Put>
+__device__ __forceinline__ void rfft4096_pow(const float2 (&ek)[2][4], const float2 (&em)[2][4], float2 e512,
+                                             const float2 (&ok)[2][4], const float2 (&om)[2][4], float2 o512,
+                                             const float2* t2048, const float2* t4096, int lane, Put&& put) {
+  // radix-2 combine (Z[k] = E[k] + W_2048^k O[k], Z[k + 1024] = E[k] - W_2048^k O[k]), the real-input split, powers
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const int q = 4 * j + d;
+      const float2 w2 = t2048[q * 64 + lane], w4 = t4096[q * 64 + lane];
+      const float2 wok = cmul(w2, ok[j][d]);
+      const float2 A = cadd(ek[j][d], wok), Bv = csub(ek[j][d], wok);            // Z[k], Z[1024 + k]
+      const float2 wom = cmulc(om[j][d], w2);                                      // conj(W^k) O[1024 - k]
+      const float2 C = csub(em[j][d], wom), D = cadd(em[j][d], wom);             // Z[1024 - k], Z[2048 - k]
+      float p0, p1, p2, p3;
+      split_pow(A, D, w4, p0, p1);
+      split_pow(C, Bv, make_float2(-w4.y, -w4.x), p2, p3);
+      const int k = bin_of(lane, j, d);
+      put(4 * q + 0, k, p0);
+      put(4 * q + 1, 2048 - k, p1);
+      put(4 * q + 2, 1024 - k, p2);
+      put(4 * q + 3, 1024 + k, p3);
+    }
+  {   // bin 512 of the two transforms: Z[512] = E - i O, Z[1536] = E + i O, split twiddle W_4096^512
+    constexpr float R = 0.70710678118654752440f;
+    const float2 A = make_float2(e512.x + o512.y, e512.y - o512.x), D = make_float2(e512.x - o512.y, e512.y + o512.x);
+    float p512, p1536;
+    split_pow(A, D, make_float2(R, -R), p512, p1536);
+    put(32, 512, p512);
+    put(33, 1536, p1536);
+  }
 }
 
 }  // namespace wfft

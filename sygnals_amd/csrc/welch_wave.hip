@@ -1,11 +1,8 @@
 // Welch partial periodograms for nperseg = nfft = 4096 (BASELINE config C5: one-hour streams, 50 % overlap), one
 // WAVE per segment: scipy.signal.welch as called by compute_psd_welch (sygnals/core/dsp.py:495-560).
 //
-// A 4096-sample real segment is the 2048-point complex sequence z[m] = x[2m] + i x[2m+1]; its transform is built from
-// two 1024-point wave FFTs (wave_fft.h) of the even and odd elements of z -- lane l loads x[4 (64 a + l) .. + 3] as one
-// 16-byte word: the first two floats feed the even transform, the last two the odd one -- followed, in registers, by
-// the radix-2 combine and the real-input split on mirror pairs: the lane that owns bin k of the 1024-point transforms
-// also owns bin 1024 - k, which is everything the bins {k, 1024 - k, 1024 + k, 2048 - k} of the segment need.
+// The transform is wave_fft.h's 4096-point real-input power spectrum (two 1024-point wave FFTs, the radix-2 combine and
+// the real-input split on mirror pairs, all in registers; lane l loads x[4 (64 a + l) .. + 3] as one 16-byte word).
 // |X|^2 is accumulated per bin in registers over the segments of a wave (segment g, g + n_waves, ...); the per-wave sums
 // go to the work buffer and are combined in float64, fixed order, by welch_final_kernel (fft_generic.hip).
 // No workgroup barrier inside the segment loop: the waves of a workgroup only share the constant tables.
@@ -22,20 +19,10 @@ struct WelchLds {
   float2 sc[WW][wfft::SC_COMPLEX];
   float2 tw2l[wfft::TW2_COMPLEX];
   float2 tw1l[wfft::TW1_COMPLEX];
-  float2 t2048[8][64];                   // W_2048^k of (lane, unit j, pair d), index j * 4 + d
-  float2 t4096[8][64];                   // W_4096^k
+  float2 t2048[wfft::RFFT4096_TW];       // W_2048^k, W_4096^k of the lanes' bins (wfft::init_rfft4096_tables)
+  float2 t4096[wfft::RFFT4096_TW];
   float win[NSEG];
 };
-
-// E = zk + conj(zm), O = -i (zk - conj(zm));  X[k] = (E + w O) / 2,  X[N/2 - k] = conj(E - w O) / 2 (powers only)
-__device__ __forceinline__ void split_pow(float2 zk, float2 zm, float2 w, float& pk, float& pm) {
-  const float2 E = make_float2(zk.x + zm.x, zk.y - zm.y);
-  const float2 O = make_float2(zk.y + zm.y, zm.x - zk.x);
-  const float2 wO = cmul(w, O);
-  const float ax = E.x + wO.x, ay = E.y + wO.y, bx = E.x - wO.x, by = E.y - wO.y;
-  pk += fmaf(ax, ax, ay * ay);           // (the factor 1/4 is applied once, by the combine kernel)
-  pm += fmaf(bx, bx, by * by);
-}
 
 template <int DETREND>
 __global__ __launch_bounds__(WW * 64) void welch_wave_kernel(const float* __restrict__ x, int64_t ldx, int step,
@@ -49,23 +36,15 @@ __global__ __launch_bounds__(WW * 64) void welch_wave_kernel(const float* __rest
   wfft::init_lane(lc, lane);
   wfft::init_tables(L.tw2l, L.tw1l, tw4096, 4096, tid, WW * 64);
   for (int i = tid; i < NSEG; i += WW * 64) L.win[i] = win[i];
-  for (int i = tid; i < 8 * 64; i += WW * 64) {
-    const int q = i >> 6, l = i & 63;
-    const int k = wfft::bin_of(l, q >> 2, q & 3);
-    L.t2048[q][l] = tw4096[2 * k];
-    L.t4096[q][l] = tw4096[k];
-  }
+  wfft::init_rfft4096_tables(L.t2048, L.t4096, tw4096, tid, WW * 64);
   __syncthreads();
 
   const int64_t b = blockIdx.y;
   const float* xr = x + b * ldx;
   const int g = blockIdx.x * WW + w;                    // this wave's slot among the nblk partial sums of the stream
-  float acc[8][4];
-  float a512 = 0.f, a1536 = 0.f;
+  float acc[34];                                        // 4 |X|^2 summed over the segments, by slot of wfft::rfft4096_pow
 #pragma unroll
-  for (int q = 0; q < 8; ++q)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[q][r] = 0.f;
+  for (int i = 0; i < 34; ++i) acc[i] = 0.f;
 
   for (int64_t sg = g; sg < nseg; sg += nblk) {
     const float4* sp = reinterpret_cast<const float4*>(xr + sg * (int64_t)step);
@@ -112,25 +91,8 @@ __global__ __launch_bounds__(WW * 64) void welch_wave_kernel(const float* __rest
     float2 ek[2][4], em[2][4], ok[2][4], om[2][4], e512, o512;
     wfft::cfft1024(ve, lc, L.sc[w], L.tw1l, L.tw2l, lane, ek, em, e512);
     wfft::cfft1024(vo, lc, L.sc[w], L.tw1l, L.tw2l, lane, ok, om, o512);
-    // radix-2 combine (Z[k] = E[k] + W_2048^k O[k], Z[k + 1024] = E[k] - W_2048^k O[k]) and the real-input split
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        const int q = 4 * j + d;
-        const float2 w2 = L.t2048[q][lane], w4 = L.t4096[q][lane];
-        const float2 wok = cmul(w2, ok[j][d]);
-        const float2 A = cadd(ek[j][d], wok), Bv = csub(ek[j][d], wok);            // Z[k], Z[1024 + k]
-        const float2 wom = cmulc(om[j][d], w2);                                      // conj(W^k) O[1024 - k]
-        const float2 C = csub(em[j][d], wom), D = cadd(em[j][d], wom);             // Z[1024 - k], Z[2048 - k]
-        split_pow(A, D, w4, acc[q][0], acc[q][1]);                                   // bins k, 2048 - k
-        split_pow(C, Bv, make_float2(-w4.y, -w4.x), acc[q][2], acc[q][3]);           // bins 1024 - k, 1024 + k
-      }
-    {   // bin 512 of the two transforms (lane 0): Z[512] = E - i O, Z[1536] = E + i O, split twiddle W_4096^512
-      constexpr float R = 0.70710678118654752440f;
-      const float2 A = make_float2(e512.x + o512.y, e512.y - o512.x), D = make_float2(e512.x - o512.y, e512.y + o512.x);
-      split_pow(A, D, make_float2(R, -R), a512, a1536);
-    }
+    // (the factor 1/4 is applied once, by the combine kernel)
+    wfft::rfft4096_pow(ek, em, e512, ok, om, o512, L.t2048, L.t4096, lane, [&](int slot, int, float p) { acc[slot] += p; });
   }
   float* po = partial + ((int64_t)b * nblk + g) * (int64_t)(MBIN + 1);
 #pragma unroll
@@ -139,17 +101,17 @@ __global__ __launch_bounds__(WW * 64) void welch_wave_kernel(const float* __rest
     for (int d = 0; d < 4; ++d) {
       const int q = 4 * j + d;
       const int k = wfft::bin_of(lane, j, d);
-      po[k] = acc[q][0];
-      po[MBIN - k] = acc[q][1];
-      po[1024 - k] = acc[q][2];
-      if (k != 0) po[1024 + k] = acc[q][3];      // (k = 0: bin 1024 once)
+      po[k] = acc[4 * q + 0];
+      po[MBIN - k] = acc[4 * q + 1];
+      po[1024 - k] = acc[4 * q + 2];
+      if (k != 0) po[1024 + k] = acc[4 * q + 3];      // (k = 0: bin 1024 once)
     }
-  if (lane == 0) { po[512] = a512; po[1536] = a1536; }
+  if (lane == 0) { po[512] = acc[32]; po[1536] = acc[33]; }
 }
 
 }  // namespace
 
-// Partial sums of nblk waves per stream into work [B, nblk, 2049]; the values carry a factor 4 (see split_pow).
+// Partial sums of nblk waves per stream into work [B, nblk, 2049]; the values carry a factor 4 (see wfft::split_pow).
 // Preconditions (checked by the caller): nperseg = nfft = 4096, 16-byte aligned segments, nblk % 4 == 0, nblk <= nseg
 // rounded up to a multiple of 4 (idle waves write zeros).
 int welch_wave_launch(const float* x, int64_t B, int64_t ldx, int step, int64_t nseg, const float* window,
