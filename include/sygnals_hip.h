@@ -408,6 +408,29 @@ int syg_sosfiltfilt_f32(const float* x, int64_t B, int64_t L, int64_t ldx, const
                         void* work, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Causal SOS filtering with state in and out: y, zf = scipy.signal.sosfilt(sos, x, zi=zi) per row.  Direct form II
+ * transposed; recurrences and states float64, signals float32.
+ *   x, y        [B, L] float32 (row strides ldx, ldy), L >= 1, any B; y may alias x
+ *   sos_host    HOST float64 [n_sections, 6], 1 <= n_sections <= 32 (more than 8 run as consecutive groups of 8, each
+ *               group filtering y in place)
+ *   zi          DEVICE float64 [B, n_sections, 2], scipy's (z0, z1) per section, or NULL = zero state
+ *   zf          DEVICE float64 [B, n_sections, 2]: the state behind sample L - 1, i.e. the next block's zi; or NULL.
+ *               zf must not alias zi
+ *   work        device workspace of syg_sosfilt_work_bytes(B, L, n_sections) bytes (-1: not served)
+ *               = 2 * min(B, 65535) * (n + ceil(n / ahead)) * 2 * min(n_sections, 8) * 8 with n = ceil(L / chunk); rows of
+ *               at most one chunk do not touch it (work may then be NULL)
+ * The chunk in which the float64 recurrence is cut and rejoined is a function of the sample index alone, so a result
+ * does not depend on a row's address or on the batch it is part of.
+ * syg_sosfilt_constants(k): 0 samples per chunk, 1 samples per tile, 2 chunks per wave, 3 chunk states the scan keeps
+ * in flight (ahead), 4 sections per group, 5 sections per call, 6 chunks of a row above which the scan over the chunks
+ * runs in segments (three short launches instead of one long one); -1 for another k.
+ * ------------------------------------------------------------------------------- */
+int64_t syg_sosfilt_constants(int which);
+int64_t syg_sosfilt_work_bytes(int64_t B, int64_t L, int n_sections);
+int syg_sosfilt_f32(const float* x, int64_t B, int64_t L, int64_t ldx, const double* sos_host, int n_sections,
+                    const double* zi, float* y, int64_t ldy, double* zf, void* work, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Welch PSD: scipy.signal.welch(..., return_onesided=True) as called by
  * compute_psd_welch, sygnals/core/dsp.py:545-555.  nfft power of two in [8, 16384],
  * nperseg <= nfft.  twiddle as for syg_stft_pow2_c2c_f32 ([nfft + nfft/2] complex).

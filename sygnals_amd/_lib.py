@@ -70,6 +70,9 @@ SIGNATURES = {
     "syg_cqt_octave_gemm_f32": (_i, [_p, _l, _l, _l, _i, _i, _l, _p, _i, _p, _l, _i, _p]),
     "syg_sosfiltfilt_work_bytes": (_l, [_l, _l, _i, _i]),
     "syg_sosfiltfilt_f32": (_i, [_p, _l, _l, _l, _p, _p, _i, _i, _p, _l, _p, _p]),
+    "syg_sosfilt_constants": (_l, [_i]),
+    "syg_sosfilt_work_bytes": (_l, [_l, _l, _i]),
+    "syg_sosfilt_f32": (_i, [_p, _l, _l, _l, _p, _i, _p, _p, _l, _p, _p, _p]),
     "syg_welch_work_bytes": (_l, [_l, _i]),
     "syg_welch_f32": (_i, [_p, _l, _l, _l, _i, _i, _i, _p, _p, _i, _d, _p, _p, _p]),
     "syg_pack_rows_work_bytes": (_l, [_l]),

@@ -562,7 +562,7 @@ def dsp_stft(input_file, output, n_fft, hop_length, window):
 # ---------------------------------------------------------------- filter
 @click.group("filter")
 def filter_cmd():
-    """Apply Butterworth filters (zero-phase)."""
+    """Apply IIR filters (zero-phase or causal), FIR filters and equalizers."""
 
 
 @filter_cmd.command("apply")
@@ -571,17 +571,31 @@ def filter_cmd():
 @click.option("--cutoff", required=True, help="Cutoff (Hz); comma-separated pair for bandpass/bandstop.")
 @click.option("--fs", type=float, default=None, help="Sampling frequency (Hz) if the file carries none.")
 @click.option("--order", type=int, default=5, show_default=True)
+@click.option("--family", type=click.Choice(["butter", "cheby1", "cheby2", "ellip", "bessel"]), default="butter",
+              show_default=True, help="IIR family.")
+@click.option("--rp", type=float, default=None, help="Pass-band ripple (dB): cheby1 and ellip.")
+@click.option("--rs", type=float, default=None, help="Stop-band attenuation (dB): cheby2 and ellip.")
+@click.option("--causal", is_flag=True, default=False,
+              help="Filter causally from rest (scipy.signal.sosfilt) instead of zero-phase.")
 @click.option("-o", "--output", required=True, type=click.Path())
-def filter_apply(input_file, ftype, cutoff, fs, order, output):
-    """Apply a Butterworth filter to a signal or audio file. Uses zero-phase filtering."""
-    from ..core.filters import apply_sos_filter, design_butterworth_sos
+def filter_apply(input_file, ftype, cutoff, fs, order, family, rp, rs, causal, output):
+    """Apply an IIR filter (Butterworth unless --family says otherwise) to a signal or audio file. Uses zero-phase
+    filtering unless --causal is given."""
+    from ..core.filters import apply_sos_filter, apply_sos_filter_causal, design_butterworth_sos, design_iir_sos
     x, sr = _load_signal(input_file, fs)
     if sr is None:
         raise click.UsageError("--fs is required: the input file carries no sampling rate.")
     parts = [float(c) for c in str(cutoff).split(",")]
     cut = parts[0] if len(parts) == 1 else (parts[0], parts[1])
     try:
-        y = apply_sos_filter(design_butterworth_sos(cut, sr, order, ftype), x)
+        if family == "butter" and rp is None and rs is None:
+            sos = design_butterworth_sos(cut, sr, order, ftype)
+        else:
+            sos = design_iir_sos(cut, sr, order, ftype, family=family, rp=rp, rs=rs)
+        if not causal and sos.shape[0] > 8:
+            raise click.UsageError(f"This design has {sos.shape[0]} second-order sections; zero-phase filtering serves at "
+                                   "most 8. Lower --order, or filter causally with --causal (up to 32 sections).")
+        y = apply_sos_filter_causal(sos, x) if causal else apply_sos_filter(sos, x)
     except (ValueError, TypeError) as e:
         raise click.UsageError(str(e))
     if Path(output).suffix.lower() == ".wav":
@@ -589,6 +603,81 @@ def filter_apply(input_file, ftype, cutoff, fs, order, output):
     else:
         sio.save_data(y, output)
     click.echo(f"Filtered signal saved to '{Path(output).name}'.")
+
+
+EQ_BAND_TYPES = ("peak", "low_shelf", "high_shelf", "notch")
+
+
+def parse_eq_band(token: str) -> dict:
+    """'TYPE:FREQ[:GAIN_DB[:Q]]' -> a stage of apply_parametric_eq ('peak:1000:-6:2', 'notch:50', 'low_shelf:120:3')."""
+    parts = [t.strip() for t in token.split(":")]
+    form = "write TYPE:FREQ[:GAIN_DB[:Q]] with TYPE one of peak, low_shelf, high_shelf, notch, e.g. peak:1000:-6:1.4"
+    if not 2 <= len(parts) <= 4 or parts[0].lower() not in EQ_BAND_TYPES:
+        raise click.UsageError(f"--band: cannot read '{token}' ({form}).")
+    try:
+        nums = [float(v) for v in parts[1:]]
+    except ValueError:
+        raise click.UsageError(f"--band: cannot read the numbers of '{token}' ({form}).")
+    if not all(np.isfinite(nums)):
+        raise click.UsageError(f"--band: the numbers of '{token}' must be finite ({form}).")
+    stage = {"type": parts[0].lower(), "freq": nums[0]}
+    if len(nums) > 1:
+        stage["gain_db"] = nums[1]
+    if len(nums) > 2:
+        stage["q"] = nums[2]
+    return stage
+
+
+@filter_cmd.command("eq")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--band", "bands", multiple=True, required=True,
+              help="One EQ stage, TYPE:FREQ[:GAIN_DB[:Q]] (peak, low_shelf, high_shelf, notch); repeatable, applied in order.")
+@click.option("--fs", type=float, default=None, help="Sampling frequency (Hz) if the file carries none.")
+def filter_eq(input_file, output, bands, fs):
+    """Apply a parametric equalizer (a causal cascade of biquads) to a signal or audio file."""
+    from ..core.audio.effects import apply_parametric_eq
+    stages = [parse_eq_band(tok) for tok in bands]
+    x, sr = _load_signal(input_file, fs)
+    if sr is None:
+        raise click.UsageError("--fs is required: the input file carries no sampling rate.")
+    try:
+        y = apply_parametric_eq(x, sr, stages)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    _save_series(y, sr, output)
+    click.echo(f"Equalized signal ({len(stages)} stages) saved to '{Path(output).name}'.")
+
+
+@filter_cmd.command("fir")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--numtaps", type=int, required=True, help="Number of taps of the filter.")
+@click.option("--cutoff", required=True, help="Cutoff (Hz); comma-separated pair for a band.")
+@click.option("--window", default="hamming", show_default=True, help="Window of the design, name[:param].")
+@click.option("--pass-zero/--no-pass-zero", "pass_zero", default=True, show_default=True,
+              help="Whether the gain at 0 Hz is 1 (low-pass / band-stop) or 0 (high-pass / band-pass).")
+@click.option("--fs", type=float, default=None, help="Sampling frequency (Hz) if the file carries none.")
+def filter_fir(input_file, output, numtaps, cutoff, window, pass_zero, fs):
+    """Apply a windowed FIR filter (scipy.signal.firwin, causal: lfilter(taps, 1, x))."""
+    from ..core.filters import apply_fir_filter_batch, design_fir
+    try:
+        parts = [float(c) for c in str(cutoff).split(",")]
+    except ValueError:
+        raise click.UsageError(f"--cutoff: cannot read '{cutoff}' as one frequency or a comma-separated pair.")
+    if len(parts) not in (1, 2):
+        raise click.UsageError(f"--cutoff: cannot read '{cutoff}' as one frequency or a comma-separated pair.")
+    w = parse_window_spec(window)
+    x, sr = _load_signal(input_file, fs)
+    if sr is None:
+        raise click.UsageError("--fs is required: the input file carries no sampling rate.")
+    try:
+        taps = design_fir(numtaps, parts[0] if len(parts) == 1 else parts, sr, window=w, pass_zero=pass_zero)
+        y = apply_fir_filter_batch(taps, np.asarray(x, dtype=np.float32)[None, :])[0].cpu().numpy().astype(np.float64)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    _save_series(y, sr, output)
+    click.echo(f"FIR-filtered signal ({numtaps} taps) saved to '{Path(output).name}'.")
 
 
 # ---------------------------------------------------------------- augment

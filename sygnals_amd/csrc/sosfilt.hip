@@ -31,17 +31,14 @@
 // recurrence over the current one.  One wave per workgroup: ordering inside the wave replaces barriers.
 #include "common.h"
 #include "sosfilt_clip.h"
+#include "sosfilt_scan.h"
 #include <string.h>
 #include <stdlib.h>
 
 namespace syg {
 namespace {
 
-constexpr int CS = 256;      // samples per chunk
-constexpr int TS = 32;       // samples per LDS tile row group
-constexpr int MAXS = 8;      // sections
-constexpr int MAXD = 2 * MAXS;
-constexpr int LSTR = 36;     // LDS tile row stride (floats): one row = the 32 samples of one chunk (+4 pad)
+using namespace sos;        // chunk / tile geometry, the scan step and the host side of A^CS: sosfilt_scan.h
 
 struct SosParams {
   double b0[MAXS], b1[MAXS], b2[MAXS], a1[MAXS], a2[MAXS];
@@ -58,7 +55,6 @@ __device__ __forceinline__ float ext_at(const float* __restrict__ xb, int64_t L,
   if (i < lext) return 2.f * xb[L - 1] - xb[L - 2 - (i - pad - L)];
   return 0.f;
 }
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte load at 4-byte alignment
 
 // ---- pass A / C
 // MODE 0: zero-state pass, writes end states.  MODE 1: true pass of the forward sweep, output reversed into the
@@ -211,41 +207,8 @@ __global__ __launch_bounds__(64) void chunk_kernel(const float* __restrict__ in,
   }
 }
 
-// ---- pass B: 16 lanes per clip (one DPP row); lane r carries state component r.  The state vector is broadcast
-// inside the row with DPP row_newbcast (two 32-bit moves per double) instead of ds_bpermute, and the zero-state
-// end states of the next chunks are loaded four steps ahead of the serial chain.
-template <int J>
-__device__ __forceinline__ double row_bcast(double v) {
-  const uint64_t u = (uint64_t)__double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, 0x150 + J, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), 0x150 + J, 0xF, 0xF, false);
-  return __longlong_as_double((long long)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
-}
-template <int D, int J>
-__device__ __forceinline__ void bcast_all(double (&b)[D], double s) {
-  if constexpr (J < D) {
-    b[J] = row_bcast<J>(s);
-    bcast_all<D, J + 1>(b, s);
-  }
-}
-
-// row . state with four independent partial sums (the serial scan is latency-bound: one accumulator would chain
-// D dependent fp64 FMAs per step); fixed summation order, so results are reproducible
-template <int D>
-__device__ __forceinline__ double row_dot(const double (&arow)[D], double s, double z) {
-  double b[D];
-  bcast_all<D, 0>(b, s);
-  double p0 = z, p1 = 0.0, p2 = 0.0, p3 = 0.0;
-#pragma unroll
-  for (int j = 0; j < D; j += 4) {
-    p0 = fma(arow[j], b[j], p0);
-    if (j + 1 < D) p1 = fma(arow[j + 1], b[j + 1], p1);
-    if (j + 2 < D) p2 = fma(arow[j + 2], b[j + 2], p2);
-    if (j + 3 < D) p3 = fma(arow[j + 3], b[j + 3], p3);
-  }
-  return (p0 + p1) + (p2 + p3);
-}
-
+// ---- pass B: 16 lanes per clip (row_dot of sosfilt_scan.h); the zero-state end states of the next chunks are loaded
+// AHEAD steps ahead of the serial chain.
 template <int S, bool SRCX>
 __global__ __launch_bounds__(256) void scan_kernel(const float* __restrict__ in, int64_t ldin, int nch, int64_t B,
                                                    int skip, SosParams P, const double* __restrict__ zs,
@@ -273,7 +236,6 @@ __global__ __launch_bounds__(256) void scan_kernel(const float* __restrict__ in,
   const int rc = (r < D) ? r : 0;
   const double* zp = zs + (int64_t)bb * nch * D + rc;
   double* ip = init + (int64_t)bb * nch * D + rc;
-  constexpr int AHEAD = 32;       // chunk states in flight: a step is ~150 cycles, memory latency an order more
   double zq[AHEAD];
 #pragma unroll
   for (int k = 0; k < AHEAD; ++k) zq[k] = (live && k < nch) ? zp[(int64_t)k * D] : 0.0;
@@ -292,40 +254,6 @@ __global__ __launch_bounds__(256) void scan_kernel(const float* __restrict__ in,
 #pragma unroll
     for (int k = 0; k < AHEAD; ++k) zq[k] = zn[k];
   }
-}
-
-void host_step(const double* sos5, int S, double* z, double x) {
-  double u = x;
-  for (int s = 0; s < S; ++s) {
-    const double* c = sos5 + 5 * s;  // b0 b1 b2 a1 a2
-    const double y = c[0] * u + z[2 * s];
-    z[2 * s] = c[1] * u - c[3] * y + z[2 * s + 1];
-    z[2 * s + 1] = c[2] * u - c[4] * y;
-    u = y;
-  }
-}
-
-// A^n (row-major D x D in a MAXD-strided array) by repeated multiplication; n <= CS
-void mat_pow(const double* A1, int D, int n, double* out) {     // square and multiply (n <= 256: at most 16 products)
-  double R[MAXD * MAXD] = {0}, Bm[MAXD * MAXD] = {0}, T[MAXD * MAXD];
-  auto mul = [&](const double* X, const double* Y, double* Z) {  // Z = X Y (Z may alias X or Y)
-    for (int i = 0; i < D; ++i)
-      for (int j = 0; j < D; ++j) {
-        double acc = 0.0;
-        for (int k = 0; k < D; ++k) acc += X[i * MAXD + k] * Y[k * MAXD + j];
-        T[i * MAXD + j] = acc;
-      }
-    for (int i = 0; i < D; ++i)
-      for (int j = 0; j < D; ++j) Z[i * MAXD + j] = T[i * MAXD + j];
-  };
-  for (int i = 0; i < D; ++i) R[i * MAXD + i] = 1.0;
-  for (int i = 0; i < D; ++i)
-    for (int j = 0; j < D; ++j) Bm[i * MAXD + j] = A1[i * MAXD + j];
-  for (int e = n; e > 0; e >>= 1) {
-    if (e & 1) mul(R, Bm, R);
-    if (e > 1) mul(Bm, Bm, Bm);
-  }
-  for (int i = 0; i < MAXD * MAXD; ++i) out[i] = R[i];
 }
 
 int64_t grid_chunks(int64_t lext, int skip) { return (lext + skip + CS - 1) / CS; }
@@ -413,14 +341,9 @@ extern "C" int syg_sosfiltfilt_f32(const float* x, int64_t B, int64_t L, int64_t
     P.zi[2 * s] = zi_host[2 * s];
     P.zi[2 * s + 1] = zi_host[2 * s + 1];
   }
-  // A: homogeneous one-step map, column j = step(e_j, x = 0); A^CS (and A^(CS - skip) per sweep) on the host
-  double A1[MAXD * MAXD] = {0};
-  for (int j = 0; j < D; ++j) {
-    double z[MAXD] = {0};
-    z[j] = 1.0;
-    host_step(sos5, S, z, 0.0);
-    for (int i = 0; i < D; ++i) A1[i * MAXD + j] = z[i];
-  }
+  // A: homogeneous one-step map; A^CS (and A^chunk of the clip-resident form) on the host
+  double A1[MAXD * MAXD];
+  one_step_matrix(sos5, S, A1);
   hipStream_t st = (hipStream_t)stream;
   // clips that fit a workgroup's registers: both sweeps in one launch (sosfilt_clip.hip); SYGNALS_AMD_SOS_CLIP=0 keeps
   // the chunked path below (development / tests)

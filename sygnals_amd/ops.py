@@ -1034,6 +1034,57 @@ def sosfiltfilt(x: torch.Tensor, sos: np.ndarray, zi: np.ndarray, padlen: int) -
     return y
 
 
+SOSFILT_KEYS = ("chunk", "tile", "chunks_per_wave", "scan_ahead", "group_sections", "max_sections", "two_level_chunks")
+
+
+def sosfilt_constants() -> dict:
+    """Geometry of the causal SOS kernels (syg_sosfilt_constants), by name."""
+    return {name: int(lib().syg_sosfilt_constants(i)) for i, name in enumerate(SOSFILT_KEYS)}
+
+
+def sosfilt(x: torch.Tensor, sos: np.ndarray, zi: Optional[torch.Tensor] = None, return_state: bool = False,
+            out: Optional[torch.Tensor] = None):
+    """Batched causal SOS filtering of x [B, L]: y, zf = scipy.signal.sosfilt(sos, x, zi=zi) per row.
+
+    x: float32 device rows, unit stride along L, any row stride.  sos: host [n_sections, 6], 1 to 32 sections.
+    zi: device float64 [B, n_sections, 2] (scipy's per-section states) or None for a zero state.  Returns y, or (y, zf)
+    with return_state=True; zf [B, n_sections, 2] float64 stays on the device and is the next block's zi.  out: the
+    tensor y is written to (it may be x itself)."""
+    sos = np.ascontiguousarray(sos, dtype=np.float64)
+    if sos.ndim != 2 or sos.shape[1] != 6:
+        raise ValueError("Input sos must be a 2D array with shape (n_sections, 6).")
+    S = sos.shape[0]
+    if not 1 <= S <= 32:
+        raise ValueError(f"sosfilt: {S} sections; the causal kernels serve 1 to 32 sections per call "
+                         "(split a longer cascade and carry y from call to call).")
+    if np.any(sos[:, 3] == 0.0):
+        raise ValueError("sosfilt: a0 of a section is zero.")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError("sosfilt: x must be a float32 tensor of shape [B, L].")
+    B, L = x.shape
+    if B < 1 or L < 1:
+        raise ValueError(f"sosfilt: x must hold at least one row of at least one sample (got [{B}, {L}]).")
+    if zi is not None and (not isinstance(zi, torch.Tensor) or zi.dtype != torch.float64 or tuple(zi.shape) != (B, S, 2)):
+        raise ValueError(f"sosfilt: zi must be a float64 tensor of shape [B, n_sections, 2] = [{B}, {S}, 2].")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B, L)
+                            or out.stride(1) != 1):
+        raise ValueError(f"sosfilt: out must be a float32 tensor of shape [{B}, {L}] with unit stride along L.")
+    require_gpu()
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    if zi is not None:
+        zi = zi.to(x.device).contiguous()
+    y = out if out is not None else torch.empty((B, L), dtype=torch.float32, device=x.device)
+    zf = torch.empty((B, S, 2), dtype=torch.float64, device=x.device) if return_state else None
+    nbytes = lib().syg_sosfilt_work_bytes(B, L, S)
+    if nbytes < 0:
+        raise SygnalsHipError(f"sosfilt: unsupported configuration (B={B}, L={L}, sections={S})")
+    work = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device) if L > sosfilt_constants()["chunk"] else None
+    _call("syg_sosfilt_f32", _ptr(x), B, L, _ld(x), sos.ctypes.data_as(C.c_void_p), S, _ptr(zi), _ptr(y), _ld(y), _ptr(zf),
+          _ptr(work))
+    return (y, zf) if return_state else y
+
+
 def detrend_code(detrend) -> int:
     """scipy's detrend argument -> the C ABI's code: 0 none (False / None / 'none'), 1 'constant' (True), 2 'linear'."""
     if detrend in (False, None, "none", 0):

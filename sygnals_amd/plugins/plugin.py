@@ -76,6 +76,9 @@ class SygnalsAmdPlugin(_Base):
                    F.band_stop_filter):
             registry.add_filter(fn.__name__, fn)
         registry.add_filter("apply_sos_filter_batch", F.apply_sos_filter_batch)
+        for fn in (F.design_iir_sos, F.sosfilt_zi, F.apply_sos_filter_causal, F.apply_sos_filter_causal_batch, F.design_fir,
+                   F.apply_fir_filter_batch):
+            registry.add_filter(fn.__name__, fn)
 
     def register_transforms(self, registry):
         from ..core import dsp as D
