@@ -817,6 +817,15 @@ int syg_idwt_f32(const float* coeffs, int64_t B, int64_t ldc, const int64_t* len
  *   float64 and rounded once.  L <= syg_fx_add_noise_resident_max(): one launch, a workgroup keeps its row in LDS between
  *   the sums and the mix.  Longer rows: two launches (slice sums, then the mix) and `work` of
  *   syg_fx_add_noise_work_bytes(B, L) bytes, 16-byte aligned.
+ *
+ * syg_fx_add_noise_gen_f32: the same mix on noise that is never stored: noise[b, n] is the standard normal
+ *   (seed, row first_row + b, sample n) of syg_rng_normal_f32 (below), generated in registers.  Rows first_row ..
+ *   first_row + B - 1 must lie in [0, 2^31).  L <= syg_fx_add_noise_resident_max(): one launch, y alone is kept in LDS
+ *   (8 bytes a sample, every normal drawn once).  Longer rows: a power pass and a mix pass that both generate (12 bytes
+ *   a sample), the power pass in as many slices as fill the device; between them one wave a row adds the slices in a
+ *   fixed order (runs of consecutive slices, the runs in order) and leaves the row's scale factor; `work` of
+ *   syg_fx_add_noise_gen_work_bytes(B, L) bytes, 16-byte aligned.  The result is within one float32 ulp of
+ *   syg_fx_add_noise_f32 on the stored noise (the sums are taken in another order).
  * ------------------------------------------------------------------------------- */
 int syg_phase_vocoder_chunk(void);
 int64_t syg_phase_vocoder_work_bytes(int64_t B, int64_t T_out, int form);
@@ -826,6 +835,9 @@ int64_t syg_fx_add_noise_resident_max(void);
 int64_t syg_fx_add_noise_work_bytes(int64_t B, int64_t L);
 int syg_fx_add_noise_f32(const float* y, int64_t B, int64_t L, int64_t ldy, const float* noise, int64_t ldn,
                          const double* snr_db, float* out, int64_t ldo, void* work, void* stream);
+int64_t syg_fx_add_noise_gen_work_bytes(int64_t B, int64_t L);
+int syg_fx_add_noise_gen_f32(const float* y, int64_t B, int64_t L, int64_t ldy, uint64_t seed, int64_t first_row,
+                             const double* snr_db, float* out, int64_t ldo, void* work, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Numerical Laplace transform (sygnals/core/transforms.py:159-199), an arbitrary-point z-transform:
@@ -1102,6 +1114,52 @@ int syg_lpc_rows_f32(const float* y, int64_t B, int64_t L, int64_t ldy, const fl
                      int64_t work_bytes, float* a, float* k, float* err, void* stream);
 int syg_lpc_envelope_f32(const float* a, const float* err, int64_t B, int order, int64_t T, int n_fft, const double* phasor, int db,
                          double amin, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Noise generation (the float64 restatement that is the contract: tests/rng_ref.py; the host-side twin in integer
+ * NumPy: sygnals_amd/_rng.py).
+ *
+ * The generator is Philox4x32-10 (Salmon et al. 2011, the Random123 constants): multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * increments 0x9E3779B9 / 0xBB67AE85, ten rounds, the key bumped between rounds, per round
+ *     (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)).
+ * Stream layout: key = (seed & 0xffffffff, seed >> 32); counter = (q & 0xffffffff, q >> 32, row, stream), q = n / 4,
+ * 0 <= row < 2^31; stream SYG_RNG_STREAM_NOISE: noise samples, SYG_RNG_STREAM_ROW: per-row draws (taken on the host).
+ * The words w0 .. w3 of one call give samples 4q .. 4q + 3: with u(w) = (2 (w >> 9) + 1) 2^-24 (exact in float32,
+ * strictly inside (0, 1)), z[4q] = r cos(t), z[4q + 1] = r sin(t), r = sqrt(-2 ln u(w0)), t = 2 pi u(w1); z[4q + 2] and
+ * z[4q + 3] likewise from (w2, w3).  |z| <= 5.77.  float32 with the accurate logf / sqrtf and sincospif(2 u).
+ * A sample depends on (seed, stream, row, n) alone: not on the launch shape, not on where the row lies in a batch; no
+ * atomics; the same call gives the same bits.  Gate: |z - z in float64| <= 1e-5 max(1, max |z|) per row.
+ *
+ * syg_rng_philox_u32: counter [n][4], key [n][2] uint32 DEVICE arrays -> out [n][4] raw words (counter / out 16-byte
+ *   aligned, key 8-byte aligned).
+ * syg_rng_normal_f32: out [B, L] (row stride ldo) = samples offset .. offset + L - 1 of rows first_row .. first_row + B - 1.
+ *   Rejected before any device work: a null pointer, B < 1, L < 1, ldo < L, first_row < 0 or first_row + B > 2^31,
+ *   offset outside [0, 2^62).
+ * Power-law ("coloured") noise, noise[r] = irfft(rfft(w_r) g, M)[:L] (Timmer & Koenig 1995): M the smallest power of two
+ *   >= max(L, 2), w_r the M white samples of (seed, row r), g[0] = 0 and g[k] = k^(-alpha / 2); alpha = 1 pink, 2 brown;
+ *   at alpha = 0 nothing diverges and g = 1 everywhere (the white row unchanged).  g is real and symmetric, so rows
+ *   r and r ^ 1 (ABSOLUTE row indices) share one complex transform, which is the caller's (the strided FFT entries):
+ *   syg_rng_normal_pairs_c64  Z [P, M][2] = w_a + i w_b for rows a = first_row + 2p, b = a + 1; first_row even.
+ *   syg_rng_power_gain_c64    X [rows, M][2] *= g[min(k, M - k)] in place; M a power of two in [2, 2^26], alpha in [0, 2].
+ *   syg_rng_unpack_pairs_f32  out [B, L] (row stride ldo): row b is the real (R even) or imaginary (R odd) part of
+ *                             Z[(R >> 1) - (first_row >> 1)][0 .. L - 1], R = first_row + b; Z [.., M][2].
+ * syg_rng_constants(key): the figures above (SYG_RNG_*), -1 for an unknown key.
+ * ------------------------------------------------------------------------------- */
+enum {
+  SYG_RNG_ROUNDS = 0,        /* Philox rounds */
+  SYG_RNG_STREAM_NOISE = 1,  /* counter word 3 of noise samples */
+  SYG_RNG_STREAM_ROW = 2,    /* counter word 3 of per-row draws */
+  SYG_RNG_ROW_LIMIT = 3,     /* rows lie in [0, this) */
+  SYG_RNG_COLORED_MAX = 4    /* longest coloured row (the longest transform) */
+};
+int64_t syg_rng_constants(int key);
+int syg_rng_philox_u32(const uint32_t* counter, const uint32_t* key, int64_t n, uint32_t* out, void* stream);
+int syg_rng_normal_f32(float* out, int64_t B, int64_t L, int64_t ldo, uint64_t seed, int64_t first_row, int64_t offset,
+                       void* stream);
+int syg_rng_normal_pairs_c64(float* Z, int64_t P, int64_t M, uint64_t seed, int64_t first_row, void* stream);
+int syg_rng_power_gain_c64(float* X, int64_t rows, int64_t M, double alpha, void* stream);
+int syg_rng_unpack_pairs_f32(const float* Z, int64_t M, int64_t first_row, float* out, int64_t B, int64_t L, int64_t ldo,
+                             void* stream);
 
 #ifdef __cplusplus
 }

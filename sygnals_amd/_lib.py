@@ -17,6 +17,7 @@ _i = C.c_int
 _l = C.c_int64
 _f = C.c_float
 _d = C.c_double
+_u = C.c_uint64
 
 # name -> (restype, argtypes); must list every symbol declared in include/sygnals_hip.h
 SIGNATURES = {
@@ -121,6 +122,8 @@ SIGNATURES = {
     "syg_fx_add_noise_resident_max": (_l, []),
     "syg_fx_add_noise_work_bytes": (_l, [_l, _l]),
     "syg_fx_add_noise_f32": (_i, [_p, _l, _l, _l, _p, _l, _p, _p, _l, _p, _p]),
+    "syg_fx_add_noise_gen_work_bytes": (_l, [_l, _l]),
+    "syg_fx_add_noise_gen_f32": (_i, [_p, _l, _l, _l, _u, _l, _p, _p, _l, _p, _p]),
     "syg_laplace_chunk": (_i, []),
     "syg_laplace_tile_rows": (_i, []),
     "syg_laplace_tile_cols": (_i, []),
@@ -167,6 +170,12 @@ SIGNATURES = {
     "syg_lpc_rows_work_bytes": (_l, [_l, _l, _i, _i]),
     "syg_lpc_rows_f32": (_i, [_p, _l, _l, _l, _p, _i, _i, _p, _l, _p, _p, _p, _p]),
     "syg_lpc_envelope_f32": (_i, [_p, _p, _l, _i, _l, _i, _p, _i, _d, _p, _p]),
+    "syg_rng_constants": (_l, [_i]),
+    "syg_rng_philox_u32": (_i, [_p, _p, _l, _p, _p]),
+    "syg_rng_normal_f32": (_i, [_p, _l, _l, _l, _u, _l, _l, _p]),
+    "syg_rng_normal_pairs_c64": (_i, [_p, _l, _l, _u, _l, _p]),
+    "syg_rng_power_gain_c64": (_i, [_p, _l, _l, _d, _p]),
+    "syg_rng_unpack_pairs_f32": (_i, [_p, _l, _l, _p, _l, _l, _l, _p]),
 }
 
 _lib = None

@@ -6,7 +6,8 @@
 `filter` groups follow the surface documented in the reference's README.md:483-533, 704-900 --
 in the reference snapshot those groups are commented out (sygnals/cli/main.py:29-33, 115-119), so
 they are provided here rather than kept.  The `augment` group keeps the option names of
-sygnals/cli/augment_cmd.py (add-noise: --snr, --noise-type, --seed; time-stretch: --rate; -o/--output);
+sygnals/cli/augment_cmd.py (add-noise: --snr, --noise-type, --seed; time-stretch: --rate; -o/--output), to which add-noise
+adds --generator host|device and --exponent (the device noise generator; the default, host, is the reference's draw);
 pitch-shift is not offered.  Run stand-alone as `python -m sygnals_amd.cli.main ...`
 or attach the features / dsp / filter groups to the reference CLI through the plugin (register_cli_commands); `augment`
 is not attached there: the reference CLI already owns a group of that name.
@@ -694,12 +695,26 @@ def augment_cmd():
 @click.option("--noise-type", type=click.Choice(["gaussian", "white", "pink", "brown"], case_sensitive=False),
               default="gaussian", show_default=True, help="Type of noise to add.")
 @click.option("--seed", type=int, default=None, help="Random seed for noise generation.")
-def augment_add_noise(input_file, output, snr, noise_type, seed):
+@click.option("--generator", type=click.Choice(["host", "device"], case_sensitive=False), default="host", show_default=True,
+              help="host: the reference's NumPy draw (pink / brown are its white-noise placeholders); "
+                   "device: drawn on the GPU, with real pink (1/f) and brown (1/f^2) noise.")
+@click.option("--exponent", type=float, default=None,
+              help="Spectral exponent in [0, 2] of the noise (density ~ 1/f^exponent); --generator device only.")
+def augment_add_noise(input_file, output, snr, noise_type, seed, generator, exponent):
     """Add noise to the audio signal."""
     from ..core.augment import add_noise
+    generator = generator.lower()
+    if exponent is not None and generator != "device":
+        raise click.UsageError("--exponent needs --generator device.")
+    if exponent is not None and not 0.0 <= exponent <= 2.0:
+        raise click.UsageError(f"--exponent must be in [0, 2] (got {exponent}).")
     x, sr = _load_signal(input_file, None)
     try:
-        y = add_noise(x, snr_db=snr, noise_type=noise_type.lower(), seed=seed)
+        if generator == "device":
+            from ..core.augment import add_noise_device
+            y = add_noise_device(x, snr_db=snr, noise_type=noise_type.lower(), seed=seed, exponent=exponent)
+        else:
+            y = add_noise(x, snr_db=snr, noise_type=noise_type.lower(), seed=seed)
     except ValueError as e:
         raise click.UsageError(f"Error during noise addition: {e}")
     _save_series(y, sr, output)

@@ -1,10 +1,12 @@
 """Device-backed mirror of sygnals/core/augment: add_noise and time_stretch.
 
 Each function takes and returns float64 NumPy like the reference; its `*_batch` form takes a float32 device tensor
-[B, L] and stays on the device.  Not mirrored: pitch_shift (the reference resamples with resampy's tabulated
+[B, L] and stays on the device.  add_noise_device / add_noise_device_batch / generate_noise_batch draw the noise on the
+device (this package's own generator, with real pink and brown noise).  Not mirrored: pitch_shift (the reference resamples with resampy's tabulated
 'kaiser_best' filter, which this package has nothing to pin a restatement against).
 """
 from .effects_based import time_stretch, time_stretch_batch
-from .noise import add_noise, add_noise_batch
+from .noise import add_noise, add_noise_batch, add_noise_device, add_noise_device_batch, generate_noise_batch
 
-__all__ = ["add_noise", "add_noise_batch", "time_stretch", "time_stretch_batch"]
+__all__ = ["add_noise", "add_noise_batch", "add_noise_device", "add_noise_device_batch", "generate_noise_batch", "time_stretch",
+           "time_stretch_batch"]

@@ -25,10 +25,12 @@
 // add_noise.  A row's two powers are needed before its first output sample.  A row of up to AN_RESIDENT samples is one
 // workgroup's: it sums while it copies y and noise into LDS and mixes from there (one launch, 12 bytes a sample).  A
 // longer row takes two launches: slice sums (so that one long row still fills the device), then the mix, which adds the
-// row's slices in slice order and reads y and noise again (20 bytes a sample).
+// row's slices in slice order and reads y and noise again (20 bytes a sample).  syg_fx_add_noise_gen_f32 is the same mix
+// on noise that is generated in registers and never stored (below, beside the kernels).
 #include <float.h>
 #include <math.h>
 #include "host.h"
+#include "rng_dev.h"
 
 namespace syg {
 namespace {
@@ -347,6 +349,200 @@ inline int noise_slices(int64_t B, int64_t L) {
   return (int)(s < most ? s : most);
 }
 
+// ------------------------------------------------------------------ add_noise with the noise generated in registers
+// The same arithmetic on noise[b, n] = the standard normal (seed, row first_row + b, n) of rng_dev.h, which never exists
+// in memory.  A thread owns whole Philox calls (four consecutive samples).  Resident (up to AN_RESIDENT samples): y alone
+// is kept in LDS, the row's noise in the threads' registers between the sums and the mix (ANG_QUADS calls a thread): one
+// launch, 8 bytes a sample, every normal drawn once.  Longer rows: the power pass and the mix pass both generate (12
+// bytes a sample); the power pass cuts a row into as many slices as make ANG_BLOCKS workgroups over the batch, each a
+// whole number of mix segments; one wave a row then adds the slices in a fixed order and leaves the row's scale factor,
+// so that no thread of the mix reads thousands of partial sums or evaluates pow.
+#ifndef SYG_ANG_THREADS
+#define SYG_ANG_THREADS 1024         // threads of the resident form; -DSYG_ANG_THREADS=512 builds the variant that
+#endif                               // tools/noise_bench.py --shapes 2048x16384 times beside it
+constexpr int ANG_THREADS = SYG_ANG_THREADS;        // (512: two workgroups a CU; measured slower)
+constexpr int ANG_QUADS = (int)(AN_RESIDENT / (4 * ANG_THREADS));
+constexpr int64_t ANG_BLOCKS = 2048;                // workgroups of the power pass that fill the device (8 a CU)
+constexpr int ANG_SEG_QUADS = AN_PER_THREAD / 4;    // calls a thread of the two-launch form owns per segment
+
+struct NoiseGenArgs {
+  const float* y; const double* snr; float* out; int64_t B, L, ldy, ldo; int S; int64_t slen; double2* part; double2* scale;
+  uint2 key; uint32_t first_row; int vy, vo;
+};
+
+// samples 4q .. 4q + 3 of a row of L: those past the end read as zero
+__device__ __forceinline__ float4 load_quad(const float* __restrict__ y, int64_t q, int64_t L, int vec) {
+  const int64_t n = 4 * q;
+  if (vec && n + 3 < L) return *(const float4*)(y + n);
+  return make_float4(n < L ? y[n] : 0.f, n + 1 < L ? y[n + 1] : 0.f, n + 2 < L ? y[n + 2] : 0.f, n + 3 < L ? y[n + 3] : 0.f);
+}
+
+__device__ __forceinline__ void store_quad(float* __restrict__ o, int64_t q, int64_t L, int vec, float4 v) {
+  const int64_t n = 4 * q;
+  if (vec && n + 3 < L) { *(float4*)(o + n) = v; return; }
+  if (n < L) o[n] = v.x;
+  if (n + 1 < L) o[n + 1] = v.y;
+  if (n + 2 < L) o[n + 2] = v.z;
+  if (n + 3 < L) o[n + 3] = v.w;
+}
+
+// the call's normals with those past the end of the row set to zero (they add nothing to the noise power)
+__device__ __forceinline__ float4 noise_quad(uint2 key, int64_t q, uint32_t row, int64_t L) {
+  float4 z = rng_normal4(key, (uint64_t)q, row);
+  const int64_t n = 4 * q;
+  if (n + 1 >= L) z.y = 0.f;
+  if (n + 2 >= L) z.z = 0.f;
+  if (n + 3 >= L) z.w = 0.f;
+  return z;
+}
+
+// noise_quad fenced in by two volatile statements, which keep their order: the calls of an unrolled loop then run one
+// after the other.  Interleaved by the compiler, the temporaries of four or eight Philox chains spill to scratch.
+__device__ __forceinline__ float4 noise_quad_fenced(uint2 key, int64_t q, uint32_t row, int64_t L) {
+  int ql = (int)q, qh = (int)(q >> 32);
+  asm volatile("" : "+v"(ql), "+v"(qh));
+  float4 z = noise_quad(key, (int64_t)(((uint64_t)(uint32_t)qh << 32) | (uint32_t)ql), row, L);
+  asm volatile("" : "+v"(z.x), "+v"(z.y), "+v"(z.z), "+v"(z.w));
+  return z;
+}
+
+__device__ __forceinline__ double quad_power(float4 v) {
+  return ((double)v.x * (double)v.x + (double)v.y * (double)v.y) + ((double)v.z * (double)v.z + (double)v.w * (double)v.w);
+}
+
+__device__ __forceinline__ float4 noise_mix4(float4 y, float4 z, double s, bool mix) {
+  if (!mix) return y;
+  return make_float4(noise_mix(y.x, z.x, s), noise_mix(y.y, z.y, s), noise_mix(y.z, z.z, s), noise_mix(y.w, z.w, s));
+}
+
+__global__ __launch_bounds__(ANG_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void noise_gen_resident_kernel(NoiseGenArgs A) {
+  constexpr int NQ = ANG_QUADS;
+  extern __shared__ float4 ang_row[];        // y [4 ceil(L / 4)], the tail zero
+  __shared__ double red[2][ANG_THREADS / 64];
+  __shared__ double2 scale;
+  float* sy = (float*)ang_row;
+  const int L = (int)A.L, Lq = (L + 3) >> 2;
+  for (int64_t b = blockIdx.x; b < A.B; b += gridDim.x) {
+    const float* y = A.y + b * A.ldy;
+    float* out = A.out + b * A.ldo;
+    int tid = threadIdx.x;                                         // taken anew for every row: what is derived from it and
+    asm volatile("" : "+v"(tid));                                  // hoisted out of the row loop would live in scratch
+    double a = 0.0, c = 0.0;
+    for (int i = tid; i < 4 * Lq; i += ANG_THREADS) {
+      const float v = i < L ? y[i] : 0.f;
+      sy[i] = v;
+      a += (double)v * (double)v;
+    }
+    float4 z[NQ];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+      const int q = tid + j * ANG_THREADS;
+      z[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (q < Lq) {
+        z[j] = noise_quad_fenced(A.key, q, A.first_row + (uint32_t)b, L);
+        c += quad_power(z[j]);
+      }
+    }
+    block_sum2<ANG_THREADS>(a, c, red);       // (its barriers also order the stores of y before the reads below)
+    if (tid == 0) {                          // one thread: pow in every wave costs as much as the wave's share of the noise
+      double s0 = 0.0;
+      const bool on = noise_scale(a / (double)A.L, c / (double)A.L, A.snr[b], s0);
+      scale = make_double2(on ? s0 : 0.0, on ? 1.0 : 0.0);
+    }
+    __syncthreads();
+    const double s = scale.x;
+    const bool mix = scale.y != 0.0;
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+      const int q = tid + j * ANG_THREADS;
+      if (q < Lq) store_quad(out, q, L, A.vo, noise_mix4(ang_row[q], z[j], s, mix));
+      asm volatile("" ::: "memory");         // one call's samples after the other: no LDS read ahead across this
+    }
+    __syncthreads();                         // the next row overwrites y
+  }
+}
+
+// part[b, sl] = (sum y^2, sum noise^2) over slice sl (slen samples, a multiple of AN_SEG) of row b; grid (S, rows)
+__global__ __launch_bounds__(FX_THREADS) void noise_gen_power_kernel(NoiseGenArgs A) {
+  __shared__ double red[2][FX_THREADS / 64];
+  const int64_t n0 = (int64_t)blockIdx.x * A.slen, n1 = (A.L - n0 > A.slen) ? n0 + A.slen : A.L;
+  for (int64_t b = blockIdx.y; b < A.B; b += gridDim.y) {
+    const float* y = A.y + b * A.ldy;
+    double a = 0.0, c = 0.0;
+    for (int64_t q = (n0 >> 2) + threadIdx.x; 4 * q < n1; q += FX_THREADS) {
+      a += quad_power(load_quad(y, q, A.L, A.vy));
+      c += quad_power(noise_quad(A.key, q, A.first_row + (uint32_t)b, A.L));
+    }
+    block_sum2<FX_THREADS>(a, c, red);
+    if (threadIdx.x == 0) A.part[b * A.S + blockIdx.x] = make_double2(a, c);
+  }
+}
+
+// scale[b] = (the row's scale factor, 1), or (0, 0) for a row that is copied.  One wave a row: lane l adds its run of
+// ceil(S / 64) consecutive slices in slice order, lane 0 the 64 runs in lane order (S <= 64: plain slice order).
+__global__ __launch_bounds__(64) void noise_gen_scale_kernel(NoiseGenArgs A) {
+  __shared__ double run[2][64];
+  const int lane = threadIdx.x, per = (A.S + 63) / 64;
+  for (int64_t b = blockIdx.x; b < A.B; b += gridDim.x) {
+    double a = 0.0, c = 0.0;
+    for (int sl = lane * per; sl < (lane + 1) * per && sl < A.S; ++sl) { const double2 p = A.part[b * A.S + sl]; a += p.x; c += p.y; }
+    run[0][lane] = a;
+    run[1][lane] = c;
+    __syncthreads();
+    if (lane == 0) {
+      a = 0.0; c = 0.0;
+      for (int l = 0; l < 64; ++l) { a += run[0][l]; c += run[1][l]; }
+      double s = 0.0;
+      const bool mix = noise_scale(a / (double)A.L, c / (double)A.L, A.snr[b], s);
+      A.scale[b] = make_double2(mix ? s : 0.0, mix ? 1.0 : 0.0);
+    }
+    __syncthreads();
+  }
+}
+
+// grid (segments of AN_SEG samples, rows); the noise is generated again
+__global__ __launch_bounds__(FX_THREADS) void noise_gen_mix_kernel(NoiseGenArgs A) {
+  const int64_t q0 = (int64_t)blockIdx.x * (AN_SEG / 4) + threadIdx.x;
+  for (int64_t b = blockIdx.y; b < A.B; b += gridDim.y) {
+    const double2 sc = A.scale[b];
+    const double s = sc.x;
+    const bool mix = sc.y != 0.0;
+    const float* y = A.y + b * A.ldy;
+    float* out = A.out + b * A.ldo;
+    float4 v[ANG_SEG_QUADS];
+#pragma unroll
+    for (int j = 0; j < ANG_SEG_QUADS; ++j) {                    // every load in flight ahead of the generator
+      const int64_t q = q0 + (int64_t)j * FX_THREADS;
+      v[j] = 4 * q < A.L ? load_quad(y, q, A.L, A.vy) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int j = 0; j < ANG_SEG_QUADS; ++j) {
+      const int64_t q = q0 + (int64_t)j * FX_THREADS;
+      if (4 * q < A.L) {
+        const float4 z = mix ? noise_quad_fenced(A.key, q, A.first_row + (uint32_t)b, A.L) : make_float4(0.f, 0.f, 0.f, 0.f);
+        store_quad(out, q, A.L, A.vo, noise_mix4(v[j], z, s, mix));
+      }
+    }
+  }
+}
+
+// the power pass of the generating form: slices of a whole number of mix segments, ANG_BLOCKS workgroups over the batch
+inline void noise_gen_slices(int64_t B, int64_t L, int& S, int64_t& slen) {
+  int64_t s = ceil_div(ANG_BLOCKS, B);
+  const int64_t most = ceil_div(L, AN_SEG);
+  if (s > most) s = most;
+  slen = ceil_div(ceil_div(L, s), AN_SEG) * AN_SEG;
+  S = (int)ceil_div(L, slen);
+}
+
+int check_noise_gen_shape(int64_t B, int64_t L, int64_t first_row) {
+  SYG_REQUIRE(B >= 1 && L >= 1 && L < ((int64_t)1 << 39), "fx_add_noise_gen: bad B / L");
+  SYG_REQUIRE(first_row >= 0 && B <= RNG_ROW_LIMIT && first_row <= RNG_ROW_LIMIT - B,
+              "fx_add_noise_gen: rows first_row .. first_row + B - 1 must lie in [0, 2^31) (got first_row = %lld, B = %lld)",
+              (long long)first_row, (long long)B);
+  return SYG_OK;
+}
+
 inline dim3 rows_grid(int64_t L, int64_t rows) {
   return dim3((unsigned)ceil_div(L, FX_THREADS), (unsigned)(rows < FX_MAX_ROWS_Y ? rows : FX_MAX_ROWS_Y));
 }
@@ -538,5 +734,45 @@ extern "C" int syg_fx_add_noise_f32(const float* y, int64_t B, int64_t L, int64_
   SYG_CHECK_LAUNCH("fx_add_noise");
   hipLaunchKernelGGL(noise_mix_kernel, dim3((unsigned)ceil_div(L, AN_SEG), gy), dim3(FX_THREADS), 0, st, A);
   SYG_CHECK_LAUNCH("fx_add_noise");
+  return SYG_OK;
+}
+
+extern "C" int64_t syg_fx_add_noise_gen_work_bytes(int64_t B, int64_t L) {
+  if (check_noise_gen_shape(B, L, 0)) return -1;
+  if (L <= AN_RESIDENT) return 0;
+  int S; int64_t slen;
+  noise_gen_slices(B, L, S, slen);
+  return (B * S + B) * (int64_t)sizeof(double2);            // the slice sums, then the rows' scale factors
+}
+
+extern "C" int syg_fx_add_noise_gen_f32(const float* y, int64_t B, int64_t L, int64_t ldy, uint64_t seed, int64_t first_row,
+                                        const double* snr_db, float* out, int64_t ldo, void* work, void* stream) {
+  SYG_REQUIRE(y && snr_db && out, "fx_add_noise_gen: null pointer argument (y / snr_db / out)");
+  if (const int rc = check_noise_gen_shape(B, L, first_row)) return rc;
+  SYG_REQUIRE(ldy >= L && ldo >= L, "fx_add_noise_gen: bad ldy / ldo");
+  hipStream_t st = (hipStream_t)stream;
+  const int vy = ((uintptr_t)y & 15) == 0 && (ldy & 3) == 0, vo = ((uintptr_t)out & 15) == 0 && (ldo & 3) == 0;
+  NoiseGenArgs A{y, snr_db, out, B, L, ldy, ldo, 1, L, nullptr, nullptr, rng_key(seed), (uint32_t)first_row, vy, vo};
+  const int64_t cap = (int64_t)device_cu_count() * 8;
+  if (L <= AN_RESIDENT) {
+    const size_t lds = (size_t)ceil_div(L, 4) * sizeof(float4);
+    if (const int rc = reserve_dynamic_lds("fx_add_noise_gen", (const void*)noise_gen_resident_kernel, lds)) return rc;
+    hipLaunchKernelGGL(noise_gen_resident_kernel, dim3((unsigned)(B < cap ? B : cap)), dim3(ANG_THREADS), lds, st, A);
+    SYG_CHECK_LAUNCH("fx_add_noise_gen");
+    return SYG_OK;
+  }
+  SYG_REQUIRE(work, "fx_add_noise_gen: a row past %lld samples takes three launches and needs `work` (syg_fx_add_noise_gen_work_bytes)",
+              (long long)AN_RESIDENT);
+  SYG_REQUIRE(((uintptr_t)work & 15) == 0, "fx_add_noise_gen: `work` must be 16-byte aligned");
+  noise_gen_slices(B, L, A.S, A.slen);
+  A.part = (double2*)work;
+  A.scale = A.part + B * A.S;
+  const unsigned gy = (unsigned)(B < FX_MAX_ROWS_Y ? B : FX_MAX_ROWS_Y);
+  hipLaunchKernelGGL(noise_gen_power_kernel, dim3((unsigned)A.S, gy), dim3(FX_THREADS), 0, st, A);
+  SYG_CHECK_LAUNCH("fx_add_noise_gen");
+  hipLaunchKernelGGL(noise_gen_scale_kernel, dim3((unsigned)(B < cap ? B : cap)), dim3(64), 0, st, A);
+  SYG_CHECK_LAUNCH("fx_add_noise_gen");
+  hipLaunchKernelGGL(noise_gen_mix_kernel, dim3((unsigned)ceil_div(L, AN_SEG), gy), dim3(FX_THREADS), 0, st, A);
+  SYG_CHECK_LAUNCH("fx_add_noise_gen");
   return SYG_OK;
 }

@@ -19,6 +19,7 @@ from . import _cwt as CW
 from . import _laplace as LP
 from . import _lpc
 from . import _resample as RS
+from . import _rng as RNG
 from . import _tables as T
 from ._fftplan import (MAX_LDS_FFT, MAX_MIXED_FFT, MAX_ROWS, conv_fft_len, fft_plan, is_pow2,      # noqa: F401 (re-exported)
                        next_direct_len, smooth_split)
@@ -2206,6 +2207,18 @@ def fx_add_noise_resident_max() -> int:
     return int(lib().syg_fx_add_noise_resident_max())
 
 
+def _snr_dev(snr_db, B: int, who: str) -> torch.Tensor:
+    """snr_db (a number, one per row, or a float64 device tensor [B]) as the float64 device array [B] of the mix."""
+    if isinstance(snr_db, torch.Tensor) and snr_db.is_cuda:          # one per row, already on the device: no round trip
+        if snr_db.dtype != torch.float64 or tuple(snr_db.shape) != (B,):
+            raise ValueError(f"{who}: a device snr_db must be a float64 tensor [B]")
+        return snr_db.contiguous()
+    snr = np.asarray(snr_db, dtype=np.float64)
+    if snr.ndim > 1 or (snr.ndim == 1 and snr.shape[0] != B) or not np.all(np.isfinite(snr)):
+        raise ValueError(f"{who}: snr_db must be a finite number or one per row")
+    return _dev(np.broadcast_to(snr, (B,)))
+
+
 def fx_add_noise(y: torch.Tensor, noise: torch.Tensor, snr_db, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y + noise scaled per row to the signal-to-noise ratio snr_db (a number, or one per row), powers in float64
     (syg_fx_add_noise_f32); a row whose signal or noise power is below the float64 epsilon is copied.  `out` may be y."""
@@ -2215,21 +2228,116 @@ def fx_add_noise(y: torch.Tensor, noise: torch.Tensor, snr_db, out: Optional[tor
     B, L = y.shape
     if B < 1 or L < 1:
         raise ValueError("fx_add_noise: empty input")
-    if isinstance(snr_db, torch.Tensor) and snr_db.is_cuda:          # one per row, already on the device: no round trip
-        if snr_db.dtype != torch.float64 or tuple(snr_db.shape) != (B,):
-            raise ValueError("fx_add_noise: a device snr_db must be a float64 tensor [B]")
-        snr = snr_db.contiguous()
-    else:
-        snr = np.asarray(snr_db, dtype=np.float64)
-        if snr.ndim > 1 or (snr.ndim == 1 and snr.shape[0] != B) or not np.all(np.isfinite(snr)):
-            raise ValueError("fx_add_noise: snr_db must be a finite number or one per row")
-        snr = _dev(np.broadcast_to(snr, (B,)))
+    snr = _snr_dev(snr_db, B, "fx_add_noise")
     out = _fx_out(y, out)
     wb = lib().syg_fx_add_noise_work_bytes(B, L)
     if wb < 0:
         check(-1, "syg_fx_add_noise_work_bytes")
     work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device) if wb > 0 else None
     _call("syg_fx_add_noise_f32", _ptr(y), B, L, _ld(y), _ptr(noise), _ld(noise), _ptr(snr), _ptr(out), _ld(out), _ptr(work))
+    return out
+
+
+# ------------------------------------------------------------------ noise generation
+def rng_constants() -> dict:
+    """The figures the device generator rests on (the library owns them): Philox rounds, the stream ids of noise samples
+    and of per-row draws, the row limit, the longest coloured row."""
+    h = lib()
+    return dict(rounds=int(h.syg_rng_constants(0)), stream_noise=int(h.syg_rng_constants(1)), stream_row=int(h.syg_rng_constants(2)),
+                row_limit=int(h.syg_rng_constants(3)), colored_max=int(h.syg_rng_constants(4)))
+
+
+def philox_words(counter, key) -> torch.Tensor:
+    """Raw Philox4x32-10 words of the device generator: counter [n, 4], key [n, 2] (or one key [2]) uint32 host arrays ->
+    int32 device tensor [n, 4] holding the words' bits (`.cpu().numpy().view(np.uint32)`)."""
+    device = require_gpu()
+    c = np.array(counter, dtype=np.uint32).reshape(-1, 4)
+    k = np.broadcast_to(np.asarray(key, dtype=np.uint32).reshape(-1, 2), (c.shape[0], 2)).copy()
+    if c.shape[0] < 1:
+        raise ValueError("philox_words: no counters")
+    cd = torch.from_numpy(c.view(np.int32)).to(device)
+    kd = torch.from_numpy(k.view(np.int32)).to(device)
+    out = torch.empty_like(cd)
+    _call("syg_rng_philox_u32", _ptr(cd), _ptr(kd), c.shape[0], _ptr(out))
+    return out
+
+
+def _rng_shape(who: str, B, L, seed, first_row):
+    if not (isinstance(B, (int, np.integer)) and isinstance(L, (int, np.integer))) or B < 1 or L < 1:
+        raise ValueError(f"{who}: B and L must be positive integers")
+    return int(B), int(L), RNG.check_seed(seed), RNG.check_rows(first_row, int(B))
+
+
+def randn(B: int, L: int, seed: int, first_row: int = 0, offset: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Standard normals [B, L] float32 on the device (syg_rng_normal_f32): samples offset .. offset + L - 1 of rows
+    first_row .. first_row + B - 1 of `seed`.  A sample depends on (seed, row, sample index) alone, so a batch equals its
+    rows and randn(L)[k:] equals randn(L - k, offset=k), bit for bit.  `out`: a float32 device tensor [B, L] with unit
+    stride along a row (any row stride) to write into."""
+    B, L, seed, first_row = _rng_shape("randn", B, L, seed, first_row)
+    if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or not 0 <= offset < (1 << 62):
+        raise ValueError(f"randn: offset must be an integer in [0, 2^62) (got {offset!r})")
+    if out is None:
+        out = torch.empty((B, L), dtype=torch.float32, device=require_gpu())
+    elif tuple(out.shape) != (B, L) or out.dtype != torch.float32 or not out.is_cuda or out.stride(1) != 1:
+        raise ValueError(f"out must be a float32 device tensor {(B, L)} with unit stride along a row")
+    _call("syg_rng_normal_f32", _ptr(out), B, L, _ld(out), seed, first_row, int(offset))
+    return out
+
+
+def colored_noise_fft_len(L: int) -> int:
+    """M of colored_noise: the smallest power of two >= max(L, 2)."""
+    return 1 << max(1, (int(L) - 1).bit_length())
+
+
+def colored_noise(B: int, L: int, seed: int, exponent: float, first_row: int = 0) -> torch.Tensor:
+    """Power-law noise [B, L] float32 on the device, spectral density ~ 1 / f^exponent (1 pink, 2 brown; 0 <= exponent <= 2):
+    noise[r] = irfft(rfft(w_r) g, M)[:L] with M = colored_noise_fft_len(L), w_r the M white samples of (seed, row r) that
+    randn gives, g[0] = 0 and g[k] = k^(-exponent / 2) (Timmer & Koenig 1995): exact in slope, zero-mean over M, free of
+    wrap-around correlation unless L = M.  At exponent 0 the gain is 1 everywhere (0^0 = 1) and the row is randn's.  Rows
+    r and r ^ 1 (absolute indices) share one complex transform, so a row's bits never depend on the batch it came in.
+    L = 1 gives a zero row (one zero-mean sample).  L <= 2^26.  The unit of the result is arbitrary: mix it at a
+    signal-to-noise ratio (fx_add_noise)."""
+    B, L, seed, first_row = _rng_shape("colored_noise", B, L, seed, first_row)
+    exponent = float(exponent)
+    if not 0.0 <= exponent <= 2.0:                                   # (NaN fails both comparisons)
+        raise ValueError(f"colored_noise: exponent must be in [0, 2] (got {exponent})")
+    M = colored_noise_fft_len(L)
+    if M > int(lib().syg_rng_constants(4)):
+        raise SygnalsHipError(f"colored_noise: L = {L} exceeds the supported maximum 2^26")
+    device = require_gpu()
+    if L == 1:
+        return torch.zeros((B, 1), dtype=torch.float32, device=device)
+    out = torch.empty((B, L), dtype=torch.float32, device=device)
+    pair0, pair1 = first_row >> 1, (first_row + B - 1) >> 1          # absolute pairs (r >> 1) the rows lie in
+    step = max(1, min(MAX_ROWS // 2, (1 << 26) // M))                # pairs of one pass: <= 512 MiB a buffer
+    for p in range(pair0, pair1 + 1, step):
+        P = min(step, pair1 + 1 - p)
+        Z = torch.empty((P, M, 2), dtype=torch.float32, device=device)
+        _call("syg_rng_normal_pairs_c64", _ptr(Z), P, M, seed, 2 * p)
+        X = fft_pow2_any(Z)
+        _call("syg_rng_power_gain_c64", _ptr(X), P, M, exponent)
+        Z = fft_pow2_any(X, inverse=True)
+        r0, r1 = max(first_row, 2 * p), min(first_row + B, 2 * (p + P))      # the asked rows of these pairs
+        rows = out[r0 - first_row:r1 - first_row]
+        _call("syg_rng_unpack_pairs_f32", _ptr(Z), M, r0, _ptr(rows), r1 - r0, L, L)
+    return out
+
+
+def fx_add_noise_gen(y: torch.Tensor, snr_db, seed: int, first_row: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fx_add_noise(y, randn(B, L, seed, first_row), snr_db) without the noise ever existing in memory
+    (syg_fx_add_noise_gen_f32): within one float32 ulp of that call (the sums are taken in another order).  `out` may be y."""
+    y = _clips(y, "y")
+    B, L = y.shape
+    if B < 1 or L < 1:
+        raise ValueError("fx_add_noise_gen: empty input")
+    seed, first_row = RNG.check_seed(seed), RNG.check_rows(first_row, B)
+    snr = _snr_dev(snr_db, B, "fx_add_noise_gen")
+    out = _fx_out(y, out)
+    wb = lib().syg_fx_add_noise_gen_work_bytes(B, L)
+    if wb < 0:
+        check(-1, "syg_fx_add_noise_gen_work_bytes")
+    work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device) if wb > 0 else None
+    _call("syg_fx_add_noise_gen_f32", _ptr(y), B, L, _ld(y), seed, first_row, _ptr(snr), _ptr(out), _ld(out), _ptr(work))
     return out
 
 
