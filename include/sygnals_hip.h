@@ -1161,6 +1161,48 @@ int syg_rng_power_gain_c64(float* X, int64_t rows, int64_t M, double alpha, void
 int syg_rng_unpack_pairs_f32(const float* Z, int64_t M, int64_t first_row, float* out, int64_t B, int64_t L, int64_t ldo,
                              void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Cross-spectral analysis of two real signals (cross_spectrum.hip): scipy.signal.csd / welch / coherence with
+ * return_onesided=True, average='mean'.  Segment s starts at s * step, nseg = (L - (nperseg - step)) / step; detrend,
+ * window, zero padding to nfft, scale and the one-sided factor as syg_welch_f32, each signal detrended on its own.
+ *   Pxy = mean_s conj(X_s) Y_s,  Pxx = mean_s |X_s|^2,  Pyy = mean_s |Y_s|^2,  Cxy = |Pxy|^2 / (Pxx Pyy)
+ * Cxy is formed in float64 from the raw float64 sums (scale and one-sided factor cancel); 0 / 0 gives NaN.
+ * Outputs: pxy_out [B, F][2], pxx_out, pyy_out, coh_out [B, F] float32, F = nfft / 2 + 1; any may be NULL, not all.
+ *
+ * syg_csd_f32, the fused form: nfft a power of two in [8, 8192], nperseg <= nfft, 1 <= step <= nperseg, B <= 65535.
+ *   x [B, L] (row stride ldx), y [By, L] (row stride ldy), By = B or 1: one reference row read by every x row.
+ *   twiddle [nfft] complex, W_nfft^k (as syg_fft_pow2_c2c_f32).  One complex transform per segment carries both signals.
+ *   A row's segments are split over workgroups by the segment count alone (runs of max(16, ceil(nseg / 2048))
+ *   consecutive segments), so a batch equals its rows bit for bit; no atomics: the same call gives the same bits.
+ *   work: syg_csd_work_bytes(B, nseg, nfft) bytes (-1 for B, nseg < 1 or nfft < 2): the float32 partial sums
+ *   [B, workgroups, 4, F], then the float64 slice sums [B, slices, 4, F] (16 slices from 64 workgroups, else 1).
+ * syg_csd_rows_f32, every other length: X, Y [rows, n][2] are the full complex spectra of `rows` consecutive segments
+ *   of ONE row pair (the caller packs and transforms them); acc [4, F] float64 is the caller's and carries the raw sums
+ *   from call to call: `first` starts them, `last` writes the outputs with scale / nseg.  Segment order, float64.
+ *
+ * Generalised cross-correlation:
+ * syg_gcc_weight_c64  out[r, k] = W X[r, k] conj(Y[ry, k]), k < n, over plain complex spectra [rows, n][2] (Y: rows_y = 1
+ *                     or rows); phat 0: W = 1; 1: W = 1 / |X conj(Y)|, 0 on a bin that is exactly 0.  out may be X.
+ * syg_gcc_crop_f32    out[r, j] = Re c[r, (j - max_lag) mod n], j in [0, 2 max_lag]; 2 max_lag + 1 <= n.
+ * syg_peak_pick_f32   per row of r [B, W] (row stride ldr), one wave: i* = the first maximum; lag = lag0 + i*; where i* is
+ *                     interior and den = r[i*-1] - 2 r[i*] + r[i*+1] < 0, delta = (r[i*-1] - r[i*+1]) / (2 den) and
+ *                     peak = r[i*] - (r[i*-1] - r[i*+1]) delta / 4, else delta = 0 and peak = r[i*] (float64);
+ *                     delay = (lag + delta) / fs.  A row of NaN gives NaN, lag 0.
+ * Every argument check is made before any device work.
+ * ------------------------------------------------------------------------------- */
+int64_t syg_csd_work_bytes(int64_t B, int64_t nseg, int nfft);
+int syg_csd_f32(const float* x, const float* y, int64_t B, int64_t By, int64_t L, int64_t ldx, int64_t ldy, int nperseg,
+                int step, int nfft, const float* window, const float* twiddle, int detrend, double scale, float* pxy_out,
+                float* pxx_out, float* pyy_out, float* coh_out, void* work, void* stream);
+int syg_csd_rows_f32(const float* X, const float* Y, int64_t rows, int64_t n, double* acc, int first, int last,
+                     int64_t nseg, double scale, float* pxy_out, float* pxx_out, float* pyy_out, float* coh_out,
+                     void* stream);
+int syg_gcc_weight_c64(const float* X, const float* Y, int64_t rows, int64_t rows_y, int64_t n, int phat, float* out,
+                       void* stream);
+int syg_gcc_crop_f32(const float* c, int64_t rows, int64_t n, int64_t max_lag, float* out, void* stream);
+int syg_peak_pick_f32(const float* r, int64_t B, int64_t W, int64_t ldr, int64_t lag0, double fs, double* delay_out,
+                      int64_t* lag_out, double* peak_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

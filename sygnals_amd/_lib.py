@@ -176,6 +176,12 @@ SIGNATURES = {
     "syg_rng_normal_pairs_c64": (_i, [_p, _l, _l, _u, _l, _p]),
     "syg_rng_power_gain_c64": (_i, [_p, _l, _l, _d, _p]),
     "syg_rng_unpack_pairs_f32": (_i, [_p, _l, _l, _p, _l, _l, _l, _p]),
+    "syg_csd_work_bytes": (_l, [_l, _l, _i]),
+    "syg_csd_f32": (_i, [_p, _p, _l, _l, _l, _l, _l, _i, _i, _i, _p, _p, _i, _d, _p, _p, _p, _p, _p, _p]),
+    "syg_csd_rows_f32": (_i, [_p, _p, _l, _l, _p, _i, _i, _l, _d, _p, _p, _p, _p, _p]),
+    "syg_gcc_weight_c64": (_i, [_p, _p, _l, _l, _l, _i, _p, _p]),
+    "syg_gcc_crop_f32": (_i, [_p, _l, _l, _l, _p, _p]),
+    "syg_peak_pick_f32": (_i, [_p, _l, _l, _l, _l, _d, _p, _p, _p, _p]),
 }
 
 _lib = None

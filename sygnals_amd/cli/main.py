@@ -278,6 +278,99 @@ def dsp_dtw(input_file_1, input_file_2, output, metric, subseq, on):
     click.echo(f"DTW path ({len(wp)} steps) saved to '{Path(output).name}'.")
 
 
+def _load_pair(input_file_1, input_file_2, fs):
+    """Two signals of ONE sampling rate: --fs when given, else the rate the files carry (both, and equal) or none."""
+    x, sr_x = _load_signal(input_file_1, None)
+    y, sr_y = _load_signal(input_file_2, None)
+    if fs is None and sr_x and sr_y and sr_x != sr_y:
+        raise click.UsageError(f"The inputs have different sampling rates ({sr_x} Hz and {sr_y} Hz): bring them to one "
+                               "rate with `dsp resample` first.")
+    return x, y, (fs if fs is not None else (sr_x or sr_y))
+
+
+def _welch_options(f):
+    for opt in (click.option("--scaling", type=click.Choice(["density", "spectrum"]), default="density", show_default=True),
+                click.option("--detrend", type=click.Choice(["none", "constant", "linear"]), default="constant", show_default=True),
+                click.option("--nfft", type=int, default=None),
+                click.option("--noverlap", type=int, default=None),
+                click.option("--nperseg", type=int, default=None),
+                click.option("--window", default="hann", show_default=True),
+                click.option("--fs", type=float, default=None, help="Sampling frequency (Hz); default: the files' own, else 1."),
+                click.option("-o", "--output", required=True, type=click.Path()),
+                click.argument("input_file_2", type=click.Path(exists=True, dir_okay=False)),
+                click.argument("input_file_1", type=click.Path(exists=True, dir_okay=False))):
+        f = opt(f)
+    return f
+
+
+@dsp_cmd.command("csd")
+@_welch_options
+def dsp_csd(input_file_1, input_file_2, output, fs, window, nperseg, noverlap, nfft, detrend, scaling):
+    """Estimate the cross-spectral density of two signals (Welch's method, scipy.signal.csd)."""
+    from ..core.dsp import compute_csd
+    x, y, fs = _load_pair(input_file_1, input_file_2, fs)
+    try:
+        f, p = compute_csd(x, y, fs=fs or 1.0, window=window, nperseg=nperseg, noverlap=noverlap, nfft=nfft,
+                           detrend=False if detrend == "none" else detrend, scaling=scaling)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    if Path(output).suffix.lower() == ".npz":
+        sio.save_data({"frequencies": f, "csd": p}, output)
+    else:
+        sio.save_data(pd.DataFrame({"Frequency (Hz)": f, "Real": p.real, "Imag": p.imag, "Magnitude": np.abs(p),
+                                    "Phase": np.angle(p)}), output)
+    click.echo(f"Cross-spectral density saved to '{Path(output).name}'.")
+
+
+@dsp_cmd.command("coherence")
+@_welch_options
+def dsp_coherence(input_file_1, input_file_2, output, fs, window, nperseg, noverlap, nfft, detrend, scaling):
+    """Estimate the magnitude-squared coherence of two signals (scipy.signal.coherence; --scaling has no effect on it)."""
+    from ..core.dsp import compute_coherence
+    x, y, fs = _load_pair(input_file_1, input_file_2, fs)
+    try:
+        f, c = compute_coherence(x, y, fs=fs or 1.0, window=window, nperseg=nperseg, noverlap=noverlap, nfft=nfft,
+                                 detrend=False if detrend == "none" else detrend)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    if Path(output).suffix.lower() == ".npz":
+        sio.save_data({"frequencies": f, "coherence": c}, output)
+    else:
+        sio.save_data(pd.DataFrame({"Frequency (Hz)": f, "Coherence": c}), output)
+    click.echo(f"Coherence saved to '{Path(output).name}'.")
+
+
+@dsp_cmd.command("delay")
+@click.argument("input_file_1", type=click.Path(exists=True, dir_okay=False))
+@click.argument("input_file_2", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--fs", type=float, default=None, help="Sampling frequency (Hz); default: the files' own, else 1.")
+@click.option("--max-lag", type=int, default=None, help="Largest lag searched, in samples.")
+@click.option("--max-delay", type=float, default=None, help="Largest delay searched, in seconds.")
+@click.option("--weighting", type=click.Choice(["none", "phat"]), default="phat", show_default=True)
+def dsp_delay(input_file_1, input_file_2, output, fs, max_lag, max_delay, weighting):
+    """Estimate the delay of the first signal against the second (generalised cross-correlation)."""
+    from ..core.alignment import estimate_delay
+    if max_lag is not None and max_delay is not None:
+        raise click.UsageError("--max-lag and --max-delay cannot be combined: give one of them.")
+    x, y, fs = _load_pair(input_file_1, input_file_2, fs)
+    fs = fs or 1.0
+    if max_delay is not None:
+        if not (max_delay >= 0):
+            raise click.UsageError("--max-delay must be at least 0 seconds.")
+        max_lag = int(np.floor(max_delay * fs + 1e-9))
+    try:
+        delay, lag, peak = estimate_delay(x, y, fs=fs, max_lag=max_lag, weighting=weighting)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    if Path(output).suffix.lower() == ".npz":
+        sio.save_data({"delay_seconds": np.array(delay), "lag": np.array(lag), "peak": np.array(peak), "fs": np.array(fs),
+                       "weighting": np.array(weighting)}, output)
+    else:
+        sio.save_data(pd.DataFrame({"delay_seconds": [delay], "lag": [lag], "peak": [peak]}), output)
+    click.echo(f"Delay {delay:.9g} s (lag {lag}) saved to '{Path(output).name}'.")
+
+
 @dsp_cmd.command("hilbert")
 @click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
 @click.option("-o", "--output", required=True, type=click.Path())

@@ -6,6 +6,8 @@ Served: the four metrics euclidean, sqeuclidean, cityblock, cosine or a caller's
 ValueError: another step set, global_constraints, another metric or a callable, a non-finite C, a step matrix above
 MAX_STEP_CELLS.  Parity is unpinned (librosa is not a dependency): the contract is the float64 restatement
 tests/dtw_ref.py.  The accumulated cost is float64 on the device and depends on nothing but the float32 cost matrix.
+
+Below DTW: generalised cross-correlation and delay estimation (gcc_batch, estimate_delay_batch, estimate_delay).
 """
 from __future__ import annotations
 
@@ -132,3 +134,72 @@ def dtw_distance_batch(X=None, Y=None, *, C=None, metric="euclidean", x_len=None
     wm, wa = _check_weights(weights_add, weights_mul)
     Cd = _batch_cost(X, Y, C, metric, x_len, y_len)
     return ops.dtw(Cd, x_len, y_len, wm, wa, bool(subseq), want_path=False)["cost"]
+
+
+# ------------------------------------------------------------------ generalised cross-correlation and delay estimation
+# (the reference's specification lists cross-correlation, docs/dev_spec_v1.0.0.md 3.5, and multi-channel handling, 3.7).
+# Served: real float32 rows, y with one row (a reference channel) or one per row of x, the weightings "none" (plain
+# cross-correlation: scipy.signal.correlate(x, y, "full") at scipy.signal.correlation_lags) and "phat" (phase transform).
+# Refused with a ValueError: another weighting (SCOT, Roth, ML), complex or empty input, a max_lag above
+# min(Lx, Ly) - 1.  The contract is the float64 restatement tests/xspec_ref.py.
+GCC_WEIGHTINGS = tuple(ops.GCC_WEIGHTINGS)
+_GCC_SERVED = ("served: real float32 rows x [B, Lx] and y [1 or B, Ly], weighting in " + ", ".join(GCC_WEIGHTINGS)
+               + ", 0 <= max_lag <= min(Lx, Ly) - 1")
+
+
+def _gcc_args(x, y, max_lag, weighting, who):
+    if not isinstance(weighting, str) or weighting not in GCC_WEIGHTINGS:
+        raise ValueError(f"{who}: weighting {weighting!r} is not served ({_GCC_SERVED})")
+    for t, name in ((x, "x"), (y, "y")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{who}: {name} must be a [rows, samples] device tensor ({_GCC_SERVED})")
+        if t.is_complex():
+            raise ValueError(f"{who}: complex input is not served ({_GCC_SERVED})")
+        if t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{who}: {name} is empty, shape {tuple(t.shape)} ({_GCC_SERVED})")
+    if y.shape[0] not in (1, x.shape[0]):
+        raise ValueError(f"{who}: y must have one row or one row per row of x ({x.shape[0]}), got {y.shape[0]} ({_GCC_SERVED})")
+    top = min(x.shape[1], y.shape[1]) - 1
+    if max_lag is None:
+        max_lag = top
+    if isinstance(max_lag, bool) or int(max_lag) != max_lag or not (0 <= max_lag <= top):
+        raise ValueError(f"{who}: max_lag={max_lag} is outside 0 ... min(Lx, Ly) - 1 = {top} ({_GCC_SERVED})")
+    return int(max_lag)
+
+
+def gcc_batch(x, y, max_lag: Optional[int] = None, weighting: str = "none"):
+    """Generalised cross-correlation of the rows of x [B, Lx] with y [1 or B, Ly] (float32 device tensors) ->
+    (lags int64 ndarray [2 max_lag + 1], r device tensor [B, 2 max_lag + 1]); r at lag t is
+    irfft(W X conj(Y), n)[t mod n], n = conv_fft_len(Lx + Ly - 1).  If x[n] = y[n - d] the peak is at lag +d."""
+    max_lag = _gcc_args(x, y, max_lag, weighting, "gcc_batch")
+    r = ops.gcc(x.to(dtype=torch.float32), y.to(dtype=torch.float32), max_lag, weighting)
+    return np.arange(-max_lag, max_lag + 1, dtype=np.int64), r
+
+
+def estimate_delay_batch(x, y, fs: float = 1.0, max_lag: Optional[int] = None, weighting: str = "phat"):
+    """The delay of every row of x against y -> (delay_seconds float64 [B], lag int64 [B], peak float64 [B]), device
+    tensors: the first maximum of gcc_batch's r over the lags, refined by the parabola through its neighbours where it is
+    interior and the parabola opens downwards (the cepstral picker's rule, float64)."""
+    if not (np.isfinite(fs) and fs > 0):
+        raise ValueError(f"estimate_delay_batch: fs must be positive and finite, got {fs}")
+    max_lag = _gcc_args(x, y, max_lag, weighting, "estimate_delay_batch")
+    r = ops.gcc(x.to(dtype=torch.float32), y.to(dtype=torch.float32), max_lag, weighting)
+    return ops.peak_pick(r, -max_lag, float(fs))
+
+
+def estimate_delay(x, y, fs: float = 1.0, max_lag: Optional[int] = None, weighting: str = "phat"):
+    """1-D NumPy x, y -> (delay_seconds, lag, peak) as Python numbers: x lags y by `delay_seconds`."""
+    x, y = np.asarray(x), np.asarray(y)
+    if x.ndim != 1 or y.ndim != 1:
+        raise ValueError("Input data must be a 1D array.")
+    if np.iscomplexobj(x) or np.iscomplexobj(y):
+        raise ValueError(f"estimate_delay: complex input is not served ({_GCC_SERVED})")
+    if x.size == 0 or y.size == 0:
+        raise ValueError(f"estimate_delay: empty input ({_GCC_SERVED})")
+    if not (np.isfinite(fs) and fs > 0):
+        raise ValueError(f"estimate_delay: fs must be positive and finite, got {fs}")
+    xt, yt = (torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))[None] for v in (x, y))
+    max_lag = _gcc_args(xt, yt, max_lag, weighting, "estimate_delay")
+    dev = ops.require_gpu()
+    d, lag, pk = ops.peak_pick(ops.gcc(xt.to(dev), yt.to(dev), max_lag, weighting), -max_lag, float(fs))
+    return float(d[0].item()), int(lag[0].item()), float(pk[0].item())

@@ -162,10 +162,8 @@ def compute_psd_welch(x, fs: float = 1.0, window: str = "hann", nperseg: Optiona
     return f, p[0].cpu().numpy().astype(np.float64)
 
 
-def welch_batch(x, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None, detrend="constant",
-                scaling="density"):
-    """[B, L] device tensor -> (freqs float64 [F], Pxx device tensor [B, F]); scipy.signal.welch rules."""
-    L = x.shape[1]
+def _welch_args(L, fs, window, nperseg, noverlap, nfft, detrend, scaling):
+    """scipy.signal.welch's defaults and argument checks for rows of L samples -> (nperseg, noverlap, nfft, window table, scale)"""
     if nperseg is None:
         nperseg = 256
     if nperseg > L:
@@ -185,8 +183,106 @@ def welch_batch(x, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None
     ops.detrend_code(detrend)                                 # ValueError for anything but constant / linear / False
     w = get_window(window, nperseg)
     scale = 1.0 / (fs * (w * w).sum()) if scaling == "density" else 1.0 / w.sum() ** 2
-    p = ops.welch(x, nperseg, int(noverlap), int(nfft), w, detrend, scale)
-    return np.fft.rfftfreq(int(nfft), 1 / fs).astype(np.float64), p
+    return nperseg, int(noverlap), int(nfft), w, scale
+
+
+def welch_batch(x, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None, detrend="constant",
+                scaling="density"):
+    """[B, L] device tensor -> (freqs float64 [F], Pxx device tensor [B, F]); scipy.signal.welch rules."""
+    nperseg, noverlap, nfft, w, scale = _welch_args(x.shape[1], fs, window, nperseg, noverlap, nfft, detrend, scaling)
+    p = ops.welch(x, nperseg, noverlap, nfft, w, detrend, scale)
+    return np.fft.rfftfreq(nfft, 1 / fs).astype(np.float64), p
+
+
+# ------------------------------------------------------------------ cross-spectral analysis (scipy.signal.csd / coherence;
+# not in the reference's code: its specification lists correlation beside Welch, docs/dev_spec_v1.0.0.md 3.5, and
+# multi-channel handling, 3.7).  Served: real float32 rows of one length, y with one row (a reference channel) or one per
+# row of x, detrend False / 'constant' / 'linear', both scalings, any nperseg >= 1 and nfft >= nperseg, average='mean'.
+_XSPEC_SERVED = ("served: real float32 rows x [B, L] and y [1 or B, L] of one length, average='mean', detrend False / "
+                 "'constant' / 'linear', scaling 'density' / 'spectrum'")
+
+
+def _xspec(x, y, fs, window, nperseg, noverlap, nfft, detrend, scaling, average, want, who, host=False):
+    """the checks (all before any device work), then ops.cross_spectrum; host: x, y are host tensors still to be moved"""
+    if average != "mean":
+        raise ValueError(f"{who}: average={average!r} is not served ({_XSPEC_SERVED})")
+    for t, name in ((x, "x"), (y, "y")):
+        if not hasattr(t, "shape") or len(t.shape) != 2:
+            raise ValueError(f"{who}: {name} must be a [rows, samples] device tensor ({_XSPEC_SERVED})")
+        if getattr(t, "is_complex", lambda: False)():
+            raise ValueError(f"{who}: complex input is not served ({_XSPEC_SERVED})")
+        if t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{who}: {name} is empty, shape {tuple(t.shape)} ({_XSPEC_SERVED})")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"{who}: rows of unequal length are not served: x has {x.shape[1]} samples and y {y.shape[1]}; scipy "
+                         f"zero-pads the shorter one, here the caller does ({_XSPEC_SERVED})")
+    if y.shape[0] not in (1, x.shape[0]):
+        raise ValueError(f"{who}: y must have one row or one row per row of x ({x.shape[0]}), got {y.shape[0]} ({_XSPEC_SERVED})")
+    nperseg, noverlap, nfft, w, scale = _welch_args(x.shape[1], fs, window, nperseg, noverlap, nfft, detrend, scaling)
+    if host:
+        x, y = ops.to_device_f32(x), ops.to_device_f32(y)
+    r = ops.cross_spectrum(x, y, nperseg, noverlap, nfft, w, detrend, scale, want=want)
+    return np.fft.rfftfreq(nfft, 1 / fs).astype(np.float64), r
+
+
+def csd_batch(x, y, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None, detrend="constant", scaling="density",
+              average="mean"):
+    """x [B, L], y [1 or B, L] device tensors -> (freqs float64 [F], Pxy device tensor [B, F, 2] = (Re, Im));
+    scipy.signal.csd rules: Pxy = mean over segments of conj(X) Y."""
+    f, r = _xspec(x, y, fs, window, nperseg, noverlap, nfft, detrend, scaling, average, ("pxy",), "csd_batch")
+    return f, r["pxy"]
+
+
+def coherence_batch(x, y, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None, detrend="constant", average="mean"):
+    """-> (freqs, Cxy device tensor [B, F]): scipy.signal.coherence, |Pxy|^2 / (Pxx Pyy) formed in float64 on the device;
+    NaN where Pxx Pyy = 0, 1 with one segment."""
+    f, r = _xspec(x, y, fs, window, nperseg, noverlap, nfft, detrend, "density", average, ("coherence",), "coherence_batch")
+    return f, r["coherence"]
+
+
+def cross_spectra_batch(x, y, fs=1.0, window="hann", nperseg=None, noverlap=None, nfft=None, detrend="constant",
+                        scaling="density", average="mean"):
+    """-> (freqs, Pxy [B, F, 2], Pxx [B, F], Pyy [B, F], Cxy [B, F]) from one pass over the two signals."""
+    f, r = _xspec(x, y, fs, window, nperseg, noverlap, nfft, detrend, scaling, average, ops.CSD_WANTS, "cross_spectra_batch")
+    return f, r["pxy"], r["pxx"], r["pyy"], r["coherence"]
+
+
+def _xspec_rows(x, y, who):
+    x, y = np.asarray(x), np.asarray(y)
+    if x.ndim != 1 or y.ndim != 1:
+        raise ValueError("Input data must be a 1D array.")
+    if np.iscomplexobj(x) or np.iscomplexobj(y):
+        raise ValueError(f"{who}: complex input is not served ({_XSPEC_SERVED})")
+    if x.size == 0 or y.size == 0:
+        raise ValueError(f"{who}: empty input ({_XSPEC_SERVED})")
+    if x.shape != y.shape:
+        raise ValueError(f"{who}: rows of unequal length are not served: x has {x.size} samples and y {y.size}; scipy "
+                         f"zero-pads the shorter one, here the caller does ({_XSPEC_SERVED})")
+    return x, y
+
+
+def _host_row(v):
+    return ops.torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))[None]
+
+
+def compute_csd(x, y, fs: float = 1.0, window: str = "hann", nperseg: Optional[int] = None, noverlap: Optional[int] = None,
+                nfft: Optional[int] = None, detrend: Union[str, bool] = "constant", scaling: str = "density",
+                average: str = "mean") -> Tuple[np.ndarray, np.ndarray]:
+    """scipy.signal.csd(x, y) of two 1-D arrays of one length -> (freqs float64, Pxy complex128)."""
+    x, y = _xspec_rows(x, y, "compute_csd")
+    f, r = _xspec(_host_row(x), _host_row(y), fs, window, nperseg, noverlap, nfft, detrend, scaling, average, ("pxy",),
+                  "compute_csd", host=True)
+    return f, _c128(r["pxy"])[0].astype(np.complex128, copy=False)
+
+
+def compute_coherence(x, y, fs: float = 1.0, window: str = "hann", nperseg: Optional[int] = None,
+                      noverlap: Optional[int] = None, nfft: Optional[int] = None, detrend: Union[str, bool] = "constant",
+                      average: str = "mean") -> Tuple[np.ndarray, np.ndarray]:
+    """scipy.signal.coherence(x, y) of two 1-D arrays of one length -> (freqs float64, Cxy float64)."""
+    x, y = _xspec_rows(x, y, "compute_coherence")
+    f, r = _xspec(_host_row(x), _host_row(y), fs, window, nperseg, noverlap, nfft, detrend, "density", average, ("coherence",),
+                  "compute_coherence", host=True)
+    return f, r["coherence"][0].cpu().numpy().astype(np.float64)
 
 
 # ------------------------------------------------------------------ convolution / correlation (dsp.py:294-433)

@@ -1140,6 +1140,134 @@ def welch_rows(x: torch.Tensor, nperseg: int, noverlap: int, nfft: int, window_h
     return out
 
 
+# ------------------------------------------------------------------ cross-spectral analysis, generalised cross-correlation
+CSD_WANTS = ("pxy", "pxx", "pyy", "coherence")
+CSD_MAX_FUSED = 8192                 # longest nfft of the fused cross-spectrum kernel (two ping-pong buffers: 128 KiB)
+GCC_WEIGHTINGS = ("none", "phat")
+
+
+def _pair_rows(x, y, who: str, same_len: bool = False):
+    """x [B, L] and y [1 or B, L] float32 device tensors with unit stride along L (made so where they are not)"""
+    for t, name in ((x, "x"), (y, "y")):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{who}: {name} must be a [rows, samples] float32 device tensor")
+        if t.is_complex():
+            raise ValueError(f"{who}: complex input is not served: {name} must be real (float32)")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name} must be float32, got {t.dtype}")
+        if t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{who}: {name} is empty (shape {tuple(t.shape)}); at least one row of one sample is needed")
+    if y.shape[0] not in (1, x.shape[0]):
+        raise ValueError(f"{who}: y must have one row (a reference channel) or one row per row of x ({x.shape[0]}), "
+                         f"got {y.shape[0]}")
+    if same_len and x.shape[1] != y.shape[1]:
+        raise ValueError(f"{who}: rows of unequal length are not served: x has {x.shape[1]} samples and y {y.shape[1]} "
+                         "(scipy zero-pads the shorter one; here the caller does)")
+    require_gpu()
+    if not x.is_cuda or not y.is_cuda:
+        raise ValueError(f"{who}: x and y must be device tensors")
+    return (x if x.stride(1) == 1 else x.contiguous()), (y if y.stride(1) == 1 else y.contiguous())
+
+
+def csd_fused_takes(nfft: int) -> bool:
+    return is_pow2(nfft) and 8 <= nfft <= CSD_MAX_FUSED
+
+
+def cross_spectrum(x: torch.Tensor, y: torch.Tensor, nperseg: int, noverlap: int, nfft: int, window_host: np.ndarray, detrend,
+                   scale: float, want=CSD_WANTS) -> dict:
+    """Segment-averaged one-sided spectra of the row pairs (x[b], y[b]) of [B, L] float32 device tensors (y: B rows or one
+    reference row, never expanded): the requested ones of pxy [B, F, 2] = mean conj(X) Y, pxx, pyy and coherence [B, F],
+    scipy.signal.csd's rules (welch's).  One fused launch for nfft a power of two in [8, 8192]; packed rows and the
+    arbitrary-length FFT for every other nperseg >= 1 and nfft >= nperseg."""
+    want = tuple(want)
+    if not want or any(w not in CSD_WANTS for w in want):
+        raise ValueError(f"cross_spectrum: want must name some of {CSD_WANTS}, got {want}")
+    x, y = _pair_rows(x, y, "cross_spectrum", same_len=True)
+    B, L = x.shape
+    step = nperseg - noverlap
+    if not (1 <= nperseg <= nfft and 1 <= step <= nperseg):
+        raise ValueError("cross_spectrum: need 1 <= nperseg <= nfft and 0 <= noverlap < nperseg")
+    nseg = (L - noverlap) // step
+    if L < nperseg or nseg < 1:
+        raise ValueError("cross_spectrum: the signal is shorter than one segment")
+    F = nfft // 2 + 1
+    dcode = detrend_code(detrend)
+    out = {k: torch.empty((B, F, 2) if k == "pxy" else (B, F), dtype=torch.float32, device=x.device) for k in want}
+    win = _dev(np.asarray(window_host, dtype=np.float32))
+    if csd_fused_takes(nfft):
+        for b0 in range(0, B, MAX_ROWS):
+            bc = min(MAX_ROWS, B - b0)
+            xs, ys = x[b0:b0 + bc], (y if y.shape[0] == 1 else y[b0:b0 + bc])
+            nbytes = lib().syg_csd_work_bytes(bc, nseg, nfft)
+            work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+            _call("syg_csd_f32", _ptr(xs), _ptr(ys), bc, ys.shape[0], L, _ld(xs), _ld(ys), nperseg, step, nfft, _ptr(win),
+                  _ptr(twiddle_dev(nfft)), dcode, float(scale), *(_ptr(out[k][b0:b0 + bc]) if k in out else None for k in CSD_WANTS),
+                  _ptr(work))
+        return out
+    acc = torch.empty((4, F), dtype=torch.float64, device=x.device)
+    one_y = y.shape[0] == 1 and nseg <= MAX_ROWS           # the reference row's spectra: once for every x row
+    Yc = None
+    for b in range(B):
+        for s0 in range(0, nseg, MAX_ROWS):
+            sc = min(MAX_ROWS, nseg - s0)
+            X = fft_any(pack_frames(x[b:b + 1], sc, nperseg, step, s0, nfft, window=win, detrend=detrend))
+            if Yc is None or not one_y:
+                yb = y if y.shape[0] == 1 else y[b:b + 1]
+                Yc = fft_any(pack_frames(yb, sc, nperseg, step, s0, nfft, window=win, detrend=detrend))
+            _call("syg_csd_rows_f32", _ptr(X), _ptr(Yc), sc, nfft, _ptr(acc), int(s0 == 0), int(s0 + sc == nseg), nseg,
+                  float(scale), *(_ptr(out[k][b]) if k in out else None for k in CSD_WANTS))
+    return out
+
+
+def gcc_fft_len(Lx: int, Ly: int) -> int:
+    return conv_fft_len(Lx + Ly - 1)
+
+
+def gcc(x: torch.Tensor, y: torch.Tensor, max_lag: int, weighting: str = "none") -> torch.Tensor:
+    """r [B, 2 max_lag + 1]: r[:, max_lag + t] = irfft(W X conj(Y), n)[t mod n] for the lags t = -max_lag .. max_lag of the
+    rows of x [B, Lx] against y [1 or B, Ly]; n = conv_fft_len(Lx + Ly - 1); W = 1 ("none") or 1 / |X conj(Y)| ("phat").
+    scipy.signal.correlate's sign: x[n] = y[n - d] peaks at lag +d.  Plain real-input transforms (true bins), the
+    weighting kernel, the inverse transform and the lag crop, all on the device."""
+    if weighting not in GCC_WEIGHTINGS:
+        raise ValueError(f"gcc: weighting {weighting!r} is not served (served: {', '.join(GCC_WEIGHTINGS)})")
+    x, y = _pair_rows(x, y, "gcc")
+    B, Lx = x.shape
+    By, Ly = y.shape
+    if not (0 <= max_lag <= min(Lx, Ly) - 1):
+        raise ValueError(f"gcc: max_lag = {max_lag} is outside 0 ... min(Lx, Ly) - 1 = {min(Lx, Ly) - 1}")
+    n = gcc_fft_len(Lx, Ly)
+    W = 2 * max_lag + 1
+    out = torch.empty((B, W), dtype=torch.float32, device=x.device)
+    Y = fft_any(pack_rows(y, n, cplx=True)) if By == 1 else None
+    for b0 in range(0, B, MAX_ROWS):
+        bc = min(MAX_ROWS, B - b0)
+        X = fft_any(pack_rows(x[b0:b0 + bc], n, cplx=True))
+        Yb = Y if By == 1 else fft_any(pack_rows(y[b0:b0 + bc], n, cplx=True))
+        _call("syg_gcc_weight_c64", _ptr(X), _ptr(Yb), bc, Yb.shape[0], n, int(weighting == "phat"), _ptr(X))
+        c = fft_any(X, True)
+        _call("syg_gcc_crop_f32", _ptr(c), bc, n, max_lag, _ptr(out[b0:b0 + bc]))
+    return out
+
+
+def peak_pick(r: torch.Tensor, lag0: int, fs: float = 1.0):
+    """Per row of r [B, W] (float32, device): (delay float64 [B], lag int64 [B], peak float64 [B]) of the first maximum,
+    refined by the parabola through its neighbours where it is interior and the parabola opens downwards; the lag of
+    column i is lag0 + i, delay = (lag + shift) / fs."""
+    require_gpu()
+    if not isinstance(r, torch.Tensor) or r.dim() != 2 or r.dtype != torch.float32 or not r.is_cuda or r.shape[0] < 1 or r.shape[1] < 1:
+        raise ValueError("peak_pick: r must be a non-empty float32 [B, W] device tensor")
+    if not (fs > 0 and np.isfinite(fs)):
+        raise ValueError(f"peak_pick: fs must be positive and finite, got {fs}")
+    if r.stride(1) != 1:
+        r = r.contiguous()
+    B, W = r.shape
+    delay = torch.empty(B, dtype=torch.float64, device=r.device)
+    lag = torch.empty(B, dtype=torch.int64, device=r.device)
+    peak = torch.empty(B, dtype=torch.float64, device=r.device)
+    _call("syg_peak_pick_f32", _ptr(r), B, W, _ld(r), int(lag0), float(fs), _ptr(delay), _ptr(lag), _ptr(peak))
+    return delay, lag, peak
+
+
 def contrast_db(pv: torch.Tensor, amin: float = 1e-10, top_db: Optional[float] = 80.0, linear: bool = False) -> torch.Tensor:
     """pv [B, 2, R, T] (peak, valley means) -> spectral contrast [B, R, T]: dB difference, or the plain difference
     of the means with linear=True (librosa's `linear` option)."""

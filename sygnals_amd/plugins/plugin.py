@@ -82,6 +82,7 @@ class SygnalsAmdPlugin(_Base):
 
     def register_transforms(self, registry):
         from ..core import dsp as D
+        from ..core import alignment as AL
         from ..core import transforms as TR
         from ..core.features import cepstral as CF
         for fn in (D.compute_fft, D.compute_ifft, D.compute_stft, D.compute_cqt, D.compute_psd_welch, D.apply_window,
@@ -89,7 +90,8 @@ class SygnalsAmdPlugin(_Base):
                    D.amplitude_envelope, D.resample, D.real_cepstrum, D.complex_cepstrum,
                    D.inverse_complex_cepstrum, CF.lpc, TR.hilbert_transform, TR.continuous_wavelet_transform,
                    TR.laplace_transform_numerical,
-                   TR.discrete_wavelet_transform, TR.inverse_discrete_wavelet_transform):
+                   TR.discrete_wavelet_transform, TR.inverse_discrete_wavelet_transform,
+                   D.compute_csd, D.compute_coherence, AL.estimate_delay):
             registry.add_transform(fn.__name__, fn)
 
     def register_feature_extractors(self, registry):
