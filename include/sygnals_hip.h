@@ -1203,6 +1203,56 @@ int syg_gcc_crop_f32(const float* c, int64_t rows, int64_t n, int64_t max_lag, f
 int syg_peak_pick_f32(const float* r, int64_t B, int64_t W, int64_t ldr, int64_t lag0, double fs, double* delay_out,
                       int64_t* lag_out, double* peak_out, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Feature dynamics along T of x [B, K, T] float32 (dynamics.hip): unit stride along T, strides sxb / sxk (in floats,
+ * non-negative) over B and K.  Everything is per row (b, k).  The float64 restatement: tests/dynamics_ref.py.
+ *
+ * syg_dynamics_f32 writes `statics + n_delta` blocks of K rows, out[b, blk K + k, t] (strides sob / sok, sok >= T):
+ *   statics  s = x, or with cmvn = 1  s = (x - m) / sqrt(max(v, 1e-20))  (variance = 0: s = x - m), rounded once to
+ *            float32.  window = 0 (or >= T): m, v the mean and the population variance of the row, float64 sums over
+ *            chunks of SYG_DYN_TILE frames combined in index order.  1 <= window < T: Kaldi's centred sliding window,
+ *            s = t - W / 2, e = s + W, shifted back into [0, T); windows up to SYG_DYN_DIRECT_WINDOW are summed
+ *            explicitly (W = 1 is exact), longer ones come from float64 prefix sums of x and x^2.
+ *   deltas   block d (1-based) = scipy.signal.savgol_filter(s, width, deriv = d0 + d - 1 .., mode), taken from the
+ *            ROUNDED statics: interior frames h <= t < T - h (h = width / 2) are sum_j w[j] s[t - h + j], float32 fmaf,
+ *            j ascending; under mode 0 (interp) the first / last h frames are sum_j e[j] s[j] / s[T - width + j] with
+ *            a table row per frame; modes 1 nearest, 2 mirror, 3 wrap, 4 constant (cval) map t - h + j into the row.
+ *            tab: per delta block width^2 floats: w [width] (savgol_coeffs reversed), the left edge rows [h][width],
+ *            the right edge rows [h][width] (sygnals_amd/_dynamics.py builds them in float64 and rounds once).
+ *            statics = 0, n_delta = 1 is the plain delta of any order (the order is the table's).
+ *   form     0: the rule (syg_dynamics_form: 0 resident, 1 tiled), 1 resident, 2 tiled.  Resident: a wave holds a whole
+ *            row in LDS, up to SYG_DYN_UNITS rows a workgroup, one launch.  Tiled: SYG_DYN_TILE frames a wave with a halo
+ *            of width (+ window) frames; global statistics come from launches ahead of it that write float64 chunk
+ *            sums and their in-order totals to work (syg_dynamics_work_bytes(B, K, T) bytes).  The deltas and the global CMVN are bit-identical in both
+ *            forms; the sliding CMVN may differ by 2 float32 ulp.  No atomics; a batch equals its rows bit for bit.
+ *   Rejected before any device work: null pointers, an empty input, bad strides, a result above 2^31 elements, width
+ *   even or outside [3, 255], an unknown mode, interp with T < width, an out that overlaps x (cmvn alone may write
+ *   onto x itself; not with a sliding window in the tiled form), a sliding window above SYG_DYN_WINDOW_MAX in the tiled
+ *   form, wrap with CMVN over more than one tile, a missing workspace.
+ * syg_stack_memory_f32: out [B, n_steps K, T] contiguous, out[b, i K + k, t] = x[b, k, t - i delay], 0 outside [0, T);
+ *   n_steps >= 1, delay != 0 (either sign).  A pure gather.
+ * ------------------------------------------------------------------------------- */
+enum {
+  SYG_DYN_TILE = 0,                /* frames of a tile and of a chunk of the global sums */
+  SYG_DYN_RESIDENT_T = 1,          /* the rule: longest resident row */
+  SYG_DYN_RESIDENT_T_SLIDING = 2,  /* the rule: longest resident row under a sliding window */
+  SYG_DYN_WINDOW_MAX = 3,          /* longest sliding window (below T) of the tiled form */
+  SYG_DYN_DIRECT_WINDOW = 4,       /* sliding windows up to this are summed explicitly */
+  SYG_DYN_WIDTH_MAX = 5,
+  SYG_DYN_ORDER_MAX = 6,
+  SYG_DYN_UNITS = 7,               /* rows (waves) of a workgroup, at most */
+  SYG_DYN_MAX_OUT = 8,             /* elements of a result, at most */
+  SYG_DYN_LDS_MAX = 9              /* LDS bytes of a one-row workgroup: what a forced resident row may take */
+};
+int64_t syg_dynamics_constants(int key);
+int syg_dynamics_form(int64_t T, int64_t window);
+int64_t syg_dynamics_work_bytes(int64_t B, int64_t K, int64_t T);
+int syg_dynamics_f32(const float* x, int64_t B, int64_t K, int64_t T, int64_t sxb, int64_t sxk, float* out, int64_t sob,
+                     int64_t sok, int cmvn, int64_t window, int variance, int statics, int n_delta, int width, int mode,
+                     float cval, const float* tab, int form, void* work, int64_t work_bytes, void* stream);
+int syg_stack_memory_f32(const float* x, int64_t B, int64_t K, int64_t T, int64_t sxb, int64_t sxk, float* out,
+                         int64_t n_steps, int64_t delay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

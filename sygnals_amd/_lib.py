@@ -182,6 +182,11 @@ SIGNATURES = {
     "syg_gcc_weight_c64": (_i, [_p, _p, _l, _l, _l, _i, _p, _p]),
     "syg_gcc_crop_f32": (_i, [_p, _l, _l, _l, _p, _p]),
     "syg_peak_pick_f32": (_i, [_p, _l, _l, _l, _l, _d, _p, _p, _p, _p]),
+    "syg_dynamics_constants": (_l, [_i]),
+    "syg_dynamics_form": (_i, [_l, _l]),
+    "syg_dynamics_work_bytes": (_l, [_l, _l, _l]),
+    "syg_dynamics_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _l, _i, _l, _i, _i, _i, _i, _i, _f, _p, _i, _p, _l, _p]),
+    "syg_stack_memory_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _l, _p]),
 }
 
 _lib = None

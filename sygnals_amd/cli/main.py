@@ -75,6 +75,70 @@ def features_extract(input_file, output, features, frame_length, hop_length):
         raise click.UsageError(f"Error during feature extraction: {e}")
 
 
+def _post_rows(data):
+    """A table or dict that `features extract` wrote -> (time or None, names, [K, T] float32); every column but `time`."""
+    if isinstance(data, pd.DataFrame):
+        cols = {c: data[c].to_numpy() for c in data.columns}
+    elif isinstance(data, dict):
+        cols = {}
+        for k, v in data.items():
+            v = np.asarray(v)
+            if v.ndim == 2 and k != "time":
+                cols.update({f"{k}_{i}": v[i] for i in range(v.shape[0])})
+            else:
+                cols[k] = v
+    else:
+        raise click.UsageError("Input must be a table (.csv) or an .npz that `features extract` wrote.")
+    time = cols.pop("time", None)
+    names = [k for k, v in cols.items() if np.ndim(v) == 1 and np.issubdtype(np.asarray(v).dtype, np.number)]
+    if not names:
+        raise click.UsageError("The input holds no feature columns (every numeric column but `time` is a row).")
+    if len({len(cols[k]) for k in names}) != 1:
+        raise click.UsageError("The feature columns have different lengths.")
+    return time, names, np.stack([np.asarray(cols[k], dtype=np.float32) for k in names])
+
+
+@features_cmd.command("post")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False, resolve_path=True))
+@click.option("-o", "--output", type=click.Path(resolve_path=True), required=True,
+              help="Output file path (same layout as the input: .csv or .npz).")
+@click.option("--cmvn", type=click.Choice(["global", "sliding"]), default=None, help="Per-utterance mean / variance normalisation.")
+@click.option("--cmvn-window", type=int, default=600, show_default=True, help="Frames of the sliding CMVN window.")
+@click.option("--no-variance", is_flag=True, help="Subtract the mean only.")
+@click.option("--deltas", type=click.IntRange(0, 2), default=0, show_default=True, help="Append delta (1) and delta-delta (2).")
+@click.option("--width", type=int, default=9, show_default=True, help="Frames of the delta filter (odd, at least 3).")
+@click.option("--mode", default="interp", show_default=True, help="Edge mode of the delta filter.")
+@click.option("--stack", type=int, default=None, help="Context stacking: copies of every row (n_steps).")
+@click.option("--delay", type=int, default=1, show_default=True, help="Frames between stacked copies (non-zero, either sign).")
+def features_post(input_file, output, cmvn, cmvn_window, no_variance, deltas, width, mode, stack, delay):
+    """Normalise (CMVN), append deltas and stack context on extracted features."""
+    from ..core.features import dynamics as DN
+    time, names, x = _post_rows(sio.read_data(Path(input_file)))
+    T = x.shape[1]
+    if deltas and mode == "interp" and T < width:
+        raise click.UsageError(f"--mode interp needs at least --width frames: the input has {T} frames and --width is {width} "
+                               "(give a smaller --width or another --mode).")
+    if cmvn == "sliding" and cmvn_window < 1:
+        raise click.UsageError("--cmvn-window must be at least 1.")
+    try:
+        if stack is not None:
+            from .. import _dynamics as DY
+            DY.check_stack(stack, delay, "--stack / --delay")
+        window = None if cmvn is None else ("global" if cmvn == "global" else cmvn_window)
+        y = DN.feature_post_batch(x[None], cmvn=window, variance=not no_variance, deltas=deltas, width=width, mode=mode)
+        out_names = [n + suffix for suffix in ("", "_delta", "_delta2")[:deltas + 1] for n in names]
+        if stack is not None:
+            y = DN.stack_memory_batch(y, stack, delay)
+            out_names = out_names + [f"{n}_m{i}" for i in range(1, stack) for n in out_names]
+        y = y[0].cpu().numpy()
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    out = {} if time is None else {"time": np.asarray(time)}
+    out.update({n: y[i] for i, n in enumerate(out_names)})
+    sio.save_data(out if Path(output).suffix.lower() == ".npz" else pd.DataFrame(out), Path(output))
+    click.echo(f"Post-processed {len(names)} feature rows x {T} frames into {len(out_names)} rows, saved to '{Path(output).name}'.")
+
+
 # ---------------------------------------------------------------- dsp
 @click.group("dsp")
 def dsp_cmd():

@@ -100,3 +100,15 @@ def lpc_envelope_batch(a, err, n_fft: int = 2048, db: bool = False, amin: float 
 
 
 CEPSTRAL_FEATURES: Dict[str, Any] = {"mfcc": mfcc, "lpc": lpc}
+
+
+def mfcc_deltas_batch(y, sr, n_fft: int = 2048, hop_length: int = 512, n_mels: int = 128, n_mfcc: int = 13, deltas: int = 2,
+                      width: int = 9, cmvn=None, variance: bool = True, mode: str = "interp", center: bool = True,
+                      window="hann", fmin: float = 0.0, fmax=None, lifter: float = 0.0):
+    """[B, L] clips -> [B, (deltas + 1) n_mfcc, T] on the device: ops.mfcc_batch followed by ops.feature_post (per-utterance
+    CMVN `cmvn`: None, "global" or a sliding window; then delta and delta-delta of the statics).  With cmvn=None the static
+    block equals mfcc_batch bit for bit."""
+    yd = y if hasattr(y, "is_cuda") else ops.to_device_f32(np.atleast_2d(np.asarray(y, dtype=np.float32)))
+    m = ops.mfcc_batch(yd, sr, n_fft=n_fft, hop=hop_length, n_mels=n_mels, n_mfcc=n_mfcc, center=center, window=window,
+                       fmin=fmin, fmax=fmax, lifter=lifter)
+    return ops.feature_post(m, cmvn=cmvn, variance=variance, deltas=deltas, width=width, mode=mode)

@@ -16,6 +16,7 @@ import torch
 
 from . import _cepstrum as CP
 from . import _cwt as CW
+from . import _dynamics as DY
 from . import _laplace as LP
 from . import _lpc
 from . import _resample as RS
@@ -3247,3 +3248,181 @@ def lpc_envelope(a: torch.Tensor, err: torch.Tensor, n_fft: int = 2048, db: bool
     ph = _cached(("lpc_phasor", n_fft), lambda: _dev(lpc_phasor_table(n_fft)))
     _call("syg_lpc_envelope_f32", _ptr(a), _ptr(err), B, p1 - 1, Tn, n_fft, _ptr(ph), int(bool(db)), amin, _ptr(out))
     return out
+
+
+# ------------------------------------------------------------------ feature dynamics: deltas, CMVN, context stacking
+_DYN_KEYS = {"tile": 0, "resident_max_t": 1, "resident_max_t_sliding": 2, "window_max": 3, "direct_window": 4, "width_max": 5,
+             "order_max": 6, "units": 7, "max_out": 8, "lds_max": 9}                 # SYG_DYN_* of include/sygnals_hip.h
+_DYN_FORMS = {None: 0, "resident": 1, "tiled": 2}
+
+
+def dynamics_constants() -> dict:
+    """The figures the dynamics kernel rests on (the library owns them): the tile (also the chunk of the global sums), the
+    rule's longest resident rows, the longest sliding window of the tiled form, the window up to which sliding sums are
+    explicit, the served widths and orders, the rows of a workgroup, the largest result, the LDS of a one-row workgroup
+    (a forced resident row fits while 4 T, or 20 T + 16 under a long sliding window, stays within it)."""
+    h = lib()
+    return {name: int(h.syg_dynamics_constants(key)) for name, key in _DYN_KEYS.items()}
+
+
+def delta_tables(width: int = 9, order: int = 1):
+    """The float32 tables of `delta` (host arrays, cached per (width, order)): c [width] = savgol_coeffs(width, order,
+    deriv=order) and the interp edge matrix E [width, width]; interior frames are np.convolve(x, c, "valid")."""
+    return DY.delta_tables(*DY.check_width_order(width, order, "delta_tables"))
+
+
+def dynamics_form(T: int, window=None) -> str:
+    """The library's rule: "resident" or "tiled" for rows of T frames (window: the sliding CMVN window, None for none)."""
+    return "tiled" if lib().syg_dynamics_form(int(T), DY.check_window(window)) == 1 else "resident"
+
+
+def _dyn_in(x, who: str) -> torch.Tensor:
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.float32:
+        raise ValueError(f"{who}: x must be a float32 tensor [B, K, T]")
+    if min(x.shape) < 1:
+        raise ValueError(f"{who}: empty input (shape {list(x.shape)})")
+    return x if (x.shape[2] == 1 or x.stride(2) == 1) else x.contiguous()
+
+
+def _dyn_strides(t: torch.Tensor):
+    B, R, Tn = t.shape
+    sk = int(t.stride(1)) if R > 1 else Tn
+    sb = int(t.stride(0)) if B > 1 else (R - 1) * sk + Tn
+    return sb, sk
+
+
+def _dyn_span(t: torch.Tensor):
+    n = sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1
+    return t.data_ptr(), t.data_ptr() + 4 * n
+
+
+def _dyn_out(who: str, out, shape, x: torch.Tensor, may_alias: bool = False) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=x.device)
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or \
+            out.device != x.device or (shape[2] > 1 and out.stride(2) != 1):
+        raise ValueError(f"{who}: out must be a float32 tensor {list(shape)} on x's device with unit stride along T")
+    (a0, a1), (b0, b1) = _dyn_span(x), _dyn_span(out)
+    same = may_alias and out.data_ptr() == x.data_ptr() and out.stride() == x.stride()
+    if a0 < b1 and b0 < a1 and not same:
+        raise ValueError(f"{who}: out overlaps x" + (" (only out = x itself is served)" if may_alias else ""))
+    return out
+
+
+def _dyn_form(form) -> int:
+    if form not in _DYN_FORMS:
+        raise ValueError(f"form must be None, 'resident' or 'tiled' (got {form!r})")
+    return _DYN_FORMS[form]
+
+
+def _dyn_table_dev(width: int, orders) -> torch.Tensor:
+    return _cached(("dyn_tab", width, tuple(orders)),
+                   lambda: _dev(np.concatenate([DY.pack_table(width, o) for o in orders])))
+
+
+def _dynamics(who, x, out, cm, W, variance, statics, orders, width, mode_code, cval, form):
+    """One syg_dynamics_f32 call; every argument has been checked."""
+    require_gpu()
+    if not (x.is_cuda and out.is_cuda):
+        raise ValueError(f"{who}: x and out must be float32 CUDA tensors")
+    B, K, Tn = x.shape
+    h = lib()
+    tiled = form == 2 or (form == 0 and h.syg_dynamics_form(Tn, W if cm else 0) == 1)
+    sliding = cm and 1 <= W < Tn
+    if sliding and tiled and out.data_ptr() == x.data_ptr():
+        x = x.clone()                                                # tiles read their neighbours' frames: not in place
+    work, wb = None, 0
+    if cm and not sliding and tiled:
+        wb = int(h.syg_dynamics_work_bytes(B, K, Tn))
+        work = torch.empty(wb // 8, dtype=torch.float64, device=x.device)
+    tab = _dyn_table_dev(width, orders) if orders else None
+    sxb, sxk = _dyn_strides(x)
+    sob, sok = _dyn_strides(out)
+    _call("syg_dynamics_f32", _ptr(x), B, K, Tn, sxb, sxk, _ptr(out), sob, sok, int(cm), W, int(bool(variance)), int(statics),
+          len(orders), width, mode_code, float(cval), _ptr(tab), form, _ptr(work), wb)
+    return out
+
+
+def delta(x: torch.Tensor, width: int = 9, order: int = 1, mode: str = "interp", cval: float = 0.0,
+          out: Optional[torch.Tensor] = None, form: Optional[str] = None) -> torch.Tensor:
+    """librosa.feature.delta along T of x [B, K, T] float32 on the device: scipy.signal.savgol_filter(x, width, deriv=order,
+    polyorder=order, mode=mode, cval=cval), float32 accumulation in a fixed order (j ascending).  Served: width odd in
+    3 ... 255, 1 <= order <= min(4, width - 1), modes interp (T >= width), nearest, mirror, wrap, constant.  Rows may be
+    strided over B and K (unit stride along T); `out` [B, K, T] must not overlap x.  Both forms give the same bits."""
+    width, order = DY.check_width_order(width, order)
+    mc = DY.check_mode(mode)
+    x = _dyn_in(x, "delta")
+    B, K, Tn = x.shape
+    DY.check_interp(width, Tn, mode)
+    DY.check_size("delta", B, K, Tn)
+    f = _dyn_form(form)
+    out = _dyn_out("delta", out, (B, K, Tn), x)
+    return _dynamics("delta", x, out, 0, 0, 0, 0, (order,), width, mc, cval, f)
+
+
+def cmvn(x: torch.Tensor, window=None, variance: bool = True, out: Optional[torch.Tensor] = None,
+         form: Optional[str] = None) -> torch.Tensor:
+    """Per-row cepstral mean / variance normalisation of x [B, K, T]: y = (x - m) / sqrt(max(v, 1e-20)) (variance=False:
+    x - m), m and v the mean and population variance over all frames (window=None) or over Kaldi's centred sliding window
+    of `window` frames; float64 sums, rounded once.  A constant row, T = 1 and window = 1 give exactly 0.  `out` may be x."""
+    W = DY.check_window(window)
+    x = _dyn_in(x, "cmvn")
+    B, K, Tn = x.shape
+    DY.check_size("cmvn", B, K, Tn)
+    f = _dyn_form(form)
+    out = _dyn_out("cmvn", out, (B, K, Tn), x, may_alias=True)
+    return _dynamics("cmvn", x, out, 1, W, variance, 1, (), 1, 0, 0.0, f)
+
+
+def stack_memory(x: torch.Tensor, n_steps: int = 2, delay: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """librosa.feature.stack_memory with zero padding: out [B, n_steps K, T], out[b, i K + k, t] = x[b, k, t - i delay] and 0
+    where that index is outside [0, T); delay any non-zero integer.  A pure gather, bit for bit."""
+    n_steps, delay = DY.check_stack(n_steps, delay)
+    x = _dyn_in(x, "stack_memory")
+    B, K, Tn = x.shape
+    DY.check_size("stack_memory", B, n_steps * K, Tn)
+    out = _dyn_out("stack_memory", out, (B, n_steps * K, Tn), x)
+    if not out.is_contiguous():
+        raise ValueError("stack_memory: out must be contiguous")
+    require_gpu()
+    if not x.is_cuda:
+        raise ValueError("stack_memory: x must be a float32 CUDA tensor")
+    sxb, sxk = _dyn_strides(x)
+    _call("syg_stack_memory_f32", _ptr(x), B, K, Tn, sxb, sxk, _ptr(out), n_steps, delay)
+    return out
+
+
+def feature_post(x: torch.Tensor, cmvn=None, variance: bool = True, deltas: int = 2, width: int = 9, mode: str = "interp",
+                 out: Optional[torch.Tensor] = None, form: Optional[str] = None) -> torch.Tensor:
+    """[statics | delta | delta-delta] of x [B, K, T] in one call: out [B, (deltas + 1) K, T].  cmvn: None, "global" or a
+    sliding window W; it comes first and the deltas (orders 1 and 2 of the statics, not delta of delta) are taken from the
+    normalised statics as rounded to float32, so the result equals cat(s, delta(s, order=1), delta(s, order=2)) with
+    s = cmvn(x) bit for bit.  One read of x, deltas + 1 writes."""
+    if isinstance(deltas, bool) or deltas not in (0, 1, 2):
+        raise ValueError(f"feature_post: deltas must be 0, 1 or 2 (got {deltas!r})")
+    if cmvn is not None and cmvn != "global" and (isinstance(cmvn, str) or isinstance(cmvn, bool)):
+        raise ValueError(f"feature_post: cmvn must be None, 'global' or a sliding window >= 1 (got {cmvn!r})")
+    cm = cmvn is not None
+    W = 0 if cmvn in (None, "global") else DY.check_window(cmvn, "feature_post")
+    mc = 0
+    if deltas:
+        width, _ = DY.check_width_order(width, deltas, "feature_post")
+        mc = DY.check_mode(mode, "feature_post")
+    x = _dyn_in(x, "feature_post")
+    B, K, Tn = x.shape
+    if deltas:
+        DY.check_interp(width, Tn, mode, "feature_post")
+    DY.check_size("feature_post", B, (deltas + 1) * K, Tn)
+    f = _dyn_form(form)
+    out = _dyn_out("feature_post", out, (B, (deltas + 1) * K, Tn), x)
+    orders = tuple(range(1, deltas + 1))
+    tiled = f == 2 or (f == 0 and lib().syg_dynamics_form(Tn, W if cm else 0) == 1)
+    if cm and deltas and mode == "wrap" and tiled and Tn > dynamics_constants()["tile"]:
+        # a wrapped frame of another tile would need that tile's statistics: the statics first, the deltas from them
+        s = torch.empty((B, K, Tn), dtype=torch.float32, device=x.device)
+        _dynamics("feature_post", x, s, 1, W, variance, 1, (), 1, 0, 0.0, f)
+        out[:, :K].copy_(s)
+        for d in orders:
+            _dynamics("feature_post", s, out[:, d * K:(d + 1) * K], 0, 0, 0, 0, (d,), width, mc, 0.0, f)
+        return out
+    return _dynamics("feature_post", x, out, int(cm), W, variance, 1, orders, width if deltas else 1, mc, 0.0, f)

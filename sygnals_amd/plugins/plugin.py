@@ -85,13 +85,14 @@ class SygnalsAmdPlugin(_Base):
         from ..core import alignment as AL
         from ..core import transforms as TR
         from ..core.features import cepstral as CF
+        from ..core.features import dynamics as DN
         for fn in (D.compute_fft, D.compute_ifft, D.compute_stft, D.compute_cqt, D.compute_psd_welch, D.apply_window,
                    D.apply_convolution, D.compute_correlation, D.compute_autocorrelation, D.compute_psd_periodogram,
                    D.amplitude_envelope, D.resample, D.real_cepstrum, D.complex_cepstrum,
                    D.inverse_complex_cepstrum, CF.lpc, TR.hilbert_transform, TR.continuous_wavelet_transform,
                    TR.laplace_transform_numerical,
                    TR.discrete_wavelet_transform, TR.inverse_discrete_wavelet_transform,
-                   D.compute_csd, D.compute_coherence, AL.estimate_delay):
+                   D.compute_csd, D.compute_coherence, AL.estimate_delay, DN.delta, DN.cmvn, DN.stack_memory):
             registry.add_transform(fn.__name__, fn)
 
     def register_feature_extractors(self, registry):
