@@ -8,7 +8,6 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import functools
 from typing import Optional
 
 import numpy as np
@@ -65,21 +64,121 @@ def to_device_f32(x, device=None) -> torch.Tensor:
     return t.contiguous()
 
 
-_dev_cache: dict = {}
+_dev_cache: dict = {}          # (device, family, ...) -> table; a limited family's entries stand least recently used first
 
 
-def _cached(key, builder):
-    dev = torch.cuda.current_device()
-    k = (dev,) + key
+def _cached(key, builder, limit: Optional[int] = None):
+    """The device table of `key` (family name first) on the current device, built on first use.  limit: the most entries
+    the family keeps (over all devices), the least recently used one going first; None: unbounded."""
+    k = (torch.cuda.current_device(),) + key
     v = _dev_cache.get(k)
     if v is None:
         v = builder()
         _dev_cache[k] = v
+        if limit:
+            held = [q for q in _dev_cache if q[1] == key[0]]
+            if len(held) > limit:
+                del _dev_cache[held[0]]
+    elif limit:
+        _dev_cache[k] = _dev_cache.pop(k)
     return v
+
+
+def clear_caches() -> None:
+    """Drops everything this module keeps on a device: the tables, the prepared MFCC calls and the side streams."""
+    _dev_cache.clear()
+    _mfcc_calls.clear()
+    _side_streams.clear()
 
 
 def _dev(arr: np.ndarray) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(arr)).to(require_gpu())
+
+
+def _f32(x, what: str, dims: int, tail: tuple = (), axes: Optional[str] = None) -> None:
+    """First stage of the input check, judged without a device: x is a float32 tensor of `dims` dimensions whose last
+    sizes are `tail`.  axes: the shape as the message names it (default: * for a free size)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != dims or x.dtype != torch.float32 or \
+            (tail and tuple(x.shape[-len(tail):]) != tuple(tail)):
+        axes = axes or "[" + ", ".join(["*"] * (dims - len(tail)) + [str(n) for n in tail]) + "]"
+        raise ValueError(f"{what} must be a float32 tensor {axes}")
+
+
+def _on_device(x: torch.Tensor, what: str) -> None:
+    """Second stage: there is a device and x is on it."""
+    require_gpu()
+    if not x.is_cuda:
+        raise ValueError(f"{what} must be a CUDA tensor")
+
+
+def _unit_stride(x: torch.Tensor) -> torch.Tensor:
+    """x with unit stride along its last axis (a copy if it has another)."""
+    return x if (x.stride(-1) == 1 or x.shape[-1] == 1) else x.contiguous()
+
+
+def _f32_in(x, what: str, dims: int, tail: tuple = (), axes: Optional[str] = None) -> torch.Tensor:
+    """The input check, both stages: a float32 device tensor of `dims` dimensions, returned with unit stride along its last
+    axis."""
+    _f32(x, what, dims, tail, axes)
+    _on_device(x, what)
+    return _unit_stride(x)
+
+
+def _out(out, shape, x: torch.Tensor, what: str = "out", dtype=torch.float32, contiguous: bool = False) -> torch.Tensor:
+    """A new tensor of this shape and dtype on x's device, or `out` checked: contiguous, or unit stride along its last
+    axis only."""
+    shape = tuple(shape)
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=x.device)
+    ok = isinstance(out, torch.Tensor) and tuple(out.shape) == shape and out.dtype == dtype and out.device == x.device
+    if not (ok and (out.is_contiguous() if contiguous else (shape[-1] <= 1 or out.stride(-1) == 1))):
+        raise ValueError(f"{what} must be a {str(dtype)[6:]} tensor {list(shape)} on the input's device, "
+                         + ("contiguous" if contiguous else "with unit stride along its last axis"))
+    return out
+
+
+# sizing entries whose refusal (a negative size) leaves no message in syg_last_error
+_SILENT_SIZERS = frozenset(("syg_pack_rows_work_bytes", "syg_welch_work_bytes", "syg_csd_work_bytes",
+                            "syg_onset_strength_work_bytes", "syg_dwt_work_bytes", "syg_dynamics_work_bytes"))
+
+
+def _work_bytes(entry: str, *args, error: Optional[Exception] = None) -> int:
+    """The bytes the sizing entry asks for at these arguments; a negative answer raises `error`, or SygnalsHipError with
+    the library's message (the entry and its arguments where it leaves none)."""
+    n = int(getattr(lib(), entry)(*args))
+    if n < 0:
+        if error is not None:
+            raise error
+        if entry in _SILENT_SIZERS:
+            raise SygnalsHipError(f"{entry}({', '.join(str(a) for a in args)}) refuses these arguments")
+        check(-1, entry)
+    return n
+
+
+def _workspace(entry: str, *args, dtype, device, error: Optional[Exception] = None) -> Optional[torch.Tensor]:
+    """The workspace of _work_bytes(entry, *args): None for 0 bytes, else a buffer of `dtype` of at least that size."""
+    n = _work_bytes(entry, *args, error=error)
+    return torch.empty(-(-n // dtype.itemsize), dtype=dtype, device=device) if n else None
+
+
+def _nbytes(work: Optional[torch.Tensor]) -> int:
+    return 0 if work is None else work.numel() * work.element_size()
+
+
+def _constants(entry: str, names) -> dict:
+    """The library's figures by name, read now: names[i] -> entry(i) of an indexed entry; a dict name -> suffix names the
+    per-figure entries entry_suffix()."""
+    h = lib()
+    if isinstance(names, dict):
+        return {name: int(getattr(h, f"{entry}_{suffix}")()) for name, suffix in names.items()}
+    fn = getattr(h, entry)
+    return {name: int(fn(i)) for i, name in enumerate(names)}
+
+
+def _row_blocks(n: int):
+    """(first row, row count) of the launches that take n rows MAX_ROWS (the grid's 65535) at a time."""
+    for lo in range(0, n, MAX_ROWS):
+        yield lo, min(MAX_ROWS, n - lo)
 
 
 def _window_key(window, win_length, n_fft):
@@ -261,14 +360,6 @@ def _basis_padded(cfg: "MelConfig", n_fft: int):
     return cfg.basis_padded, cfg.Fp
 
 
-def _clips(y: torch.Tensor, what: str = "y") -> torch.Tensor:
-    """The clips argument of a front end, checked: a float32 device tensor [B, L] with unit stride along a clip (copied if not)."""
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError(f"{what} must be a float32 CUDA tensor of shape [B, L]")
-    return y if y.stride(1) == 1 else y.contiguous()
-
-
 def _at_least_one(Tn: int) -> int:
     if Tn <= 0:
         raise ValueError("signal too short for one frame")
@@ -297,7 +388,7 @@ def _rows_out(B, Tn, want_stats, contrast, device, who=None):
 
 
 def _pow2_front(y, sr, n_fft, hop, center, window, win_length, n_mels, fmin, fmax):
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     if not fused_pow2_ok(n_fft, n_mels):
         raise SygnalsHipError(f"no fused kernel for n_fft={n_fft}, n_mels={n_mels} (powers of two 64 ... 1024; 2048: stft2048_mel)")
     B, L = y.shape
@@ -391,7 +482,7 @@ def _seg_args(k, y, n_fft, hop, center, Tn, window, win_length):
 def _seg_mel(n_fft, y, sr, hop, center, window, win_length, n_mels, fmin, fmax):
     """Mel power [B, n_mels, T] from the segment-sum kernel of frame length n_fft (power 2)."""
     k = _SEG[n_fft]
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     tab = _segtab(n_fft, sr, n_mels, fmin, fmax)
     if tab is None:
         raise SygnalsHipError(f"{k['mel'][4:-4]}: no piece table for this frame length / filterbank "
@@ -408,7 +499,7 @@ def _seg_rows(n_fft, y, sr, hop, center, window, win_length, n_mels, fmin, fmax,
     given (1024 / 4096).  Returns (mel | None, stats | None, contrast_pv | None)."""
     k = _SEG[n_fft]
     who = k["rows"][4:-4]
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     B, L = y.shape
     Tn = _frames(L, n_fft, hop, center)
     smask, stats, cpv, cplan_p = _rows_out(B, Tn, want_stats, contrast, y.device, who)
@@ -507,7 +598,7 @@ def stft2048_mel(y: torch.Tensor, sr: float, hop: int = 512, center: bool = True
     projection: "segments" (syg_stft2048_mel_tri_f32: per-wave segment sums -- the two-pass table where the filterbank has
     one, else the four-pass table -- no barriers in the projection; tri_waves = 16 | 8 waves per workgroup), "matrix"
     (syg_stft2048_mel_f32: block-sparse weights on the matrix cores), "auto": the matrix form wherever it has a plan."""
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     B, L = y.shape
     Tn = _frames(L, 2048, hop, center)
     cfg = mel_config(sr, 2048, n_mels, fmin, fmax)
@@ -551,7 +642,7 @@ def stft2048_stats(y: torch.Tensor, sr: float, hop: int = 512, center: bool = Tr
     functions, nothing projected) -- what spectral_centroid / bandwidth / flatness / rolloff / contrast need
     (manager.py:289-343).  Returns (stats [B, 8, T] | None, contrast_pv [B, 2, R, T] | None), bit-identical to
     stft2048_mel's."""
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     B, L = y.shape
     Tn = _frames(L, 2048, hop, center)
     smask, stats, cpv, cplan_p = _rows_out(B, Tn, want_stats, contrast, y.device, "stft2048_stats")
@@ -615,7 +706,7 @@ def stft_front(y, sr, n_fft, hop, center=True, window="hann", win_length=None, n
 
 def stft2048_c2c(y: torch.Tensor, hop: int = 512, center: bool = True, window="hann", win_length: int = 2048):
     """Complex STFT, frame-major [B, T, 1025, 2] float32."""
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     B, L = y.shape
     Tn = _frames(L, 2048, hop, center)
     win = window_dev(window, win_length, 2048)
@@ -903,7 +994,7 @@ def pack_frames(y: torch.Tensor, n_rows: int, length: int, step: int, first: int
     rows = B * n_rows
     out = torch.empty((rows, n_out, 2) if cplx else (rows, n_out), dtype=torch.float32, device=y.device)
     dcode = detrend_code(detrend)
-    work = torch.empty(lib().syg_pack_rows_work_bytes(rows) // 8, dtype=torch.float64, device=y.device) if dcode else None
+    work = _workspace("syg_pack_rows_work_bytes", rows, dtype=torch.float64, device=y.device) if dcode else None
     base = y.data_ptr() + 4 * first * step
     _call("syg_pack_frames_f32", C.c_void_p(base), rows, length, step, n_rows, Lp, _ptr(window), dcode, 0, int(cplx),
           _ptr(out), n_out, _ptr(work))
@@ -935,8 +1026,7 @@ def stft_rows(y: torch.Tensor, n_fft: int, hop: int, center: bool = True, window
             out[b0:b0 + bc] = X.view(bc, Tn, n_fft, 2)[:, :, :F]
         return out
     for b in range(B):                                        # long clips: 65535 frames of one clip at a time
-        for t0 in range(0, Tn, MAX_ROWS):
-            tc = min(MAX_ROWS, Tn - t0)
+        for t0, tc in _row_blocks(Tn):
             X = fft_any(pack_frames(yp[b:b + 1], tc, n_fft, hop, t0, n_fft, window=win))
             out[b, t0:t0 + tc] = X[:, :F]
     return out
@@ -984,7 +1074,7 @@ def frame_stats(y: torch.Tensor, frame_length: int = 2048, hop: int = 512, cente
                 mask: int = 0x1FF) -> torch.Tensor:
     """Time-domain frame features of clips y [B, L]: [B, 9, T] float32, rows as FS_ROWS (only the rows
     selected by `mask` are written)."""
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     B, L = y.shape
     Tn = _frames(L, frame_length, hop, center)
     out = torch.zeros((B, 9, Tn), dtype=torch.float32, device=y.device)
@@ -1025,14 +1115,12 @@ def sosfiltfilt(x: torch.Tensor, sos: np.ndarray, zi: np.ndarray, padlen: int) -
     S = sos.shape[0]
     if L <= padlen:
         raise ValueError(f"The length of the input vector x must be greater than padlen, which is {padlen}.")
-    nbytes = lib().syg_sosfiltfilt_work_bytes(B, L, padlen, S)
-    if nbytes < 0:
-        raise SygnalsHipError(f"sosfiltfilt: unsupported configuration (sections={S}, max 8)")
     # (0 bytes: the clip-resident form keeps the clip in registers and needs no workspace)
-    work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device) if nbytes > 0 else None
+    work = _workspace("syg_sosfiltfilt_work_bytes", B, L, padlen, S, dtype=torch.float64, device=x.device,
+                      error=SygnalsHipError(f"sosfiltfilt: unsupported configuration (sections={S}, max 8)"))
     y = torch.empty((B, L), dtype=torch.float32, device=x.device)
     _call("syg_sosfiltfilt_f32", _ptr(x), B, L, _ld(x), sos.ctypes.data_as(C.c_void_p), zi.ctypes.data_as(C.c_void_p), S,
-          int(padlen), _ptr(y), _ld(y), None if work is None else _ptr(work))
+          int(padlen), _ptr(y), _ld(y), _ptr(work))
     return y
 
 
@@ -1041,7 +1129,7 @@ SOSFILT_KEYS = ("chunk", "tile", "chunks_per_wave", "scan_ahead", "group_section
 
 def sosfilt_constants() -> dict:
     """Geometry of the causal SOS kernels (syg_sosfilt_constants), by name."""
-    return {name: int(lib().syg_sosfilt_constants(i)) for i, name in enumerate(SOSFILT_KEYS)}
+    return _constants("syg_sosfilt_constants", SOSFILT_KEYS)
 
 
 def sosfilt(x: torch.Tensor, sos: np.ndarray, zi: Optional[torch.Tensor] = None, return_state: bool = False,
@@ -1078,9 +1166,8 @@ def sosfilt(x: torch.Tensor, sos: np.ndarray, zi: Optional[torch.Tensor] = None,
         zi = zi.to(x.device).contiguous()
     y = out if out is not None else torch.empty((B, L), dtype=torch.float32, device=x.device)
     zf = torch.empty((B, S, 2), dtype=torch.float64, device=x.device) if return_state else None
-    nbytes = lib().syg_sosfilt_work_bytes(B, L, S)
-    if nbytes < 0:
-        raise SygnalsHipError(f"sosfilt: unsupported configuration (B={B}, L={L}, sections={S})")
+    nbytes = _work_bytes("syg_sosfilt_work_bytes", B, L, S,
+                         error=SygnalsHipError(f"sosfilt: unsupported configuration (B={B}, L={L}, sections={S})"))
     work = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device) if L > sosfilt_constants()["chunk"] else None
     _call("syg_sosfilt_f32", _ptr(x), B, L, _ld(x), sos.ctypes.data_as(C.c_void_p), S, _ptr(zi), _ptr(y), _ld(y), _ptr(zf),
           _ptr(work))
@@ -1108,8 +1195,7 @@ def welch(x: torch.Tensor, nperseg: int, noverlap: int, nfft: int, window_host: 
     if not (is_pow2(nfft) and 8 <= nfft <= 16384):
         return welch_rows(x, nperseg, noverlap, nfft, window_host, detrend, scale)
     win = _dev(np.asarray(window_host, dtype=np.float32))
-    nbytes = lib().syg_welch_work_bytes(B, nfft)
-    work = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    work = _workspace("syg_welch_work_bytes", B, nfft, dtype=torch.float32, device=x.device)
     out = torch.empty((B, nfft // 2 + 1), dtype=torch.float32, device=x.device)
     _call("syg_welch_f32", _ptr(x), B, L, _ld(x), nperseg, nperseg - noverlap, nfft, _ptr(win), _ptr(twiddle_rfft_dev(nfft)),
           detrend_code(detrend), float(scale), _ptr(out), _ptr(work))
@@ -1131,8 +1217,7 @@ def welch_rows(x: torch.Tensor, nperseg: int, noverlap: int, nfft: int, window_h
     acc = torch.empty(F, dtype=torch.float64, device=x.device)
     x = x.contiguous()
     for b in range(B):
-        for s0 in range(0, nseg, MAX_ROWS):
-            sc = min(MAX_ROWS, nseg - s0)
+        for s0, sc in _row_blocks(nseg):
             X = fft_any(pack_frames(x[b:b + 1], sc, nperseg, step, s0, nfft, window=win, detrend=detrend))
             P = torch.empty((sc, F), dtype=torch.float32, device=x.device)
             _call("syg_psd_onesided_f32", _ptr(X), sc, nfft, float(scale), _ptr(P))
@@ -1164,10 +1249,9 @@ def _pair_rows(x, y, who: str, same_len: bool = False):
     if same_len and x.shape[1] != y.shape[1]:
         raise ValueError(f"{who}: rows of unequal length are not served: x has {x.shape[1]} samples and y {y.shape[1]} "
                          "(scipy zero-pads the shorter one; here the caller does)")
-    require_gpu()
-    if not x.is_cuda or not y.is_cuda:
-        raise ValueError(f"{who}: x and y must be device tensors")
-    return (x if x.stride(1) == 1 else x.contiguous()), (y if y.stride(1) == 1 else y.contiguous())
+    _on_device(x, f"{who}: x")
+    _on_device(y, f"{who}: y")
+    return _unit_stride(x), _unit_stride(y)
 
 
 def csd_fused_takes(nfft: int) -> bool:
@@ -1196,11 +1280,9 @@ def cross_spectrum(x: torch.Tensor, y: torch.Tensor, nperseg: int, noverlap: int
     out = {k: torch.empty((B, F, 2) if k == "pxy" else (B, F), dtype=torch.float32, device=x.device) for k in want}
     win = _dev(np.asarray(window_host, dtype=np.float32))
     if csd_fused_takes(nfft):
-        for b0 in range(0, B, MAX_ROWS):
-            bc = min(MAX_ROWS, B - b0)
+        for b0, bc in _row_blocks(B):
             xs, ys = x[b0:b0 + bc], (y if y.shape[0] == 1 else y[b0:b0 + bc])
-            nbytes = lib().syg_csd_work_bytes(bc, nseg, nfft)
-            work = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x.device)
+            work = _workspace("syg_csd_work_bytes", bc, nseg, nfft, dtype=torch.float64, device=x.device)
             _call("syg_csd_f32", _ptr(xs), _ptr(ys), bc, ys.shape[0], L, _ld(xs), _ld(ys), nperseg, step, nfft, _ptr(win),
                   _ptr(twiddle_dev(nfft)), dcode, float(scale), *(_ptr(out[k][b0:b0 + bc]) if k in out else None for k in CSD_WANTS),
                   _ptr(work))
@@ -1209,8 +1291,7 @@ def cross_spectrum(x: torch.Tensor, y: torch.Tensor, nperseg: int, noverlap: int
     one_y = y.shape[0] == 1 and nseg <= MAX_ROWS           # the reference row's spectra: once for every x row
     Yc = None
     for b in range(B):
-        for s0 in range(0, nseg, MAX_ROWS):
-            sc = min(MAX_ROWS, nseg - s0)
+        for s0, sc in _row_blocks(nseg):
             X = fft_any(pack_frames(x[b:b + 1], sc, nperseg, step, s0, nfft, window=win, detrend=detrend))
             if Yc is None or not one_y:
                 yb = y if y.shape[0] == 1 else y[b:b + 1]
@@ -1240,8 +1321,7 @@ def gcc(x: torch.Tensor, y: torch.Tensor, max_lag: int, weighting: str = "none")
     W = 2 * max_lag + 1
     out = torch.empty((B, W), dtype=torch.float32, device=x.device)
     Y = fft_any(pack_rows(y, n, cplx=True)) if By == 1 else None
-    for b0 in range(0, B, MAX_ROWS):
-        bc = min(MAX_ROWS, B - b0)
+    for b0, bc in _row_blocks(B):
         X = fft_any(pack_rows(x[b0:b0 + bc], n, cplx=True))
         Yb = Y if By == 1 else fft_any(pack_rows(y[b0:b0 + bc], n, cplx=True))
         _call("syg_gcc_weight_c64", _ptr(X), _ptr(Yb), bc, Yb.shape[0], n, int(weighting == "phat"), _ptr(X))
@@ -1254,14 +1334,12 @@ def peak_pick(r: torch.Tensor, lag0: int, fs: float = 1.0):
     """Per row of r [B, W] (float32, device): (delay float64 [B], lag int64 [B], peak float64 [B]) of the first maximum,
     refined by the parabola through its neighbours where it is interior and the parabola opens downwards; the lag of
     column i is lag0 + i, delay = (lag + shift) / fs."""
-    require_gpu()
-    if not isinstance(r, torch.Tensor) or r.dim() != 2 or r.dtype != torch.float32 or not r.is_cuda or r.shape[0] < 1 or r.shape[1] < 1:
-        raise ValueError("peak_pick: r must be a non-empty float32 [B, W] device tensor")
+    r = _f32_in(r, "peak_pick: r", 2)
+    B, W = r.shape
+    if B < 1 or W < 1:
+        raise ValueError("peak_pick: empty input")
     if not (fs > 0 and np.isfinite(fs)):
         raise ValueError(f"peak_pick: fs must be positive and finite, got {fs}")
-    if r.stride(1) != 1:
-        r = r.contiguous()
-    B, W = r.shape
     delay = torch.empty(B, dtype=torch.float64, device=r.device)
     lag = torch.empty(B, dtype=torch.int64, device=r.device)
     peak = torch.empty(B, dtype=torch.float64, device=r.device)
@@ -1397,8 +1475,8 @@ def fft_any(x: torch.Tensor, inverse: bool = False) -> torch.Tensor:
         # the four-step passes put the rows on a grid axis of at most 65535: long transforms of very many rows go
         # through in blocks (without this a Bluestein length above 8192 would recurse on the same row count)
         out = torch.empty_like(x)
-        for r0 in range(0, rows, MAX_ROWS):
-            out[r0:r0 + MAX_ROWS] = fft_any(x[r0:r0 + MAX_ROWS], inverse)
+        for r0, rc in _row_blocks(rows):
+            out[r0:r0 + rc] = fft_any(x[r0:r0 + rc], inverse)
         return out
     plan = fft_plan(n)
     if plan is not None or is_pow2(n):           # (a power of two without a plan is too long: _fft_direct says so)
@@ -1415,10 +1493,7 @@ def fft_any(x: torch.Tensor, inverse: bool = False) -> torch.Tensor:
 
 # ------------------------------------------------------------------ feature formatting for ML
 def _mat32(x: torch.Tensor) -> torch.Tensor:
-    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda:
-        require_gpu()
-        raise ValueError("x must be a float32 [n, F] device tensor")
-    return x.contiguous()
+    return _f32_in(x, "x", 2).contiguous()
 
 
 def col_stats(x: torch.Tensor) -> torch.Tensor:
@@ -1492,17 +1567,11 @@ def pack_rows(x: torch.Tensor, n: int, window: Optional[torch.Tensor] = None, de
               reverse: bool = False, cplx: bool = False) -> torch.Tensor:
     """Rows of x [rows, len] -> [rows, n] real (or [rows, n, 2] complex) rows: mean ('constant') or least-squares
     line ('linear') removed, windowed, optionally time-reversed, zero-padded / truncated to n."""
-    require_gpu()
-    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda:
-        raise ValueError("x must be a float32 [rows, len] device tensor")
-    if x.stride(1) != 1:
-        x = x.contiguous()
+    x = _f32_in(x, "x", 2)
     rows, ln = x.shape
     out = torch.empty((rows, n, 2) if cplx else (rows, n), dtype=torch.float32, device=x.device)
-    work = None
     dcode = detrend_code(detrend)
-    if dcode:
-        work = torch.empty(lib().syg_pack_rows_work_bytes(rows) // 8, dtype=torch.float64, device=x.device)
+    work = _workspace("syg_pack_rows_work_bytes", rows, dtype=torch.float64, device=x.device) if dcode else None
     _call("syg_pack_rows_f32", _ptr(x), rows, ln, _ld(x), _ptr(window), dcode, int(bool(reverse)), int(bool(cplx)),
           _ptr(out), n, _ptr(work))
     return out
@@ -1833,7 +1902,7 @@ def cqt(y: torch.Tensor, sr: float, hop_length: int = 512, fmin=None, n_bins: in
 # ------------------------------------------------------------------ pitch (yin / pyin)
 def _pitch_setup(y, sr, fmin, fmax, frame_length, win_length, hop, center):
     from . import _pitch as P
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     win_length = int(win_length) if win_length is not None else frame_length // 2
     hop = int(hop) if hop is not None else frame_length // 4
     if not (0 < fmin < fmax <= sr / 2):
@@ -1886,16 +1955,14 @@ def pyin_viterbi(cand_bin: torch.Tensor, cand_prob: torch.Tensor, cand_count: to
     tabs, R, h = P.transition_tables(int(n_bins), int(width))
     ltab = _cached(("pyin_ltab", int(n_bins), int(width)), lambda: _dev(tabs))
     lconst = np.ascontiguousarray(P.log_consts(int(n_bins)))
-    wb = lib().syg_pyin_work_bytes(B, Tn, int(n_bins))
-    if wb < 0:
-        raise ValueError(f"pyin_viterbi: bad shape B={B} T={Tn} n_bins={n_bins}")
-    work = torch.empty((wb,), dtype=torch.uint8, device=dev)
+    work = _workspace("syg_pyin_work_bytes", B, Tn, int(n_bins), dtype=torch.uint8, device=dev,
+                      error=ValueError(f"pyin_viterbi: bad shape B={B} T={Tn} n_bins={n_bins}"))
     f0 = torch.empty((B, Tn), dtype=torch.float32, device=dev)
     voiced = torch.empty((B, Tn), dtype=torch.uint8, device=dev)
     state = torch.empty((B, Tn), dtype=torch.int32, device=dev)
     _call("syg_pyin_viterbi_f32", _ptr(cand_bin.contiguous()), _ptr(cand_prob.contiguous()), _ptr(cand_count.contiguous()),
           _ptr(voiced_prob.contiguous()), B, Tn, K, int(n_bins), h, _ptr(ltab), R, lconst.ctypes.data_as(C.c_void_p),
-          float(fmin), _ptr(work), wb, _ptr(f0), _ptr(voiced), _ptr(state))
+          float(fmin), _ptr(work), _nbytes(work), _ptr(f0), _ptr(voiced), _ptr(state))
     return f0, voiced.bool(), state
 
 
@@ -1950,9 +2017,7 @@ def istft2048(D: torch.Tensor, hop: int = 512, length: Optional[int] = None, cen
     length defaults to 512 (T - 1), librosa's center=True length.  ldy: row stride of the output (>= length)."""
     require_gpu()
     _hpss_stft_args(2048, hop, win_length, window, center)
-    if D.dim() != 4 or D.shape[2] != 1025 or D.shape[3] != 2 or D.dtype != torch.float32 or not D.is_cuda:
-        raise ValueError("D must be a float32 CUDA tensor [B, T, 1025, 2]")
-    D = D.contiguous()
+    D = _f32_in(D, "D", 4, (1025, 2)).contiguous()
     B, Tn = D.shape[0], D.shape[1]
     length = 512 * (Tn - 1) if length is None else int(length)
     if length < 1:
@@ -1981,9 +2046,7 @@ def hpss_masks(D: torch.Tensor, kernel_size=31, power: float = 2.0, margin=1.0, 
         raise ValueError("Margins must be >= 1.0. A typical range is between 1 and 10.")
     if not (power > 0):
         raise ValueError("power must be strictly positive")
-    if D.dim() != 4 or D.shape[2] != 1025 or D.shape[3] != 2 or D.dtype != torch.float32 or not D.is_cuda:
-        raise ValueError("D must be a float32 CUDA tensor [B, T, 1025, 2]")
-    D = D.contiguous()
+    D = _f32_in(D, "D", 4, (1025, 2)).contiguous()
     B, Tn = D.shape[0], D.shape[1]
     new = lambda: torch.empty((B, Tn, 1025), dtype=torch.float32, device=D.device)  # noqa: E731
     Mh, Mp = new(), new()
@@ -1999,7 +2062,7 @@ def hpss(y: torch.Tensor, kernel_size=31, power: float = 2.0, margin=1.0, hop_le
     syg_stft2048_c2c_f32 -> syg_hpss_masks_f32 -> syg_istft2048_f32 (both components from one read of D)."""
     require_gpu()
     hop = _hpss_stft_args(n_fft, hop_length, win_length, window, center)
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     if y.shape[0] < 1 or y.shape[1] < 1:
         raise ValueError("hpss: empty input")
     D = stft2048_c2c(y, hop, True, "hann", 2048)
@@ -2036,9 +2099,7 @@ def onset_strength(mel: torch.Tensor, lag: int = 1, max_size: int = 1, pad: int 
     """librosa.onset.onset_strength after the mel front end (syg_onset_strength_f32): mel POWER [B, M, T] -> envelope
     [B, T_out] float32, `pad` zeros in front (T_out defaults to pad + T - lag, the uncut envelope).  The dB matrix is
     formed on the fly (ref 1.0, top_db relative to each clip's maximum) and never stored."""
-    require_gpu()
-    if mel.dim() != 3 or mel.dtype != torch.float32 or not mel.is_cuda:
-        raise ValueError("mel must be a float32 CUDA tensor [B, M, T]")
+    mel = _f32_in(mel, "mel", 3, axes="[B, M, T]")
     if not isinstance(lag, (int, np.integer)) or lag < 1:
         raise ValueError("lag must be a positive integer")
     if not isinstance(max_size, (int, np.integer)) or max_size < 1:
@@ -2046,8 +2107,7 @@ def onset_strength(mel: torch.Tensor, lag: int = 1, max_size: int = 1, pad: int 
     mel = mel.contiguous()
     B, M, Tn = mel.shape
     T_out = int(pad) + Tn - int(lag) if T_out is None else int(T_out)
-    wb = lib().syg_onset_strength_work_bytes(B, M, Tn)
-    work = torch.empty((wb // 4,), dtype=torch.float32, device=mel.device) if wb > 0 else None
+    work = _workspace("syg_onset_strength_work_bytes", B, M, Tn, dtype=torch.float32, device=mel.device)
     env = torch.empty((B, max(T_out, 0)), dtype=torch.float32, device=mel.device)
     _call("syg_onset_strength_f32", _ptr(mel), B, M, Tn, float(amin), float(top_db) if top_db is not None else -1.0,
           int(lag), int(max_size), int(pad), T_out, int(bool(detrend)), _ptr(env), _ptr(work))
@@ -2058,10 +2118,10 @@ def onset_peaks(env: torch.Tensor, pre_max: int, post_max: int, pre_avg: int, po
                 normalize: bool = True, backtrack: bool = False, energy: Optional[torch.Tensor] = None):
     """util.peak_pick with onset_detect's normalisation and backtracking (syg_onset_peaks_f32) on envelopes [B, T] ->
     (frames [B, T] int32: the onsets in ascending order, -1 beyond them; count [B] int32), both on the device."""
-    env = _clips(env, "env")
+    env = _f32_in(env, "env", 2)
     B, Tn = env.shape
     if energy is not None:
-        energy = _clips(energy, "energy")
+        energy = _f32_in(energy, "energy", 2)
         if energy.shape != env.shape:
             raise ValueError("energy must have the envelope's shape")
         if _ld(energy) != _ld(env):
@@ -2075,7 +2135,7 @@ def onset_peaks(env: torch.Tensor, pre_max: int, post_max: int, pre_avg: int, po
 
 def clip_metrics(y: torch.Tensor) -> torch.Tensor:
     """Per-clip totals of y [B, L] (syg_clip_metrics_f32) -> [B, 2] float32: sum of squares, peak |y|."""
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     B, L = y.shape
     out = torch.empty((B, 2), dtype=torch.float32, device=y.device)
     _call("syg_clip_metrics_f32", _ptr(y), B, L, _ld(y), _ptr(out))
@@ -2102,7 +2162,7 @@ def dwt(y: torch.Tensor, wavelet="db4", level: Optional[int] = None, mode: str =
     directly a feature vector and `packed.split(lens, dim=1)` the coefficient arrays.  `level=None` is
     max(1, dwt_max_level); a level above the maximum warns, as PyWavelets does."""
     from . import _wavelets as W
-    y = _clips(y)
+    y = _f32_in(y, "y", 2)
     B, L = y.shape
     if L < 1:
         raise ValueError("y must hold at least one sample")
@@ -2114,8 +2174,7 @@ def dwt(y: torch.Tensor, wavelet="db4", level: Optional[int] = None, mode: str =
     total = h.syg_dwt_lengths(L, F, level, C.cast(lens_c, C.c_void_p))
     if total < 0:
         check(-1, "syg_dwt_lengths")
-    wb = h.syg_dwt_work_bytes(B, L, F, level)
-    work = torch.empty((wb // 4,), dtype=torch.float32, device=y.device) if wb > 0 else None
+    work = _workspace("syg_dwt_work_bytes", B, L, F, level, dtype=torch.float32, device=y.device)
     out = torch.empty((B, total), dtype=torch.float32, device=y.device)
     _call("syg_dwt_f32", _ptr(y), B, L, _ld(y), _ptr(dec_lo), _ptr(dec_hi), F, code, level, _ptr(out), total, _ptr(work))
     return out, [int(v) for v in lens_c]
@@ -2127,7 +2186,7 @@ def idwt(packed: torch.Tensor, lens, wavelet="db4", mode: str = "symmetric") -> 
     sample is dropped, as pywt.waverec does; any other mismatch is a ValueError.  The served modes extend nothing on the
     way back, so `mode` is only checked."""
     from . import _wavelets as W
-    packed = _clips(packed, "packed")
+    packed = _f32_in(packed, "packed", 2)
     W.mode_code(mode)
     (_, _, rec_lo, rec_hi), F = _wavelet_dev(wavelet)
     lens = [int(v) for v in lens]
@@ -2136,13 +2195,9 @@ def idwt(packed: torch.Tensor, lens, wavelet="db4", mode: str = "symmetric") -> 
     if packed.shape[1] != sum(lens):
         raise ValueError(f"packed rows hold {packed.shape[1]} coefficients, lens adds up to {sum(lens)}")
     levels = len(lens) - 1
-    h = lib()
     lens_c = (C.c_int64 * len(lens))(*lens)
     lp = C.cast(lens_c, C.c_void_p)
-    wb = h.syg_idwt_work_bytes(B, lp, levels, F)
-    if wb < 0:
-        check(-1, "syg_idwt_work_bytes")
-    work = torch.empty((wb // 4,), dtype=torch.float32, device=packed.device) if wb > 0 else None
+    work = _workspace("syg_idwt_work_bytes", B, lp, levels, F, dtype=torch.float32, device=packed.device)
     y = torch.empty((B, Lout), dtype=torch.float32, device=packed.device)
     _call("syg_idwt_f32", _ptr(packed), B, _ld(packed), lp, levels, _ptr(rec_lo), _ptr(rec_hi), F, _ptr(y), Lout, _ptr(work))
     return y
@@ -2150,16 +2205,6 @@ def idwt(packed: torch.Tensor, lens, wavelet="db4", mode: str = "symmetric") -> 
 
 # ------------------------------------------------------------------ audio effects
 LFO_SHAPES = {"sine": 0, "triangle": 1, "square": 2}          # SYG_LFO_* of include/sygnals_hip.h
-
-
-def _fx_out(x: torch.Tensor, out: Optional[torch.Tensor], L: Optional[int] = None) -> torch.Tensor:
-    """The output rows of an effect: a new [B, L] tensor, or `out` checked (x itself for an in-place call)."""
-    shape = (x.shape[0], x.shape[1] if L is None else L)
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=x.device)
-    if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != x.device or out.stride(1) != 1:
-        raise ValueError(f"out must be a float32 tensor {shape} on x's device with unit stride along a row")
-    return out
 
 
 def fx_delay_chunk() -> int:
@@ -2171,7 +2216,7 @@ def fx_delay(x: torch.Tensor, delay_samples: int, feedback: float = 0.4, wet: fl
              out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Feedback delay of every row of x [B, L] (syg_fx_delay_f32): w[n] = x[n] + feedback w[n - D], out[n] = dry x[n] +
     wet w[n - D] with D = delay_samples >= 1 (D >= L: out = dry x).  `out` may be x."""
-    x = _clips(x, "x")
+    x = _f32_in(x, "x", 2)
     B, L = x.shape
     D = int(delay_samples)
     if B < 1 or L < 1:
@@ -2180,11 +2225,8 @@ def fx_delay(x: torch.Tensor, delay_samples: int, feedback: float = 0.4, wet: fl
         raise ValueError("fx_delay: delay_samples must be >= 1")
     if not 0.0 <= feedback < 1.0:
         raise ValueError("fx_delay: feedback must be in [0, 1)")
-    out = _fx_out(x, out)
-    wb = lib().syg_fx_delay_work_bytes(B, L, D)
-    if wb < 0:
-        check(-1, "syg_fx_delay_work_bytes")
-    work = torch.empty((wb // 4,), dtype=torch.float32, device=x.device) if wb > 0 else None
+    out = _out(out, x.shape, x)
+    work = _workspace("syg_fx_delay_work_bytes", B, L, D, dtype=torch.float32, device=x.device)
     _call("syg_fx_delay_f32", _ptr(x), B, L, _ld(x), D, float(feedback), float(dry), float(wet), _ptr(out), _ld(out),
           _ptr(work))
     return out
@@ -2194,18 +2236,18 @@ def fx_mix(x: torch.Tensor, y: Optional[torch.Tensor] = None, a: float = 1.0, b:
            out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[r, n] = a x[r, n] + b y[r, n] for n < length (syg_fx_mix_f32); x [B, Lx] and y [B, Ly] read as zero past
     their own lengths, y may be None (a x); length defaults to the longer of the two.  `out` may be x."""
-    x = _clips(x, "x")
+    x = _f32_in(x, "x", 2)
     B, Lx = x.shape
     Ly = 0
     if y is not None:
-        y = _clips(y, "y")
+        y = _f32_in(y, "y", 2)
         if y.shape[0] != B:
             raise ValueError("fx_mix: x and y must hold the same number of rows")
         Ly = y.shape[1]
     L = max(Lx, Ly) if length is None else int(length)
     if B < 1 or L < 1 or Lx < 1 or (y is not None and Ly < 1):
         raise ValueError("fx_mix: empty input")
-    out = _fx_out(x, out, L)
+    out = _out(out, (B, L), x)
     _call("syg_fx_mix_f32", _ptr(x), Lx, _ld(x), _ptr(y), Ly, _ld(y) if y is not None else 0, B, L, float(a), float(b),
           _ptr(out), _ld(out))
     return out
@@ -2215,7 +2257,7 @@ def fx_tremolo(x: torch.Tensor, sr: float, rate: float = 5.0, depth: float = 0.5
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x ((1 - depth) + depth lfo) on rows x [B, L] (syg_fx_tremolo_f32), the LFO in float64 on the device; n0 is the
     index of the rows' first sample (a row that continues an earlier one).  `out` may be x."""
-    x = _clips(x, "x")
+    x = _f32_in(x, "x", 2)
     if shape not in LFO_SHAPES:
         raise ValueError("LFO shape must be 'sine', 'triangle', or 'square'.")
     if not 0.0 <= depth <= 1.0:
@@ -2224,7 +2266,7 @@ def fx_tremolo(x: torch.Tensor, sr: float, rate: float = 5.0, depth: float = 0.5
         raise ValueError("fx_tremolo: rate and sr must be positive")
     if x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError("fx_tremolo: empty input")
-    out = _fx_out(x, out)
+    out = _out(out, x.shape, x)
     _call("syg_fx_tremolo_f32", _ptr(x), x.shape[0], x.shape[1], _ld(x), float(sr), float(rate), float(depth),
           LFO_SHAPES[shape], int(n0), _ptr(out), _ld(out))
     return out
@@ -2233,14 +2275,14 @@ def fx_tremolo(x: torch.Tensor, sr: float, rate: float = 5.0, depth: float = 0.5
 def fx_compress(x: torch.Tensor, threshold: float = 0.8, ratio: float = 4.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Downward compression of rows x [B, L] (syg_fx_compress_f32): |x| > threshold -> threshold + (|x| - threshold) /
     ratio with the sign kept; the other samples are copied bit for bit.  `out` may be x."""
-    x = _clips(x, "x")
+    x = _f32_in(x, "x", 2)
     if not threshold >= 0.0:
         raise ValueError("fx_compress: threshold must be >= 0")
     if not ratio >= 1.0:
         raise ValueError("fx_compress: ratio must be >= 1")
     if x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError("fx_compress: empty input")
-    out = _fx_out(x, out)
+    out = _out(out, x.shape, x)
     _call("syg_fx_compress_f32", _ptr(x), x.shape[0], x.shape[1], _ld(x), float(threshold), float(ratio), _ptr(out), _ld(out))
     return out
 
@@ -2265,15 +2307,11 @@ def spectral_gate(D: torch.Tensor, Dn: torch.Tensor, amount: float = 1.0, profil
     """The spectral-subtraction gain of noise_reduction_spectral (syg_spectral_gate_f32): D [B, T, 1025, 2] the clip's
     STFT, Dn [B, Tn, 1025, 2] the STFT of its noise segment -> G [B, T, 1025] float32 = sqrt(max(0, 1 - amount N / |D|^2))
     (0 where |D|^2 is 0), a mask for istft2048; with `profile` also N [B, 1025], the mean noise power per bin."""
-    require_gpu()
-    for name, t in (("D", D), ("Dn", Dn)):
-        if t.dim() != 4 or t.shape[2] != 1025 or t.shape[3] != 2 or t.dtype != torch.float32 or not t.is_cuda:
-            raise ValueError(f"{name} must be a float32 CUDA tensor [B, T, 1025, 2]")
+    D, Dn = (_f32_in(t, name, 4, (1025, 2)).contiguous() for name, t in (("D", D), ("Dn", Dn)))
     if Dn.shape[0] != D.shape[0]:
         raise ValueError("D and Dn must hold the same number of clips")
     if not amount >= 0.0:
         raise ValueError("reduction_amount must be non-negative.")
-    D, Dn = D.contiguous(), Dn.contiguous()
     B, Tn = D.shape[0], D.shape[1]
     if B < 1 or Tn < 1 or Dn.shape[1] < 1:
         raise ValueError("spectral_gate: empty input")
@@ -2295,9 +2333,7 @@ def phase_vocoder_chunk() -> int:
 def phase_vocoder(D: torch.Tensor, rate: float, form: Optional[str] = None) -> torch.Tensor:
     """librosa.phase_vocoder (n_fft 2048, hop 512) on the frame-major STFT D [B, T, 1025, 2] -> [B, ceil(T / rate), 1025, 2]
     (syg_phase_vocoder_f32).  form: None (the library's rule) | "chain" | "chunked", for tests and the benchmark."""
-    require_gpu()
-    if D.dim() != 4 or D.shape[2] != 1025 or D.shape[3] != 2 or D.dtype != torch.float32 or not D.is_cuda:
-        raise ValueError("D must be a float32 CUDA tensor [B, T, 1025, 2]")
+    D = _f32_in(D, "D", 4, (1025, 2))
     if form not in VOCODER_FORMS:
         raise ValueError("form must be None, 'chain' or 'chunked'")
     if not rate > 0:
@@ -2308,10 +2344,7 @@ def phase_vocoder(D: torch.Tensor, rate: float, form: Optional[str] = None) -> t
         raise ValueError("phase_vocoder: empty input")
     col, alpha = (_dev(a) for a in T.vocoder_steps(Tn, rate))      # not cached: an augmenter draws a new rate per call
     To, f = int(col.shape[0]), VOCODER_FORMS[form]
-    wb = lib().syg_phase_vocoder_work_bytes(B, To, f)
-    if wb < 0:
-        check(-1, "syg_phase_vocoder_work_bytes")
-    work = torch.empty((wb // 8,), dtype=torch.float64, device=D.device) if wb > 0 else None
+    work = _workspace("syg_phase_vocoder_work_bytes", B, To, f, dtype=torch.float64, device=D.device)
     out = torch.empty((B, To, 1025, 2), dtype=torch.float32, device=D.device)
     _call("syg_phase_vocoder_f32", _ptr(D), B, Tn, _ptr(col), _ptr(alpha), To, _ptr(out), _ptr(work), f)
     return out
@@ -2320,7 +2353,7 @@ def phase_vocoder(D: torch.Tensor, rate: float, form: Optional[str] = None) -> t
 def time_stretch(y: torch.Tensor, rate: float) -> torch.Tensor:
     """librosa.effects.time_stretch of clips y [B, L] -> [B, round(L / rate)] (Python's round, half to even, as librosa):
     stft2048_c2c -> phase_vocoder -> istft2048(length=...), hann, hop 512, centred."""
-    y = _clips(y, "y")
+    y = _f32_in(y, "y", 2)
     if not rate > 0:
         raise ValueError("Time stretch rate must be positive.")
     if y.shape[0] < 1 or y.shape[1] < 1:
@@ -2351,18 +2384,15 @@ def _snr_dev(snr_db, B: int, who: str) -> torch.Tensor:
 def fx_add_noise(y: torch.Tensor, noise: torch.Tensor, snr_db, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y + noise scaled per row to the signal-to-noise ratio snr_db (a number, or one per row), powers in float64
     (syg_fx_add_noise_f32); a row whose signal or noise power is below the float64 epsilon is copied.  `out` may be y."""
-    y, noise = _clips(y, "y"), _clips(noise, "noise")
+    y, noise = _f32_in(y, "y", 2), _f32_in(noise, "noise", 2)
     if noise.shape != y.shape:
         raise ValueError("fx_add_noise: y and noise must have the same shape")
     B, L = y.shape
     if B < 1 or L < 1:
         raise ValueError("fx_add_noise: empty input")
     snr = _snr_dev(snr_db, B, "fx_add_noise")
-    out = _fx_out(y, out)
-    wb = lib().syg_fx_add_noise_work_bytes(B, L)
-    if wb < 0:
-        check(-1, "syg_fx_add_noise_work_bytes")
-    work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device) if wb > 0 else None
+    out = _out(out, y.shape, y)
+    work = _workspace("syg_fx_add_noise_work_bytes", B, L, dtype=torch.float64, device=y.device)
     _call("syg_fx_add_noise_f32", _ptr(y), B, L, _ld(y), _ptr(noise), _ld(noise), _ptr(snr), _ptr(out), _ld(out), _ptr(work))
     return out
 
@@ -2371,9 +2401,7 @@ def fx_add_noise(y: torch.Tensor, noise: torch.Tensor, snr_db, out: Optional[tor
 def rng_constants() -> dict:
     """The figures the device generator rests on (the library owns them): Philox rounds, the stream ids of noise samples
     and of per-row draws, the row limit, the longest coloured row."""
-    h = lib()
-    return dict(rounds=int(h.syg_rng_constants(0)), stream_noise=int(h.syg_rng_constants(1)), stream_row=int(h.syg_rng_constants(2)),
-                row_limit=int(h.syg_rng_constants(3)), colored_max=int(h.syg_rng_constants(4)))
+    return _constants("syg_rng_constants", ("rounds", "stream_noise", "stream_row", "row_limit", "colored_max"))
 
 
 def philox_words(counter, key) -> torch.Tensor:
@@ -2455,44 +2483,41 @@ def colored_noise(B: int, L: int, seed: int, exponent: float, first_row: int = 0
 def fx_add_noise_gen(y: torch.Tensor, snr_db, seed: int, first_row: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fx_add_noise(y, randn(B, L, seed, first_row), snr_db) without the noise ever existing in memory
     (syg_fx_add_noise_gen_f32): within one float32 ulp of that call (the sums are taken in another order).  `out` may be y."""
-    y = _clips(y, "y")
+    y = _f32_in(y, "y", 2)
     B, L = y.shape
     if B < 1 or L < 1:
         raise ValueError("fx_add_noise_gen: empty input")
     seed, first_row = RNG.check_seed(seed), RNG.check_rows(first_row, B)
     snr = _snr_dev(snr_db, B, "fx_add_noise_gen")
-    out = _fx_out(y, out)
-    wb = lib().syg_fx_add_noise_gen_work_bytes(B, L)
-    if wb < 0:
-        check(-1, "syg_fx_add_noise_gen_work_bytes")
-    work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device) if wb > 0 else None
+    out = _out(out, y.shape, y)
+    work = _workspace("syg_fx_add_noise_gen_work_bytes", B, L, dtype=torch.float64, device=y.device)
     _call("syg_fx_add_noise_gen_f32", _ptr(y), B, L, _ld(y), seed, first_row, _ptr(snr), _ptr(out), _ld(out), _ptr(work))
     return out
 
 
 # ------------------------------------------------------------------ numerical Laplace transform
 LAPLACE_FORMS = {None: -1, "whole": 0, "segmented": 1}
+_LAPLACE_FIGURES = {"C": "chunk", **{n: n for n in ("tile_rows", "tile_cols", "segment", "steep", "fac_stride")}}
 
 
 def laplace_constants() -> dict:
     """The figures syg_laplace_f32 rests on (the library owns them): samples per chunk, the tile's chunk rows and s-value
     columns, samples per segment of the segmented form, samples a steep column reads, float64 factors per column."""
-    h = lib()
-    return dict(C=int(h.syg_laplace_chunk()), tile_rows=int(h.syg_laplace_tile_rows()), tile_cols=int(h.syg_laplace_tile_cols()),
-                segment=int(h.syg_laplace_segment()), steep=int(h.syg_laplace_steep()), fac_stride=int(h.syg_laplace_fac_stride()))
+    return _constants("syg_laplace", _LAPLACE_FIGURES)
 
 
-@functools.lru_cache(maxsize=16)
-def _laplace_plan_dev(dev: int, s_bytes: bytes, t_step: float):
-    k = laplace_constants()
-    p = LP.plan(np.frombuffer(s_bytes, dtype=np.complex128), t_step, k["C"], k["tile_cols"], k["segment"], k["steep"],
-                k["fac_stride"])
-    return p, _dev(p.table), _dev(p.fac), _dev(p.col)
+def _laplace_plan_dev(s_bytes: bytes, t_step: float):
+    def build():
+        k = laplace_constants()
+        p = LP.plan(np.frombuffer(s_bytes, dtype=np.complex128), t_step, k["C"], k["tile_cols"], k["segment"], k["steep"],
+                    k["fac_stride"])
+        return p, _dev(p.table), _dev(p.fac), _dev(p.col)
+    return _cached(("laplace_plan", s_bytes, t_step), build, 16)
 
 
-@functools.lru_cache(maxsize=64)
-def _laplace_anchor_dev(dev: int, s_bytes: bytes, t_step: float, L: int):
-    return _dev(LP.anchors(_laplace_plan_dev(dev, s_bytes, t_step)[0], L))
+def _laplace_anchor_dev(s_bytes: bytes, t_step: float, L: int):
+    return _cached(("laplace_anchor", s_bytes, t_step, L),
+                   lambda: _dev(LP.anchors(_laplace_plan_dev(s_bytes, t_step)[0], L)), 64)
 
 
 def laplace_plan(s_values, t_step: float = 1.0):
@@ -2500,7 +2525,7 @@ def laplace_plan(s_values, t_step: float = 1.0):
     tables, cached on the s-values' bytes and t_step."""
     require_gpu()
     s = LP.check_s_values(s_values, t_step)
-    return _laplace_plan_dev(torch.cuda.current_device(), s.tobytes(), float(t_step))
+    return _laplace_plan_dev(s.tobytes(), float(t_step))
 
 
 def laplace(y: torch.Tensor, s_values, t_step: float = 1.0, out: Optional[torch.Tensor] = None,
@@ -2509,30 +2534,20 @@ def laplace(y: torch.Tensor, s_values, t_step: float = 1.0, out: Optional[torch.
     F[b, i] = t_step sum_n y[b, n] exp(-s_i n t_step) -> [B, S] complex128 on the device (syg_laplace_f32).  Served:
     finite t_step and s with -Re(s) t_step (L - 1) <= 700.  form: None (the library's rule) | "whole" | "segmented", for
     tests and the benchmark."""
-    require_gpu()
-    if y.dim() != 2 or y.dtype != torch.float32 or not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor [B, L]")
+    y = _f32_in(y, "y", 2)
     if form not in LAPLACE_FORMS:
         raise ValueError("form must be None, 'whole' or 'segmented'")
-    if y.stride(1) != 1:
-        y = y.contiguous()
     B, L = y.shape
     s = LP.check_s_values(s_values, t_step)
     S = s.size
     if B < 1 or L < 1 or S < 1:
         raise ValueError("laplace: empty input")
     LP.check_domain(s, t_step, L)
-    if out is None:
-        out = torch.empty((B, S), dtype=torch.complex128, device=y.device)
-    elif out.shape != (B, S) or out.dtype != torch.complex128 or not out.is_cuda or not out.is_contiguous():
-        raise ValueError("out must be a contiguous complex128 CUDA tensor [B, S]")
-    dev, key, f = torch.cuda.current_device(), s.tobytes(), LAPLACE_FORMS[form]
-    p, table, fac, col = _laplace_plan_dev(dev, key, float(t_step))
-    anchor = _laplace_anchor_dev(dev, key, float(t_step), int(L))
-    wb = lib().syg_laplace_work_bytes(B, L, p.S16, f)
-    if wb < 0:
-        check(-1, "syg_laplace_work_bytes")
-    work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device) if wb > 0 else None
+    out = _out(out, (B, S), y, dtype=torch.complex128, contiguous=True)
+    key, f = s.tobytes(), LAPLACE_FORMS[form]
+    p, table, fac, col = _laplace_plan_dev(key, float(t_step))
+    anchor = _laplace_anchor_dev(key, float(t_step), int(L))
+    work = _workspace("syg_laplace_work_bytes", B, L, p.S16, f, dtype=torch.float64, device=y.device)
     _call("syg_laplace_f32", _ptr(y), B, L, _ld(y), _ptr(table), _ptr(fac), _ptr(anchor), _ptr(col), p.S_fwd, p.S_rev,
           p.S_steep_fwd, p.S_steep_rev, S, float(t_step), _ptr(out), _ptr(work), f)
     return out
@@ -2540,6 +2555,7 @@ def laplace(y: torch.Tensor, s_values, t_step: float = 1.0, out: Optional[torch.
 
 # ------------------------------------------------------------------ polyphase resampling
 RESAMPLE_FORMS = {None: -1, "lds": 0, "global": 1}
+_RESAMPLE_FIGURES = {n: n for n in ("tile", "table_lds_rule", "table_lds_max", "table_max", "span_max", "rate_max")}
 
 
 def resample_constants() -> dict:
@@ -2547,11 +2563,7 @@ def resample_constants() -> dict:
     bytes) up to which the rule puts the table in LDS, the size up to which form='lds' may (on up * (Kp | 1) * 4: rows
     are stored with an odd stride), the size of a served table (up * Kp * 4), the input samples a tile stages at most,
     the largest up / down."""
-    h = lib()
-    return dict(tile=int(h.syg_resample_tile()), table_lds_rule=int(h.syg_resample_table_lds_rule()),
-                table_lds_max=int(h.syg_resample_table_lds_max()),
-                table_max=int(h.syg_resample_table_max()), span_max=int(h.syg_resample_span_max()),
-                rate_max=int(h.syg_resample_rate_max()))
+    return _constants("syg_resample", _RESAMPLE_FIGURES)
 
 
 def resample_table_in_lds(up: int, Kp: int) -> bool:
@@ -2573,10 +2585,11 @@ def _resample_check_size(up: int, down: int, nbytes: int) -> None:
                          f"{k['table_max']} bytes")
 
 
-@functools.lru_cache(maxsize=64)
-def _resample_table_dev(dev: int, up: int, down: int, wkey, L: int):
-    p = RS._plan(up, down, wkey, L)
-    return p, _dev(p.table)
+def _resample_table_dev(up: int, down: int, wkey, L: int):
+    def build():
+        p = RS._plan(up, down, wkey, L)
+        return p, _dev(p.table)
+    return _cached(("resample", up, down, wkey, L), build, 64)
 
 
 def resample_plan(up, down, L, window=RS.DEFAULT_WINDOW):
@@ -2590,7 +2603,7 @@ def resample_plan(up, down, L, window=RS.DEFAULT_WINDOW):
     require_gpu()
     if int(L) != L or L < 1:
         raise ValueError(f"L must be a positive integer, got {L}")
-    return _resample_table_dev(torch.cuda.current_device(), up, down, wkey, int(L))
+    return _resample_table_dev(up, down, wkey, int(L))
 
 
 def resample_poly(y: torch.Tensor, up, down, window=RS.DEFAULT_WINDOW, padtype: str = "constant", cval=None,
@@ -2603,8 +2616,7 @@ def resample_poly(y: torch.Tensor, up, down, window=RS.DEFAULT_WINDOW, padtype: 
     up, down = RS.reduce_ratio(up, down)
     if form not in RESAMPLE_FORMS:
         raise ValueError("form must be None, 'lds' or 'global'")
-    if not isinstance(y, torch.Tensor) or y.dim() != 2 or y.dtype != torch.float32:
-        raise ValueError("y must be a float32 CUDA tensor [B, L]")
+    _f32(y, "y", 2)
     B, L = y.shape
     if B < 1 or L < 1:
         raise ValueError("resample_poly: empty input")
@@ -2614,9 +2626,7 @@ def resample_poly(y: torch.Tensor, up, down, window=RS.DEFAULT_WINDOW, padtype: 
     same = up == 1 and down == 1
     if not same:
         _resample_check_size(up, down, RS.table_bytes(up, down, window))
-    require_gpu()
-    if not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor [B, L]")
+    _on_device(y, "y")
     if same:
         if out is None:
             return y.clone(memory_format=torch.contiguous_format)
@@ -2627,12 +2637,8 @@ def resample_poly(y: torch.Tensor, up, down, window=RS.DEFAULT_WINDOW, padtype: 
     if form == "lds" and not resample_table_fits_lds(p.up, p.Kp):
         raise ValueError(f"resample_poly: form='lds' needs up * (Kp | 1) * 4 <= {resample_constants()['table_lds_max']} bytes "
                          f"(up={p.up}, Kp={p.Kp})")
-    if y.stride(1) != 1:
-        y = y.contiguous()
-    if out is None:
-        out = torch.empty((B, p.n_out), dtype=torch.float32, device=y.device)
-    elif out.shape != (B, p.n_out) or out.dtype != torch.float32 or not out.is_cuda or out.stride(1) != 1:
-        raise ValueError(f"out must be a float32 CUDA tensor [B, {p.n_out}] with unit column stride")
+    y = _unit_stride(y)
+    out = _out(out, (B, p.n_out), y)
     stat = None
     if padtype in RS.STAT_PADS:                                  # the row minus its statistic, zeros outside, added back
         stat = {"mean": lambda t: t.mean(dim=1, keepdim=True), "minimum": lambda t: t.amin(dim=1, keepdim=True),
@@ -2640,9 +2646,9 @@ def resample_poly(y: torch.Tensor, up, down, window=RS.DEFAULT_WINDOW, padtype: 
         y = y - stat
     pad = RS.PAD_CODES.get(padtype, 0)
     fill = float(cval) if (cval is not None and stat is None) else 0.0
-    for lo in range(0, B, 65535):                                # grid rows of one launch
-        yb, ob = y[lo:lo + 65535], out[lo:lo + 65535]
-        _call("syg_resample_poly_f32", _ptr(yb), yb.shape[0], L, _ld(yb), p.up, p.down, p.n_pre_remove, p.Kp, _ptr(table), pad,
+    for lo, n in _row_blocks(B):
+        yb, ob = y[lo:lo + n], out[lo:lo + n]
+        _call("syg_resample_poly_f32", _ptr(yb), n, L, _ld(yb), p.up, p.down, p.n_pre_remove, p.Kp, _ptr(table), pad,
               fill, RESAMPLE_FORMS[form], p.n_out, _ptr(ob), _ld(ob))
     if stat is not None:
         out += stat
@@ -2653,30 +2659,30 @@ def resample_poly(y: torch.Tensor, up, down, window=RS.DEFAULT_WINDOW, padtype: 
 CWT_FORMS = (None, "direct", "spectral")
 CWT_WORK_BYTES = 1 << 30            # the spectral form takes the clips in blocks whose work buffers stay below this
 CWT_MAX_ELEMS = 1 << 31             # B S ceil(L / stride) at most
+_CWT_FIGURES = {n: n for n in ("tile", "direct_taps_max", "scales_per_group", "span_max", "taps_lds_max")}
 
 
 def cwt_constants() -> dict:
     """The figures syg_cwt_f32 rests on (the library owns them): output columns per tile, the tap count up to which the
     rule runs a filter direct, the scales a block serves from one staged span, the input samples a block stages at most,
     the words of taps a block stages at most (the stride-1 form)."""
-    h = lib()
-    return dict(tile=int(h.syg_cwt_tile()), direct_taps_max=int(h.syg_cwt_direct_taps_max()),
-                scales_per_group=int(h.syg_cwt_scales_per_group()), span_max=int(h.syg_cwt_span_max()),
-                taps_lds_max=int(h.syg_cwt_taps_lds_max()))
+    return _constants("syg_cwt", _CWT_FIGURES)
 
 
-@functools.lru_cache(maxsize=32)
-def _cwt_table_dev(dev: int, name: str, s_bytes: bytes):
-    p = CW._plan(name, s_bytes)
-    return p, _dev(p.table)
+def _cwt_table_dev(name: str, s_bytes: bytes):
+    def build():
+        p = CW._plan(name, s_bytes)
+        return p, _dev(p.table)
+    return _cached(("cwt_table", name, s_bytes), build, 32)
 
 
-@functools.lru_cache(maxsize=64)
-def _cwt_direct_dev(dev: int, name: str, s_bytes: bytes, idx_bytes: bytes):
-    p = CW._plan(name, s_bytes)
-    idx = np.frombuffer(idx_bytes, dtype=np.int64)
-    idx = idx[np.argsort(p.taps[idx], kind="stable")]              # filters of like length share a group's span
-    return _dev(p.meta(idx)), p.reach(idx, cwt_constants()["scales_per_group"])
+def _cwt_direct_dev(name: str, s_bytes: bytes, idx_bytes: bytes):
+    def build():
+        p = CW._plan(name, s_bytes)
+        idx = np.frombuffer(idx_bytes, dtype=np.int64)
+        idx = idx[np.argsort(p.taps[idx], kind="stable")]          # filters of like length share a group's span
+        return _dev(p.meta(idx)), p.reach(idx, cwt_constants()["scales_per_group"])
+    return _cached(("cwt_direct", name, s_bytes, idx_bytes), build, 64)
 
 
 def cwt_fft_len(L: int, taps_max: int) -> int:
@@ -2690,15 +2696,16 @@ def cwt_fft_len(L: int, taps_max: int) -> int:
     return M
 
 
-@functools.lru_cache(maxsize=8)
-def _cwt_spectral_dev(dev: int, name: str, s_bytes: bytes, idx_bytes: bytes, L: int):
+def _cwt_spectral_dev(name: str, s_bytes: bytes, idx_bytes: bytes, L: int):
     """(M, R, H [R, M, 2] the filter rows' transforms, rmeta): per wavelet, scale list, spectral subset and row length."""
-    p = CW._plan(name, s_bytes)
-    idx = np.frombuffer(idx_bytes, dtype=np.int64)
-    rows = CW.spectral_rows(p, idx)
-    M = cwt_fft_len(L, int(p.taps[idx].max()))
-    h, rmeta = CW.spectral_tables(p, rows, M)
-    return M, len(rows), fft_any(_dev(h)), _dev(rmeta)
+    def build():
+        p = CW._plan(name, s_bytes)
+        idx = np.frombuffer(idx_bytes, dtype=np.int64)
+        rows = CW.spectral_rows(p, idx)
+        M = cwt_fft_len(L, int(p.taps[idx].max()))
+        h, rmeta = CW.spectral_tables(p, rows, M)
+        return M, len(rows), fft_any(_dev(h)), _dev(rmeta)
+    return _cached(("cwt_spectral", name, s_bytes, idx_bytes, L), build, 8)
 
 
 def cwt_plan(scales, wavelet="morl", L=None):
@@ -2707,14 +2714,14 @@ def cwt_plan(scales, wavelet="morl", L=None):
     form's filter rows for rows of L samples are made and cached as well."""
     p = CW.cwt_plan(scales, wavelet)
     require_gpu()
-    dev, key = torch.cuda.current_device(), p.scales.tobytes()
+    key = p.scales.tobytes()
     if L is not None:
         if int(L) != L or L < 1:
             raise ValueError(f"L must be a positive integer, got {L}")
         _, spec = CW.split_forms(p, cwt_constants()["direct_taps_max"], None)
         if spec.size:
-            _cwt_spectral_dev(dev, p.wavelet.name, key, spec.astype(np.int64).tobytes(), int(L))
-    return _cwt_table_dev(dev, p.wavelet.name, key)
+            _cwt_spectral_dev(p.wavelet.name, key, spec.astype(np.int64).tobytes(), int(L))
+    return _cwt_table_dev(p.wavelet.name, key)
 
 
 def cwt_out_shape(B: int, S: int, L: int, stride: int, cplx: bool, output: str):
@@ -2738,8 +2745,7 @@ def cwt(y: torch.Tensor, scales, wavelet="morl", output: str = "coef", stride: i
     if isinstance(stride, bool) or int(stride) != stride or stride < 1:
         raise ValueError(f"stride must be an integer >= 1, got {stride}")
     stride = int(stride)
-    if not isinstance(y, torch.Tensor) or y.dim() != 2 or y.dtype != torch.float32:
-        raise ValueError("y must be a float32 CUDA tensor [B, L]")
+    _f32(y, "y", 2)
     B, L = y.shape
     if B < 1 or L < 1:
         raise ValueError("cwt: empty input")
@@ -2750,30 +2756,23 @@ def cwt(y: torch.Tensor, scales, wavelet="morl", output: str = "coef", stride: i
     if B * S * n_out > CWT_MAX_ELEMS:
         raise ValueError(f"cwt: the result of {B} clips x {S} scales x {n_out} columns has {B * S * n_out} elements, above the "
                          f"bound of 2^31; take fewer clips a call or a larger stride")
-    require_gpu()
-    if not y.is_cuda:
-        raise ValueError("y must be a float32 CUDA tensor [B, L]")
+    _on_device(y, "y")
     if y.stride(1) != 1 or _ld(y) < L:                               # (rows that overlap, an expanded row: a copy)
         y = y.contiguous()
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=y.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous float32 CUDA tensor {list(shape)}")
-    dev, key, code, cplx = torch.cuda.current_device(), p.scales.tobytes(), CW.OUTPUTS[output], int(w.complex)
-    _, table = _cwt_table_dev(dev, w.name, key)
+    out = _out(out, shape, y, contiguous=True)
+    key, code, cplx = p.scales.tobytes(), CW.OUTPUTS[output], int(w.complex)
+    _, table = _cwt_table_dev(w.name, key)
     direct, spec = CW.split_forms(p, cwt_constants()["direct_taps_max"], form)
     if direct.size:
-        meta, reach = _cwt_direct_dev(dev, w.name, key, direct.astype(np.int64).tobytes())
-        for lo in range(0, B, 65535):                                # grid rows of one launch
-            yb, ob = y[lo:lo + 65535], out[lo:lo + 65535]
-            _call("syg_cwt_f32", _ptr(yb), yb.shape[0], L, _ld(yb), _ptr(table), _ptr(meta), int(direct.size), S, cplx, reach,
+        meta, reach = _cwt_direct_dev(w.name, key, direct.astype(np.int64).tobytes())
+        for lo, n in _row_blocks(B):
+            yb, ob = y[lo:lo + n], out[lo:lo + n]
+            _call("syg_cwt_f32", _ptr(yb), n, L, _ld(yb), _ptr(table), _ptr(meta), int(direct.size), S, cplx, reach,
                   code, stride, n_out, _ptr(ob))
     if spec.size:
-        M, R, H, rmeta = _cwt_spectral_dev(dev, w.name, key, spec.astype(np.int64).tobytes(), int(L))
+        M, R, H, rmeta = _cwt_spectral_dev(w.name, key, spec.astype(np.int64).tobytes(), int(L))
         plan = fft_plan(M)
-        per_clip = lib().syg_cwt_work_bytes(1, R, M)
-        if per_clip < 0:
-            check(-1, "syg_cwt_work_bytes")
+        per_clip = _work_bytes("syg_cwt_work_bytes", 1, R, M)
         bb = int(max(1, min(B, MAX_ROWS // R, CWT_WORK_BYTES // per_clip)))
         for lo in range(0, B, bb):
             yb, ob = y[lo:lo + bb], out[lo:lo + bb]
@@ -2790,16 +2789,14 @@ def cwt(y: torch.Tensor, scales, wavelet="morl", output: str = "coef", stride: i
 # ------------------------------------------------------------------ dynamic time warping
 DTW_FORMS ={None: -1, "resident": 0, "tiled": 1}
 DTW_METRICS = {"euclidean": 0, "sqeuclidean": 1, "cityblock": 2, "cosine": 3}
+_DTW_FIGURES = {n: n for n in ("tile", "tile_max", "resident_max_cols", "run_max", "cost_tile")}
 
 
 def dtw_constants() -> dict:
     """The figures syg_dtw_f32 / syg_dtw_cost_f32 rest on (the library owns them): the tiled form's product tile edge and
     the largest edge it takes, the widest matrix of the pair-resident form, the longest column run of a lane, the cost
     kernel's tile edge."""
-    h = lib()
-    return dict(tile=int(h.syg_dtw_tile()), tile_max=int(h.syg_dtw_tile_max()),
-                resident_max_cols=int(h.syg_dtw_resident_max_cols()), run_max=int(h.syg_dtw_run_max()),
-                cost_tile=int(h.syg_dtw_cost_tile()))
+    return _constants("syg_dtw", _DTW_FIGURES)
 
 
 def dtw_plan(B: int, N: int, M: int, want_steps: bool = True, form: Optional[str] = None, tile: int = 0) -> dict:
@@ -2808,12 +2805,11 @@ def dtw_plan(B: int, N: int, M: int, want_steps: bool = True, form: Optional[str
     wanted, which the path needs).  No device work."""
     if form not in DTW_FORMS:
         raise ValueError("form must be None, 'resident' or 'tiled'")
-    h = lib()
-    f = h.syg_dtw_form(int(B), int(N), int(M), DTW_FORMS[form])
-    wb = h.syg_dtw_work_bytes(int(B), int(N), int(M), DTW_FORMS[form], int(tile))
-    if f < 0 or wb < 0:
+    f = lib().syg_dtw_form(int(B), int(N), int(M), DTW_FORMS[form])
+    wb = _work_bytes("syg_dtw_work_bytes", int(B), int(N), int(M), DTW_FORMS[form], int(tile))
+    if f < 0:
         check(-1, "syg_dtw_work_bytes")
-    return dict(form="tiled" if f == 1 else "resident", work_bytes=int(wb),
+    return dict(form="tiled" if f == 1 else "resident", work_bytes=wb,
                 steps_bytes=int(B) * int(N) * int(M) if want_steps else 0)
 
 
@@ -2830,10 +2826,8 @@ def _dtw_lens(v, B: int, device, name: str):
 
 
 def _dtw_seq(t, name):
-    if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != torch.float32 or not t.is_cuda:
-        raise ValueError(f"{name} must be a float32 CUDA tensor [B, K, length]")
-    if t.shape[2] > 1 and t.stride(2) != 1:
-        t = t.contiguous()
+    """t [B, K, length] checked, with its row and batch strides (copied where rows overlap or a stride is negative)."""
+    t = _f32_in(t, name, 3)
     B, K, L = t.shape
     ld = int(t.stride(1)) if K > 1 else L
     bs = int(t.stride(0)) if B > 1 else 0
@@ -2876,19 +2870,10 @@ def dtw(C_: torch.Tensor, x_len=None, y_len=None, weights_mul=None, weights_add=
     three finite values each (default 1 and 0).  x_len / y_len [B]: ragged batches; cells of D and steps outside a pair's
     corner are 0.  form: None (the library's rule) | 'resident' | 'tiled'; tile: the tiled form's tile edge (0: the
     product tile), for tests and the benchmark."""
-    require_gpu()
-    if not isinstance(C_, torch.Tensor) or C_.dim() != 3 or C_.dtype != torch.float32 or not C_.is_cuda:
-        raise ValueError("C must be a float32 CUDA tensor [B, N, M]")
+    C_, ldc, bsc = _dtw_seq(C_, "C")
     if form not in DTW_FORMS:
         raise ValueError("form must be None, 'resident' or 'tiled'")
-    if C_.shape[2] > 1 and C_.stride(2) != 1:
-        C_ = C_.contiguous()
     B, N, M = C_.shape
-    ldc = int(C_.stride(1)) if N > 1 else M
-    bsc = int(C_.stride(0)) if B > 1 else 0
-    if ldc < M or bsc < 0:
-        C_ = C_.contiguous()
-        ldc, bsc = M, (N * M if B > 1 else 0)
     w = []
     for v, name in ((weights_mul, "weights_mul"), (weights_add, "weights_add")):
         if v is None:
@@ -2904,10 +2889,7 @@ def dtw(C_: torch.Tensor, x_len=None, y_len=None, weights_mul=None, weights_add=
     ragged = xd is not None or yd is not None
     alloc = torch.zeros if ragged else torch.empty
     f = DTW_FORMS[form]
-    wb = lib().syg_dtw_work_bytes(B, N, M, f, int(tile))
-    if wb < 0:
-        check(-1, "syg_dtw_work_bytes")
-    work = torch.empty((wb // 8,), dtype=torch.float64, device=dev) if wb > 0 else None
+    work = _workspace("syg_dtw_work_bytes", B, N, M, f, int(tile), dtype=torch.float64, device=dev)
     D = alloc((B, N, M), dtype=torch.float64, device=dev) if want_D else None
     steps = alloc((B, N, M), dtype=torch.uint8, device=dev) if (want_steps or want_path) else None
     cost = torch.empty((B,), dtype=torch.float64, device=dev)
@@ -2918,38 +2900,34 @@ def dtw(C_: torch.Tensor, x_len=None, y_len=None, weights_mul=None, weights_add=
           w[0].ctypes.data_as(C.c_void_p) if w[0] is not None else None,
           w[1].ctypes.data_as(C.c_void_p) if w[1] is not None else None,
           1 if subseq else 0, f, int(tile), _ptr(D), _ptr(steps), _ptr(cost), _ptr(end_col), _ptr(path), _ptr(path_len),
-          _ptr(work), wb)
+          _ptr(work), _nbytes(work))
     return dict(cost=cost, end_col=end_col, D=D, steps=steps, path=path, path_len=path_len)
 
 
 # ------------------------------------------------------------------ cepstral analysis
 CEPSTRUM_FORMS = (None, "fused", "chain")
 CEPS_SLAB_ELEMS = 1 << 26          # complex points a buffer of the chain form holds at most (512 MiB)
-_CEPS_KEYS = {"frame": 0, "tile_frames": 1, "waves": 2, "scan": 3, "lds_fixed": 4, "lds_max": 5}      # SYG_CEPS_* of include/sygnals_hip.h
+_CEPS_KEYS = ("frame", "tile_frames", "waves", "scan", "lds_fixed", "lds_max")      # SYG_CEPS_* of include/sygnals_hip.h
 
 
 def cepstrum_constants() -> dict:
     """The figures csrc/cepstrum.hip rests on (the library owns them): the fused kernel's frame length, the frames a
     workgroup stages and stores together, its waves, the bins a block of the phase unwrap scans, and the bytes of LDS a
     workgroup holds beside its stage and at n_ceps = 2048."""
-    h = lib()
-    return {k: int(h.syg_cepstrum_constants(v)) for k, v in _CEPS_KEYS.items()}
+    return _constants("syg_cepstrum_constants", _CEPS_KEYS)
 
 
 def _ceps_tensor(x, what: str, dims: int = 2):
-    if not isinstance(x, torch.Tensor) or x.dim() != dims or x.dtype != torch.float32:
-        raise ValueError(f"{what} must be a float32 CUDA tensor of {dims} dimensions")
+    """_f32, and no empty axis."""
+    _f32(x, what, dims)
     if min(x.shape) < 1:
         raise ValueError(f"{what}: empty input")
 
 
 def _ceps_on_device(x, what: str):
-    require_gpu()
-    if not x.is_cuda:
-        raise ValueError(f"{what} must be a float32 CUDA tensor")
-    if x.stride(-1) != 1 or (x.dim() == 2 and _ld(x) < x.shape[1]):
-        x = x.contiguous()
-    return x
+    """_on_device; rows with unit stride that do not overlap (copied if not)."""
+    _on_device(x, what)
+    return x.contiguous() if (x.dim() == 2 and _ld(x) < x.shape[1]) else _unit_stride(x)
 
 
 def cepstrogram_frames(L: int, n_fft: int, hop: int, center: bool) -> int:
@@ -2991,11 +2969,7 @@ def cepstrogram(y: torch.Tensor, n_fft: int = 2048, hop: int = 512, center: bool
     T = cepstrogram_frames(L, n_fft, hop, bool(center))
     CP.check_size("cepstrogram", (B, Q, T), ("clips", "quefrencies", "frames"))
     y = _ceps_on_device(y, "y")
-    shape = (B, Q, T)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=y.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous float32 CUDA tensor {list(shape)}")
+    out = _out(out, (B, Q, T), y, contiguous=True)
     if n_fft == 2048 and form != "chain":
         win = window_dev(window, 2048 if win_length is None else win_length, 2048)
         _call("syg_cepstrogram2048_f32", _ptr(y), B, L, _ld(y), 2048, hop, int(bool(center)), T, _ptr(win), _ptr(twiddle_dev(2048)),
@@ -3052,12 +3026,9 @@ def complex_cepstrum(x: torch.Tensor, n=None, amin: float = CP.AMIN):
     nd = torch.empty((B,), dtype=torch.int32, device=x.device)
     for b0, bc in _ceps_slabs(B, n):
         X = fft_any(pack_real(x[b0:b0 + bc], n))
-        wb = lib().syg_cepstrum_unwrap_work_bytes(bc, n)
-        if wb < 0:
-            check(-1, "syg_cepstrum_unwrap_work_bytes")
-        work = torch.empty((wb // 4,), dtype=torch.int32, device=x.device)
+        work = _workspace("syg_cepstrum_unwrap_work_bytes", bc, n, dtype=torch.int32, device=x.device)
         Z = torch.empty_like(X)
-        _call("syg_cepstrum_unwrap_c64", _ptr(X), bc, n, amin, _ptr(work), wb, _ptr(Z), _ptr(nd[b0:b0 + bc]))
+        _call("syg_cepstrum_unwrap_c64", _ptr(X), bc, n, amin, _ptr(work), _nbytes(work), _ptr(Z), _ptr(nd[b0:b0 + bc]))
         _call("syg_cepstrum_gather_f32", _ptr(fft_any(Z, inverse=True)), bc, n, n, 1, amin, _ptr(out[b0:b0 + bc]))
     return out, nd
 
@@ -3090,9 +3061,7 @@ def cepstrum_peaks(ceps: torch.Tensor, qmin: int, qmax: int, sr: float, threshol
         raise ValueError(f"cepstrum_peaks: need 1 <= qmin <= qmax < Q (got qmin={qmin}, qmax={qmax}, Q={Q})")
     if not (float(sr) > 0 and np.isfinite(float(sr))) or np.isnan(float(threshold)):
         raise ValueError(f"cepstrum_peaks: bad sr={sr} / threshold={threshold}")
-    require_gpu()
-    if not ceps.is_cuda:
-        raise ValueError("ceps must be a float32 CUDA tensor of 3 dimensions")
+    _on_device(ceps, "ceps")
     ceps = ceps.contiguous()
     dev = ceps.device
     f0 = torch.empty((B, Tn), dtype=torch.float64, device=dev)
@@ -3117,16 +3086,14 @@ def pitch_cepstrum(y: torch.Tensor, sr: float, fmin: float, fmax: float, frame_l
 
 
 # ------------------------------------------------------------------ linear prediction
-_LPC_KEYS = {"max_frame": 0, "max_order": 1, "waves": 2, "tile_frames": 3, "span_max": 4, "stage_chunk": 5,
-             "acorr_chunk": 6}                 # SYG_LPC_* of include/sygnals_hip.h
+_LPC_KEYS = ("max_frame", "max_order", "waves", "tile_frames", "span_max", "stage_chunk", "acorr_chunk")      # SYG_LPC_* of include/sygnals_hip.h
 
 
 def lpc_constants() -> dict:
     """The figures csrc/lpc.hip rests on (the library owns them): the longest frame of the frame kernel, the highest
     order, the waves of its workgroup, the frames a workgroup takes together, the floats of a tile's span that are read
     once into LDS, and the samples a workgroup of the two whole-row forms owns."""
-    h = lib()
-    return {k: int(h.syg_lpc_constants(v)) for k, v in _LPC_KEYS.items()}
+    return _constants("syg_lpc_constants", _LPC_KEYS)
 
 
 def lpc_window_table(window, N: int):
@@ -3144,14 +3111,6 @@ def _lpc_window_dev(window, N: int):
     if isinstance(window, str) and window == "ones":
         return _cached(("lpc_ones", N), lambda: _dev(np.ones(N, dtype=np.float32)))
     return window_dev(window, N, N)
-
-
-def _lpc_out(t, shape, what: str, device):
-    if t is None:
-        return torch.empty(shape, dtype=torch.float32, device=device)
-    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-        raise ValueError(f"{what} must be a contiguous float32 CUDA tensor {list(shape)}")
-    return t
 
 
 def _lpc_result(a, k, err, return_reflection, return_error):
@@ -3178,9 +3137,9 @@ def lpc_frames(y: torch.Tensor, order: int, frame_length: int = 2048, hop: int =
     _lpc.check_size("lpc_frames", (B, p + 1, Tn), ("clips", "coefficients", "frames"))
     y = _ceps_on_device(y, "y")
     win = _lpc_window_dev(_lpc.default_window(method, window), N)
-    a = _lpc_out(out, (B, p + 1, Tn), "out", y.device)
-    k = _lpc_out(out_k, (B, p, Tn), "out_k", y.device) if (return_reflection or out_k is not None) else None
-    err = _lpc_out(out_err, (B, Tn), "out_err", y.device) if (return_error or out_err is not None) else None
+    a = _out(out, (B, p + 1, Tn), y, "out", contiguous=True)
+    k = _out(out_k, (B, p, Tn), y, "out_k", contiguous=True) if (return_reflection or out_k is not None) else None
+    err = _out(out_err, (B, Tn), y, "out_err", contiguous=True) if (return_error or out_err is not None) else None
     _call("syg_lpc_frames_f32", _ptr(y), B, L, _ld(y), N, hop, int(bool(center)), Tn, _ptr(win), p, m, _ptr(a), _ptr(k), _ptr(err))
     return _lpc_result(a, k, err, return_reflection, return_error)
 
@@ -3204,17 +3163,14 @@ def lpc_rows(y: torch.Tensor, order: int, method: str = "burg", window=None, for
     _lpc.check_size("lpc_rows", (B, L), ("rows", "samples"))
     y = _ceps_on_device(y, "y")
     win = _lpc_window_dev(_lpc.default_window(method, window), L)
-    a = _lpc_out(out, (B, p + 1), "out", y.device)
-    k = _lpc_out(out_k, (B, p), "out_k", y.device) if (return_reflection or out_k is not None) else None
-    err = _lpc_out(out_err, (B,), "out_err", y.device) if (return_error or out_err is not None) else None
+    a = _out(out, (B, p + 1), y, "out", contiguous=True)
+    k = _out(out_k, (B, p), y, "out_k", contiguous=True) if (return_reflection or out_k is not None) else None
+    err = _out(out_err, (B,), y, "out_err", contiguous=True) if (return_error or out_err is not None) else None
     if form == "frame" or (form is None and L <= _lpc.MAX_FRAME):
         _call("syg_lpc_frames_f32", _ptr(y), B, L, _ld(y), L, L, 0, 1, _ptr(win), p, m, _ptr(a), _ptr(k), _ptr(err))
     else:
-        wb = lib().syg_lpc_rows_work_bytes(B, L, p, m)
-        if wb < 0:
-            check(-1, "syg_lpc_rows_work_bytes")
-        work = torch.empty((wb // 8,), dtype=torch.float64, device=y.device)
-        _call("syg_lpc_rows_f32", _ptr(y), B, L, _ld(y), _ptr(win), p, m, _ptr(work), wb, _ptr(a), _ptr(k), _ptr(err))
+        work = _workspace("syg_lpc_rows_work_bytes", B, L, p, m, dtype=torch.float64, device=y.device)
+        _call("syg_lpc_rows_f32", _ptr(y), B, L, _ld(y), _ptr(win), p, m, _ptr(work), _nbytes(work), _ptr(a), _ptr(k), _ptr(err))
     return _lpc_result(a, k, err, return_reflection, return_error)
 
 
@@ -3240,19 +3196,18 @@ def lpc_envelope(a: torch.Tensor, err: torch.Tensor, n_fft: int = 2048, db: bool
         raise ValueError(f"err must be [B, T] = [{B}, {Tn}], got {list(err.shape)}")
     K = n_fft // 2 + 1
     _lpc.check_size("lpc_envelope", (B, K, Tn), ("clips", "bins", "frames"))
-    require_gpu()
-    if not (a.is_cuda and err.is_cuda):
-        raise ValueError("a and err must be float32 CUDA tensors")
+    _on_device(a, "a")
+    _on_device(err, "err")
     a, err = a.contiguous(), err.contiguous()
-    out = _lpc_out(out, (B, K, Tn), "out", a.device)
+    out = _out(out, (B, K, Tn), a, "out", contiguous=True)
     ph = _cached(("lpc_phasor", n_fft), lambda: _dev(lpc_phasor_table(n_fft)))
     _call("syg_lpc_envelope_f32", _ptr(a), _ptr(err), B, p1 - 1, Tn, n_fft, _ptr(ph), int(bool(db)), amin, _ptr(out))
     return out
 
 
 # ------------------------------------------------------------------ feature dynamics: deltas, CMVN, context stacking
-_DYN_KEYS = {"tile": 0, "resident_max_t": 1, "resident_max_t_sliding": 2, "window_max": 3, "direct_window": 4, "width_max": 5,
-             "order_max": 6, "units": 7, "max_out": 8, "lds_max": 9}                 # SYG_DYN_* of include/sygnals_hip.h
+_DYN_KEYS = ("tile", "resident_max_t", "resident_max_t_sliding", "window_max", "direct_window", "width_max", "order_max", "units",
+             "max_out", "lds_max")                 # SYG_DYN_* of include/sygnals_hip.h
 _DYN_FORMS = {None: 0, "resident": 1, "tiled": 2}
 
 
@@ -3261,8 +3216,7 @@ def dynamics_constants() -> dict:
     rule's longest resident rows, the longest sliding window of the tiled form, the window up to which sliding sums are
     explicit, the served widths and orders, the rows of a workgroup, the largest result, the LDS of a one-row workgroup
     (a forced resident row fits while 4 T, or 20 T + 16 under a long sliding window, stays within it)."""
-    h = lib()
-    return {name: int(h.syg_dynamics_constants(key)) for name, key in _DYN_KEYS.items()}
+    return _constants("syg_dynamics_constants", _DYN_KEYS)
 
 
 def delta_tables(width: int = 9, order: int = 1):
@@ -3277,11 +3231,11 @@ def dynamics_form(T: int, window=None) -> str:
 
 
 def _dyn_in(x, who: str) -> torch.Tensor:
-    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.float32:
-        raise ValueError(f"{who}: x must be a float32 tensor [B, K, T]")
+    """_f32 and no empty axis; x with unit stride along T (the device is judged last, in _dynamics)."""
+    _f32(x, f"{who}: x", 3, axes="[B, K, T]")
     if min(x.shape) < 1:
         raise ValueError(f"{who}: empty input (shape {list(x.shape)})")
-    return x if (x.shape[2] == 1 or x.stride(2) == 1) else x.contiguous()
+    return _unit_stride(x)
 
 
 def _dyn_strides(t: torch.Tensor):
@@ -3297,11 +3251,9 @@ def _dyn_span(t: torch.Tensor):
 
 
 def _dyn_out(who: str, out, shape, x: torch.Tensor, may_alias: bool = False) -> torch.Tensor:
-    if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=x.device)
-    if not isinstance(out, torch.Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or \
-            out.device != x.device or (shape[2] > 1 and out.stride(2) != 1):
-        raise ValueError(f"{who}: out must be a float32 tensor {list(shape)} on x's device with unit stride along T")
+    new, out = out is None, _out(out, shape, x, f"{who}: out")
+    if new:
+        return out
     (a0, a1), (b0, b1) = _dyn_span(x), _dyn_span(out)
     same = may_alias and out.data_ptr() == x.data_ptr() and out.stride() == x.stride()
     if a0 < b1 and b0 < a1 and not same:
@@ -3322,24 +3274,20 @@ def _dyn_table_dev(width: int, orders) -> torch.Tensor:
 
 def _dynamics(who, x, out, cm, W, variance, statics, orders, width, mode_code, cval, form):
     """One syg_dynamics_f32 call; every argument has been checked."""
-    require_gpu()
-    if not (x.is_cuda and out.is_cuda):
-        raise ValueError(f"{who}: x and out must be float32 CUDA tensors")
+    _on_device(x, f"{who}: x")                                       # (out is on x's device: _dyn_out)
     B, K, Tn = x.shape
-    h = lib()
-    tiled = form == 2 or (form == 0 and h.syg_dynamics_form(Tn, W if cm else 0) == 1)
+    tiled = form == 2 or (form == 0 and lib().syg_dynamics_form(Tn, W if cm else 0) == 1)
     sliding = cm and 1 <= W < Tn
     if sliding and tiled and out.data_ptr() == x.data_ptr():
         x = x.clone()                                                # tiles read their neighbours' frames: not in place
-    work, wb = None, 0
+    work = None
     if cm and not sliding and tiled:
-        wb = int(h.syg_dynamics_work_bytes(B, K, Tn))
-        work = torch.empty(wb // 8, dtype=torch.float64, device=x.device)
+        work = _workspace("syg_dynamics_work_bytes", B, K, Tn, dtype=torch.float64, device=x.device)
     tab = _dyn_table_dev(width, orders) if orders else None
     sxb, sxk = _dyn_strides(x)
     sob, sok = _dyn_strides(out)
     _call("syg_dynamics_f32", _ptr(x), B, K, Tn, sxb, sxk, _ptr(out), sob, sok, int(cm), W, int(bool(variance)), int(statics),
-          len(orders), width, mode_code, float(cval), _ptr(tab), form, _ptr(work), wb)
+          len(orders), width, mode_code, float(cval), _ptr(tab), form, _ptr(work), _nbytes(work))
     return out
 
 
@@ -3384,9 +3332,7 @@ def stack_memory(x: torch.Tensor, n_steps: int = 2, delay: int = 1, out: Optiona
     out = _dyn_out("stack_memory", out, (B, n_steps * K, Tn), x)
     if not out.is_contiguous():
         raise ValueError("stack_memory: out must be contiguous")
-    require_gpu()
-    if not x.is_cuda:
-        raise ValueError("stack_memory: x must be a float32 CUDA tensor")
+    _on_device(x, "stack_memory: x")
     sxb, sxk = _dyn_strides(x)
     _call("syg_stack_memory_f32", _ptr(x), B, K, Tn, sxb, sxk, _ptr(out), n_steps, delay)
     return out

@@ -66,8 +66,7 @@ class SygnalsAmdPlugin(_Base):
 
     def teardown(self):
         from .. import ops
-        ops._dev_cache.clear()
-        ops._mfcc_calls.clear()
+        ops.clear_caches()
 
     # ---- registration hooks (call order fixed by loader.py:266-274) -----------------------
     def register_filters(self, registry):

@@ -166,6 +166,18 @@ def test_batch_determinism_and_strides(ops):
         ops.resample_poly(view, 160, 441, out=torch.zeros((5, 1486), device="cuda"))
 
 
+def test_more_rows_than_a_launch_takes(ops):
+    """65537 rows go through in launches of 65535 and 2: the same bits as those rows in two calls, and right against scipy."""
+    B, L = 65537, 4
+    x = ops.to_device_f32(_rows(B, L, 4))
+    got = ops.resample_poly(x, 2, 1)
+    assert got.shape == (B, 8)
+    assert torch.equal(got[:65535], ops.resample_poly(x[:65535], 2, 1))
+    assert torch.equal(got[65535:], ops.resample_poly(x[65535:], 2, 1))
+    rows = [0, 65534, 65535, 65536]
+    _worst(got[rows].cpu().numpy(), sp_resample_poly(x[rows].cpu().numpy().astype(np.float64), 2, 1, axis=1))
+
+
 def test_identity_is_a_copy(ops):
     import sygnals_amd.core.dsp as D
     x = ops.to_device_f32(_rows(3, 1000, 3))
