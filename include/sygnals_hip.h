@@ -1253,6 +1253,45 @@ int syg_dynamics_f32(const float* x, int64_t B, int64_t K, int64_t T, int64_t sx
 int syg_stack_memory_f32(const float* x, int64_t B, int64_t K, int64_t T, int64_t sxb, int64_t sxk, float* out,
                          int64_t n_steps, int64_t delay, void* stream);
 
+/* -------------------------------------------------------------------------------
+ * SpecAugment of x [B, K, T] float32 (spec_augment.hip): a time warp, then the union of frequency and time masks, drawn
+ * per clip.  Rows as in syg_dynamics_f32 (unit stride along T, strides in floats over B and K).  The package's own
+ * definition; the integer / float64 restatement: tests/specaug_ref.py, the host twin: sygnals_amd/_specaug.py.
+ *
+ * Clip b has T_b = lengths[b] valid frames (device int64 [B], each in [1, T]; NULL: T) and generator row
+ * r = first_row + b.  Frames t >= T_b are copied and nothing is drawn from them.  Item q is one Philox call at counter
+ * (q, 0, r, SYG_SPEC_STREAM) with key `seed`; words w0, w1 are used; draw(w, n) = (uint64(w) n) >> 32.
+ *   warp (q = 0), only if time_warp = W > 0 and T_b > 2 W:  c = W + draw(w0, T_b - 2 W), w' = c - W + 1 + draw(w1, 2 W);
+ *     frames [0, c) are resized to w' frames and [c, T_b) to T_b - w', each as torch's linear interpolate with
+ *     align_corners = False: s = max(0, ((2u + 1) n_in - n_out) / (2 n_out)) by integer quotient and remainder,
+ *     i0 = min(floor(s), n_in - 1), i1 = min(i0 + 1, n_in - 1), value a + (s - floor(s)) (b - a) in float32.
+ *   frequency mask i (q = 1 + i):  f = draw(w0, freq_width + 1), f0 = draw(w1, K - f + 1): rows [f0, f0 + f).
+ *   time mask j (q = 17 + j):  We = min(time_width, floor(time_ratio T_b)) (float64), t = draw(w0, We + 1),
+ *     t0 = draw(w1, T_b - t + 1): frames [t0, t0 + t).
+ * A masked cell (t < T_b) holds mask_value bit for bit, or with mean = 1 the mean of x[b, :, :T_b] before the warp:
+ * float64 sums over chunks of SYG_SPEC_TILE cells (cell j: row j / T_b, frame j % T_b) added in index order, rounded once.
+ * form (mean only): 0 the rule (resident up to SYG_SPEC_RESIDENT_MAX cells a clip), 1 resident (one launch, a workgroup a
+ * clip), 2 tiled (two small launches ahead, `work` of syg_spec_augment_work_bytes(B, K, T) bytes); same bits.
+ * out = x itself (same strides) with time_warp = 0 writes the masked cells only (mean: the tiled sums, `work` needed).
+ * No atomics: the same call gives the same bits, and a batch equals its clips called with first_row + b.
+ * Rejected before any device work: null x / out, an empty input, more than 2^31 elements, bad strides, counts outside
+ * 0 .. 16, freq_width outside [0, K], a negative time_width or time_warp, time_ratio outside (0, 1], a non-finite
+ * mask_value, rows beyond 2^31, an out that overlaps x otherwise, a missing workspace.
+ * ------------------------------------------------------------------------------- */
+enum {
+  SYG_SPEC_STREAM = 0,        /* counter word 3 of the draws */
+  SYG_SPEC_MAX_MASKS = 1,     /* masks of one kind, at most */
+  SYG_SPEC_TILE = 2,          /* cells of a workgroup's tile and of a chunk of the mean's sums */
+  SYG_SPEC_RESIDENT_MAX = 3,  /* the rule: cells of a clip up to which the mean is taken in the one launch */
+  SYG_SPEC_MAX_ELEMS = 4      /* elements of a call, at most */
+};
+int64_t syg_spec_augment_constants(int key);
+int64_t syg_spec_augment_work_bytes(int64_t B, int64_t K, int64_t T);
+int syg_spec_augment_f32(const float* x, int64_t B, int64_t K, int64_t T, int64_t sxb, int64_t sxk, float* out, int64_t sob,
+                         int64_t sok, const int64_t* lengths, uint64_t seed, int64_t first_row, int freq_masks,
+                         int64_t freq_width, int time_masks, int64_t time_width, double time_ratio, int64_t time_warp, int mean,
+                         float mask_value, int form, void* work, int64_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,9 @@ SIGNATURES = {
     "syg_dynamics_work_bytes": (_l, [_l, _l, _l]),
     "syg_dynamics_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _l, _i, _l, _i, _i, _i, _i, _i, _f, _p, _i, _p, _l, _p]),
     "syg_stack_memory_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _l, _p]),
+    "syg_spec_augment_constants": (_l, [_i]),
+    "syg_spec_augment_work_bytes": (_l, [_l, _l, _l]),
+    "syg_spec_augment_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _l, _p, _u, _l, _i, _l, _i, _l, _d, _l, _i, _f, _i, _p, _l, _p]),
 }
 
 _lib = None

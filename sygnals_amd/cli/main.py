@@ -8,7 +8,8 @@ in the reference snapshot those groups are commented out (sygnals/cli/main.py:29
 they are provided here rather than kept.  The `augment` group keeps the option names of
 sygnals/cli/augment_cmd.py (add-noise: --snr, --noise-type, --seed; time-stretch: --rate; -o/--output), to which add-noise
 adds --generator host|device and --exponent (the device noise generator; the default, host, is the reference's draw);
-pitch-shift is not offered.  Run stand-alone as `python -m sygnals_amd.cli.main ...`
+pitch-shift is not offered; spec-augment (time warp, frequency and time masks on the tables `features extract` writes) is
+this package's own.  Run stand-alone as `python -m sygnals_amd.cli.main ...`
 or attach the features / dsp / filter groups to the reference CLI through the plugin (register_cli_commands); `augment`
 is not attached there: the reference CLI already owns a group of that name.
 """
@@ -897,6 +898,51 @@ def augment_time_stretch(input_file, output, rate):
     _save_series(y, sr, output)
     click.echo(f"Successfully applied time stretch (rate={rate}) to '{Path(input_file).name}', "
                f"saved to '{Path(output).name}'.")
+
+
+def _mask_value(text: str):
+    """--mask-value: 'mean' or a float."""
+    if text.strip().lower() == "mean":
+        return "mean"
+    try:
+        return float(text)
+    except ValueError:
+        raise click.UsageError(f"--mask-value must be 'mean' or a float (got '{text}').")
+
+
+@augment_cmd.command("spec-augment")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False, resolve_path=True))
+@click.option("-o", "--output", type=click.Path(resolve_path=True), required=True,
+              help="Output file path (same layout as the input: .csv or .npz).")
+@click.option("--freq-masks", type=click.IntRange(0, 16), default=2, show_default=True, help="Frequency masks.")
+@click.option("--freq-width", type=int, default=27, show_default=True, help="Most rows of a frequency mask.")
+@click.option("--time-masks", type=click.IntRange(0, 16), default=2, show_default=True, help="Time masks.")
+@click.option("--time-width", type=int, default=100, show_default=True, help="Most frames of a time mask.")
+@click.option("--time-ratio", type=float, default=1.0, show_default=True,
+              help="A time mask is at most this share of the frames, in (0, 1].")
+@click.option("--time-warp", type=int, default=0, show_default=True, help="Most frames the warp moves its centre (0: no warp).")
+@click.option("--mask-value", default="0", show_default=True, help="What a masked cell holds: a float, or 'mean'.")
+@click.option("--seed", type=int, default=None, help="Random seed of the draws (64-bit).")
+def augment_spec_augment(input_file, output, freq_masks, freq_width, time_masks, time_width, time_ratio, time_warp, mask_value,
+                         seed):
+    """SpecAugment on extracted features: every column but `time` is a row."""
+    from ..core.augment import spec_augment
+    value = _mask_value(mask_value)
+    if not 0.0 < time_ratio <= 1.0:
+        raise click.UsageError(f"--time-ratio must be in (0, 1] (got {time_ratio}).")
+    time, names, x = _post_rows(sio.read_data(Path(input_file)))
+    K, T = x.shape
+    if not 0 <= freq_width <= K:
+        raise click.UsageError(f"--freq-width must be in [0, {K}]: the input has {K} rows (got {freq_width}).")
+    try:
+        y, used = spec_augment(x, freq_masks, freq_width, time_masks, time_width, time_ratio, time_warp, value, seed=seed,
+                               return_seed=True)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    out = {} if time is None else {"time": np.asarray(time)}
+    out.update({n: y[i] for i, n in enumerate(names)})
+    sio.save_data(out if Path(output).suffix.lower() == ".npz" else pd.DataFrame(out), Path(output))
+    click.echo(f"Applied SpecAugment (seed={used}) to {K} feature rows x {T} frames, saved to '{Path(output).name}'.")
 
 
 cli.add_command(features_cmd)

@@ -17,6 +17,7 @@ constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;      // key
 constexpr int PHILOX_ROUNDS = 10;
 constexpr int RNG_STREAM_NOISE = 0;        // counter word 3: noise samples
 constexpr int RNG_STREAM_ROW = 1;          //                 per-row draws (a row's random SNR), host side only
+constexpr int RNG_STREAM_SPEC = 2;         //                 SpecAugment's per-clip draws (spec_augment.hip)
 constexpr int64_t RNG_ROW_LIMIT = (int64_t)1 << 31;
 
 // ten rounds, the key bumped between them; per round (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0))

@@ -20,6 +20,7 @@ from . import _laplace as LP
 from . import _lpc
 from . import _resample as RS
 from . import _rng as RNG
+from . import _specaug as SA
 from . import _tables as T
 from ._fftplan import (MAX_LDS_FFT, MAX_MIXED_FFT, MAX_ROWS, conv_fft_len, fft_plan, is_pow2,      # noqa: F401 (re-exported)
                        next_direct_len, smooth_split)
@@ -139,7 +140,8 @@ def _out(out, shape, x: torch.Tensor, what: str = "out", dtype=torch.float32, co
 
 # sizing entries whose refusal (a negative size) leaves no message in syg_last_error
 _SILENT_SIZERS = frozenset(("syg_pack_rows_work_bytes", "syg_welch_work_bytes", "syg_csd_work_bytes",
-                            "syg_onset_strength_work_bytes", "syg_dwt_work_bytes", "syg_dynamics_work_bytes"))
+                            "syg_onset_strength_work_bytes", "syg_dwt_work_bytes", "syg_dynamics_work_bytes",
+                            "syg_spec_augment_work_bytes"))
 
 
 def _work_bytes(entry: str, *args, error: Optional[Exception] = None) -> int:
@@ -3372,3 +3374,61 @@ def feature_post(x: torch.Tensor, cmvn=None, variance: bool = True, deltas: int 
             _dynamics("feature_post", s, out[:, d * K:(d + 1) * K], 0, 0, 0, 0, (d,), width, mc, 0.0, f)
         return out
     return _dynamics("feature_post", x, out, int(cm), W, variance, 1, orders, width if deltas else 1, mc, 0.0, f)
+
+
+# ------------------------------------------------------------------ SpecAugment: time warp, frequency and time masks
+_SPEC_KEYS = ("stream", "max_masks", "tile", "resident_max", "max_elems")                  # SYG_SPEC_* of include/sygnals_hip.h
+
+
+def spec_augment_constants() -> dict:
+    """The figures the SpecAugment kernel rests on (the library owns them): the generator stream of its draws, the most
+    masks of one kind, the cells of a tile (also the chunk of the mean's sums), the cells of a clip up to which "mean" is
+    taken inside the one launch, the most elements of a call."""
+    return _constants("syg_spec_augment_constants", _SPEC_KEYS)
+
+
+def _spec_lengths(lengths, B: int, Tn: int, who: str) -> np.ndarray:
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+            raise ValueError(f"{who}: lengths must be {B} integers, one per clip (got dtype {lengths.dtype})")
+        lengths = lengths.detach().cpu().numpy()
+    return SA.check_lengths(lengths, B, Tn, who)
+
+
+def spec_augment(x: torch.Tensor, seed: int, first_row: int = 0, freq_masks: int = 2, freq_width: int = 27, time_masks: int = 2,
+                 time_width: int = 100, time_ratio: float = 1.0, time_warp: int = 0, mask_value=0.0, lengths=None,
+                 out: Optional[torch.Tensor] = None, form: Optional[str] = None) -> torch.Tensor:
+    """SpecAugment of x [B, K, T] float32 on the device (syg_spec_augment_f32): per clip a time warp of up to `time_warp`
+    frames (two linear resizes, torch's interpolate with align_corners=False), then the union of `freq_masks` masks of up to
+    `freq_width` rows and `time_masks` masks of up to min(time_width, floor(time_ratio T_b)) frames, written with
+    `mask_value` (a finite float, bit for bit) or "mean" (the clip's mean over its valid frames before the warp, float64
+    sums).  Clip b draws from row first_row + b of `seed` alone (sygnals_amd._specaug.params gives the same integers), so a
+    batch equals its clips.  lengths [B]: valid frames T_b in [1, T]; later frames are copied.  Rows may be strided over B
+    and K.  `out` may be x itself when time_warp = 0: then only masked cells are written.  form: "resident" / "tiled"
+    forces how "mean" takes its sums (None: the library's rule; same bits)."""
+    who = "spec_augment"
+    given = x
+    x = _dyn_in(x, who)
+    B, K, Tn = x.shape
+    SA.check_shape(B, K, Tn, who)
+    nf, F, nt, Wt, p, W = SA.check_args(K, Tn, freq_masks, freq_width, time_masks, time_width, time_ratio, time_warp, who)
+    mean, value = SA.check_mask_value(mask_value, who)
+    seed, first_row = RNG.check_seed(seed), RNG.check_rows(first_row, B)
+    f = _dyn_form(form)
+    Tb = None if lengths is None else _spec_lengths(lengths, B, Tn, who)
+    sxb, sxk = _dyn_strides(x)
+    if out is given and x is given and W == 0:                       # onto the input itself: nothing of `out` is left to check
+        sob, sok, inplace = sxb, sxk, True
+    else:
+        aliased = isinstance(out, torch.Tensor) and out.data_ptr() == x.data_ptr()
+        out = _dyn_out(who, out, (B, K, Tn), x, may_alias=W == 0)
+        sob, sok = _dyn_strides(out)
+        inplace = aliased and (sob, sok) == (sxb, sxk)
+    _on_device(x, f"{who}: x")
+    work = None
+    if mean and nf + nt and (inplace or f == 2 or (f == 0 and K * Tn > spec_augment_constants()["resident_max"])):
+        work = _workspace("syg_spec_augment_work_bytes", B, K, Tn, dtype=torch.float64, device=x.device)
+    ld = None if Tb is None else torch.from_numpy(Tb).to(x.device)
+    _call("syg_spec_augment_f32", _ptr(x), B, K, Tn, sxb, sxk, _ptr(out), sob, sok, _ptr(ld), seed, first_row, nf, F, nt, Wt, p, W,
+          int(mean), value, f, _ptr(work), _nbytes(work))
+    return out
