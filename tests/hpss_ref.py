@@ -108,18 +108,21 @@ def hpss(y, kernel_size=31, power=2.0, margin=1.0):
     return istft(Mh * D, len(y)), istft(Mp * D, len(y))
 
 
-def rms_power(y, frame_length, hop):
-    """(librosa.feature.rms(center=True, constant padding))^2 per frame, as the reference squares it."""
-    y = np.pad(np.asarray(y, dtype=np.float64), frame_length // 2, mode="constant")
+def rms_power(y, frame_length, hop, center=True):
+    """(librosa.feature.rms(constant padding))^2 per frame, as the reference squares it.  center=False frames the
+    unpadded signal: 1 + (L - frame_length) // hop frames."""
+    y = np.asarray(y, dtype=np.float64)
+    if center:
+        y = np.pad(y, frame_length // 2, mode="constant")
     T = 1 + (len(y) - frame_length) // hop
     idx = np.arange(frame_length)[None, :] + hop * np.arange(T)[:, None]
     return np.sqrt(np.mean(y[idx] ** 2, axis=1)) ** 2
 
 
-def hnr_from_components(yh, yp, frame_length=2048, hop_length=None):
+def hnr_from_components(yh, yp, frame_length=2048, hop_length=None, center=True):
     hop = hop_length if hop_length is not None else frame_length // 4
-    ph = rms_power(yh, frame_length, hop)
-    pp = rms_power(yp, frame_length, hop)
+    ph = rms_power(yh, frame_length, hop, center)
+    pp = rms_power(yp, frame_length, hop, center)
     n = min(len(ph), len(pp))
     ph, pp = ph[:n], pp[:n]
     out = np.full(n, np.nan)

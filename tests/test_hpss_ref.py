@@ -56,6 +56,63 @@ def test_median_is_rank_of_folded_window():
     assert np.array_equal(R.median_filter_axis(np.array([[1.0, 2.0]]), 2, axis=1), [[1.0, 2.0]])
 
 
+def test_median_with_ties_against_scipy():
+    """The window pairs of tests/hpss_cases.py on an input of nine values (ties, zeros next to non-zeros), T below the window
+    included, wherever scipy keeps to the definition (SCIPY_DEPARTURES)."""
+    from tests import hpss_cases as K
+    compared = 0
+    for T in K.MEDIAN_T:
+        S = K.mag32(K.tie_spectrum(2, T))[:, :, :200]                                # [2, T, 200]
+        for kh, kp in K.MEDIAN_WINDOWS:
+            H = R.median_filter_axis(S, kh, axis=1)
+            P = R.median_filter_axis(S, kp, axis=2)
+            for b in range(2):                           # (scipy in the 2-D form test_median_definition_against_scipy pins)
+                X = np.ascontiguousarray(S[b])
+                if T not in SCIPY_DEPARTURES or kh < SCIPY_DEPARTURES[T]:
+                    assert np.array_equal(H[b], nd.median_filter(X.T.copy(), size=(1, kh), mode="reflect").T), (T, kh)
+                    compared += 1
+                assert np.array_equal(P[b], nd.median_filter(X, size=(1, kp), mode="reflect")), (T, kp)
+                # the batch axis is a plain leading axis
+                assert np.array_equal(H[b], R.median_filter_axis(S[b], kh, axis=0))
+                assert np.array_equal(P[b], R.median_filter_axis(S[b], kp, axis=1))
+    assert compared == 2 * len(K.MEDIAN_T) * len(K.MEDIAN_WINDOWS)                   # none of these T is a departure
+
+
+def test_rms_power_uncentred_against_a_loop():
+    rng = np.random.default_rng(5)
+    for fl, hop, L in ((63, 7, 1000), (4096, 1024, 4096), (64, 64, 640), (5, 3, 6)):
+        y = rng.standard_normal(L)
+        got = R.rms_power(y, fl, hop, center=False)
+        want = np.array([np.mean(y[s:s + fl] ** 2) for s in range(0, L - fl + 1, hop)])
+        assert got.shape == want.shape == (1 + (L - fl) // hop,)
+        np.testing.assert_allclose(got, want, rtol=1e-14)
+        yh, yp = y, rng.standard_normal(L) * 0.1
+        hnr, ph, pp = R.hnr_from_components(yh, yp, fl, hop, center=False)
+        np.testing.assert_allclose(hnr, 10 * np.log10(want / R.rms_power(yp, fl, hop, center=False)), rtol=1e-12)
+    # the defaults are the centred framing existing callers have
+    y = rng.standard_normal(700)
+    assert np.array_equal(R.rms_power(y, 64, 16), R.rms_power(y, 64, 16, center=True))
+    assert len(R.rms_power(y, 64, 16)) == 1 + 700 // 16
+    assert np.array_equal(R.hnr_from_components(y, y[::-1], 64, 16)[0], R.hnr_from_components(y, y[::-1], 64, 16, True)[0])
+
+
+def test_istft_of_fewer_frames_than_the_length_asks():
+    rng = np.random.default_rng(6)
+    D = rng.standard_normal((1025, 5)) + 1j * rng.standard_normal((1025, 5))
+    y = R.istft(D, 8000)
+    assert y.shape == (8000,) and np.isfinite(y).all()
+    assert np.flatnonzero(y).max() == 3071 and not y[3072:].any()                    # frame 4 ends at sample 4 * 512 + 1023
+    assert np.array_equal(y[:3000], R.istft(D, 3000))
+    # irfft ignores the imaginary parts of the first and the last bin
+    D0 = D.copy()
+    D0[0] = D0[0].real
+    D0[1024] = D0[1024].real
+    assert np.array_equal(R.istft(D0, 8000), y)
+    # frames past those the length needs are not read
+    D9 = np.concatenate([D, np.full((1025, 4), np.nan)], axis=1)
+    assert np.array_equal(R.istft(D9, 500), R.istft(D, 500))
+
+
 def test_softmask_rules():
     X = np.array([0.0, 1.0, 2.0, 0.0])
     Xr = np.array([0.0, 1.0, 1.0, 3.0])
