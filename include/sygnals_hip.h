@@ -1292,6 +1292,70 @@ int syg_spec_augment_f32(const float* x, int64_t B, int64_t K, int64_t T, int64_
                          int64_t freq_width, int time_masks, int64_t time_width, double time_ratio, int64_t time_warp, int mean,
                          float mask_value, int form, void* work, int64_t work_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------
+ * Rhythm after the onset envelope (beat.hip): librosa 0.10 feature.tempogram (autocorrelation), feature.tempo and
+ * beat.beat_track.  Parity is unpinned (librosa is not a dependency): the float64 restatement of tests/beat_ref.py is the
+ * contract.  env [B, T] float32, row stride ld >= T, unit stride along T.  No atomics: the same call gives the same bits
+ * and a batch equals its rows.  Every entry checks its arguments before any device work.
+ *
+ * syg_tempogram_f32: center != 0: the envelope is padded by p = win_length / 2 linear ramps to zero on both sides
+ *   (np.pad(..., "linear_ramp"), formed on the fly) and n = T; else n = T - win_length + 1 >= 1.  With f_t[j] =
+ *   window[j] xp[t + j] (window: device float32 [win_length]), r_t[k] = sum_j f_t[j] f_t[j + k]: float32 products summed
+ *   64 at a time, the sums added in float64, in a fixed order.  norm 1 (inf): the column is divided by max_k |r_t[k]|
+ *   unless that is below FLT_MIN; norm 0: as it is.  tg [B, win_length, n] float32, frames fastest, or NULL.
+ *   agg [B, win_length] float64 or NULL: the mean of tg over frames, summed in frame order (a partial row per
+ *   SYG_BEAT_SLICE_TILES tiles of syg_tempogram_tile(win_length) frames, the rows added in order); needs `work`,
+ *   syg_tempogram_work_bytes(B, T, win_length, center) bytes.  win_length 2 .. SYG_BEAT_WIN_MAX; the result at most
+ *   SYG_BEAT_MAX_ELEMS elements.  Cost: win_length^2 / 2 multiply-adds a frame, of which the kernel issues twice as many.
+ * syg_tempo_pick_f32: the first argmax over k of log1p(1e6 a[k]) + logprior[k] (float64; a NaN score wins, as in
+ *   numpy), a = the aggregate [B, win_length] (then n = 1) or each column of tg [B, win_length, n]: exactly one of the
+ *   two is given.  logprior, bpms: device float64 [win_length], made on the host.  kstar [B, n] int32, tempo [B, n]
+ *   float64 = bpms[kstar].  A row whose envelope env is all zeros gives 0 and 0.0.  work: syg_tempo_pick_work_bytes(B).
+ * syg_beat_local_score_f32: e = env / std(env, ddof 1) (float64 sums; e = env when T < 2 or the deviation is not a
+ *   positive finite number); ls[i] = sum_q exp(-0.5 (32 q / P)^2) e[i - q], |q| <= min(P, ceil(7 P / 32)) (the taps
+ *   beyond are below 2.3e-11), zeros outside the row, float64, stored as float32; P = period[b], device int32 [B].
+ *   lsmax [B] float32 = max_i ls[i].  A period outside 2 .. SYG_BEAT_PERIOD_MAX: ls = 0.
+ *   work: syg_beat_local_score_work_bytes(B).
+ * syg_beat_dp_f32: offsets o_j = -2 P + j up to -round_half_even(P / 2); tx[j] = -tightness (d d), d = logtab[-o_j - 1]
+ *   - logtab[P - 1], logtab: device float64 [SYG_BEAT_LOG_TABLE], log of 1 .. SYG_BEAT_LOG_TABLE made on the host.
+ *   cum[i] = ls[i] + max_j (tx[j] + (cum[i + o_j] if i + o_j >= 0 else 0)), the first j among equals; back[i] = -1 while
+ *   no beat has been admitted and ls[i] < 0.01 lsmax, else i + o_j (which may be below -1 in the first 2 P frames: any
+ *   negative link ends a walk).  Float64 additions and comparisons only.  cum [B, T] float64, back [B, T] int32.
+ *   period_max: a bound on every period[b] known to the host, 2 .. SYG_BEAT_PERIOD_MAX; it chooses the kernel (one wave a
+ *   clip up to SYG_BEAT_DP_WAVE_PERIOD, four beyond) and the LDS ring.  A period outside 2 .. period_max: cum = 0,
+ *   back = -1.  Serial in T: about J = 1.5 P additions over the wave and one reduction a frame.
+ * syg_beat_track_f32: the local maxima of cum (interior: cum[i] > cum[i - 1] and cum[i] >= cum[i + 1]; frame 0 never;
+ *   frame T - 1: cum[T - 1] > cum[T - 2]); their exact median (numpy's: the mean of the two middle values of an even
+ *   count); the last beat = the largest i with 2 cum[i] lm[i] > median; the walk along `back`; the trim: sm[i] =
+ *   (0.5 ls[b[i - 1]] + ls[b[i]]) + 0.5 ls[b[i + 1]], th = 0.5 sqrt(sum sm^2 / count) in index order (trim = 0: th = 0),
+ *   v = {i : sm[i] > th}, result b[min v : max v] with the upper end EXCLUSIVE.  beats [B, T] int32 ascending, -1 beyond
+ *   them; count [B] int32; last [B] int32 (the last beat before the trim, -1: none) or NULL.
+ * ------------------------------------------------------------------------------- */
+enum {
+  SYG_BEAT_WIN_MAX = 0,         /* largest win_length */
+  SYG_BEAT_PERIOD_MAX = 1,      /* largest beat period in frames */
+  SYG_BEAT_LOG_TABLE = 2,       /* entries of logtab */
+  SYG_BEAT_SLICE_TILES = 3,     /* tiles of frames a tempogram workgroup takes: one partial row of the aggregate */
+  SYG_BEAT_DP_WAVE_PERIOD = 4,  /* period_max up to which the DP runs one wave a clip */
+  SYG_BEAT_MAX_ELEMS = 5        /* elements of a result, at most */
+};
+int64_t syg_beat_constants(int key);
+int syg_tempogram_tile(int win_length);
+int64_t syg_tempogram_work_bytes(int64_t B, int64_t T, int win_length, int center);
+int syg_tempogram_f32(const float* env, int64_t B, int64_t T, int64_t ld, int win_length, int center, const float* window,
+                      int norm, float* tg, double* agg, void* work, int64_t work_bytes, void* stream);
+int64_t syg_tempo_pick_work_bytes(int64_t B);
+int syg_tempo_pick_f32(const double* a, const float* tg, int64_t B, int win_length, int64_t n, const float* env, int64_t T,
+                       int64_t ld, const double* logprior, const double* bpms, int32_t* kstar, double* tempo, void* work,
+                       void* stream);
+int64_t syg_beat_local_score_work_bytes(int64_t B);
+int syg_beat_local_score_f32(const float* env, int64_t B, int64_t T, int64_t ld, const int32_t* period, float* ls,
+                             float* lsmax, void* work, void* stream);
+int syg_beat_dp_f32(const float* ls, const float* lsmax, int64_t B, int64_t T, const int32_t* period, int period_max,
+                    double tightness, const double* logtab, double* cum, int32_t* back, void* stream);
+int syg_beat_track_f32(const float* ls, const double* cum, const int32_t* back, int64_t B, int64_t T, const int32_t* period,
+                       int trim, int32_t* beats, int32_t* count, int32_t* last, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,6 +190,16 @@ SIGNATURES = {
     "syg_spec_augment_constants": (_l, [_i]),
     "syg_spec_augment_work_bytes": (_l, [_l, _l, _l]),
     "syg_spec_augment_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _l, _p, _u, _l, _i, _l, _i, _l, _d, _l, _i, _f, _i, _p, _l, _p]),
+    "syg_beat_constants": (_l, [_i]),
+    "syg_tempogram_tile": (_i, [_i]),
+    "syg_tempogram_work_bytes": (_l, [_l, _l, _i, _i]),
+    "syg_tempogram_f32": (_i, [_p, _l, _l, _l, _i, _i, _p, _i, _p, _p, _p, _l, _p]),
+    "syg_tempo_pick_work_bytes": (_l, [_l]),
+    "syg_tempo_pick_f32": (_i, [_p, _p, _l, _i, _l, _p, _l, _l, _p, _p, _p, _p, _p, _p]),
+    "syg_beat_local_score_work_bytes": (_l, [_l]),
+    "syg_beat_local_score_f32": (_i, [_p, _l, _l, _l, _p, _p, _p, _p, _p]),
+    "syg_beat_dp_f32": (_i, [_p, _p, _l, _l, _p, _i, _d, _p, _p, _p, _p]),
+    "syg_beat_track_f32": (_i, [_p, _p, _p, _l, _l, _p, _i, _p, _p, _p, _p]),
 }
 
 _lib = None

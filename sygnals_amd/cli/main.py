@@ -436,6 +436,45 @@ def dsp_delay(input_file_1, input_file_2, output, fs, max_lag, max_delay, weight
     click.echo(f"Delay {delay:.9g} s (lag {lag}) saved to '{Path(output).name}'.")
 
 
+@dsp_cmd.command("beats")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--hop-length", type=int, default=512, show_default=True)
+@click.option("--start-bpm", type=float, default=120.0, show_default=True, help="Centre of the tempo prior.")
+@click.option("--tightness", type=float, default=100.0, show_default=True)
+@click.option("--no-trim", is_flag=True, help="Keep leading and trailing beats with weak onsets.")
+@click.option("--bpm", type=float, default=None, help="Track at this tempo instead of estimating it.")
+@click.option("--units", type=click.Choice(["time", "frames", "samples"]), default="time", show_default=True)
+def dsp_beats(input_file, output, hop_length, start_bpm, tightness, no_trim, bpm, units):
+    """Estimate the tempo and track the beats of an audio file (librosa.beat.beat_track)."""
+    from ..core.rhythm import beat_track
+    if bpm is not None and not bpm > 0:
+        raise click.UsageError("--bpm must be positive.")
+    if not tightness > 0:
+        raise click.UsageError("--tightness must be positive.")
+    if hop_length < 1:
+        raise click.UsageError("--hop-length must be positive.")
+    x, sr = _load_signal(input_file, None)
+    if not sr:
+        raise click.UsageError("`dsp beats` needs an input that carries a sampling rate (audio).")
+    try:
+        tempo, frames = beat_track(x, sr=sr, hop_length=hop_length, start_bpm=start_bpm, tightness=tightness, trim=not no_trim,
+                                   bpm=bpm, units="frames")
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    times = frames * hop_length / float(sr)
+    beats = {"time": times, "frames": frames, "samples": frames * hop_length}[units]
+    if Path(output).suffix.lower() == ".npz":
+        sio.save_data({"tempo": np.array(tempo), "beats": beats, "hop_length": np.array(hop_length), "units": np.array(units)},
+                      output)
+    else:
+        try:
+            sio.save_data(pd.DataFrame({"index": np.arange(len(frames)), "frame": frames, "time": times}), output)
+        except ValueError as e:
+            raise click.UsageError(str(e))
+    click.echo(f"Tempo {tempo:.6g} BPM, {len(frames)} beats saved to '{Path(output).name}'.")
+
+
 @dsp_cmd.command("hilbert")
 @click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
 @click.option("-o", "--output", required=True, type=click.Path())

@@ -173,3 +173,11 @@ def segment_by_onsets(y, sr: int, hop_length: int = 512, segment_duration_sec: O
     from .audio.features import detect_onsets
     times = detect_onsets(y, sr=sr, hop_length=hop_length, units="time", **onset_kwargs)
     return segment_by_event(y, sr, times, segment_duration_sec, pre_event_sec, post_event_sec)
+
+
+def segment_by_beats(y, sr: int, hop_length: int = 512, segment_duration_sec: Optional[float] = None,
+                     pre_event_sec: float = 0.05, post_event_sec: float = 0.2, **beat_kwargs: Any):
+    """Segments around the tracked beats: beat_track(units='time') then segment_by_event."""
+    from .rhythm import beat_track
+    _, times = beat_track(y, sr=sr, hop_length=hop_length, units="time", **beat_kwargs)
+    return segment_by_event(y, sr, times, segment_duration_sec, pre_event_sec, post_event_sec)

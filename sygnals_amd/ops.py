@@ -19,6 +19,7 @@ from . import _dynamics as DY
 from . import _laplace as LP
 from . import _lpc
 from . import _resample as RS
+from . import _rhythm as RH
 from . import _rng as RNG
 from . import _specaug as SA
 from . import _tables as T
@@ -141,7 +142,8 @@ def _out(out, shape, x: torch.Tensor, what: str = "out", dtype=torch.float32, co
 # sizing entries whose refusal (a negative size) leaves no message in syg_last_error
 _SILENT_SIZERS = frozenset(("syg_pack_rows_work_bytes", "syg_welch_work_bytes", "syg_csd_work_bytes",
                             "syg_onset_strength_work_bytes", "syg_dwt_work_bytes", "syg_dynamics_work_bytes",
-                            "syg_spec_augment_work_bytes"))
+                            "syg_spec_augment_work_bytes", "syg_tempogram_work_bytes", "syg_tempo_pick_work_bytes",
+                            "syg_beat_local_score_work_bytes"))
 
 
 def _work_bytes(entry: str, *args, error: Optional[Exception] = None) -> int:
@@ -3432,3 +3434,144 @@ def spec_augment(x: torch.Tensor, seed: int, first_row: int = 0, freq_masks: int
     _call("syg_spec_augment_f32", _ptr(x), B, K, Tn, sxb, sxk, _ptr(out), sob, sok, _ptr(ld), seed, first_row, nf, F, nt, Wt, p, W,
           int(mean), value, f, _ptr(work), _nbytes(work))
     return out
+
+
+# ------------------------------------------------------------------ rhythm: tempogram, tempo, beat tracking
+_BEAT_KEYS = ("win_max", "period_max", "log_table", "slice_tiles", "dp_wave_period", "max_elems")      # SYG_BEAT_* of include/sygnals_hip.h
+
+
+def beat_constants() -> dict:
+    """The figures the rhythm kernels rest on (the library owns them): the largest win_length and beat period, the entries
+    of the log table, the tiles of frames behind one partial row of the aggregate, the period up to which the DP runs one
+    wave a clip, the most elements of a result."""
+    return _constants("syg_beat_constants", _BEAT_KEYS)
+
+
+def tempogram_tile(win_length: int) -> int:
+    """Frames of a tempogram workgroup's tile at this win_length."""
+    return int(lib().syg_tempogram_tile(RH.check_win_length(win_length, "tempogram")))
+
+
+def _beat_periods(period, B: int, device, who: str):
+    """(device int32 [B], the host's bound on them or None) of periods given on either side."""
+    if isinstance(period, torch.Tensor):
+        if period.dtype != torch.int32 or tuple(period.shape) != (B,) or not period.is_cuda:
+            raise ValueError(f"{who}: period must be an int32 device tensor [{B}] (or integers on the host)")
+        return period.contiguous(), None
+    p = RH.check_periods(period, B, who)
+    return torch.from_numpy(p).to(device), max(2, int(p.max()))
+
+
+def tempogram(env: torch.Tensor, win_length: int = 384, center: bool = True, window="hann", norm=np.inf,
+              aggregate: Optional[str] = None, out: Optional[torch.Tensor] = None):
+    """librosa.feature.tempogram (autocorrelation) of envelopes env [B, T] (rows of any stride) on the device
+    (syg_tempogram_f32) -> tg [B, win_length, n] float32, frames fastest; n = T centred, else T - win_length + 1.
+    aggregate: None: tg alone; "also": (tg, a) with a [B, win_length] float64, the mean of tg over frames; "only": a alone,
+    and nothing of size B win_length n is written."""
+    who = "tempogram"
+    win = RH.check_win_length(win_length, who)
+    nrm = RH.check_norm(norm, who)
+    if aggregate not in (None, "also", "only"):
+        raise ValueError(f'{who}: aggregate must be None, "also" or "only"')
+    _f32(env, "env", 2, axes="[B, T]")
+    B, Tn = env.shape
+    n = RH.check_frames(Tn, win, bool(center), who)
+    if aggregate != "only":
+        RH.check_size(B, win, n, who)
+    env = _f32_in(env, "env", 2, axes="[B, T]")
+    wdev = _cached(("beat_win",) + _window_key(window, win, win), lambda: _dev(RH.window_table(window, win)), limit=16)
+    tg = _out(out, (B, win, n), env, contiguous=True) if aggregate != "only" else None
+    a = work = None
+    if aggregate is not None:
+        a = torch.empty((B, win), dtype=torch.float64, device=env.device)
+        work = _workspace("syg_tempogram_work_bytes", B, Tn, win, int(bool(center)), dtype=torch.float64, device=env.device)
+    _call("syg_tempogram_f32", _ptr(env), B, Tn, _ld(env), win, int(bool(center)), _ptr(wdev), nrm, _ptr(tg), _ptr(a), _ptr(work),
+          _nbytes(work))
+    return tg if aggregate is None else ((tg, a) if aggregate == "also" else a)
+
+
+def tempo_pick(a: torch.Tensor, env: torch.Tensor, logprior: np.ndarray, bpms: np.ndarray):
+    """The tempo of every row (a: the aggregate, float64 [B, win_length]) or of every frame (a: a tempogram, float32
+    [B, win_length, n]) under the host-made prior (syg_tempo_pick_f32) -> (k* int32, tempo float64), [B] or [B, n]: the first
+    argmax of log1p(1e6 a[k]) + logprior[k] and bpms[k*].  A row whose envelope env [B, T] is all zeros gives 0 and 0.0."""
+    who = "tempo_pick"
+    if not isinstance(a, torch.Tensor) or (a.dim(), a.dtype) not in ((2, torch.float64), (3, torch.float32)):
+        raise ValueError(f"{who}: a must be the aggregate (float64 [B, win_length]) or a tempogram (float32 [B, win_length, n])")
+    _f32(env, "env", 2, axes="[B, T]")
+    B, win = a.shape[:2]
+    win = RH.check_win_length(int(win), who)
+    lp, bp = (np.ascontiguousarray(v, dtype=np.float64) for v in (logprior, bpms))
+    if lp.shape != (win,) or bp.shape != (win,) or env.shape[0] != B:
+        raise ValueError(f"{who}: logprior and bpms must hold win_length = {win} values and env {B} rows")
+    _on_device(a, "a")
+    env = _f32_in(env, "env", 2, axes="[B, T]")
+    a = a.contiguous()
+    n = 1 if a.dim() == 2 else int(a.shape[2])
+    lpd, bpd = _cached(("tempo_prior", lp.tobytes(), bp.tobytes()), lambda: (_dev(lp), _dev(bp)), limit=16)
+    shape = (B,) if a.dim() == 2 else (B, n)
+    kstar = torch.empty(shape, dtype=torch.int32, device=a.device)
+    bpm = torch.empty(shape, dtype=torch.float64, device=a.device)
+    work = _workspace("syg_tempo_pick_work_bytes", B, dtype=torch.float32, device=a.device)
+    _call("syg_tempo_pick_f32", _ptr(a) if a.dim() == 2 else None, _ptr(a) if a.dim() == 3 else None, B, win, n, _ptr(env),
+          int(env.shape[1]), _ld(env), _ptr(lpd), _ptr(bpd), _ptr(kstar), _ptr(bpm), _ptr(work))
+    return kstar, bpm
+
+
+def beat_local_score(env: torch.Tensor, period):
+    """beat_track's local score of envelopes env [B, T] (syg_beat_local_score_f32): the envelope over its standard
+    deviation against the Gaussian taps of each row's own period (device int32 [B], or integers on the host)
+    -> (ls [B, T] float32, its maxima [B] float32)."""
+    env = _f32_in(env, "env", 2, axes="[B, T]")
+    B, Tn = env.shape
+    pd, _ = _beat_periods(period, B, env.device, "beat_local_score")
+    ls = torch.empty((B, Tn), dtype=torch.float32, device=env.device)
+    lsmax = torch.empty((B,), dtype=torch.float32, device=env.device)
+    work = _workspace("syg_beat_local_score_work_bytes", B, dtype=torch.float64, device=env.device)
+    _call("syg_beat_local_score_f32", _ptr(env), B, Tn, _ld(env), _ptr(pd), _ptr(ls), _ptr(lsmax), _ptr(work))
+    return ls, lsmax
+
+
+def beat_dp(ls: torch.Tensor, lsmax: torch.Tensor, period, tightness: float = 100.0, period_max: Optional[int] = None,
+            out=None):
+    """beat_track's dynamic programme over local scores ls [B, T] (syg_beat_dp_f32) -> (cum [B, T] float64, back [B, T]
+    int32).  period: device int32 [B] or integers on the host; period_max: a bound on them (default: the largest of host
+    periods, the library's maximum for a device tensor); a row above it, or below 2, gets no beats.  out: (cum, back)."""
+    who = "beat_dp"
+    tight = RH.check_tightness(tightness, who)
+    _f32(ls, "ls", 2, axes="[B, T]")
+    _f32(lsmax, "lsmax", 1, axes="[B]")
+    B, Tn = ls.shape
+    if lsmax.shape[0] != B:
+        raise ValueError(f"{who}: lsmax must hold {B} values")
+    _on_device(ls, "ls")
+    ls, lsmax = ls.contiguous(), lsmax.contiguous()
+    pd, bound = _beat_periods(period, B, ls.device, who)
+    pmax = int(period_max) if period_max is not None else (bound or RH.PERIOD_MAX)
+    if not 2 <= pmax <= RH.PERIOD_MAX:
+        raise ValueError(f"{who}: period_max={pmax} is outside 2 .. {RH.PERIOD_MAX}")
+    cum = _out(out[0] if out else None, (B, Tn), ls, "out[0]", torch.float64, contiguous=True)
+    back = _out(out[1] if out else None, (B, Tn), ls, "out[1]", torch.int32, contiguous=True)
+    logtab = _cached(("beat_log",), lambda: _dev(RH.log_table()))
+    _call("syg_beat_dp_f32", _ptr(ls), _ptr(lsmax), B, Tn, _ptr(pd), pmax, tight, _ptr(logtab), _ptr(cum), _ptr(back))
+    return cum, back
+
+
+def beat_track(ls: torch.Tensor, cum: torch.Tensor, back: torch.Tensor, period, trim: bool = True, out=None):
+    """The beats of every row from its local score and the DP's tables (syg_beat_track_f32): the last beat by the median
+    of cum's local maxima, the walk along back, the trim -> (beats [B, T] int32 ascending, -1 beyond them; count [B] int32;
+    last [B] int32, the last beat before the trim or -1).  out: (beats, count)."""
+    who = "beat_track"
+    _f32(ls, "ls", 2, axes="[B, T]")
+    B, Tn = ls.shape
+    for t, name, dt in ((cum, "cum", torch.float64), (back, "back", torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (B, Tn):
+            raise ValueError(f"{who}: {name} must be a {str(dt)[6:]} tensor [{B}, {Tn}]")
+    _on_device(ls, "ls")
+    ls, cum, back = ls.contiguous(), cum.contiguous(), back.contiguous()
+    pd, _ = _beat_periods(period, B, ls.device, who)
+    beats = _out(out[0] if out else None, (B, Tn), ls, "out[0]", torch.int32, contiguous=True)
+    count = _out(out[1] if out else None, (B,), ls, "out[1]", torch.int32, contiguous=True)
+    last = torch.empty((B,), dtype=torch.int32, device=ls.device)
+    _call("syg_beat_track_f32", _ptr(ls), _ptr(cum), _ptr(back), B, Tn, _ptr(pd), int(bool(trim)), _ptr(beats), _ptr(count),
+          _ptr(last))
+    return beats, count, last

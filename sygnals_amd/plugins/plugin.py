@@ -82,6 +82,7 @@ class SygnalsAmdPlugin(_Base):
     def register_transforms(self, registry):
         from ..core import dsp as D
         from ..core import alignment as AL
+        from ..core import rhythm as RY
         from ..core import transforms as TR
         from ..core.features import cepstral as CF
         from ..core.features import dynamics as DN
@@ -91,7 +92,8 @@ class SygnalsAmdPlugin(_Base):
                    D.inverse_complex_cepstrum, CF.lpc, TR.hilbert_transform, TR.continuous_wavelet_transform,
                    TR.laplace_transform_numerical,
                    TR.discrete_wavelet_transform, TR.inverse_discrete_wavelet_transform,
-                   D.compute_csd, D.compute_coherence, AL.estimate_delay, DN.delta, DN.cmvn, DN.stack_memory):
+                   D.compute_csd, D.compute_coherence, AL.estimate_delay, DN.delta, DN.cmvn, DN.stack_memory,
+                   RY.beat_track, RY.tempo):
             registry.add_transform(fn.__name__, fn)
 
     def register_feature_extractors(self, registry):
