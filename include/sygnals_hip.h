@@ -56,8 +56,13 @@ const char* syg_last_error(void);
  *                         lane per residue, always) | 1 (chunked, always): form of syg_fx_delay_f32
  *   SYG_OPT_STFT_FREERUN  -1 (default: the library decides) | 0 (off) | 1 (on where syg_stft2048_mfcc_tri_freerun() holds):
  *                         free-running form of syg_stft2048_mfcc_tri_f32 -- no stage buffer, every wave loads its next frame
- *                         under its projection, one workgroup barrier per clip.  An explicit SYG_OPT_STFT_LOAD >= 0 turns
- *                         the -1 default off
+ *                         under its projection (how its waves hand a clip over: SYG_OPT_STFT_MEET).  An explicit
+ *                         SYG_OPT_STFT_LOAD >= 0 turns the -1 default off
+ *   SYG_OPT_STFT_MEET     -1 (default: the library decides) | 0 | 1: how the free-running form hands a finished clip to its
+ *                         dB + DCT epilogue, and the clip's LDS matrix back.  1: one workgroup barrier per clip.  0: no barrier
+ *                         inside the tile loop -- counters in LDS that only grow; a wait on one is a bounded poll, and a bound
+ *                         that runs out turns the clip's output into NaN.  Same bits either way; no effect where the
+ *                         free-running form does not run
  * syg_set_option returns SYG_OK or SYG_E_INVALID (unknown key / value out of range); syg_get_option the current value. */
 #define SYG_OPT_RESERVED_CUS 0
 #define SYG_OPT_STFT_LOAD 1
@@ -66,7 +71,8 @@ const char* syg_last_error(void);
 #define SYG_OPT_DWT_FORM 4
 #define SYG_OPT_FX_DELAY_FORM 5
 #define SYG_OPT_STFT_FREERUN 6
-#define SYG_OPT_COUNT 7
+#define SYG_OPT_STFT_MEET 7
+#define SYG_OPT_COUNT 8
 int syg_set_option(int key, int value);
 int syg_get_option(int key);
 

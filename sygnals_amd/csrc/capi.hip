@@ -13,7 +13,7 @@ void set_error(const char* fmt, ...) {
 }
 // Process-wide options (syg_set_option): plain atomics, read where a launch is planned.  They select between kernels that
 // the tests hold to the same results, or size the grid; nothing here is read from the environment.
-static std::atomic<int> g_opt[SYG_OPT_COUNT] = {{0}, {-1}, {1}, {-1}, {1}, {-1}, {-1}};
+static std::atomic<int> g_opt[SYG_OPT_COUNT] = {{0}, {-1}, {1}, {-1}, {1}, {-1}, {-1}, {-1}};
 int option(int key) { return (key >= 0 && key < SYG_OPT_COUNT) ? g_opt[key].load(std::memory_order_relaxed) : 0; }
 }  // namespace syg
 
@@ -26,6 +26,7 @@ extern "C" int syg_set_option(int key, int value) {
     case SYG_OPT_CQT_STAGED: SYG_REQUIRE(value >= -1 && value <= 2, "syg_set_option: cqt_staged must be -1 (default), 0, 1 or 2"); break;
     case SYG_OPT_DWT_FORM: SYG_REQUIRE(value == 0 || value == 1, "syg_set_option: dwt_form must be 0 or 1"); break;
     case SYG_OPT_STFT_FREERUN: SYG_REQUIRE(value >= -1 && value <= 1, "syg_set_option: stft_freerun must be -1 (default), 0 or 1"); break;
+    case SYG_OPT_STFT_MEET: SYG_REQUIRE(value >= -1 && value <= 1, "syg_set_option: stft_meet must be -1 (default), 0 or 1"); break;
     case SYG_OPT_FX_DELAY_FORM: SYG_REQUIRE(value >= -1 && value <= 1, "syg_set_option: fx_delay_form must be -1 (default), 0 or 1"); break;
   }
   syg::g_opt[key].store(value, std::memory_order_relaxed);

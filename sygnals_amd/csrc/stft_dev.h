@@ -1,6 +1,7 @@
 // Development instrumentation of stft_mel.hip (not part of the product build): with -DSYG_DEV=1 the kernel carries
 // per-wave cycle accumulators per phase (s_memtime stamps) and dumps them into its statistics / mel output
-// (tools/timeline.py reads them).  Such a build reports itself through syg_build_variant() and the Python binding refuses
+// (tools/timeline.py reads them; the free-running forms of MODE 6 have neither output and write them to the buffer given to
+// syg_dev_set_timeline(), an entry point that only such a build has).  Such a build reports itself through syg_build_variant() and the Python binding refuses
 // to load it as the product.  -DSYG_TICK_NOVM: the stamps do not drain vector memory (the DMA / store waits then show up
 // where the product waits).
 #pragma once

@@ -37,7 +37,8 @@
 //   10   TileSeg2      8 | 16  ... n_segtab = 1024: MODE 8 with the TWO-pass table of MODE 6;  11 TileSeg2Rows: + row functions
 // Every (waves, mode) is built for the three frame load paths (LOAD 0 / 1 / 2, see fetch_frame()); MODE 6 also has the
 // free-running form LOAD 3: no stage buffer, every wave prefetches its next frame from global memory under its own
-// projection and the workgroup meets once per clip (syg_stft2048_mfcc_tri_freerun() says where it is used).
+// projection and the workgroup meets once per clip (syg_stft2048_mfcc_tri_freerun() says where it is used), and LOAD 4: the
+// same without that barrier, a clip handed over by counters in LDS (SYG_OPT_STFT_MEET chooses between the two).
 // Nothing but the input samples and the outputs touches HBM.
 //
 // Reference behaviour reproduced: librosa.stft (center zero padding, periodic window, rfft) -> np.abs ->
@@ -499,6 +500,36 @@ __device__ __noinline__ void clip_dct(int clipmel_addr, int red_addr, int dct_ad
   }
 }
 
+// LOAD 4 (the free-running form whose waves never meet): a clip's two hand-overs go through counters in LDS that only grow
+// (the tile loop says what they count).  A wait is a poll at the lowest issue priority: load, sleep, load again.  It is
+// bounded, so that a protocol error shows as NaN in the clip's output and never as a hung device: false when the bound ran out.
+// HANDOVER_ROUNDS: the longest single wait at the clip barrier of the barrier form, stamped per wave over the 1024-clip
+// launch (tools/timeline.py freerun), was 17.6 k cycles = 8.4 us; a round is s_sleep 8 (512 cycles) + an LDS load, >= 0.3 us
+// at 2.1 GHz; 65536 rounds are >= 20 ms = 2400 x that wait, and expire within 50 ms unless a round takes 2.5 x as long.
+constexpr int HANDOVER_ROUNDS = 1 << 16;
+typedef __attribute__((address_space(3))) int* lds_ctr;
+__device__ __forceinline__ int handover_load(lds_ctr c) {
+  return __builtin_amdgcn_readfirstlane(__hip_atomic_load(c, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+// PRIO_BACK: the level the wave goes on at (< 0: it runs at level 0 throughout)
+template <int PRIO_BACK>
+__device__ __forceinline__ bool handover_wait(lds_ctr c, int target) {
+  if (handover_load(c) >= target) return true;
+  if (PRIO_BACK >= 0) SETPRIO(0);
+  bool ok = false;
+#pragma unroll 1
+  for (int r = 0; r < HANDOVER_ROUNDS && !ok; ++r) {
+    __builtin_amdgcn_s_sleep(8);
+    ok = handover_load(c) >= target;
+  }
+  if (PRIO_BACK >= 0) SETPRIO(PRIO_BACK);
+  return ok;
+}
+// one lane per wave, behind the wave's own LDS stores and reads (the LDS executes a wave's DS operations in order)
+__device__ __forceinline__ void handover_add(lds_ctr c, int lane) {
+  if (lane == 0) __hip_atomic_fetch_add(c, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 // ----------------------------------------------------------------------------------
 // LOAD 0 / 1: frames read straight from global memory   LOAD 2: tiles staged in LDS by LDS-DMA (hop <= 512)
 //
@@ -597,8 +628,11 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
   constexpr bool COMPLEX_OUT = M.complex_out, ROWFN = M.rowfn, CLIPM = M.clip, X2 = M.x2();
   // free-running waves: no stage buffer; a wave holds its next frame in registers across its projection (loaded from
   // global memory) and the workgroup meets once per clip
-  constexpr bool FREERUN = (LOAD == 3);
-  static_assert(!FREERUN || (M.freerun && WAVES == 16 && TRI && CLIPM && !ROWFN), "LOAD 3: the free-running form of the mode");
+  // LOAD 4: the same, and the workgroup never meets inside the tile loop -- a clip is handed from the waves that fill its
+  // matrix to the waves that run its epilogue, and the matrix back, by counters in LDS (NOMEET)
+  constexpr bool FREERUN = (LOAD >= 3), NOMEET = (LOAD == 4);
+  static_assert(!FREERUN || (M.freerun && WAVES == 16 && TRI && CLIPM && !ROWFN), "LOAD 3 / 4: the free-running forms of the mode");
+  constexpr int FLOAD = FREERUN ? 3 : LOAD;      // fetch_frame()'s path
 #ifdef SYG_DEV_NO_RELC
   constexpr bool RELC = false;                                       // (timeline builds: round 3's form, for the before / after table)
 #else
@@ -683,6 +717,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
     if (!TRI)
       for (int i = tid; i < MTAB_INTS; i += NTHREADS) mtab[i] = reinterpret_cast<const int*>(wpacked)[plan.table_off + i];
   }
+  if (NOMEET && tid < 8) cplc[tid] = 0;               // the hand-over counters (below)
   if (LOAD == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -701,6 +736,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
   const int tri_ndct = ((mf.n_mfcc + 15) >> 4) * (mf.tp >> 4);
   const int tri_idle = (TRI && !TRIMEL) ? mf.tp - (int)T : 0;
   const bool tri_defer = TRI && !TRIMEL && tri_idle > 0 && (tri_ndct + tri_idle - 1) / (tri_idle > 0 ? tri_idle : 1) <= 3;
+  const int tri_nepi = tri_defer ? tri_idle : (tri_ndct < WAVES ? tri_ndct : WAVES);   // waves that run clip_dct per clip
   // staged mode: the frame of the NEXT tile is fetched (LDS -> registers) one phase ahead, so that the stage
   // buffer can be refilled behind the FFT phase; direct modes load at the top of the tile loop
   float2 v[16];
@@ -711,7 +747,7 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
     have = t < T;
     int lf = lane;                    // laundered like lv below: no hoisted per-lane addresses
     asm volatile("" : "+v"(lf));
-    if (have) fetch_frame<LOAD>(v, y + (int64_t)cq * ldy, L, t * (int64_t)hop - pad, stage + w * hop, lf);
+    if (have) fetch_frame<FLOAD>(v, y + (int64_t)cq * ldy, L, t * (int64_t)hop - pad, stage + w * hop, lf);
   };
   if (LOAD == 2) {
     fetch(tile_begin);
@@ -719,9 +755,25 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
     if (tile_begin + 1 < tile_end) dma(tile_begin + 1);
   }
   if (FREERUN) fetch(tile_begin);
+  // LOAD 4: the hand-over counters, in the words of the contrast plan (this mode has none).  They only grow; a target is
+  // formed from the clip's ordinal within the workgroup (kclip), so nothing is ever reset or reused:
+  //   filled[p]   + 1 by every wave that is through with a clip that fills matrix p (behind its last column store and its
+  //               publish_max(); waves without a frame in the clip's last tile add too).  clip_dct of the n-th clip on p
+  //               (n = 0, 1, ...) starts once filled[p] >= 16 (n + 1), wherever it runs.
+  //   drained[p]  + 1 by every wave that ran clip_dct on p, behind its last read of the matrix and of red[p][].  tri_nepi
+  //               waves run it per clip, so a wave may store into matrix p or red[p][w] for the n-th clip on p once
+  //               drained[p] >= tri_nepi n; it checks once per clip, in front of its first projection.
+  //   bad         set (never cleared) by a wave whose wait for drained[] ran out: it goes on, and every epilogue that starts
+  //               from then on writes NaN (the one it did not wait for is past its check: that clip is not marked).
+  // No wait is circular: what a wave of clip c + 2 waits for in drained[] is added by waves running the epilogue of clip
+  // c, and those reached that epilogue by passing only waits for clips <= c (their own drained[] waits of clips <= c + 1
+  // concern epilogues of clips <= c - 1, and filled[] of clip c needs every wave past clip c only).
+  lds_ctr hand = (lds_ctr)cplc;
+  lds_ctr filled = hand, drained = hand + 2, bad = hand + 4;
+  int kclip = 0;          // LOAD 4: ordinal of the current clip within the workgroup (cur == kclip & 1)
 
 #if SYG_DEV
-  unsigned long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev;
+  unsigned long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev, tmaxw[2] = {0, 0}, tw0;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tprev)::"memory");
 #endif
 #pragma unroll 1
@@ -738,6 +790,8 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
     // 373-390 us per 1024 clips of C4; other splits no better).  MODE 0 / 3: projection, clip epilogue and slab combine at
     // the top level, the transform one level lower (150.3 against 151.0 us for the one-launch MFCC at C2).
     constexpr int PD = 1;
+    // (LOAD 4, waves that never meet: the same levels -- all equal 151.4, the transform at one constant level below
+    // projection and epilogue 148.2, against 127.7 us for these: DESIGN.md section 5.0-nm)
     SETPRIO(3 - PD);
     // The filterbank operands of this wave's slots are the same for every tile but cannot stay resident (the FFT needs
     // all 128 VGPRs): the first NPRE groups of four steps are re-fetched every tile, behind pass 3 of the transform.
@@ -759,7 +813,11 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
       // trip that nothing hides (it sat directly behind both call sites: the fixed cost of "any real row function")
       if (RELC) init_lane_const<false>(lc, lv, twid);
       apply_window(v, winl, lv);
+#if SYG_DEV
+      tw0 = tacc[0];
       TICK(0, v[0].x);
+      if (tacc[0] - tw0 > tmaxw[1]) tmaxw[1] = tacc[0] - tw0;
+#endif
       float2 xs[2][4], xm[2][4], x512;
       wave_rfft2048<PD, X2>(v, lc, sc, tw1l, tw2l, lv, xs, xm, x512 TPASS);
       if (COMPLEX_OUT) {
@@ -822,6 +880,14 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
           });
         }
       };
+      // LOAD 4: the epilogue of the workgroup's clip number k waits for all sixteen waves to be through with it; a wait
+      // that ran out, or a matrix marked bad, turns the clip's output into NaN (amin and the reference: every dB value)
+      auto epilogue_args = [&](lds_ctr fill, int k) {
+        MfccArgs a = mf;
+        const bool ok = handover_wait<3>(fill, WAVES * ((k >> 1) + 1));
+        if (!ok || handover_load(bad) != 0) { a.ref_is_max = 0; a.ref_value = a.amin = __builtin_nanf(""); }
+        return a;
+      };
       auto publish_max = [&]() {
         const float cm = wave_max(cmax);
         cmax = 0.f;
@@ -841,12 +907,17 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
       };
       const bool dct_behind = FREERUN && clip_done && !tri_defer && w < tri_ndct;   // clip_dct behind the clip barrier
       if (FREERUN && mine && !dct_behind) prefetch();
+      // LOAD 4: the matrix and red[cur][w] are this clip's once the epilogue of the clip before last has left them
+      if (NOMEET && t0 == 0 && kclip >= 2 && !handover_wait<3>(drained + cur, tri_nepi * (kclip >> 1)) && lane == 0)
+        __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       if (mine) {
         if (tri_proj) project();
       } else if (tri_defer && pend_b >= 0) {
         float* cmp = clipmel + (cur ^ 1) * (n_mels * mf.tp);
+        const MfccArgs mfe = NOMEET ? epilogue_args(filled + (cur ^ 1), kclip - 1) : mf;
         clip_dct<WAVES>((int)(uintptr_t)(lds_fptr)cmp, (int)(uintptr_t)(lds_fptr)(tri_red + (cur ^ 1) * WAVES),
-                        (int)(uintptr_t)(lds_fptr)tri_dct, mf, n_mels, (int)T, (int)pend_b, w - (WAVES - tri_idle), lane, tri_idle);
+                        (int)(uintptr_t)(lds_fptr)tri_dct, mfe, n_mels, (int)T, (int)pend_b, w - (WAVES - tri_idle), lane, tri_idle);
+        if (NOMEET) handover_add(drained + (cur ^ 1), lane);
       }
       if (FREERUN && !mine && !dct_behind) prefetch();
       // MODE 7: statistics / contrast of this wave's own row.  Out-of-line: the entry of such a function waits for every
@@ -880,7 +951,10 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
       }
       if (CLIPM && clip_done) publish_max();
       TICK(7, tdep);                   // row functions of the early half
-      if (FREERUN) {
+      if (NOMEET) {
+        // no barrier: this wave is through with the clip (the tile loop's preamble says what the counters carry)
+        if (clip_done) handover_add(filled + cur, lane);
+      } else if (FREERUN) {
         // The clip barrier, the only one of the tile loop: nothing inside a clip is shared -- a wave reads its own power
         // row, writes its own column of the clip's mel matrix and keeps its own maximum.  What hangs on this barrier:
         //   - clip c's matrix and its maxima red[cur][] (publish_max above) are complete behind it: clip_dct of clip c runs
@@ -896,7 +970,11 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                // X1: the clip's columns of this tile are written too
       }
-      TICK(8, tdep);                   // wait at X1
+#if SYG_DEV
+      tw0 = tacc[8];
+      TICK(8, tdep);                   // wait at X1 (free-running forms: at the clip hand-over)
+      if (tacc[8] - tw0 > tmaxw[0]) tmaxw[0] = tacc[8] - tw0;
+#endif
       if (LOAD == 2) {
         have = false;
         if (tile + 1 < tile_end) fetch(tile + 1);
@@ -906,10 +984,14 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
       if (CLIPM && clip_done) {
         // (clip_dct's entry waits for outstanding memory operations, so the refill is issued behind it)
         if (tri_defer) pend_b = mf.n_mfcc > 0 ? (int64_t)b : pend_b;
-        else if (w < tri_ndct)
+        else if (w < tri_ndct) {
+          const MfccArgs mfe = NOMEET ? epilogue_args(filled + cur, kclip) : mf;
           clip_dct<WAVES>((int)(uintptr_t)(lds_fptr)cmc, (int)(uintptr_t)(lds_fptr)(tri_red + cur * WAVES),
-                          (int)(uintptr_t)(lds_fptr)tri_dct, mf, n_mels, (int)T, (int)b, w, lane);
+                          (int)(uintptr_t)(lds_fptr)tri_dct, mfe, n_mels, (int)T, (int)b, w, lane);
+          if (NOMEET) handover_add(drained + cur, lane);
+        }
         cur ^= 1;
+        ++kclip;
       }
       if (dct_behind) prefetch();
       if (ROWFN && mine) {
@@ -1114,10 +1196,17 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
     // (no clip epilogue: the mel columns are in HBM)
   } else if (TRI) {
     // (deferred epilogue: the last clip's matrix is complete behind X1 of its last tile)
-    if (pend_b >= 0 && w < tri_ndct)
+    if (pend_b >= 0 && w < tri_ndct) {
+      MfccArgs mfe = mf;
+      if (NOMEET) {      // (like every other epilogue: behind the sixteen increments of its clip)
+        if (!handover_wait<-1>(filled + (cur ^ 1), WAVES * (((kclip - 1) >> 1) + 1)) || handover_load(bad) != 0) {
+          mfe.ref_is_max = 0; mfe.ref_value = mfe.amin = __builtin_nanf("");
+        }
+      }
       clip_dct<WAVES>((int)(uintptr_t)(lds_fptr)(clipmel + (cur ^ 1) * (n_mels * mf.tp)),
-                      (int)(uintptr_t)(lds_fptr)(tri_red + (cur ^ 1) * WAVES), (int)(uintptr_t)(lds_fptr)tri_dct, mf, n_mels,
+                      (int)(uintptr_t)(lds_fptr)(tri_red + (cur ^ 1) * WAVES), (int)(uintptr_t)(lds_fptr)tri_dct, mfe, n_mels,
                       (int)T, (int)pend_b, w, lane);
+    }
   } else if (CLIPM && pend_b >= 0) {
     __syncthreads();
     if (w < ((mf.n_mfcc + 15) >> 4) * (mf.tp >> 4))
@@ -1127,6 +1216,11 @@ __global__ __launch_bounds__(WAVES * 64, 4) void stft2048_kernel(
 #if SYG_DEV
   if (CLIPM && !TRI && lane < 12)
     mel_out[((int64_t)blockIdx.x * WAVES + w) * 16 + lane] = (float)tacc[lane] / (float)(tile_end - tile_begin);
+  // (the free-running forms have no statistics or mel output: the counters leave through syg_dev_set_timeline()'s buffer;
+  // words 12 / 13: the longest single wait at the clip hand-over / in front of the window multiply)
+  if (FREERUN && mel_out != nullptr && lane < 14)
+    mel_out[((int64_t)blockIdx.x * WAVES + w) * 16 + lane] =
+        lane < 12 ? (float)tacc[lane] / (float)(tile_end - tile_begin) : (float)(lane == 12 ? tmaxw[0] : tmaxw[1]);
   if (ROWFN && stats_out != nullptr && lane < 12)
     stats_out[((int64_t)blockIdx.x * WAVES + w) * 16 + lane] = (float)tacc[lane] / (float)(tile_end - tile_begin);
 #endif
@@ -1155,9 +1249,16 @@ int load_mode() {
   return (v >= 0 && v <= 2) ? v : 2;
 }
 
+#if SYG_DEV
+// timeline builds: where the free-running forms leave their per-wave counters, [workgroups][16 waves][16] floats
+// (syg_dev_set_timeline(), tools/timeline.py freerun | nomeet); null: nowhere
+float* g_dev_timeline = nullptr;
+#endif
 // Default of SYG_OPT_STFT_FREERUN = -1: on -- at C2 every run of it was faster than every run of the staged form, by several times
 // the run-to-run spread
 constexpr bool FREERUN_DEFAULT = true;
+// Default of SYG_OPT_STFT_MEET = -1 where the free-running form runs: its waves never meet (LOAD 4) -- DESIGN.md section 5.0-nm
+constexpr bool NOMEET_DEFAULT = true;
 // Where the free-running form can run (syg_stft2048_mfcc_tri_freerun): 8-byte loads of sample pairs that the descriptor's
 // range check takes or leaves as a whole (hop, L, ldy even, y 8-byte aligned), byte offsets inside a clip in 32 bits
 bool freerun_ok(int hop, int64_t L, int64_t ldy, const float* y) {
@@ -1229,7 +1330,10 @@ int launch(const LaunchArgs& a) {
   if (M.freerun && WAVES == 16) {
     const int fr = option(SYG_OPT_STFT_FREERUN);
     const bool want = fr == 1 || (fr < 0 && FREERUN_DEFAULT && option(SYG_OPT_STFT_LOAD) < 0);
-    if (want && freerun_ok(c.hop, c.L, c.ldy, c.y)) load = 3;
+    if (want && freerun_ok(c.hop, c.L, c.ldy, c.y)) {
+      const int meet = option(SYG_OPT_STFT_MEET);
+      load = (meet == 0 || (meet < 0 && NOMEET_DEFAULT)) ? 4 : 3;
+    }
   }
   if (M.clip) {       // (no stage buffer unless the tiles are staged)
     lds = lds - (load != 2 ? (size_t)LM::STAGE_FLOATS * sizeof(float) : 0) + (size_t)clip_extra;
@@ -1240,12 +1344,16 @@ int launch(const LaunchArgs& a) {
   auto kern = load == 2 ? stft2048_kernel<WAVES, 2, MODE>
                         : load == 1 ? stft2048_kernel<WAVES, 1, MODE> : stft2048_kernel<WAVES, 0, MODE>;
   if constexpr (M.freerun && WAVES == 16)
-    if (load == 3) kern = stft2048_kernel<WAVES, 3, MODE>;
+    if (load >= 3) kern = load == 4 ? stft2048_kernel<WAVES, 4, MODE> : stft2048_kernel<WAVES, 3, MODE>;
+  float* mel_out = a.mel.mel_out;
+#if SYG_DEV
+  if (load >= 3) mel_out = g_dev_timeline;      // (the free-running forms write no mel output: their counters' way out)
+#endif
   const size_t cap = M.clip ? (size_t)LDS_LIMIT : (size_t)LM::TOTAL * sizeof(float);
   if (const int rc = reserve_dynamic_lds("stft2048", (const void*)kern, cap)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(WAVES * 64), lds, a.stream, c.y, c.L, c.ldy, c.hop, pad, c.T,
                      tiles, total_tiles, per, (const float2*)c.window, (const float2*)c.twiddle, a.mel.table, a.mel.plan,
-                     n_mels, a.mel.mel_out, a.st.binhz, a.st.roll_percent, a.st.bw_p, a.st.smask, a.st.stats_out, a.st.cp,
+                     n_mels, mel_out, a.st.binhz, a.st.roll_percent, a.st.bw_p, a.st.smask, a.st.stats_out, a.st.cp,
                      a.st.contrast_out, (float2*)a.cout, dma_wide, mf);
   SYG_CHECK_LAUNCH("stft2048");
   return SYG_OK;
@@ -1353,6 +1461,9 @@ extern "C" int syg_stft2048_mfcc_tri_fits(int n_mels, int64_t T, int n_mfcc) {
   return clip_lds_fit<ModeLds<16, Mode::ClipSeg>>(clip_lds_bytes<Mode::ClipSeg>(n_mels, T, n_mfcc)) == 2;
 }
 
+#if SYG_DEV
+extern "C" void syg_dev_set_timeline(float* buf) { g_dev_timeline = buf; }
+#endif
 extern "C" int syg_stft2048_mfcc_tri_freerun(int hop, int64_t L, int64_t ldy, const float* y) {
   return freerun_ok(hop, L, ldy, y) ? 1 : 0;
 }

@@ -231,7 +231,7 @@ class _Settings:
       cqt_fused             True: the one-launch form (syg_cqt_fused_f32) where the plan has its shape; False: level by level
       one_launch_features   True: extract_features routes MFCC + statistics / contrast requests to the one-launch kernels
     Options that live in the library (syg_set_option): reserved_cus, stft_load, sos_clip, cqt_staged, dwt_form,
-    fx_delay_form, stft_freerun."""
+    fx_delay_form, stft_freerun, stft_meet."""
     waves = T.WAVES
     cqt_mode = "bf16x3"
     cqt_streams = 1
@@ -242,11 +242,11 @@ class _Settings:
 
 settings = _Settings()
 _LIB_OPTIONS = {"reserved_cus": 0, "stft_load": 1, "sos_clip": 2, "cqt_staged": 3, "dwt_form": 4, "fx_delay_form": 5,
-                "stft_freerun": 6}      # SYG_OPT_* of include/sygnals_hip.h
+                "stft_freerun": 6, "stft_meet": 7}      # SYG_OPT_* of include/sygnals_hip.h
 
 
 def set_option(name: str, value: int) -> None:
-    """syg_set_option by name (reserved_cus | stft_load | sos_clip | cqt_staged | dwt_form | fx_delay_form | stft_freerun)."""
+    """syg_set_option by name (reserved_cus | stft_load | sos_clip | cqt_staged | dwt_form | fx_delay_form | stft_freerun | stft_meet)."""
     check(lib().syg_set_option(_LIB_OPTIONS[name], int(value)), "syg_set_option")
 
 

@@ -16,6 +16,31 @@ from sygnals_amd import _tables as T
 CP = T.contrast_plan(np.fft.rfftfreq(2048, 1 / 48000), 48000)
 CP0 = np.zeros_like(CP); CP0[0] = 1; CP0[1] = CP[1]; CP0[17] = CP[17]; CP0[33] = CP[33]
 ONE = VAR.startswith("c4one")
+FREE = VAR in ("freerun", "nomeet")
+if FREE:
+    # the free-running forms of the headline launch (<16,3,6>: barrier per clip; <16,4,6>: LDS counters): no statistics or
+    # mel output, so the development build leaves the counters in a buffer of its own (syg_dev_set_timeline)
+    import ctypes as C
+    from sygnals_amd import _lib
+    tl = torch.zeros((256, 16, 16), dtype=torch.float32, device="cuda")
+    raw = C.CDLL(_lib.LIB_PATH)
+    raw.syg_dev_set_timeline.argtypes = [C.c_void_p]; raw.syg_dev_set_timeline.restype = None
+    raw.syg_dev_set_timeline(C.c_void_p(tl.data_ptr()))
+    with ops.override(stft_freerun=1, **({"stft_meet": 0 if VAR == "nomeet" else 1} if "stft_meet" in ops._LIB_OPTIONS else {})):
+        for _ in range(2):
+            ops.stft2048_mfcc(y, 48000, 512, True, "hann", 40, 13)
+    torch.cuda.synchronize()
+    d = tl.cpu().numpy()
+    names = ["load wait+window", "pass1+tw1", "exchange1", "pass2+tw2", "exch2+pass3", "split+P store", "projection/epilogue",
+             "publish max", "clip hand-over wait", "(unused)", "(unused)", "epilogue behind + prefetch issue"]
+    tot = d[:, :, :12].sum(axis=2)
+    print(f"{VAR}: cycles per tile, mean over the workgroups, per wave (s_memtime counts)")
+    print("wave " + " ".join(f"{n[:10]:>10s}" for n in names[:9] + names[11:]) + "      total  max-handover  max-loadwait")
+    for wv in range(16):
+        cols = [d[:, wv, i].mean() for i in list(range(9)) + [11]]
+        print(f"{wv:4d} " + " ".join(f"{c:10.0f}" for c in cols) + f" {tot[:, wv].mean():10.0f} {d[:, wv, 12].max():13.0f} {d[:, wv, 13].max():13.0f}")
+    print(f"all  " + " ".join(f"{d[:, :, i].mean():10.0f}" for i in list(range(9)) + [11]) + f" {tot.mean():10.0f} {d[:, :, 12].max():13.0f} {d[:, :, 13].max():13.0f}")
+    sys.exit(0)
 if ONE:
     import ctypes as C
     from sygnals_amd._lib import check, lib
