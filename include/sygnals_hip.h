@@ -1362,6 +1362,61 @@ int syg_beat_dp_f32(const float* ls, const float* lsmax, int64_t B, int64_t T, c
 int syg_beat_track_f32(const float* ls, const double* cum, const int32_t* back, int64_t B, int64_t T, const int32_t* period,
                        int trim, int32_t* beats, int32_t* count, int32_t* last, void* stream);
 
+/* -------------------------------------------------------------------------------
+ * Tonal features (chroma.hip): librosa 0.10 feature.chroma_stft / chroma_cqt / chroma_cens / tonnetz and estimate_tuning
+ * after the transforms.  Parity is unpinned (librosa is not a dependency): the float64 restatement of
+ * tests/chroma_ref.py is the contract; the host tables are made by sygnals_amd/_chroma.py.  No floating-point atomics:
+ * the same call gives the same bits and a batch equals its rows.  Every entry checks its arguments before any device work.
+ *
+ * norm: 0 none, 1 inf (max |x|), 2 L1, 3 L2, per frame over the n_chroma rows, the length in float64; a frame whose
+ * length is below FLT_MIN is left as it is (librosa.util.normalize).  has_threshold != 0: sums below `threshold` (<)
+ * become 0 before the norm.  complex != 0: x is interleaved (re, im) and |z|^power (1 or 2) is taken on load,
+ * fmaf(re, re, im * im) as syg_cabs_pow_f32 forms it (x aligned to 8 bytes); complex = 0: x is used as it is.  1 <= n_chroma <= SYG_CHROMA_NC_MAX.
+ *
+ * syg_chroma_fold_rows_f32: x [B, T, F(, 2)] contiguous (frame-major, as the STFT entries leave it), tab [n_chroma, F]
+ *   -> out [B, n_chroma, T] contiguous.  A wave a frame, the lanes along the bins, float32 sums k = lane, lane + 64, ...
+ *   then a butterfly; the table is staged in LDS where it fits SYG_CHROMA_TABLE_LDS_MAX bytes beside the tile's sums.
+ * syg_chroma_fold_bins_f32: x [B, K, T(, 2)], unit stride along T, strides sxb / sxk in floats (even for complex input);
+ *   wt [K, n_chroma] (the weights of one bin side by side) -> out [B, n_chroma, T].  A lane a frame, k ascending.
+ *   P > 0: after the norm the frame is L1-normalised and out [B, P, T] = phi [P, n_chroma] times it (tonnetz: P = 6),
+ *   P <= SYG_CHROMA_P_MAX.  At most 65535 clips a call.
+ * syg_chroma_cens_f32: x [B, n_chroma, T] (strides in floats) -> out [B, n_chroma, T] contiguous: the L1 norm per frame,
+ *   q = 0.25 (count of steps 0.4 / 0.2 / 0.1 / 0.05 below the value), out[c, t] = sum_j win[j] q[c, t - left + j] (zeros
+ *   beyond the row, j ascending; win [n_win] <= SYG_CHROMA_CENS_WIN_MAX taps as scipy.ndimage.convolve applies them),
+ *   then the norm `norm` (librosa: 3, L2).  n_win = 1, win = {1}: no smoothing.  SYG_CHROMA_CENS_TILE frames a workgroup, any T.
+ * syg_tuning_hist_f32: x = S [B, T, F(, 2)], F = 1 + n_fft / 2.  The peaks of librosa.piptrack: with ref = threshold
+ *   max_k S and x = S where S > ref, else 0, bin k in [k_lo, k_hi) is a peak where x[k] > x[k - 1] and x[k] >= x[k + 1]
+ *   (edges repeated); a = S[k + 1] + S[k - 1] - 2 S[k], b = (S[k + 1] - S[k - 1]) / 2, shift = -b / a where |b| < |a| (0 at
+ *   the last bin), pitch = (k + shift) sr / n_fft, mag = S[k] + 0.5 b shift, all float64 from the float32 S.
+ *   counts != NULL: per clip th = the exact median of mag (the mean of the two middle values of an even count; radix
+ *   selection over the bit patterns), r = frac(bins_per_octave log2(pitch / 27.5)) moved into [-0.5, 0.5), and
+ *   counts [B, n_bins] int32 = the peaks with mag >= th by edges[i] <= r < edges[i + 1] (edges: device float64
+ *   [n_bins + 1]); n_peaks [B] int32 = all peaks of the clip.  Needs `work` of syg_tuning_hist_work_bytes(B, T, k_lo, k_hi)
+ *   bytes, 8-byte aligned.  pitch_out / mag_out (both or neither) [B, T, F] float32: piptrack's dense pair.
+ * ------------------------------------------------------------------------------- */
+enum {
+  SYG_CHROMA_NC_MAX = 0,         /* largest n_chroma */
+  SYG_CHROMA_ROW_TILE = 1,       /* frames of a wave's tile of syg_chroma_fold_rows_f32 */
+  SYG_CHROMA_TABLE_LDS_MAX = 2,  /* LDS bytes up to which syg_chroma_fold_rows_f32 stages its table */
+  SYG_CHROMA_P_MAX = 3,          /* rows of the output transform, at most */
+  SYG_CHROMA_CENS_TILE = 4,      /* frames of a CENS workgroup */
+  SYG_CHROMA_CENS_WIN_MAX = 5,   /* taps of the CENS window, at most */
+  SYG_CHROMA_HIST_BINS_MAX = 6,  /* bins of the tuning histogram, at most */
+  SYG_CHROMA_MAX_ELEMS = 7       /* elements of an input, at most */
+};
+int64_t syg_chroma_constants(int key);
+int syg_chroma_fold_rows_f32(const float* x, int64_t B, int64_t T, int F, int complex_in, int power, const float* tab, int n_chroma,
+                             int has_threshold, float threshold, int norm, float* out, void* stream);
+int syg_chroma_fold_bins_f32(const float* x, int64_t B, int64_t K, int64_t T, int64_t sxb, int64_t sxk, int complex_in, int power,
+                             const float* wt, int n_chroma, int has_threshold, float threshold, int norm, const float* phi, int P,
+                             float* out, void* stream);
+int syg_chroma_cens_f32(const float* x, int64_t B, int n_chroma, int64_t T, int64_t sxb, int64_t sxk, const float* win, int n_win,
+                        int left, int norm, float* out, void* stream);
+int64_t syg_tuning_hist_work_bytes(int64_t B, int64_t T, int k_lo, int k_hi);
+int syg_tuning_hist_f32(const float* x, int64_t B, int64_t T, int F, int complex_in, int power, double sr, int n_fft, int k_lo,
+                        int k_hi, double threshold, double bins_per_octave, const double* edges, int n_bins, int32_t* counts,
+                        int32_t* n_peaks, float* pitch_out, float* mag_out, void* work, int64_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

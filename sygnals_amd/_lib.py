@@ -200,6 +200,12 @@ SIGNATURES = {
     "syg_beat_local_score_f32": (_i, [_p, _l, _l, _l, _p, _p, _p, _p, _p]),
     "syg_beat_dp_f32": (_i, [_p, _p, _l, _l, _p, _i, _d, _p, _p, _p, _p]),
     "syg_beat_track_f32": (_i, [_p, _p, _p, _l, _l, _p, _i, _p, _p, _p, _p]),
+    "syg_chroma_constants": (_l, [_i]),
+    "syg_chroma_fold_rows_f32": (_i, [_p, _l, _l, _i, _i, _i, _p, _i, _i, _f, _i, _p, _p]),
+    "syg_chroma_fold_bins_f32": (_i, [_p, _l, _l, _l, _l, _l, _i, _i, _p, _i, _i, _f, _i, _p, _i, _p, _p]),
+    "syg_chroma_cens_f32": (_i, [_p, _l, _i, _l, _l, _l, _p, _i, _i, _i, _p, _p]),
+    "syg_tuning_hist_work_bytes": (_l, [_l, _l, _i, _i]),
+    "syg_tuning_hist_f32": (_i, [_p, _l, _l, _i, _i, _i, _d, _i, _i, _i, _d, _d, _p, _i, _p, _p, _p, _p, _p, _l, _p]),
 }
 
 _lib = None

@@ -140,6 +140,60 @@ def features_post(input_file, output, cmvn, cmvn_window, no_variance, deltas, wi
     click.echo(f"Post-processed {len(names)} feature rows x {T} frames into {len(out_names)} rows, saved to '{Path(output).name}'.")
 
 
+@features_cmd.command("chroma")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False, resolve_path=True))
+@click.option("-o", "--output", type=click.Path(resolve_path=True), required=True,
+              help="Output file path (.npz: time, the matrix and tuning; any other suffix: a table time, chroma_0 ...).")
+@click.option("--kind", type=click.Choice(["stft", "cqt", "cens", "tonnetz"]), default="stft", show_default=True,
+              help="chroma_stft, chroma_cqt, chroma_cens or tonnetz.")
+@click.option("--tuning", default="auto", show_default=True, help="Deviation from A440 in fractions of a bin, or auto (estimated).")
+@click.option("--hop-length", type=int, default=512, show_default=True, help="Hop length between frames (samples).")
+@click.option("--norm", type=click.Choice(["inf", "1", "2", "none"]), default=None,
+              help="Per-frame norm (default: inf; 2 for cens; tonnetz: the norm of its chroma).")
+def features_chroma(input_file, output, kind, tuning, hop_length, norm):
+    """Chroma (STFT, CQT, CENS) or tonnetz features of an audio signal."""
+    from ..core.features import tonal as TN
+    if tuning.strip().lower() == "auto":
+        tun = None
+    else:
+        try:
+            tun = float(tuning)
+        except ValueError:
+            raise click.UsageError(f"--tuning: cannot read '{tuning}' as a number (write e.g. 0.12, or auto).")
+    if hop_length < 1:
+        raise click.UsageError("--hop-length must be at least 1.")
+    nrm = {None: 2 if kind == "cens" else np.inf, "inf": np.inf, "1": 1, "2": 2, "none": None}[norm]
+    res = sio.read_data(Path(input_file))
+    if not isinstance(res, tuple) or len(res) != 2 or not res[1]:
+        raise click.UsageError(f"Input file '{Path(input_file).name}' is not recognized as audio.")
+    signal, sr = res
+    if signal.ndim != 1:
+        signal = np.mean(signal, axis=0)
+    try:
+        y = signal[None, :]
+        if kind == "stft":
+            m, t = TN.chroma_stft_batch(y, sr, norm=nrm, hop_length=hop_length, tuning=tun, return_tuning=True)
+        elif kind == "cqt":
+            m, t = TN.chroma_cqt_batch(y, sr, hop_length=hop_length, norm=nrm, tuning=tun, return_tuning=True)
+        elif kind == "cens":
+            m, t = TN.chroma_cens_batch(y, sr, hop_length=hop_length, norm=nrm, tuning=tun, return_tuning=True)
+        else:
+            m, t = TN.tonnetz_batch(y, sr, hop_length=hop_length, norm=nrm, tuning=tun, return_tuning=True)
+        tun = float(t[0])                            # the estimate where --tuning is auto
+        m = m[0].cpu().numpy()
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    name = "tonnetz" if kind == "tonnetz" else "chroma"
+    time = np.arange(m.shape[1]) * hop_length / float(sr)
+    if Path(output).suffix.lower() == ".npz":
+        sio.save_data({"time": time, name: m, "tuning": np.array(tun)}, Path(output))
+    else:
+        table = {"time": time}
+        table.update({f"{name}_{i}": m[i] for i in range(m.shape[0])})
+        sio.save_data(pd.DataFrame(table), Path(output))
+    click.echo(f"{name} ({kind}: {m.shape[0]} rows x {m.shape[1]} frames, tuning {tun:+.2f}) saved to '{Path(output).name}'.")
+
+
 # ---------------------------------------------------------------- dsp
 @click.group("dsp")
 def dsp_cmd():
@@ -304,9 +358,10 @@ DTW_FRAME, DTW_HOP, DTW_MFCC = 2048, 512, 13
 @click.option("--metric", type=click.Choice(["euclidean", "sqeuclidean", "cityblock", "cosine"]), default="euclidean",
               show_default=True)
 @click.option("--subseq", is_flag=True, help="Align the first input to a part of the second.")
-@click.option("--on", "on", type=click.Choice(["mfcc", "samples"]), default=None,
-              help="What is aligned: the MFCC sequences (13 coefficients, frame 2048, hop 512; the default for audio) or the "
-                   "raw samples (the default for CSV / NPZ series).")
+@click.option("--on", "on", type=click.Choice(["mfcc", "chroma", "samples"]), default=None,
+              help="What is aligned: the MFCC sequences (13 coefficients, frame 2048, hop 512; the default for audio), the "
+                   "chroma sequences (chroma_cqt, hop 512, tuning estimated per input) or the raw samples (the default for "
+                   "CSV / NPZ series).")
 def dsp_dtw(input_file_1, input_file_2, output, metric, subseq, on):
     """Align two signals by dynamic time warping (librosa.sequence.dtw's default steps)."""
     from .. import ops
@@ -317,14 +372,18 @@ def dsp_dtw(input_file_1, input_file_2, output, metric, subseq, on):
         on = "mfcc" if (sr_x and sr_y) else "samples"
     hop = 1
     try:
-        if on == "mfcc":
+        if on in ("mfcc", "chroma"):
             if not sr_x or not sr_y:
-                raise click.UsageError("--on mfcc needs inputs that carry a sampling rate (audio); use --on samples for a series.")
+                raise click.UsageError(f"--on {on} needs inputs that carry a sampling rate (audio); use --on samples for a series.")
             if sr_x != sr_y:
                 raise click.UsageError(f"The inputs have different sampling rates ({sr_x} Hz and {sr_y} Hz): bring them to one "
                                        "rate with `dsp resample` first.")
             hop = DTW_HOP
-            X, Y = (ops.mfcc_batch(ops.to_device_f32(v[None, :]), sr_x, DTW_FRAME, DTW_HOP, n_mfcc=DTW_MFCC)[0] for v in (x, y))
+            if on == "chroma":
+                from ..core.features.tonal import chroma_cqt_batch
+                X, Y = (chroma_cqt_batch(ops.to_device_f32(v[None, :]), sr_x, hop_length=DTW_HOP)[0] for v in (x, y))
+            else:
+                X, Y = (ops.mfcc_batch(ops.to_device_f32(v[None, :]), sr_x, DTW_FRAME, DTW_HOP, n_mfcc=DTW_MFCC)[0] for v in (x, y))
         else:
             X, Y = x, y
         D, wp = dtw(X, Y, metric=metric, subseq=subseq)

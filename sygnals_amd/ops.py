@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _cepstrum as CP
+from . import _chroma as CH
 from . import _cwt as CW
 from . import _dynamics as DY
 from . import _laplace as LP
@@ -143,7 +144,7 @@ def _out(out, shape, x: torch.Tensor, what: str = "out", dtype=torch.float32, co
 _SILENT_SIZERS = frozenset(("syg_pack_rows_work_bytes", "syg_welch_work_bytes", "syg_csd_work_bytes",
                             "syg_onset_strength_work_bytes", "syg_dwt_work_bytes", "syg_dynamics_work_bytes",
                             "syg_spec_augment_work_bytes", "syg_tempogram_work_bytes", "syg_tempo_pick_work_bytes",
-                            "syg_beat_local_score_work_bytes"))
+                            "syg_beat_local_score_work_bytes", "syg_tuning_hist_work_bytes"))
 
 
 def _work_bytes(entry: str, *args, error: Optional[Exception] = None) -> int:
@@ -3575,3 +3576,219 @@ def beat_track(ls: torch.Tensor, cum: torch.Tensor, back: torch.Tensor, period, 
     _call("syg_beat_track_f32", _ptr(ls), _ptr(cum), _ptr(back), B, Tn, _ptr(pd), int(bool(trim)), _ptr(beats), _ptr(count),
           _ptr(last))
     return beats, count, last
+
+
+# ------------------------------------------------------------------ tonal: chroma folds, CENS, tonnetz, tuning
+_CHROMA_KEYS = ("nc_max", "row_tile", "table_lds_max", "p_max", "cens_tile", "cens_win_max", "hist_bins_max",
+                "max_elems")                       # SYG_CHROMA_* of include/sygnals_hip.h
+
+
+def chroma_constants() -> dict:
+    """The figures the tonal kernels rest on (the library owns them): the largest n_chroma, the frames of a wave's tile of
+    the frame-major fold, the LDS up to which that fold stages its table, the rows of the output transform, the frames of a
+    CENS workgroup, the taps of its window, the bins of the tuning histogram, the most elements of an input."""
+    return _constants("syg_chroma_constants", _CHROMA_KEYS)
+
+
+class ChromaTable:
+    """A fold table [n_chroma, cols] held on the device in both orientations, each made once: what a caller that folds with
+    the same table again and again (core.features.tonal) hands to chroma_fold, so that no call hashes or transposes it."""
+
+    def __init__(self, table: np.ndarray):
+        a = np.ascontiguousarray(table, dtype=np.float32)
+        if a.ndim != 2 or min(a.shape) < 1:
+            raise ValueError("ChromaTable: the table must be a 2-D array [n_chroma, cols]")
+        self.shape = tuple(a.shape)
+        self._host, self._dev = a, {}
+
+    def dev(self, transpose: bool) -> torch.Tensor:
+        k = (torch.cuda.current_device(), bool(transpose))
+        if k not in self._dev:
+            self._dev[k] = _dev(self._host.T if transpose else self._host)
+        return self._dev[k]
+
+
+def _chroma_table(table, rows: Optional[int], who: str, what: str = "table", transpose: bool = False) -> torch.Tensor:
+    """A float32 device table [n, cols] from a ChromaTable, a host array (cached by content: the whole array is hashed at
+    every call) or a device tensor (transposed by a copy at every call); transpose: [cols, n]."""
+    if isinstance(table, ChromaTable):
+        require_gpu()
+        return table.dev(transpose)
+    if isinstance(table, torch.Tensor):
+        _f32(table, f"{who}: {what}", 2)
+        if rows is not None and table.shape[0] != rows:
+            raise ValueError(f"{who}: {what} must have {rows} rows (got {table.shape[0]})")
+        _on_device(table, f"{who}: {what}")
+        return (table.t() if transpose else table).contiguous()
+    a = np.ascontiguousarray(table, dtype=np.float32)
+    if a.ndim != 2 or min(a.shape) < 1 or (rows is not None and a.shape[0] != rows):
+        raise ValueError(f"{who}: {what} must be a 2-D float32 array" + (f" of {rows} rows" if rows is not None else ""))
+    return _cached(("chroma_tab", a.shape, a.tobytes(), transpose), lambda: _dev(a.T if transpose else a), limit=32)
+
+
+def _chroma_spec(x, who: str, axes: str):
+    """(x, complex) of a real [B, *, *] or interleaved complex [B, *, *, 2] float32 spectrogram, judged without a device."""
+    if isinstance(x, torch.Tensor) and x.dim() == 4:
+        _f32(x, f"{who}: x", 4, (2,), axes=axes)
+        cplx = True
+    else:
+        _f32(x, f"{who}: x", 3, axes=axes)
+        cplx = False
+    if min(x.shape) < 1:
+        raise ValueError(f"{who}: empty input (shape {list(x.shape)})")
+    if x.numel() // (2 if cplx else 1) > CH.MAX_ELEMS:
+        raise ValueError(f"{who}: an input of more than 2^31 elements; call it on fewer rows")
+    return x, cplx
+
+
+def _chroma_power(power, who: str) -> int:
+    if power not in (1, 2) or isinstance(power, bool):
+        raise ValueError(f"{who}: power must be 1 (magnitude) or 2 (power) of a complex input (got {power!r})")
+    return int(power)
+
+
+def chroma_fold(x: torch.Tensor, table, layout: str = "rows", power: int = 2, threshold=None, norm=np.inf, transform=None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The chroma fold with librosa's threshold and per-frame normalisation -> [B, n_chroma, T] float32 on the device.
+    layout "rows" (syg_chroma_fold_rows_f32): x frame-major [B, T, F] real or [B, T, F, 2] complex (as stft_any leaves it),
+    table [n_chroma, F]; layout "bins" (syg_chroma_fold_bins_f32): x bin-major [B, K, T] real or [B, K, T, 2] complex (as
+    cqt leaves it; rows may be strided over B and K), table [n_chroma, K].  A complex input gives |x|^power (1 or 2) on
+    load.  threshold: sums below it become 0 (None: none); norm: inf, 1, 2 or None.  transform [P, n_chroma] (bins only):
+    the result is transform @ the L1-normalised frame, [B, P, T] (tonnetz).  float32 sums in a fixed order: a batch equals
+    its rows and a call repeats its bits."""
+    who = "chroma_fold"
+    if layout not in ("rows", "bins"):
+        raise ValueError(f"{who}: layout must be 'rows' or 'bins' (got {layout!r})")
+    pw = _chroma_power(power, who)
+    has_thr, thr = CH.check_threshold(threshold, who)
+    nrm = CH.check_norm(norm, who)
+    if transform is not None and layout != "bins":
+        raise ValueError(f"{who}: transform= is served by layout 'bins' alone")
+    x, cplx = _chroma_spec(x, who, "[B, T, F(, 2)]" if layout == "rows" else "[B, K, T(, 2)]")
+    cols = int(x.shape[2] if layout == "rows" else x.shape[1])
+    tshape = tuple(table.shape) if hasattr(table, "shape") else np.shape(table)
+    if len(tshape) != 2 or tshape[1] != cols:
+        raise ValueError(f"{who}: table must be [n_chroma, {cols}] for this input (got {list(tshape)})")
+    nc = CH.check_n_chroma(int(tshape[0]), who)
+    P = 0
+    if transform is not None:
+        pshape = tuple(transform.shape) if hasattr(transform, "shape") else np.shape(transform)
+        if len(pshape) != 2 or pshape[1] != nc or not 1 <= pshape[0] <= 8:
+            raise ValueError(f"{who}: transform must be [P, {nc}] with 1 <= P <= 8 (got {list(pshape)})")
+        P = int(pshape[0])
+    B = int(x.shape[0])
+    _on_device(x, f"{who}: x")
+    if cplx and x.data_ptr() % 8:
+        x = x.clone(memory_format=torch.contiguous_format)           # the kernels load (re, im) as one 8-byte word
+    if layout == "rows":
+        x = x.contiguous()
+        Tn = int(x.shape[1])
+        out = _out(out, (B, nc, Tn), x, f"{who}: out", contiguous=True)
+        tab = _chroma_table(table, nc, who)
+        _call("syg_chroma_fold_rows_f32", _ptr(x), B, Tn, cols, int(cplx), pw, _ptr(tab), nc, has_thr, thr, nrm, _ptr(out))
+        return out
+    if x.stride(-1) != 1 or (cplx and x.stride(2) != 2) or (not cplx and x.shape[2] > 1 and x.stride(2) != 1):
+        x = x.contiguous()
+    Tn = int(x.shape[2])
+    w = 2 * Tn if cplx else Tn
+    sxk = int(x.stride(1)) if cols > 1 else w
+    sxb = int(x.stride(0)) if B > 1 else (cols - 1) * sxk + w
+    if sxk < w or sxb < (cols - 1) * sxk + w or (cplx and (sxk % 2 or sxb % 2)):
+        x = x.contiguous()
+        sxk, sxb = w, cols * w
+    out = _out(out, (B, P or nc, Tn), x, f"{who}: out", contiguous=True)
+    wt = _chroma_table(table, nc, who, transpose=True)
+    phi = _chroma_table(transform, P, who, "transform") if P else None
+    for b0, bc in _row_blocks(B):
+        _call("syg_chroma_fold_bins_f32", _ptr(x[b0:b0 + bc]), bc, cols, Tn, sxb, sxk, int(cplx), pw, _ptr(wt), nc, has_thr, thr,
+              nrm, _ptr(phi), P, _ptr(out[b0:b0 + bc]))
+    return out
+
+
+def chroma_cens(chroma: torch.Tensor, win_len_smooth=41, smoothing_window="hann", norm=2,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The CENS steps after the fold (syg_chroma_cens_f32) of an unnormalised chroma [B, n_chroma, T]: the L1 norm per frame,
+    the quantiser (0.25 per step 0.4 / 0.2 / 0.1 / 0.05 below the value), the smoothing along T with
+    get_window(smoothing_window, win_len_smooth + 2, fftbins=False) / its sum (zeros beyond the row; None: none), the
+    closing norm (librosa: 2).  Rows may be strided over B and n_chroma; `out` is contiguous."""
+    who = "chroma_cens"
+    wl = CH.check_win_len_smooth(win_len_smooth, who)
+    nrm = CH.check_norm(norm, who)
+    x = _dyn_in(chroma, who)
+    B, nc, Tn = x.shape
+    CH.check_n_chroma(nc, who)
+    if B * nc * Tn > CH.MAX_ELEMS:
+        raise ValueError(f"{who}: an input of more than 2^31 elements; call it on fewer rows")
+    taps, left = CH.cens_window(wl, smoothing_window)
+    _on_device(x, f"{who}: chroma")
+    out = _out(out, (B, nc, Tn), x, f"{who}: out", contiguous=True)
+    wkey = smoothing_window if isinstance(smoothing_window, (str, tuple)) else ("arr", np.asarray(smoothing_window).tobytes())
+    wdev = _cached(("cens_win", wl, wkey), lambda: _dev(taps), limit=16)
+    sxb, sxk = _dyn_strides(x)
+    _call("syg_chroma_cens_f32", _ptr(x), B, nc, Tn, sxb, sxk, _ptr(wdev), len(taps), left, nrm, _ptr(out))
+    return out
+
+
+def _tuning_in(S, sr, n_fft, power, fmin, fmax, threshold, who: str):
+    n_fft = CH.check_n_fft(n_fft, who)
+    pw = _chroma_power(power, who)
+    thr = CH.check_pip(threshold, None, who)
+    k_lo, k_hi = CH.pip_bins(sr, n_fft, fmin, fmax)
+    S, cplx = _chroma_spec(S, who, "[B, T, F(, 2)]")
+    if S.shape[2] != 1 + n_fft // 2:
+        raise ValueError(f"{who}: S has {S.shape[2]} bins, not 1 + n_fft // 2 = {1 + n_fft // 2}")
+    _on_device(S, f"{who}: S")
+    S = S.contiguous()
+    if cplx and S.data_ptr() % 8:
+        S = S.clone()                                                # (re, im) is loaded as one 8-byte word
+    return S, cplx, n_fft, pw, thr, k_lo, k_hi
+
+
+def tuning_hist(S: torch.Tensor, sr: float = 22050, n_fft: int = 2048, power: int = 1, fmin: float = 150.0, fmax: float = 4000.0,
+                threshold: float = 0.1, resolution: float = 0.01, bins_per_octave: int = 12, out=None):
+    """estimate_tuning's histogram per clip (syg_tuning_hist_f32) of S frame-major [B, T, F] real, or [B, T, F, 2] complex with
+    |S|^power taken on load -> (counts [B, ceil(1 / resolution)] int32, n_peaks [B] int32): piptrack's peaks in float64 from the
+    float32 S, the exact median of their magnitudes, the residuals of those at or above it counted by
+    _chroma.tuning_bins(resolution).  out: (counts, n_peaks)."""
+    who = "tuning_hist"
+    nb = CH.check_resolution(resolution, who)
+    if not (isinstance(bins_per_octave, (int, np.integer)) and bins_per_octave >= 1):
+        raise ValueError(f"{who}: bins_per_octave must be a positive integer")
+    S, cplx, n_fft, pw, thr, k_lo, k_hi = _tuning_in(S, sr, n_fft, power, fmin, fmax, threshold, who)
+    B, Tn, F = (int(v) for v in S.shape[:3])
+    counts = _out(out[0] if out else None, (B, nb), S, f"{who}: out[0]", torch.int32, contiguous=True)
+    npk = _out(out[1] if out else None, (B,), S, f"{who}: out[1]", torch.int32, contiguous=True)
+    edges = _cached(("tuning_bins", nb), lambda: _dev(CH.tuning_bins(resolution)))
+    work = _workspace("syg_tuning_hist_work_bytes", B, Tn, k_lo, k_hi, dtype=torch.float64, device=S.device)
+    _call("syg_tuning_hist_f32", _ptr(S), B, Tn, F, int(cplx), pw, float(sr), n_fft, k_lo, k_hi, thr, float(bins_per_octave),
+          _ptr(edges), nb, _ptr(counts), _ptr(npk), None, None, _ptr(work), _nbytes(work))
+    return counts, npk
+
+
+def piptrack(S: torch.Tensor, sr: float = 22050, n_fft: int = 2048, power: int = 1, fmin: float = 150.0, fmax: float = 4000.0,
+             threshold: float = 0.1, out=None):
+    """librosa.piptrack of S frame-major [B, T, F] (or complex [B, T, F, 2], |S|^power on load) -> (pitches, magnitudes)
+    float32 [B, T, F], zero away from the peaks (syg_tuning_hist_f32 without the histogram)."""
+    who = "piptrack"
+    S, cplx, n_fft, pw, thr, k_lo, k_hi = _tuning_in(S, sr, n_fft, power, fmin, fmax, threshold, who)
+    B, Tn, F = (int(v) for v in S.shape[:3])
+    pitch = _out(out[0] if out else None, (B, Tn, F), S, f"{who}: out[0]", contiguous=True)
+    mag = _out(out[1] if out else None, (B, Tn, F), S, f"{who}: out[1]", contiguous=True)
+    _call("syg_tuning_hist_f32", _ptr(S), B, Tn, F, int(cplx), pw, float(sr), n_fft, k_lo, k_hi, thr, 12.0, None, 0, None, None,
+          _ptr(pitch), _ptr(mag), None, 0)
+    return pitch, mag
+
+
+def estimate_tuning(S: torch.Tensor, sr: float = 22050, n_fft: int = 2048, power: int = 1, resolution: float = 0.01,
+                    bins_per_octave: int = 12, fmin: float = 150.0, fmax: float = 4000.0, threshold: float = 0.1) -> np.ndarray:
+    """librosa.estimate_tuning of every clip of S (as tuning_hist takes it) -> float64 [B] on the host: the left edge of the
+    first fullest bin of tuning_hist's counts, in fractions of a bin; a clip without a peak gives 0.0 under librosa's
+    warning."""
+    import warnings
+    counts, npk = tuning_hist(S, sr, n_fft, power, fmin, fmax, threshold, resolution, bins_per_octave)
+    edges = CH.tuning_bins(resolution)
+    k = np.argmax(counts.cpu().numpy(), axis=1)                      # the first fullest bin
+    n = npk.cpu().numpy()
+    if (n == 0).any():
+        warnings.warn("Trying to estimate tuning from empty frequency set.", stacklevel=2)
+    return np.where(n == 0, 0.0, edges[k])

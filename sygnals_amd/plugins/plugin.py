@@ -86,6 +86,8 @@ class SygnalsAmdPlugin(_Base):
         from ..core import transforms as TR
         from ..core.features import cepstral as CF
         from ..core.features import dynamics as DN
+        from ..core.features import tonal as TN
+        registry.add_transform("estimate_tuning", TN.estimate_tuning)
         for fn in (D.compute_fft, D.compute_ifft, D.compute_stft, D.compute_cqt, D.compute_psd_welch, D.apply_window,
                    D.apply_convolution, D.compute_correlation, D.compute_autocorrelation, D.compute_psd_periodogram,
                    D.amplitude_envelope, D.resample, D.real_cepstrum, D.complex_cepstrum,
@@ -107,6 +109,9 @@ class SygnalsAmdPlugin(_Base):
         registry.add_feature("rms_energy", af.rms_energy)
         registry.add_feature("spectral_contrast", fd.spectral_contrast)
         registry.add_feature("mfcc", cepstral.mfcc)
+        from ..core.features import tonal
+        for fn in (tonal.chroma_stft, tonal.chroma_cqt, tonal.chroma_cens, tonal.tonnetz):
+            registry.add_feature(fn.__name__, fn)
         registry.add_feature("extract_features", manager.extract_features)
         registry.add_feature("extract_features_batch", manager.extract_features_batch)
 
