@@ -1417,6 +1417,50 @@ int syg_tuning_hist_f32(const float* x, int64_t B, int64_t T, int F, int complex
                         int k_hi, double threshold, double bins_per_octave, const double* edges, int n_bins, int32_t* counts,
                         int32_t* n_peaks, float* pitch_out, float* mag_out, void* work, int64_t work_bytes, void* stream);
 
+/* -------------------------------------------------------------------------------
+ * Per-channel energy normalisation (pcen.hip): librosa 0.10's pcen of x [B, M, T] float32 >= 0, unit stride along T,
+ * strides sxb / sxk (in floats, non-negative) over B and M; out strided the same way (sok >= T).  The float64
+ * restatement tests/pcen_ref.py is the contract.  Per row (b, m), with S = scale x:
+ *   ref    = S, or for max_size > 1 scipy.ndimage.maximum_filter1d(S, max_size, axis = bands) (mode reflect, origin 0:
+ *            bands m - max_size / 2 ... m - max_size / 2 + max_size - 1)
+ *   y      = scipy.signal.lfilter([b], [1, b - 1], ref, zi = z):  y[0] = b ref[0] + z,  y[t] = y[t-1] + b (ref[t] - y[t-1]),
+ *            closing state (1 - b) y[T-1]; the state is float64.  zi [B, M] float64 (NULL: 1 - b, lfilter_zi's value,
+ *            not scaled by the first frame); zf [B, M] float64 (NULL: not wanted).
+ *   smooth = exp(-gain log(eps + y))
+ *   out    = log1p(S smooth) where power = 0; exp(power (log S + log smooth)) where bias = 0 (0 at S = 0); otherwise
+ *            bias^power expm1(power log1p(S smooth / bias)); float32.
+ * Parameters: the scalars gain, bias, power >= 0, eps > 0, 0 < b <= 1, or with tab != NULL a device table [M]
+ * [SYG_PCEN_TABLE_WORDS] of float64 per band: b, (1 - b)^SYG_PCEN_TILE, eps, gain, power, bias, bias^power, the case
+ * (0 general, 1 power = 0, 2 bias = 0); the scalars are then ignored and the table's values are its maker's to check
+ * (sygnals_amd/_pcen.py).
+ * form 0: the rule (syg_pcen_form: 0 resident, 1 tiled; -1 for arguments it does not serve), 1 resident, 2 tiled.
+ *   Resident: a workgroup holds up to SYG_PCEN_BANDS bands of a clip and the max_size - 1 halo bands in LDS (at most
+ *   SYG_PCEN_LDS_MAX bytes: fewer bands where rows are long), a lane a row; the rule takes it for T <= SYG_PCEN_RESIDENT_T
+ *   while a band fits.  Tiled: a wave takes SYG_PCEN_TILE frames of a row; with more than one tile a row a first launch
+ *   writes every tile's closing state from rest to work (syg_pcen_work_bytes(B, M, T) bytes, 0 for one tile) and the
+ *   second folds them in index order in float64.  No atomics: a call repeats its bits, a batch equals its rows.
+ * Rejected before any device work: null x / out, an empty axis, bad strides, a result above 2^31 elements, a scalar
+ * outside its range, max_size outside [1, M], a scale that is not positive and finite, an unknown form, an out that
+ * overlaps x (out = x itself is served with max_size = 1), a resident row that does not fit, a missing workspace.
+ * ------------------------------------------------------------------------------- */
+enum {
+  SYG_PCEN_TILE = 0,         /* frames of a tile of the tiled form */
+  SYG_PCEN_BANDS = 1,        /* bands of a resident workgroup, at most */
+  SYG_PCEN_RESIDENT_T = 2,   /* the rule: longest resident row */
+  SYG_PCEN_LDS_MAX = 3,      /* LDS bytes of a workgroup, at most: two workgroups a CU */
+  SYG_PCEN_GRID_MAX = 4,     /* workgroups of a launch, at most */
+  SYG_PCEN_UNITS = 5,        /* tiles (waves) of a workgroup of the tiled form */
+  SYG_PCEN_MAX_OUT = 6,      /* elements of a result, at most */
+  SYG_PCEN_TABLE_WORDS = 7   /* float64 words of a band in tab */
+};
+int64_t syg_pcen_constants(int key);
+int syg_pcen_form(int64_t T, int64_t M, int64_t max_size);
+int64_t syg_pcen_work_bytes(int64_t B, int64_t M, int64_t T);
+int syg_pcen_f32(const float* x, int64_t B, int64_t M, int64_t T, int64_t sxb, int64_t sxk, float* out, int64_t sob,
+                 int64_t sok, double gain, double bias, double power, double eps, double b, const double* tab,
+                 int64_t max_size, double scale, const double* zi, double* zf, int form, void* work, int64_t work_bytes,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

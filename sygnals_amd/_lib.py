@@ -206,6 +206,10 @@ SIGNATURES = {
     "syg_chroma_cens_f32": (_i, [_p, _l, _i, _l, _l, _l, _p, _i, _i, _i, _p, _p]),
     "syg_tuning_hist_work_bytes": (_l, [_l, _l, _i, _i]),
     "syg_tuning_hist_f32": (_i, [_p, _l, _l, _i, _i, _i, _d, _i, _i, _i, _d, _d, _p, _i, _p, _p, _p, _p, _p, _l, _p]),
+    "syg_pcen_constants": (_l, [_i]),
+    "syg_pcen_form": (_i, [_l, _l, _l]),
+    "syg_pcen_work_bytes": (_l, [_l, _l, _l]),
+    "syg_pcen_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _l, _d, _d, _d, _d, _d, _p, _l, _d, _p, _p, _i, _p, _l, _p]),
 }
 
 _lib = None

@@ -194,6 +194,59 @@ def features_chroma(input_file, output, kind, tuning, hop_length, norm):
     click.echo(f"{name} ({kind}: {m.shape[0]} rows x {m.shape[1]} frames, tuning {tun:+.2f}) saved to '{Path(output).name}'.")
 
 
+@features_cmd.command("pcen")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False, resolve_path=True))
+@click.option("-o", "--output", type=click.Path(resolve_path=True), required=True,
+              help="Output file path (.npz: time and the matrix; any other suffix: a table time, pcen_0 ...).")
+@click.option("--n-mels", type=int, default=128, show_default=True, help="Mel bands.")
+@click.option("--n-fft", type=int, default=2048, show_default=True, help="Analysis frame length (samples).")
+@click.option("--hop-length", type=int, default=512, show_default=True, help="Hop length between frames (samples).")
+@click.option("--gain", type=float, default=0.98, show_default=True, help="Gain of the smoother (alpha), non-negative.")
+@click.option("--bias", type=float, default=2.0, show_default=True, help="Bias (delta), non-negative.")
+@click.option("--power", type=float, default=0.5, show_default=True, help="Compression exponent (r), non-negative.")
+@click.option("--time-constant", type=float, default=0.4, show_default=True, help="Time constant of the smoother (seconds).")
+@click.option("--eps", type=float, default=1e-6, show_default=True, help="Stabiliser, strictly positive.")
+@click.option("--max-size", type=int, default=1, show_default=True, help="Bands of the running maximum the smoother follows.")
+@click.option("--scale", type=float, default=float(2 ** 31), show_default=True, help="Factor on the magnitude mel block.")
+def features_pcen(input_file, output, n_mels, n_fft, hop_length, gain, bias, power, time_constant, eps, max_size, scale):
+    """PCEN (per-channel energy normalisation) of the mel spectrogram of an audio signal."""
+    from .. import _pcen as PC
+    from ..core.features import pcen as PN
+    if n_mels < 1:
+        raise click.UsageError("--n-mels must be at least 1.")
+    if n_fft < 2:
+        raise click.UsageError("--n-fft must be at least 2.")
+    if hop_length < 1:
+        raise click.UsageError("--hop-length must be at least 1.")
+    try:
+        PC.check_params(n_mels, gain, bias, power, eps, 1.0, "features pcen")
+        PC.check_max_size(max_size, n_mels, "features pcen")
+        PC.check_scale(scale, "features pcen")
+        if not time_constant > 0:
+            raise ValueError("features pcen: --time-constant must be strictly positive.")
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    res = sio.read_data(Path(input_file))
+    if not isinstance(res, tuple) or len(res) != 2 or not res[1]:
+        raise click.UsageError(f"Input file '{Path(input_file).name}' is not recognized as audio.")
+    signal, sr = res
+    if signal.ndim != 1:
+        signal = np.mean(signal, axis=0)
+    try:
+        m = PN.pcen_mel_batch(signal[None, :], sr, n_fft=n_fft, hop=hop_length, n_mels=n_mels, scale=scale, gain=gain, bias=bias,
+                              power=power, time_constant=time_constant, eps=eps, max_size=max_size)[0].cpu().numpy()
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    time = np.arange(m.shape[1]) * hop_length / float(sr)
+    if Path(output).suffix.lower() == ".npz":
+        sio.save_data({"time": time, "pcen": m}, Path(output))
+    else:
+        table = {"time": time}
+        table.update({f"pcen_{i}": m[i] for i in range(m.shape[0])})
+        sio.save_data(pd.DataFrame(table), Path(output))
+    click.echo(f"pcen ({m.shape[0]} bands x {m.shape[1]} frames) saved to '{Path(output).name}'.")
+
+
 # ---------------------------------------------------------------- dsp
 @click.group("dsp")
 def dsp_cmd():

@@ -41,6 +41,8 @@ extern "C" int syg_abi_version(void) { return SYG_ABI_VERSION; }
 extern "C" int syg_build_variant(void) { return 100 + SYG_SOSC_ABL; }      // sosfilt_clip.hip timing ablations
 #elif defined(SYG_DEV) && SYG_DEV
 extern "C" int syg_build_variant(void) { return 9; }                       // stft_mel.hip with per-phase stamps (stft_dev.h)
+#elif defined(SYG_PCEN_WAVE_ROW)
+extern "C" int syg_build_variant(void) { return 200; }                     // pcen.hip: the resident form's other mapping (A/B)
 #else
 extern "C" int syg_build_variant(void) { return 0; }
 #endif

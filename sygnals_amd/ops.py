@@ -19,6 +19,7 @@ from . import _cwt as CW
 from . import _dynamics as DY
 from . import _laplace as LP
 from . import _lpc
+from . import _pcen as PC
 from . import _resample as RS
 from . import _rhythm as RH
 from . import _rng as RNG
@@ -3377,6 +3378,71 @@ def feature_post(x: torch.Tensor, cmvn=None, variance: bool = True, deltas: int 
             _dynamics("feature_post", s, out[:, d * K:(d + 1) * K], 0, 0, 0, 0, (d,), width, mc, 0.0, f)
         return out
     return _dynamics("feature_post", x, out, int(cm), W, variance, 1, orders, width if deltas else 1, mc, 0.0, f)
+
+
+# ------------------------------------------------------------------ PCEN: per-channel energy normalisation
+_PCEN_KEYS = ("tile", "bands", "resident_max_t", "lds_max", "grid_max", "units", "max_out", "table_words")   # SYG_PCEN_*
+
+
+def pcen_constants() -> dict:
+    """The figures the PCEN kernels rest on (the library owns them): the frames of a tile of the tiled form, the bands of
+    a resident workgroup, the rule's longest resident row, the LDS of a workgroup (two fit a CU), the workgroups of a
+    launch, the tiles of a tiled workgroup, the largest result, the float64 words of a band in the parameter table."""
+    return _constants("syg_pcen_constants", _PCEN_KEYS)
+
+
+def pcen_form(T: int, M: int, max_size: int = 1) -> str:
+    """The library's rule: "resident" or "tiled" for [*, M, T] under a running maximum of max_size bands."""
+    f = lib().syg_pcen_form(int(T), int(M), PC.check_max_size(max_size, int(M)))
+    if f < 0:
+        raise ValueError(f"pcen_form: T = {T} and M = {M} must be at least 1")
+    return "tiled" if f == 1 else "resident"
+
+
+def pcen(S: torch.Tensor, sr: float = 22050, hop_length: int = 512, gain=0.98, bias=2.0, power=0.5, time_constant: float = 0.4,
+         eps=1e-6, b=None, max_size: int = 1, scale: float = 1.0, zi=None, return_zf: bool = False,
+         out: Optional[torch.Tensor] = None, form: Optional[str] = None):
+    """librosa.pcen along T of S [B, M, T] float32 >= 0 on the device (the definition: _pcen.py; the contract:
+    tests/pcen_ref.py).  b=None takes librosa's rule from time_constant, sr and hop_length.  gain, bias, power, eps and b
+    are scalars or vectors of one value per band (the special cases power = 0 and bias = 0 are decided per band).  max_size
+    > 1 smooths the running maximum over that many bands (scipy's maximum_filter1d).  scale multiplies S on load.  zi
+    [B, M] float64 is scipy.signal.lfilter's state of every row (None: 1 - b); return_zf adds the closing state, so a clip
+    fed in pieces chained through it equals the whole.  The smoother state is float64, the law float32.  Rows may be
+    strided over B and M (unit stride along T); `out` may be strided the same way and may be S itself.  form: None (the
+    library's rule), "resident" or "tiled".  Negative or non-finite S is outside the contract (NaN, never a fault)."""
+    who = "pcen"
+    if b is None:
+        b = PC.b_from_time_constant(time_constant, sr, hop_length)
+    _f32(S, f"{who}: S", 3, axes="[B, M, T] (a non-negative magnitude or power mel block)")
+    B, M, Tn = S.shape
+    PC.check_size(who, B, M, Tn)
+    vals, per_band = PC.check_params(M, gain, bias, power, eps, b)
+    ms = PC.check_max_size(max_size, M)
+    scale = PC.check_scale(scale)
+    if Tn > 1 and S.stride(-1) != 1:
+        raise ValueError(f"{who}: S must have unit stride along T (got {S.stride(-1)}; rows may be strided over B and M)")
+    PC.check_zi(zi, B, M)
+    f = _dyn_form(form)
+    out = _dyn_out(who, out, (B, M, Tn), S, may_alias=True)
+    _on_device(S, f"{who}: S")
+    if ms > 1 and out.data_ptr() == S.data_ptr():
+        S = S.clone()                                               # neighbouring bands are read: not in place
+    tiled = f == 2 or (f == 0 and lib().syg_pcen_form(Tn, M, ms) == 1)
+    work = _workspace("syg_pcen_work_bytes", B, M, Tn, dtype=torch.float64, device=S.device) if tiled else None
+    tab = None
+    if per_band:
+        t64 = PC.pack_table(vals, pcen_constants()["tile"])
+        tab = _cached(("pcen_tab", t64.tobytes()), lambda: _dev(t64), limit=16)
+        vals = [0.0, 0.0, 0.0, 1.0, 1.0]                            # the entry ignores the scalars beside a table
+    if zi is not None:
+        zi = (zi if isinstance(zi, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(zi, dtype=np.float64)))
+        zi = zi.to(device=S.device, dtype=torch.float64).contiguous()
+    zf = torch.empty((B, M), dtype=torch.float64, device=S.device) if return_zf else None
+    sxb, sxk = _dyn_strides(S)
+    sob, sok = _dyn_strides(out)
+    _call("syg_pcen_f32", _ptr(S), B, M, Tn, sxb, sxk, _ptr(out), sob, sok, *vals, _ptr(tab), ms, scale, _ptr(zi), _ptr(zf), f,
+          _ptr(work), _nbytes(work))
+    return (out, zf) if return_zf else out
 
 
 # ------------------------------------------------------------------ SpecAugment: time warp, frequency and time masks

@@ -86,6 +86,7 @@ class SygnalsAmdPlugin(_Base):
         from ..core import transforms as TR
         from ..core.features import cepstral as CF
         from ..core.features import dynamics as DN
+        from ..core.features import pcen as PN
         from ..core.features import tonal as TN
         registry.add_transform("estimate_tuning", TN.estimate_tuning)
         for fn in (D.compute_fft, D.compute_ifft, D.compute_stft, D.compute_cqt, D.compute_psd_welch, D.apply_window,
@@ -95,7 +96,7 @@ class SygnalsAmdPlugin(_Base):
                    TR.laplace_transform_numerical,
                    TR.discrete_wavelet_transform, TR.inverse_discrete_wavelet_transform,
                    D.compute_csd, D.compute_coherence, AL.estimate_delay, DN.delta, DN.cmvn, DN.stack_memory,
-                   RY.beat_track, RY.tempo):
+                   PN.pcen, RY.beat_track, RY.tempo):
             registry.add_transform(fn.__name__, fn)
 
     def register_feature_extractors(self, registry):
