@@ -313,38 +313,6 @@ __global__ __launch_bounds__(LS_ST) void ls_max_kernel(const float* ls, int64_t 
 // ------------------------------------------------------------------ beat DP
 __device__ __forceinline__ int half_even(int P) { return (P & 1) ? ((P >> 1) + ((P >> 1) & 1)) : (P >> 1); }
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-  const int lo = dpp_i<CTRL>(__double2loint(v)), hi = dpp_i<CTRL>(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double rl_d(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-// the larger value, the smaller offset among equals: numpy's first argmax
-__device__ __forceinline__ void take_better(double& v, int& j, double ov, int oj) {
-  if (ov > v || (ov == v && oj < j)) { v = ov; j = oj; }
-}
-template <int CTRL>
-__device__ __forceinline__ void best_step(double& v, int& j) {
-  const double ov = dpp_d<CTRL>(v);
-  const int oj = dpp_i<CTRL>(j);
-  take_better(v, j, ov, oj);
-}
-__device__ __forceinline__ void wave_best(double& v, int& j) {      // all 64 lanes active
-  best_step<DPP_QP_1032>(v, j);
-  best_step<DPP_QP_2301>(v, j);
-  best_step<DPP_ROW_HALF_MIRROR>(v, j);
-  best_step<DPP_ROW_MIRROR>(v, j);
-  double bv = rl_d(v, 0);
-  int bj = __builtin_amdgcn_readlane(j, 0);
-  take_better(bv, bj, rl_d(v, 16), __builtin_amdgcn_readlane(j, 16));
-  take_better(bv, bj, rl_d(v, 32), __builtin_amdgcn_readlane(j, 32));
-  take_better(bv, bj, rl_d(v, 48), __builtin_amdgcn_readlane(j, 48));
-  v = bv;
-  j = bj;
-}
-
 constexpr int DP_CHUNK = 256;             // local scores staged at a time
 
 struct DpArgs {
@@ -400,7 +368,7 @@ __global__ __launch_bounds__(NT) void beat_dp_kernel(DpArgs A) {
           if (c > best) { best = c; bj = j; }
         }
       }
-      wave_best(best, bj);
+      wave_pick<true>(best, bj);                 // the larger value, the smaller offset among equals: numpy's first argmax
       if (NT > 64) {
         const int par = ci & 1;                  // two sets of slots: a wave may be a step ahead of its reader
         if ((tid & 63) == 0) { rv[par][tid >> 6] = best; rj[par][tid >> 6] = bj; }
@@ -408,7 +376,7 @@ __global__ __launch_bounds__(NT) void beat_dp_kernel(DpArgs A) {
         best = rv[par][0];
         bj = rj[par][0];
 #pragma unroll
-        for (int q = 1; q < NT / 64; ++q) take_better(best, bj, rv[par][q], rj[par][q]);
+        for (int q = 1; q < NT / 64; ++q) take_better<true>(best, bj, rv[par][q], rj[par][q]);
       }
       const double li = (double)lsb[ci];
       const double cs = li + best;

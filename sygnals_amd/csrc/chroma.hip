@@ -53,12 +53,8 @@ __device__ __forceinline__ float cpow_of(float re, float im, int power) {
 
 // librosa.util.normalize's length of v[0 .. n) held one per lane (0 beyond n) in float64; every lane returns it
 __device__ __forceinline__ double wave_norm_len(float v, int norm) {
-  double a = norm == NORM_L2 ? (double)v * (double)v : fabs((double)v);
-#pragma unroll
-  for (int d = 1; d < CH_WAVE; d <<= 1) {
-    const double o = __shfl_xor(a, d);
-    a = norm == NORM_INF ? (a > o ? a : o) : a + o;
-  }
+  if (norm == NORM_INF) return (double)wave_max(fabsf(v));                   // a maximum of floats is exact in either width
+  const double a = wave_sum_d(norm == NORM_L2 ? (double)v * (double)v : fabs((double)v));
   return norm == NORM_L2 ? sqrt(a) : a;
 }
 
@@ -126,18 +122,12 @@ __global__ __launch_bounds__(CH_WAVE * CH_ROW_WAVES) void chroma_fold_rows_kerne
           }
         }
       }
-      // the butterfly step by step over all rows at once: CH_GROUP independent exchanges in flight, not one chain of six a row
+      // CH_GROUP independent wave sums: the compiler interleaves their steps
 #pragma unroll
-      for (int d = 1; d < CH_WAVE; d <<= 1) {
-        float o[CH_GROUP];
-#pragma unroll
-        for (int j = 0; j < CH_GROUP; ++j) o[j] = __shfl_xor(acc[j], d);
-#pragma unroll
-        for (int j = 0; j < CH_GROUP; ++j) acc[j] = acc[j] + o[j];
+      for (int j = 0; j < CH_GROUP; ++j) {
+        const float s = wave_sum(acc[j]);
+        if (lane == c0 + j) mine = s;
       }
-#pragma unroll
-      for (int j = 0; j < CH_GROUP; ++j)
-        if (lane == c0 + j) mine = acc[j];
     }
     if (lane >= nc) mine = 0.f;
     if (A.has_thr && mine < A.thr) mine = 0.f;
@@ -326,11 +316,7 @@ __global__ __launch_bounds__(CH_WAVE * 4) void tuning_peaks_kernel(TuneArgs A) {
     const float v = tune_load(A, xr, k);
     mx = v > mx ? v : mx;
   }
-#pragma unroll
-  for (int d = 1; d < CH_WAVE; d <<= 1) {
-    const float o = __shfl_xor(mx, d);
-    mx = o > mx ? o : mx;
-  }
+  mx = wave_max(mx);
   const double ref = A.threshold * (double)mx;
   for (int k = lane; k < F; k += CH_WAVE) {
     const int km = k > 0 ? k - 1 : 0, kp = k + 1 < F ? k + 1 : F - 1;

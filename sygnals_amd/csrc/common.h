@@ -187,6 +187,11 @@ __device__ __forceinline__ float2* block_fft(float2* x, float2* y, int N, const 
 // (the LDS crossbar, >100 cycles per hop, six dependent hops per reduction); the DPP row operations below
 // cost a few cycles each: butterfly inside each row of 16 lanes (quad_perm, row_half_mirror, row_mirror),
 // then the four row results are combined through v_readlane.
+// float64 takes the same path with two 32-bit DPP moves (or two v_readlane) per value, where __shfl_xor would be two
+// crossbar trips per hop.  The sums add in a fixed order: after each in-row step all lanes of a group of 2, 4, 8, 16 hold
+// the same value, so the mirror partners deliver what the xor partners would: the tree is that of the ascending xor
+// butterfly 1, 2, 4, 8 inside a row, then (r0 + r16) + (r32 + r48), which is the butterfly's 16, 32.  Every lane returns
+// the result, and every function here needs all 64 lanes active at the call (an idle lane's register is read as is).
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
@@ -278,6 +283,48 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   v += dpp_i<DPP_ROW_MIRROR>(v);
   return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) +
          (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double v) {      // lanes without a source get 0
+  const int lo = dpp_i<CTRL>(__double2loint(v)), hi = dpp_i<CTRL>(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+// lane l (uniform) of v
+__device__ __forceinline__ double rl_d(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+  v += dpp_d<DPP_QP_1032>(v);
+  v += dpp_d<DPP_QP_2301>(v);
+  v += dpp_d<DPP_ROW_HALF_MIRROR>(v);
+  v += dpp_d<DPP_ROW_MIRROR>(v);
+  return (rl_d(v, 0) + rl_d(v, 16)) + (rl_d(v, 32) + rl_d(v, 48));
+}
+// (value, index) pick: the larger (LARGER) or the smaller value wins, the smaller index among equal values, which are
+// numpy's first argmax / argmin; without a NaN the winner does not depend on the order of the comparisons
+template <bool LARGER>
+__device__ __forceinline__ void take_better(double& v, int& j, double ov, int oj) {
+  if ((LARGER ? ov > v : ov < v) || (ov == v && oj < j)) { v = ov; j = oj; }
+}
+template <bool LARGER, int CTRL>
+__device__ __forceinline__ void pick_step(double& v, int& j) {
+  const double ov = dpp_d<CTRL>(v);
+  const int oj = dpp_i<CTRL>(j);
+  take_better<LARGER>(v, j, ov, oj);
+}
+template <bool LARGER>
+__device__ __forceinline__ void wave_pick(double& v, int& j) {
+  pick_step<LARGER, DPP_QP_1032>(v, j);
+  pick_step<LARGER, DPP_QP_2301>(v, j);
+  pick_step<LARGER, DPP_ROW_HALF_MIRROR>(v, j);
+  pick_step<LARGER, DPP_ROW_MIRROR>(v, j);
+  double bv = rl_d(v, 0);
+  int bj = __builtin_amdgcn_readlane(j, 0);
+  take_better<LARGER>(bv, bj, rl_d(v, 16), __builtin_amdgcn_readlane(j, 16));
+  take_better<LARGER>(bv, bj, rl_d(v, 32), __builtin_amdgcn_readlane(j, 32));
+  take_better<LARGER>(bv, bj, rl_d(v, 48), __builtin_amdgcn_readlane(j, 48));
+  v = bv;
+  j = bj;
 }
 // exclusive prefix sum over the 64 lanes: Hillis-Steele inside each row of 16 (row_shr with zero fill),
 // then the sums of the lower rows are added

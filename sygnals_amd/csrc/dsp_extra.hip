@@ -43,6 +43,7 @@ __global__ void row_sum_kernel(const float* __restrict__ x, int64_t len, int64_t
     s += v;
     if (linear) sj += ((double)i - jc) * v;
   }
+  // a descending butterfly (32 .. 1): another addition tree than common.h's wave_sum_d, and the order is this file's
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) { s += __shfl_xor(s, o, 64); sj += __shfl_xor(sj, o, 64); }
   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; red[4 + (threadIdx.x >> 6)] = sj; }
@@ -67,6 +68,7 @@ __global__ void pack_rows_kernel(const float* __restrict__ x, int64_t len, int64
   if (part) {
     if (threadIdx.x < 64) {
       double s = part[r * SUMCH + threadIdx.x], sj = linear ? part[(rows + r) * SUMCH + threadIdx.x] : 0.0;
+      // descending as above: the order is this file's
 #pragma unroll
       for (int o = 32; o >= 1; o >>= 1) { s += __shfl_xor(s, o, 64); sj += __shfl_xor(sj, o, 64); }
       if (threadIdx.x == 0) {

@@ -317,12 +317,7 @@ __global__ __launch_bounds__(64 * DW_WAVES) void dtw_accum_kernel(DwArgs A) {
 
   if (A.subseq && n0 + h == xl) {                          // the tile holds part of the pair's last row
     // first arg-min as np.argmin: the lesser value, the lesser column on a tie
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const double ov = __shfl_xor(bv, off);
-      const int oi = __shfl_xor(bi, off);
-      if (ov < bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
+    wave_pick<false>(bv, bi);
     // the tiles of a tile row run in launches of their own, left to right: a later one replaces only if strictly less
     if (lane == 0 && (j == 0 || bv < A.cost[b])) { A.cost[b] = bv; A.end_col[b] = bi; }
   }

@@ -55,9 +55,7 @@ __device__ __forceinline__ double chunk_sum(const float* p, int n, int lane, dou
     if (sq) { v = v - m; v = v * v; }
     a = a + v;
   }
-#pragma unroll
-  for (int d = 1; d < DYN_WAVE; d <<= 1) a = a + __shfl_xor(a, d);
-  return a;
+  return wave_sum_d(a);
 }
 
 // Kaldi's centred window of frame t: [s, e)

@@ -252,17 +252,11 @@ struct NoiseArgs {
   const float* y; const float* noise; const double* snr; float* out; int64_t B, L, ldy, ldn, ldo; int S; int64_t slen; double2* part;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 // sums of (a, c) over the workgroup, the waves' sums added in wave order; every thread gets the same pair
 template <int NT>
 __device__ __forceinline__ void block_sum2(double& a, double& c, double (*red)[NT / 64]) {
-  a = wave_sum_f64(a);
-  c = wave_sum_f64(c);
+  a = wave_sum_d(a);
+  c = wave_sum_d(c);
   __syncthreads();                           // a second call reuses `red`
   if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = c; }
   __syncthreads();

@@ -29,24 +29,6 @@ namespace {
 constexpr int FS_WAVES = 4;       // frames per workgroup
 constexpr int FS_MAXBINS = 256;
 
-// float64 wave sums on the DPP path (two 32-bit DPP moves per hop; __shfl_xor would be two ds_bpermute_b32 round
-// trips through the LDS crossbar per hop).  Fixed order: butterfly inside each row of 16 lanes, then the four rows.
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-  const int lo = dpp_i<CTRL>(__double2loint(v)), hi = dpp_i<CTRL>(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double rl_d(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double wsum(double v) {
-  v += dpp_d<DPP_QP_1032>(v);
-  v += dpp_d<DPP_QP_2301>(v);
-  v += dpp_d<DPP_ROW_HALF_MIRROR>(v);
-  v += dpp_d<DPP_ROW_MIRROR>(v);
-  return (rl_d(v, 0) + rl_d(v, 16)) + (rl_d(v, 32) + rl_d(v, 48));
-}
-
 // np.linspace(first, last, nb + 1)[j]: arange(j) * step + start with the end point set exactly; mul and add are
 // separate roundings in NumPy, so FMA contraction is switched off here
 __device__ __forceinline__ double edge_at(double first, double last, double step, int j, int nb) {
@@ -167,7 +149,7 @@ __global__ __launch_bounds__(FS_WAVES * 64) void frame_stats_kernel(
     else pass1(T_{}, T_{});
   }
   double zc = (double)wave_sum_i(zci);
-  sx = wsum(sx); sa = wsum(sa);
+  sx = wave_sum_d(sx); sa = wave_sum_d(sa);
   wave_maxmin(mxf, mnf);
   const double mx = (double)mxf, mn = (double)mnf, pk = fmax(fabs(mx), fabs(mn));
   const double mean = sx / n;
@@ -280,7 +262,7 @@ __global__ __launch_bounds__(FS_WAVES * 64) void frame_stats_kernel(
   }
   {
     const double isc = 1.0 / (double)sc, i2 = isc * isc;
-    m2 = wsum(m2) / n * i2; m3 = wsum(m3) / n * (i2 * isc); m4 = wsum(m4) / n * (i2 * i2);
+    m2 = wave_sum_d(m2) / n * i2; m3 = wave_sum_d(m3) / n * (i2 * isc); m4 = wave_sum_d(m4) / n * (i2 * i2);
   }
   sq = n * (m2 + mean * mean);                              // sum x^2 from the well-conditioned central sum
   __syncthreads();
@@ -296,7 +278,7 @@ __global__ __launch_bounds__(FS_WAVES * 64) void frame_stats_kernel(
       const double p = (double)mine / n;                    // counts sum to n: scipy's renormalisation is exact
       ent -= p * log(p);
     }
-    ent = wsum(ent);
+    ent = wave_sum_d(ent);
   } else if (want_hist) {
     for (int i = lane; i < nb; i += 64) {
       const unsigned c = hist[w][i];
@@ -305,7 +287,7 @@ __global__ __launch_bounds__(FS_WAVES * 64) void frame_stats_kernel(
         ent -= p * log(p);
       }
     }
-    ent = wsum(ent);
+    ent = wave_sum_d(ent);
   }
   if (!live || lane != 0) return;
 
@@ -344,7 +326,7 @@ __global__ __launch_bounds__(256) void rms_spec_kernel(const float* __restrict__
     const double wgt = (k == 0 || (k == F - 1 && (flen % 2 == 0))) ? 0.5 : 1.0;
     acc += wgt * v * v;
   }
-  acc = wsum(acc);
+  acc = wave_sum_d(acc);
   if (lane == 0) out[r] = (float)sqrt(2.0 * acc / ((double)flen * (double)flen));
 }
 

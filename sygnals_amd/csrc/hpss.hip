@@ -317,12 +317,6 @@ struct HnrArgs {
   float* hnr; float* rh; float* rp;
 };
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(HPW * 64) void hnr_rows_kernel(HnrArgs A) {
   const int lane = threadIdx.x & 63;
   const int64_t f = (int64_t)blockIdx.x * HPW + (threadIdx.x >> 6);

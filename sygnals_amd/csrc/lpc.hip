@@ -59,24 +59,6 @@ constexpr int LPC_PART = 5;               // doubles a workgroup of a stage leav
 constexpr int LPC_WAVE_ROL1 = 0x134, LPC_WAVE_ROR1 = 0x13C;   // whole-wave rotate left / right by one lane (gfx9 DPP)
 constexpr double LPC_TINY = DBL_MIN;      // the smallest normal float64
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {      // lanes without a source get 0
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-// lane l (uniform) of v
-__device__ __forceinline__ double rl_d(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-  v += dpp_d<DPP_QP_1032>(v);
-  v += dpp_d<DPP_QP_2301>(v);
-  v += dpp_d<DPP_ROW_HALF_MIRROR>(v);
-  v += dpp_d<DPP_ROW_MIRROR>(v);
-  return (rl_d(v, 0) + rl_d(v, 16)) + (rl_d(v, 32) + rl_d(v, 48));
-}
-
 // a <- a + k reversed(a) for stage i: lane l holds a[l + 1]; a_new[j] = a[j] + k a[i + 1 - j], j = 1 .. i + 1, a[0] = 1
 __device__ __forceinline__ double step_up(double A, double k, int i, int lane) {
   const int src = i - lane - 1;

@@ -48,13 +48,8 @@ struct PitchLds {
 constexpr int PT_THR = 0, PT_BETA = 100, PT_NOTR = 200, PT_FACT = 301;
 
 __device__ __forceinline__ double shfl_up_d(double v, int d) { return __shfl_up(v, d, 64); }
-__device__ __forceinline__ double shfl_xor_d(double v, int d) { return __shfl_xor(v, d, 64); }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) v += shfl_xor_d(v, d);
-  return v;
-}
+// a 64-lane Hillis-Steele: its order of additions differs from common.h's float scan (rows of 16, then the rows)
 __device__ __forceinline__ double wave_excl_scan_d(double v, int lane) {
   double s = v;
 #pragma unroll
@@ -253,15 +248,7 @@ __global__ __launch_bounds__(PW * 64) void pitch_frames_kernel(FrameArgs A, cons
       }
     }
     // first index of the global minimum: wave min of value, then of index among the lanes that hold it
-    {
-      float v = vmin;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) v = fminf(v, __shfl_xor(v, d, 64));
-      int ii = (vmin == v) ? imin : 0x7fffffff;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) ii = min(ii, __shfl_xor(ii, d, 64));
-      imin = ii;
-    }
+    imin = wave_min_i(vmin == wave_min(vmin) ? imin : 0x7fffffff);
     wave_lds_sync();
 
     if (A.mode == 0) {
@@ -367,12 +354,7 @@ __device__ __forceinline__ int table_row(int i, int n, int h) {
 // (value, index) max with the lowest index on ties, over the workgroup; red: 2 * nwaves doubles of LDS
 __device__ void block_argmax(double v, int i, double* red_v, int* red_i, double& ov, int& oi) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const double v2 = __shfl_xor(v, d, 64);
-    const int i2 = __shfl_xor(i, d, 64);
-    if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-  }
+  wave_pick<true>(v, i);
   __syncthreads();
   if (lane == 0) { red_v[wv] = v; red_i[wv] = i; }
   __syncthreads();

@@ -121,8 +121,7 @@ __device__ __forceinline__ double chunk_sum(const float* xb, int64_t sxk, int64_
 #pragma unroll
   for (int m = 0; m < SPEC_PER; ++m)
     if (4 * (tid + SPEC_THREADS * (m / 4)) + (m & 3) < n) a = a + (double)v[m];
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) a = a + __shfl_xor(a, d);
+  a = wave_sum_d(a);
   __syncthreads();                                   // red may still be read from the chunk before
   if ((tid & 63) == 0) red[tid >> 6] = a;
   __syncthreads();
@@ -132,8 +131,7 @@ __device__ __forceinline__ double chunk_sum(const float* xb, int64_t sxk, int64_
 // The sum of a clip from its chunk sums, the same in both forms: thread t adds chunks t, t + 256, ... in index order
 // (`mine`), then a butterfly over each wave and the four waves in order.
 __device__ __forceinline__ double clip_total(double mine, double* red) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) mine = mine + __shfl_xor(mine, d);
+  mine = wave_sum_d(mine);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mine;
   __syncthreads();
