@@ -1461,6 +1461,65 @@ int syg_pcen_f32(const float* x, int64_t B, int64_t M, int64_t T, int64_t sxb, i
                  int64_t max_size, double scale, const double* zi, double* zf, int form, void* work, int64_t work_bytes,
                  void* stream);
 
+/* -------------------------------------------------------------------------------
+ * Loudness metering (loudness.hip): ITU-R BS.1770 / EBU R128 on clips x [B, C, L] float32, unit stride along L, strides
+ * sb / sc (in floats, non-negative, rows not overlapping) over B and C; mono rows are C = 1.  The float64 restatement
+ * tests/loudness_ref.py is the contract; the K-weighting design is sygnals_amd/_loudness.py's.  fs is an integer rate in
+ * [SYG_LOUDNESS_FS_MIN, SYG_LOUDNESS_FS_MAX].  Segment j is samples [s_j, s_j+1), s_j = j fs div 10; a row has
+ * n_seg = 10 L div fs whole segments, n_m = max(0, n_seg - 3) momentary blocks (segments j ... j + 3) and
+ * n_s = max(0, n_seg - 29) short-term blocks (segments j ... j + 29).
+ *   syg_loudness_segments_f32   seg [B, C, n_seg] float64 = sum y^2 per segment, y = x through the cascade sos_host
+ *       ([2, 6] float64 on the HOST, scipy's b0 b1 b2 a0 a1 a2 per section) from rest, in float64; y is never written.
+ *       work: syg_loudness_segments_work_bytes(B, C, L, fs) bytes on the device, 8-byte aligned (0 bytes where
+ *       n_seg = 0: nothing is launched, seg and work may be NULL).  Chunks of SYG_LOUDNESS_CHUNK samples, the scan of
+ *       syg_sosfilt_f32; a chunk holds at most one segment boundary and writes two partial sums, added per segment
+ *       with the chunks ascending.
+ *   syg_loudness_blocks_f64     from seg and the channel weights [C] float64 (on the DEVICE), block power
+ *       z_j = sum_c w_c (sum of the block's segments) / (s_j+K - s_j), loudness l_j = -0.691 + 10 log10 z_j:
+ *       M [B, n_m] and S [B, n_s] float32 (row strides ldm / lds; -inf where z_j = 0), integ [B] float64 (blocks above
+ *       -70, then above the power-mean of those less 10 LU; -inf where none is left), lra_thr [B] float64
+ *       = max(-70, power-mean of the short-term values above -70, less 20 LU), +inf where none is above -70.  Any of
+ *       the four may be NULL.  One workgroup per clip, float64 sums in a fixed order.
+ *   syg_loudness_lra_f32        s_sorted [B, n_s] float32 ASCENDING (row stride lds) and thr [B] -> lra [B] float32
+ *       (EBU Tech 3342): of the n values above thr, v[floor((n - 1) 0.95 + 1/2)] - v[floor((n - 1) 0.10 + 1/2)], the
+ *       ranks in integers; 0 where n < 2.
+ *   syg_true_peak_f32           peak [B] float32 = max over channels and samples of |scipy.signal.resample_poly(x, up, 1)|
+ *       (padtype constant) without the oversampled signal: table [up, Kp] float32, n_pre_remove and Kp are the plan of
+ *       syg_resample_poly_f32 at down = 1, and every value is that entry's, fma for fma.  up in [1, SYG_LOUDNESS_TP_UP_MAX]
+ *       (up = 1: the sample peak, table may be NULL), Kp <= SYG_LOUDNESS_TP_KP_MAX.  The maximum is an integer maximum on
+ *       the bit pattern of |y| (a NaN comes out on top), peak is cleared on the stream first.
+ *   syg_loudness_gain_f64       gain [B] float64 = 10^((target_lufs - integ) / 20); with peak != NULL (linear true peak
+ *       [B] float32) lowered to 10^(limit_dbtp / 20) / peak where gain peak is above that; 1 where integ is not finite.
+ *   syg_gain_rows_f32           y[b, c, n] = float32(float64(x[b, c, n]) gain[b]), y strided yb / yc; y may be x.
+ * No floating-point atomics anywhere: a call repeats its bits, and a batch equals its rows bit for bit wherever they lie.
+ * Rejected before any device work: null pointers, B / C / L < 1, overlapping rows, fs outside the served rates, a zero
+ * a0, up or Kp outside their bounds, a non-finite target or limit.
+ * ------------------------------------------------------------------------------- */
+enum {
+  SYG_LOUDNESS_CHUNK = 0,       /* samples of a chunk of the segment-power passes */
+  SYG_LOUDNESS_FS_MIN = 1,      /* lowest rate served: a chunk holds at most one segment boundary */
+  SYG_LOUDNESS_FS_MAX = 2,      /* highest rate served */
+  SYG_LOUDNESS_MOMENTARY = 3,   /* segments of a momentary block */
+  SYG_LOUDNESS_SHORT_TERM = 4,  /* segments of a short-term block */
+  SYG_LOUDNESS_TP_TILE = 5,     /* input samples a true-peak workgroup stages at a time */
+  SYG_LOUDNESS_TP_UP_MAX = 6,   /* largest oversampling factor */
+  SYG_LOUDNESS_TP_KP_MAX = 7    /* taps per phase, at most */
+};
+int64_t syg_loudness_constants(int key);
+int64_t syg_loudness_segments_work_bytes(int64_t B, int64_t C, int64_t L, int fs);
+int syg_loudness_segments_f32(const float* x, int64_t B, int64_t C, int64_t L, int64_t sb, int64_t sc, int fs,
+                              const double* sos_host, double* seg, void* work, void* stream);
+int syg_loudness_blocks_f64(const double* seg, int64_t B, int64_t C, int64_t n_seg, int fs, const double* weights, float* M,
+                            int64_t ldm, float* S, int64_t lds, double* integ, double* lra_thr, void* stream);
+int syg_loudness_lra_f32(const float* s_sorted, int64_t B, int64_t n_s, int64_t lds, const double* thr, float* lra,
+                         void* stream);
+int syg_true_peak_f32(const float* x, int64_t B, int64_t C, int64_t L, int64_t sb, int64_t sc, int up, int64_t n_pre_remove,
+                      int Kp, const float* table, float* peak, void* stream);
+int syg_loudness_gain_f64(const double* integ, const float* peak, int64_t B, double target_lufs, double limit_dbtp,
+                          double* gain, void* stream);
+int syg_gain_rows_f32(const float* x, int64_t B, int64_t C, int64_t L, int64_t sb, int64_t sc, const double* gain, float* y,
+                      int64_t yb, int64_t yc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

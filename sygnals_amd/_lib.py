@@ -210,6 +210,14 @@ SIGNATURES = {
     "syg_pcen_form": (_i, [_l, _l, _l]),
     "syg_pcen_work_bytes": (_l, [_l, _l, _l]),
     "syg_pcen_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _l, _d, _d, _d, _d, _d, _p, _l, _d, _p, _p, _i, _p, _l, _p]),
+    "syg_loudness_constants": (_l, [_i]),
+    "syg_loudness_segments_work_bytes": (_l, [_l, _l, _l, _i]),
+    "syg_loudness_segments_f32": (_i, [_p, _l, _l, _l, _l, _l, _i, _p, _p, _p, _p]),
+    "syg_loudness_blocks_f64": (_i, [_p, _l, _l, _l, _i, _p, _p, _l, _p, _l, _p, _p, _p]),
+    "syg_loudness_lra_f32": (_i, [_p, _l, _l, _l, _p, _p, _p]),
+    "syg_true_peak_f32": (_i, [_p, _l, _l, _l, _l, _l, _i, _l, _i, _p, _p, _p]),
+    "syg_loudness_gain_f64": (_i, [_p, _p, _l, _d, _d, _p, _p]),
+    "syg_gain_rows_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _l, _l, _p]),
 }
 
 _lib = None

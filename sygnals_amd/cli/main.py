@@ -851,6 +851,37 @@ def dsp_resample(input_file, output, target_sr, fs, window, padtype):
     click.echo(f"Resampled signal ({sr} Hz -> {target_sr} Hz, {y.size} samples) saved to '{Path(output).name}'.")
 
 
+@dsp_cmd.command("loudness")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("--fs", type=int, default=None, help="Sampling rate of the input (Hz). Required if the input carries no rate.")
+@click.option("--target", type=float, default=None, help="Normalise to this integrated loudness (LUFS) and write -o.")
+@click.option("--peak-limit", "peak_limit", type=float, default=None,
+              help="With --target: lower the gain so that the true peak stays at or under this level (dBTP).")
+@click.option("-o", "--output", default=None, type=click.Path(), help="Where --target writes the normalised signal.")
+def dsp_loudness(input_file, fs, target, peak_limit, output):
+    """Measure integrated loudness (LUFS), loudness range (LU) and true peak (dBTP) after ITU-R BS.1770 / EBU R128;
+    with --target, write the signal normalised to that loudness.  A multi-channel file is mixed down first."""
+    from ..core.audio import loudness as LN
+    if target is not None and output is None:
+        raise click.UsageError("--target needs -o / --output: where to write the normalised signal.")
+    if target is None and (output is not None or peak_limit is not None):
+        raise click.UsageError("-o / --output and --peak-limit go with --target (without it the command only measures).")
+    x, sr = _load_signal(input_file, fs)
+    if not sr:
+        raise click.UsageError("--fs is required: the input file carries no sampling rate.")
+    try:
+        m = LN.loudness_metrics(x, sr)
+        click.echo(f"I = {m['I']:.2f} LUFS, LRA = {m['LRA']:.2f} LU, TP = {m['TP_dbtp']:.2f} dBTP "
+                   f"({np.size(x)} samples at {int(sr)} Hz)")
+        if target is not None:
+            y = LN.normalize_loudness(x, sr, target, peak_limit)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    if target is not None:
+        _save_series(y, sr, output)
+        click.echo(f"Normalised to {target:g} LUFS, saved to '{Path(output).name}'.")
+
+
 @dsp_cmd.command("stft")
 @click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
 @click.option("-o", "--output", required=True, type=click.Path())

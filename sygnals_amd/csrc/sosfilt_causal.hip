@@ -41,9 +41,6 @@ constexpr int64_t MAX_GRID_Y = 65535;
 struct CausalCoef {
   double b0[MAXS], b1[MAXS], b2[MAXS], a1[MAXS], a2[MAXS];   // a0 = 1
 };
-struct CausalPow {
-  double apow[MAXD * MAXD];  // A^CS, row-major D x D (MAXD-strided)
-};
 
 // ---- pass A (MODE 0: zero state, writes end states) and pass C (MODE 1: true state, writes y and zf)
 //   zi / zf   this group's slice of the [B, n_sections, 2] states, row stride ldz doubles; either may be null
@@ -166,82 +163,7 @@ __global__ __launch_bounds__(64) void causal_chunk_kernel(const float* in, int64
   }
 }
 
-// ---- pass B: 16 lanes per (row, segment) (row_dot of sosfilt_scan.h), the zero-state end states AHEAD chunks ahead of
-// the chain.  A segment is G consecutive chunks of a row; the chain runs s <- A s + zs[c] over its chunks, writing s to
-// init[c] in front of each step.  Chunk 0 ran pass A from zi[b]: its report is the state at chunk 1 as it is, and pass C
-// never reads init[b, 0].
-//   start   [B, nseg, D] state at each segment's first chunk (segment 0: not read), or null = zero
-//   init    [B, nch, D] written where given;  ends  [B, nseg, D] the state behind each segment, written where given
-// One segment per row (G = nch) is the whole scan.  A long row takes three launches (two_level below): every segment
-// from a zero state -> ends; the same kernel over the ends as if they were chunks, with A^(CS G) -> the segments' true
-// starts; every segment again from its start -> init.  2 G + nch / G serial steps instead of nch.
-template <int S>
-__global__ __launch_bounds__(256) void causal_scan_kernel(int nch, int G, int nseg, int64_t B, CausalPow P,
-                                                          const double* __restrict__ zs, const double* __restrict__ start,
-                                                          double* __restrict__ init, double* __restrict__ ends) {
-  constexpr int D = 2 * S;
-  const int r = threadIdx.x & 15;
-  const int64_t np = B * nseg;
-  const int64_t p = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-  const bool live = (p < np) && (r < D);
-  const int64_t pp = (p < np) ? p : (np - 1);
-  const int64_t b = pp / nseg;
-  const int cbeg = (int)(pp % nseg) * G;                 // first chunk of the segment
-  const int n = (nch - cbeg < G) ? (nch - cbeg) : G;     // its chunks (>= 1: nseg = ceil(nch / G))
-  double arow[D];
-#pragma unroll
-  for (int j = 0; j < D; ++j) arow[j] = 0.0;
-#pragma unroll
-  for (int rr = 0; rr < D; ++rr)
-    if (r == rr) {
-#pragma unroll
-      for (int j = 0; j < D; ++j) arow[j] = P.apow[rr * MAXD + j];
-    }
-  const int rc = (r < D) ? r : 0;
-  double s = (live && start && cbeg > 0) ? start[pp * D + rc] : 0.0;
-  const double* zp = zs + ((int64_t)b * nch + cbeg) * D + rc;
-  double* ip = init ? init + ((int64_t)b * nch + cbeg) * D + rc : nullptr;
-  const bool fill = live && init;
-  double zq[AHEAD];
-#pragma unroll
-  for (int k = 0; k < AHEAD; ++k) zq[k] = (live && k < n) ? zp[(int64_t)k * D] : 0.0;
-#pragma unroll
-  for (int k = 0; k < AHEAD; ++k) asm volatile("" : "+v"(zq[k]));      // (landed before the chain starts: see below)
-  for (int c0 = 0; c0 < G; c0 += AHEAD) {
-    double zn[AHEAD];
-#pragma unroll
-    for (int k = 0; k < AHEAD; ++k) zn[k] = (live && c0 + AHEAD + k < n) ? zp[(int64_t)(c0 + AHEAD + k) * D] : 0.0;
-#pragma unroll
-    for (int k = 0; k < AHEAD; ++k) {
-      if (c0 + k < G) {                                    // (uniform; a shorter last segment sits its tail out below)
-        const bool in = c0 + k < n;
-        if (fill && in) ip[(int64_t)(c0 + k) * D] = s;     // (init[b, 0] = 0: never read)
-        const double t = (cbeg + c0 + k == 0) ? zq[k] : row_dot<D>(arow, s, zq[k]);
-        s = in ? t : s;
-      }
-    }
-    // the look-ahead lands HERE, once per AHEAD steps: left to itself the compiler waits for it inside the chain, step
-    // by step with vmcnt(0), and so for each step's own store of init as well (1.8 x the time of a step)
-#pragma unroll
-    for (int k = 0; k < AHEAD; ++k) {
-      zq[k] = zn[k];
-      asm volatile("" : "+v"(zq[k]));
-    }
-  }
-  if (live && ends) ends[pp * D + rc] = s;
-}
-
 int64_t chunks(int64_t L) { return (L + CS - 1) / CS; }
-
-constexpr int TWO_LEVEL = 256;       // rows of more chunks than this take the three-launch scan
-// chunks per segment: the whole row up to TWO_LEVEL chunks, above it the multiple of AHEAD next to sqrt(nch / 2), which
-// minimises the 2 G + nch / G serial steps.  A function of the row's length alone: so are the bits of a result.
-int scan_segment(int nch) {
-  if (nch <= TWO_LEVEL) return nch;
-  int g = AHEAD;
-  while ((int64_t)2 * g * g < nch) g += AHEAD;
-  return g;
-}
 
 // one group of S sections over rows [0, B): `in` -> y (in may be y).  AG = A^(CS G) (two-level scan only)
 template <int S>
@@ -263,21 +185,10 @@ int launch_group(const float* in, int64_t B, int64_t L, int64_t ldin, const Caus
     double* ends = init + nb * (int64_t)nch * D;                   // [nb, nseg, D]
     double* segs = ends + nb * (int64_t)nseg * D;                  // [nb, nseg, D]
     const dim3 g(gx, (unsigned)nb);
-    auto scan_grid = [](int64_t rows) { return dim3((unsigned)((rows + 15) / 16)); };
     if (nch > 1) {
       hipLaunchKernelGGL((causal_chunk_kernel<S, 0>), g, dim3(64), 0, st, inb, ldin, nch, L, P, zib, ldz,
                          (const double*)nullptr, zs, (float*)nullptr, (int64_t)0, (double*)nullptr);
-      if (nseg == 1) {
-        hipLaunchKernelGGL((causal_scan_kernel<S>), scan_grid(nb), dim3(256), 0, st, nch, nch, 1, nb, A, (const double*)zs,
-                           (const double*)nullptr, init, (double*)nullptr);
-      } else {
-        hipLaunchKernelGGL((causal_scan_kernel<S>), scan_grid(nb * nseg), dim3(256), 0, st, nch, G, nseg, nb, A,
-                           (const double*)zs, (const double*)nullptr, (double*)nullptr, ends);
-        hipLaunchKernelGGL((causal_scan_kernel<S>), scan_grid(nb), dim3(256), 0, st, nseg, nseg, 1, nb, AG,
-                           (const double*)ends, (const double*)nullptr, segs, (double*)nullptr);
-        hipLaunchKernelGGL((causal_scan_kernel<S>), scan_grid(nb * nseg), dim3(256), 0, st, nch, G, nseg, nb, A,
-                           (const double*)zs, (const double*)segs, init, (double*)nullptr);
-      }
+      scan_rows<S>(nb, nch, A, AG, zs, init, ends, segs, st);
     }
     hipLaunchKernelGGL((causal_chunk_kernel<S, 1>), g, dim3(64), 0, st, inb, ldin, nch, L, P, zib, ldz,
                        (const double*)init, (double*)nullptr, yb, ldy, zfb);

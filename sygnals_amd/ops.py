@@ -18,6 +18,7 @@ from . import _chroma as CH
 from . import _cwt as CW
 from . import _dynamics as DY
 from . import _laplace as LP
+from . import _loudness as LD
 from . import _lpc
 from . import _pcen as PC
 from . import _resample as RS
@@ -3858,3 +3859,172 @@ def estimate_tuning(S: torch.Tensor, sr: float = 22050, n_fft: int = 2048, power
     if (n == 0).any():
         warnings.warn("Trying to estimate tuning from empty frequency set.", stacklevel=2)
     return np.where(n == 0, 0.0, edges[k])
+
+
+# ------------------------------------------------------------------ loudness: BS.1770 / EBU R128 meter and normaliser
+_LOUDNESS_KEYS = ("chunk", "fs_min", "fs_max", "momentary_segments", "short_term_segments", "true_peak_tile", "true_peak_up_max",
+                  "true_peak_taps_max")                                                              # SYG_LOUDNESS_*
+
+
+def loudness_constants() -> dict:
+    """The figures the loudness kernels rest on (the library owns them): samples of a chunk of the segment-power passes, the
+    lowest and highest rate served, the 100 ms segments of a momentary and of a short-term block, the input samples a
+    true-peak workgroup stages at a time, the largest oversampling factor and the most taps per phase."""
+    return _constants("syg_loudness_constants", _LOUDNESS_KEYS)
+
+
+def _loud_clips(y, who: str):
+    """First stage, judged without a device: y is float32 [B, L] (mono) or [B, C, L] with at least one sample.  Returns
+    the [B, C, L] view."""
+    if not isinstance(y, torch.Tensor) or y.dtype != torch.float32 or y.dim() not in (2, 3):
+        raise ValueError(f"{who}: y must be a float32 tensor [B, L] (mono) or [B, C, L]")
+    if y.dim() == 2:
+        y = y.unsqueeze(1)
+    if min(y.shape) < 1:
+        raise ValueError(f"{who}: empty input (shape {list(y.shape)}: at least one clip, one channel and one sample)")
+    return y
+
+
+def _loud_strides(x: torch.Tensor):
+    return int(x.stride(0)) if x.shape[0] > 1 else 0, int(x.stride(1)) if x.shape[1] > 1 else 0
+
+
+def loudness_segments(y: torch.Tensor, fs: int) -> torch.Tensor:
+    """Sum of the squared K-weighted signal over every whole 100 ms segment (syg_loudness_segments_f32): y [B, L] or
+    [B, C, L] float32 on the device (unit stride along L, any stride over B and C) -> float64 [B, C, n_seg],
+    n_seg = 10 L div fs.  The filtered signal is never written."""
+    who = "loudness_segments"
+    x = _loud_clips(y, who)
+    fs = LD.check_fs(fs, who)
+    _on_device(x, f"{who}: y")
+    x = _unit_stride(x)
+    B, Cn, L = x.shape
+    n_seg = LD.n_segments(L, fs)
+    seg = torch.empty((B, Cn, n_seg), dtype=torch.float64, device=x.device)
+    if n_seg:
+        work = _workspace("syg_loudness_segments_work_bytes", B, Cn, L, fs, dtype=torch.float64, device=x.device)
+        sos = LD.k_weighting_sos(fs)
+        _call("syg_loudness_segments_f32", _ptr(x), B, Cn, L, *_loud_strides(x), fs, sos.ctypes.data_as(C.c_void_p), _ptr(seg),
+              _ptr(work))
+    return seg
+
+
+def loudness_blocks(seg: torch.Tensor, fs: int, channel_weights=None):
+    """Segment powers [B, C, n_seg] float64 -> (M, S, I, lra_thr) on the device (syg_loudness_blocks_f64): momentary
+    [B, n_m] and short-term [B, n_s] LUFS float32 (-inf where the power is 0), integrated loudness [B] float64 (-inf where
+    no block passes the gates) and the threshold [B] float64 that loudness_range gates S with.  channel_weights: one per
+    channel; default ones up to 3 channels and BS.1770's 1, 1, 1, 1.41, 1.41 for 5."""
+    who = "loudness_blocks"
+    if not isinstance(seg, torch.Tensor) or seg.dtype != torch.float64 or seg.dim() != 3 or seg.shape[0] < 1 or seg.shape[1] < 1:
+        raise ValueError(f"{who}: seg must be a float64 tensor [B, C, n_seg] (loudness_segments' result)")
+    fs = LD.check_fs(fs, who)
+    B, Cn, n_seg = seg.shape
+    w64 = LD.channel_weights(Cn, channel_weights)
+    _on_device(seg, f"{who}: seg")
+    seg = seg.contiguous()
+    w = _cached(("loudness_w", w64.tobytes()), lambda: _dev(w64), limit=16)
+    M = torch.empty((B, max(0, n_seg - LD.MOMENTARY + 1)), dtype=torch.float32, device=seg.device)
+    S = torch.empty((B, max(0, n_seg - LD.SHORT_TERM + 1)), dtype=torch.float32, device=seg.device)
+    integ = torch.empty(B, dtype=torch.float64, device=seg.device)
+    thr = torch.empty(B, dtype=torch.float64, device=seg.device)
+    _call("syg_loudness_blocks_f64", _ptr(seg), B, Cn, n_seg, fs, _ptr(w), _ptr(M), M.shape[1], _ptr(S), S.shape[1], _ptr(integ),
+          _ptr(thr))
+    return M, S, integ, thr
+
+
+def loudness_range(S: torch.Tensor, lra_thr: torch.Tensor) -> torch.Tensor:
+    """EBU Tech 3342's loudness range [B] float32 (LU) from loudness_blocks' short-term rows S [B, n_s] and threshold
+    [B]: the rows are sorted by torch.sort (1/4800 of the input) and the two percentiles of the values above the threshold
+    are picked on the device (syg_loudness_lra_f32); 0 where fewer than two values are."""
+    _f32(S, "loudness_range: S", 2)
+    B, n_s = S.shape
+    if B < 1 or not isinstance(lra_thr, torch.Tensor) or lra_thr.dtype != torch.float64 or tuple(lra_thr.shape) != (B,):
+        raise ValueError(f"loudness_range: lra_thr must be a float64 tensor [{B}] (loudness_blocks' threshold), S at least one row")
+    _on_device(S, "loudness_range: S")
+    v = torch.sort(S, dim=1).values.contiguous()
+    lra = torch.empty(B, dtype=torch.float32, device=S.device)
+    _call("syg_loudness_lra_f32", _ptr(v), B, n_s, n_s, _ptr(lra_thr.contiguous()), _ptr(lra))
+    return lra
+
+
+def integrated_loudness(y: torch.Tensor, fs: int, channel_weights=None) -> torch.Tensor:
+    """Integrated loudness [B] float64 (LUFS) of y [B, L] or [B, C, L]: loudness_segments, then loudness_blocks' gates."""
+    who = "integrated_loudness"
+    x = _loud_clips(y, who)
+    fs = LD.check_fs(fs, who)
+    LD.channel_weights(x.shape[1], channel_weights)
+    return loudness_blocks(loudness_segments(x, fs), fs, channel_weights)[2]
+
+
+def true_peak(y: torch.Tensor, fs: int) -> torch.Tensor:
+    """Linear true peak [B] float32 of y [B, L] or [B, C, L] (syg_true_peak_f32): the largest |value| over the channels of
+    resample_poly(y, up, 1) with the default filter and padtype="constant", up = 4 below 96 kHz, 2 below 192 kHz, else 1
+    (the sample peak).  Every value is resample_poly's own; the oversampled signal is never written."""
+    who = "true_peak"
+    x = _loud_clips(y, who)
+    fs = LD.check_fs(fs, who)
+    _on_device(x, f"{who}: y")
+    x = _unit_stride(x)
+    B, Cn, L = x.shape
+    up = LD.true_peak_up(fs)
+    p, table = resample_plan(up, 1, L) if up > 1 else (None, None)
+    peak = torch.empty(B, dtype=torch.float32, device=x.device)
+    _call("syg_true_peak_f32", _ptr(x), B, Cn, L, *_loud_strides(x), up, p.n_pre_remove if p else 0, p.Kp if p else 0, _ptr(table),
+          _ptr(peak))
+    return peak
+
+
+def loudness_gain(integ: torch.Tensor, target_lufs: float, peak: Optional[torch.Tensor] = None,
+                  peak_limit_dbtp: Optional[float] = None) -> torch.Tensor:
+    """Gains [B] float64 on the device (syg_loudness_gain_f64): 10^((target - I) / 20), lowered where gain x peak would
+    pass 10^(peak_limit_dbtp / 20) (peak: true_peak's linear [B]), 1 where I is not finite."""
+    who = "loudness_gain"
+    if not isinstance(integ, torch.Tensor) or integ.dtype != torch.float64 or integ.dim() != 1 or integ.shape[0] < 1:
+        raise ValueError(f"{who}: integ must be a float64 tensor [B]")
+    if not np.isfinite(target_lufs) or (peak_limit_dbtp is not None and not np.isfinite(peak_limit_dbtp)):
+        raise ValueError(f"{who}: target_lufs and peak_limit_dbtp must be finite")
+    if (peak is None) != (peak_limit_dbtp is None):
+        raise ValueError(f"{who}: peak and peak_limit_dbtp go together")
+    if peak is not None:
+        _f32(peak, f"{who}: peak", 1, (integ.shape[0],))
+    _on_device(integ, f"{who}: integ")
+    gain = torch.empty_like(integ, memory_format=torch.contiguous_format)
+    _call("syg_loudness_gain_f64", _ptr(integ.contiguous()), _ptr(peak.contiguous() if peak is not None else None), integ.shape[0],
+          float(target_lufs), float(peak_limit_dbtp or 0.0), _ptr(gain))
+    return gain
+
+
+def gain_rows(y: torch.Tensor, gain: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y [B, L] or [B, C, L] float32 times the clip's gain[b] (float64 [B] on the device), rounded once
+    (syg_gain_rows_f32).  `out` may be y."""
+    who = "gain_rows"
+    x = _loud_clips(y, who)
+    B, Cn, L = x.shape
+    if not isinstance(gain, torch.Tensor) or gain.dtype != torch.float64 or tuple(gain.shape) != (B,):
+        raise ValueError(f"{who}: gain must be a float64 tensor [{B}]")
+    _on_device(x, f"{who}: y")
+    x = _unit_stride(x)
+    out = _out(out, y.shape, x)
+    o = out.unsqueeze(1) if out.dim() == 2 else out
+    _call("syg_gain_rows_f32", _ptr(x), B, Cn, L, *_loud_strides(x), _ptr(gain.contiguous()), _ptr(o), int(o.stride(0)),
+          int(o.stride(1)))
+    return out
+
+
+def normalize_loudness(y: torch.Tensor, fs: int, target_lufs: float = -23.0, peak_limit_dbtp: Optional[float] = None,
+                       channel_weights=None, return_gain: bool = False):
+    """y [B, L] or [B, C, L] scaled so that every clip's integrated loudness is target_lufs; with peak_limit_dbtp the gain is
+    lowered so that the true peak stays at or under it.  A clip without a finite loudness (silence, shorter than a block)
+    is copied.  Measuring, the gain and its application are launches on one stream: the host waits for nothing.
+    return_gain: (out, gain [B] float64, I [B] float64)."""
+    who = "normalize_loudness"
+    x = _loud_clips(y, who)
+    fs = LD.check_fs(fs, who)
+    LD.channel_weights(x.shape[1], channel_weights)
+    if not np.isfinite(target_lufs) or (peak_limit_dbtp is not None and not np.isfinite(peak_limit_dbtp)):
+        raise ValueError(f"{who}: target_lufs and peak_limit_dbtp must be finite")
+    integ = integrated_loudness(x, fs, channel_weights)
+    peak = true_peak(x, fs) if peak_limit_dbtp is not None else None
+    gain = loudness_gain(integ, target_lufs, peak, peak_limit_dbtp)
+    out = gain_rows(y, gain)
+    return (out, gain, integ) if return_gain else out

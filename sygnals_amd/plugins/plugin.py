@@ -113,8 +113,16 @@ class SygnalsAmdPlugin(_Base):
         from ..core.features import tonal
         for fn in (tonal.chroma_stft, tonal.chroma_cqt, tonal.chroma_cens, tonal.tonnetz):
             registry.add_feature(fn.__name__, fn)
+        from ..core.audio import loudness
+        registry.add_feature("integrated_loudness", loudness.integrated_loudness)
         registry.add_feature("extract_features", manager.extract_features)
         registry.add_feature("extract_features_batch", manager.extract_features_batch)
+
+    def register_audio_effects(self, registry):
+        from ..core.audio import loudness
+        add = getattr(registry, "add_effect", None)       # api.py:201; a registry that keeps no effects has nowhere to put one
+        if add is not None:
+            add("normalize_loudness", loudness.normalize_loudness)
 
     def register_cli_commands(self, registry):
         from ..cli.main import dsp_cmd, features_cmd, filter_cmd
