@@ -1520,6 +1520,31 @@ int syg_loudness_gain_f64(const double* integ, const float* peak, int64_t B, dou
 int syg_gain_rows_f32(const float* x, int64_t B, int64_t C, int64_t L, int64_t sb, int64_t sc, const double* gain, float* y,
                       int64_t yb, int64_t yc, void* stream);
 
+/* -------------------------------------------------------------------------------
+ * Features back to audio (csrc/griffinlim.hip): the projection step of Griffin-Lim as librosa 0.10 `griffinlim` runs it
+ * (the loop's other steps are syg_istft2048_f32 and syg_stft2048_c2c_f32), and the dense inversions of the mel and MFCC
+ * maps.  tests/inverse_ref.py is the contract.
+ * Geometry is the inverse STFT's: n_fft 2048, hann, hop 512, centred; spectra are frame-major [B, T, 1025, 2] float32,
+ * magnitudes S [B, T, 1025] float32, all contiguous.
+ *   syg_gl_project_f32      D = S A / (|A| + FLT_MIN), A = R - alpha P per bin (P NULL: A = R); alpha is
+ *       momentum / (1 + momentum) rounded to float32 by the caller, in [0, 0.5).  The modulus is formed on A scaled by a
+ *       power of two: a component of 1e-25 or 1e30 neither underflows nor overflows, |D| <= S (1 + 1e-6), A = 0 gives
+ *       D = 0.  D may be R.  sums (may be NULL) [B, 2] float64: per clip sum (|R| - S)^2 and sum S^2 in float64, added in
+ *       a fixed order that depends on T alone (no atomics: a call repeats its bits and a batch equals its rows); it needs
+ *       work, syg_gl_project_work_bytes(B, T) bytes on the device, 8-byte aligned.
+ *   syg_inv_dense_f32       out[b, t, f] = post(sum_m W[f, m] pre(X[b, m, t])): X mel-major [B, M, T], W [F, M] row-major,
+ *       out frame-major [B, T, F], or [B, F, T] with out_mel_major = 1; float32 sums with m ascending.  pre 0: identity;
+ *       1: db_to_power, pre_ref 10^(x / 10) (-inf dB is 0).  post 0: identity; 1: max(., 0)^(1 / post_arg), post_arg the
+ *       power; 2: db_to_power, post_arg 10^(. / 10), post_arg the reference.  M <= 4096, F <= 65536.
+ * Rejected before any device work: null pointers, B / T / M / F < 1, alpha outside [0, 0.5), sums without work, a
+ * non-positive or non-finite pre_ref or post_arg.
+ * ------------------------------------------------------------------------------- */
+int64_t syg_gl_project_work_bytes(int64_t B, int64_t T);
+int syg_gl_project_f32(const float* R, const float* P, const float* S, int64_t B, int64_t T, float alpha, float* D,
+                       double* sums, void* work, void* stream);
+int syg_inv_dense_f32(const float* X, int64_t B, int64_t M, int64_t T, const float* W, int64_t F, int pre, float pre_ref,
+                      int post, float post_arg, float* out, int out_mel_major, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,9 @@ SIGNATURES = {
     "syg_true_peak_f32": (_i, [_p, _l, _l, _l, _l, _l, _i, _l, _i, _p, _p, _p]),
     "syg_loudness_gain_f64": (_i, [_p, _p, _l, _d, _d, _p, _p]),
     "syg_gain_rows_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _l, _l, _p]),
+    "syg_gl_project_work_bytes": (_l, [_l, _l]),
+    "syg_gl_project_f32": (_i, [_p, _p, _p, _l, _l, _f, _p, _p, _p, _p]),
+    "syg_inv_dense_f32": (_i, [_p, _l, _l, _l, _p, _l, _i, _f, _i, _f, _p, _i, _p]),
 }
 
 _lib = None

@@ -882,6 +882,54 @@ def dsp_loudness(input_file, fs, target, peak_limit, output):
         click.echo(f"Normalised to {target:g} LUFS, saved to '{Path(output).name}'.")
 
 
+@dsp_cmd.command("griffinlim")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", default=None, type=click.Path(), help="Where the rebuilt clip is written (.wav or a series).")
+@click.option("--n-iter", "n_iter", type=int, default=32, show_default=True)
+@click.option("--momentum", type=float, default=0.99, show_default=True)
+@click.option("--seed", type=int, default=0, show_default=True, help="Seed of the random starting phases.")
+@click.option("--from", "source", type=click.Choice(["stft", "mel", "mfcc"]), default="stft", show_default=True,
+              help="What the input is reduced to before it is inverted.")
+@click.option("--n-mels", "n_mels", type=int, default=128, show_default=True)
+@click.option("--n-mfcc", "n_mfcc", type=int, default=13, show_default=True)
+@click.option("--fs", type=int, default=None, help="Sampling rate of the input (Hz) if the file carries none.")
+def dsp_griffinlim(input_file, output, n_iter, momentum, seed, source, n_mels, n_mfcc, fs):
+    """Analyse INPUT (STFT magnitudes, mel power or MFCC; n_fft 2048, hop 512), throw the phases away, rebuild a clip by
+    Griffin-Lim and print the final spectral convergence.  From mel and MFCC the magnitudes are the clipped minimum-norm
+    inverse of the mel basis (torchaudio's InverseMelScale, not librosa's NNLS)."""
+    if output is None:
+        raise click.UsageError("-o / --output is required: where to write the rebuilt clip.")
+    if n_iter < 0:
+        raise click.UsageError(f"--n-iter must be non-negative (got {n_iter}).")
+    if not 0 <= momentum < 1:
+        raise click.UsageError(f"--momentum must be in [0, 1) (got {momentum:g}).")
+    if n_mels < 1 or n_mels > 1025 or n_mfcc < 1 or n_mfcc > n_mels:
+        raise click.UsageError(f"--n-mels must be in [1, 1025] and --n-mfcc in [1, n_mels] (got {n_mels}, {n_mfcc}).")
+    x, sr = _load_signal(input_file, fs)
+    if source != "stft" and not sr:
+        raise click.UsageError("--fs is required: the input file carries no sampling rate.")
+    if np.size(x) < 512:
+        raise click.UsageError(f"The input has {np.size(x)} samples; at least 512 (two frames) are needed.")
+    from .. import ops
+    try:
+        y = ops.to_device_f32(np.asarray(x, dtype=np.float32)[None])
+        L = int(y.shape[1])
+        D = ops.stft2048_c2c(y)
+        S = ops.cabs_pow(D, 1)
+        if source != "stft":
+            mel = ops.mel_dense(ops.cabs_pow(D, 2), ops._dev(ops.T.mel_filterbank(float(sr), 2048, n_mels)))
+            if source == "mfcc":
+                mel = ops.mfcc_to_mel(ops.mel_mfcc(mel, n_mfcc, top_db=None, ref=1.0), n_mels)
+            S = ops.mel_to_stft(mel, float(sr))
+        out, trace = ops.griffinlim(S, n_iter, momentum, "random", seed, length=L, return_trace=True)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    _save_series(out[0].cpu().numpy(), sr, output)
+    sc = f"{float(trace[0, -1].item()):.6f}" if n_iter else "n/a (no iteration)"
+    click.echo(f"Rebuilt {L} samples from {source} in {n_iter} iterations, spectral convergence {sc}, "
+               f"saved to '{Path(output).name}'.")
+
+
 @dsp_cmd.command("stft")
 @click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
 @click.option("-o", "--output", required=True, type=click.Path())

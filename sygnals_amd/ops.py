@@ -4028,3 +4028,252 @@ def normalize_loudness(y: torch.Tensor, fs: int, target_lufs: float = -23.0, pea
     gain = loudness_gain(integ, target_lufs, peak, peak_limit_dbtp)
     out = gain_rows(y, gain)
     return (out, gain, integ) if return_gain else out
+
+
+# ------------------------------------------------------------------ features back to audio
+# Geometry of everything here: n_fft 2048, hann, win_length 2048, hop 512, centred (what istft2048 serves).
+
+
+def _gl_stft_args(who, n_fft=2048, hop_length=None, win_length=None, window="hann", center=True):
+    win_length = 2048 if win_length is None else win_length
+    hop = 512 if hop_length is None else hop_length
+    if n_fft != 2048 or win_length != 2048 or hop != 512 or not isinstance(window, str) or window != "hann" or not center:
+        raise ValueError(f"{who}: only n_fft=2048, window='hann', win_length=2048, hop_length=512 and center=True are served "
+                         f"(got n_fft={n_fft}, window={window!r}, win_length={win_length}, hop_length={hop}, center={center})")
+
+
+def gl_alpha(momentum) -> float:
+    """momentum / (1 + momentum) rounded once to float32: the alpha every projection of a run is given.  momentum must be
+    in [0, 1) (librosa warns above 1; here it is refused)."""
+    if isinstance(momentum, bool) or not isinstance(momentum, (int, float, np.integer, np.floating)) or not 0 <= momentum < 1:
+        raise ValueError(f"griffinlim: momentum must be in [0, 1) (got {momentum!r})")
+    return float(np.float32(float(momentum) / (1.0 + float(momentum))))
+
+
+def _gl_spectra(who, R, P, S):
+    """The checks of a projection's inputs: S [B, T, 1025], R and P [B, T, 1025, 2], float32 on the device, made
+    contiguous (as istft2048 makes D)."""
+    _f32(S, f"{who}: S", 3, (1025,), "[B, T, 1025]")
+    B, Tn = int(S.shape[0]), int(S.shape[1])
+    if B < 1 or Tn < 1:
+        raise ValueError(f"{who}: empty input (S has shape {list(S.shape)})")
+    for t, name in ((R, "R"), (P, "P")):
+        if t is not None:
+            _f32(t, f"{who}: {name}", 4, (Tn, 1025, 2), f"[{B}, {Tn}, 1025, 2]")
+            if t.shape[0] != B:
+                raise ValueError(f"{who}: {name} must be a float32 tensor [{B}, {Tn}, 1025, 2]")
+    _on_device(S, f"{who}: S")
+    return (R.contiguous(), P.contiguous() if P is not None else None, S.contiguous(), B, Tn)
+
+
+def gl_project(R: torch.Tensor, S: torch.Tensor, P: Optional[torch.Tensor] = None, alpha: float = 0.0,
+               out: Optional[torch.Tensor] = None, return_sums: bool = False):
+    """Griffin-Lim's projection (syg_gl_project_f32): D = S A / (|A| + FLT_MIN), A = R - alpha P (A = R without P), for
+    spectra [B, T, 1025, 2] and magnitudes S [B, T, 1025].  alpha: gl_alpha(momentum).  `out` may be R.  return_sums adds
+    [B, 2] float64: per clip sum (|R| - S)^2 and sum S^2, whose ratio's root is the spectral convergence of R."""
+    who = "gl_project"
+    if R is None:
+        raise ValueError(f"{who}: R must be a float32 tensor [B, T, 1025, 2]")
+    if not 0 <= alpha < 0.5:
+        raise ValueError(f"{who}: alpha = momentum / (1 + momentum) must be in [0, 0.5) (got {alpha!r})")
+    R, P, S, B, Tn = _gl_spectra(who, R, P, S)
+    D = _out(out, R.shape, R, contiguous=True)
+    sums = work = None
+    if return_sums:
+        sums = torch.empty((B, 2), dtype=torch.float64, device=R.device)
+        work = _workspace("syg_gl_project_work_bytes", B, Tn, dtype=torch.float64, device=R.device)
+    _call("syg_gl_project_f32", _ptr(R), _ptr(P), _ptr(S), B, Tn, float(alpha), _ptr(D), _ptr(sums), _ptr(work))
+    return (D, sums) if return_sums else D
+
+
+def griffinlim(S: torch.Tensor, n_iter: int = 32, momentum: float = 0.99, init="random", seed: int = 0, first_row: int = 0,
+               length: Optional[int] = None, angles: Optional[torch.Tensor] = None, return_trace: bool = False,
+               chunk: Optional[int] = None):
+    """librosa 0.10 `griffinlim` on magnitudes S [B, T, 1025] float32 (frame-major, as stft2048_c2c lays its frames) ->
+    y [B, length] float32; n_fft 2048, hann, hop 512, centred.  Project, then n_iter x (inverse, forward, project with the
+    previous rebuilt spectrum), then a final inverse.
+
+    init: "random" draws the first spectrum as randn(B, T * 1025 * 2, seed, first_row) -- a normalised pair of normals is
+    a uniform phase; clip b of a batch is the single clip first_row + b --, None starts from phases of 1; `angles`
+    [B, T, 1025, 2] gives the starting phases instead (any modulus: it is projected).  length defaults to 512 (T - 1) and
+    must frame to T (1 + length // 512 == T).  momentum in [0, 1).
+
+    An iteration is three launches: syg_gl_project_f32, syg_istft2048_f32, syg_stft2048_c2c_f32, over two rebuilt spectra
+    and the projected one.  (An inverse STFT that projected on its load, so that the projected spectrum was never written,
+    measured slower than the two launches and is not kept: DESIGN.md, "Feature inversion".)  return_trace adds
+    [B, n_iter] float64, the spectral convergence sqrt(sum (|R| - S)^2 / sum S^2) of each rebuilt spectrum, from sums the
+    projection adds in float64 while it reads R and S anyway; the clip is the same bit for bit with or without it.
+
+    chunk: clips that run all their iterations before the next ones start, to bound the three work spectra (clips are
+    independent: the result is the same bit for bit whatever the chunk).  None: the whole batch at once.  Chunks sized to
+    keep a chunk's spectra in the Infinity Cache measured three times slower at 1024 clips of 65 frames (the inverse's
+    waves no longer fill the device), so no chunk is chosen for the caller."""
+    who = "griffinlim"
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or n_iter < 0:
+        raise ValueError(f"{who}: n_iter must be a non-negative integer (got {n_iter!r})")
+    alpha = gl_alpha(momentum)
+    if not (init is None or (isinstance(init, str) and init == "random")):
+        raise ValueError(f"{who}: init must be 'random' or None (got {init!r})")
+    _f32(S, f"{who}: S", 3, (1025,), "[B, T, 1025]")
+    B, Tn = int(S.shape[0]), int(S.shape[1])
+    if B < 1 or Tn < 1:
+        raise ValueError(f"{who}: empty input (S has shape {list(S.shape)})")
+    if length is None:
+        if Tn < 2:
+            raise ValueError(f"{who}: T={Tn} frames give the default length 512 (T - 1) = 0; pass length")
+        length = 512 * (Tn - 1)
+    length = int(length)
+    if length < 1 or 1 + length // 512 != Tn:
+        raise ValueError(f"{who}: length={length} frames to {1 + max(length, 0) // 512} frames, S has {Tn}")
+    if angles is not None:
+        _f32(angles, f"{who}: angles", 4, (Tn, 1025, 2), f"[{B}, {Tn}, 1025, 2]")
+        if angles.shape[0] != B:
+            raise ValueError(f"{who}: angles must be a float32 tensor [{B}, {Tn}, 1025, 2]")
+    elif init == "random":
+        seed, first_row = RNG.check_seed(seed), RNG.check_rows(first_row, B)
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1):
+        raise ValueError(f"{who}: chunk must be a positive integer or None (got {chunk!r})")
+    _on_device(S, f"{who}: S")
+    S = S.contiguous()
+    step = B if chunk is None else min(int(chunk), B)
+    y = torch.empty((B, length), dtype=torch.float32, device=S.device)
+    trace = torch.empty((B, n_iter), dtype=torch.float64, device=S.device) if return_trace else None
+    nb = min(step, B)
+    bufs = [torch.empty((nb, Tn, 1025, 2), dtype=torch.float32, device=S.device) for _ in range(3)]
+    for lo in range(0, B, step):
+        n = min(step, B - lo)
+        Sc = S[lo:lo + n]
+        cur, prev, D = bufs[0][:n], bufs[1][:n], bufs[2][:n]
+        if angles is not None:
+            cur.copy_(angles[lo:lo + n])
+        elif init == "random":
+            randn(n, Tn * 1025 * 2, seed, first_row + lo, out=cur.view(n, -1))
+        else:
+            cur.zero_()
+            cur[..., 0] = 1.0
+        yc = y[lo:lo + n]
+        P = None
+        for i in range(n_iter + 1):
+            # cur: the rebuilt spectrum of iteration i (the starting spectrum at i = 0); P: the one before it
+            if return_trace and i > 0:
+                _, sums = gl_project(cur, Sc, P, alpha, out=D, return_sums=True)
+                trace[lo:lo + n, i - 1] = torch.sqrt(sums[:, 0] / sums[:, 1])
+            else:
+                gl_project(cur, Sc, P, alpha, out=D)
+            _call("syg_istft2048_f32", _ptr(D), n, Tn, 512, 1, length, _ptr(window64_dev()), _ptr(twiddle_dev(2048)), None,
+                  _ptr(yc), None, None, length)
+            if i == n_iter:
+                break
+            nxt = prev                     # the spectrum before last is no longer needed: the forward STFT overwrites it
+            _call("syg_stft2048_c2c_f32", _ptr(yc), n, length, length, 512, 1, Tn, _ptr(window_dev("hann", 2048, 2048)),
+                  _ptr(twiddle_dev(2048)), _ptr(nxt))
+            # (the starting spectrum is nobody's previous one: the first rebuilt spectrum is projected alone)
+            prev, cur, P = cur, nxt, (cur if i >= 1 else None)
+    return (y, trace) if return_trace else y
+
+
+def _inv_dense(who, X, W: torch.Tensor, pre_ref=None, post=None, power: float = 2.0, ref: float = 1.0,
+               mel_major_out: bool = False) -> torch.Tensor:
+    X = _f32_in(X, f"{who}: input", 3).contiguous()
+    B, M, Tn = (int(v) for v in X.shape)
+    F = int(W.shape[0])
+    if B < 1 or M < 1 or Tn < 1 or W.shape[1] != M:
+        raise ValueError(f"{who}: input must be [B, {int(W.shape[1])}, T] with B, T >= 1 (got {list(X.shape)})")
+    out = torch.empty((B, F, Tn) if mel_major_out else (B, Tn, F), dtype=torch.float32, device=X.device)
+    _call("syg_inv_dense_f32", _ptr(X), B, M, Tn, _ptr(W), F, int(pre_ref is not None), float(pre_ref or 1.0),
+          {None: 0, "root": 1, "db": 2}[post], float(ref if post == "db" else power), _ptr(out), int(mel_major_out))
+    return out
+
+
+def inv_dense(X: torch.Tensor, W: torch.Tensor, pre_ref: Optional[float] = None, post: Optional[str] = None, power: float = 2.0,
+              ref: float = 1.0, mel_major_out: bool = False) -> torch.Tensor:
+    """out[b, t, f] = post(sum_m W[f, m] pre(X[b, m, t])) (syg_inv_dense_f32): X mel-major [B, M, T], W [F, M] float32 on
+    the device, out frame-major [B, T, F], or [B, F, T] with mel_major_out.  pre_ref: X is in dB relative to it
+    (pre = pre_ref 10^(x / 10)); post: None, "root" (max(., 0)^(1 / power)) or "db" (ref 10^(. / 10))."""
+    who = "inv_dense"
+    if post not in (None, "root", "db"):
+        raise ValueError(f"{who}: post must be None, 'root' or 'db' (got {post!r})")
+    for v, name in ((pre_ref, "pre_ref"), (power, "power"), (ref, "ref")):
+        if v is not None and not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{who}: {name} must be positive and finite (got {v!r})")
+    _f32(W, f"{who}: W", 2)
+    _on_device(W, f"{who}: W")
+    return _inv_dense(who, X, W.contiguous(), pre_ref, post, power, ref, mel_major_out)
+
+
+def idct_lifter_table(n_mfcc: int, n_mels: int, dct_type: int = 2, norm="ortho", lifter: float = 0) -> np.ndarray:
+    """W [n_mels, n_mfcc] float32 of mfcc_to_mel: the transpose of _tables.dct_matrix -- the inverse of the orthonormal
+    DCT of zero-padded coefficients, scipy's idct(n=n_mels) -- with the lifter divided out as librosa does."""
+    who = "mfcc_to_mel"
+    if norm != "ortho" or dct_type not in (2, 3):
+        raise ValueError(f"{who}: only norm='ortho' with dct_type 2 or 3 is served: the transpose inverts no other "
+                         f"(got dct_type={dct_type}, norm={norm!r})")
+    W = T.dct_matrix(int(n_mfcc), int(n_mels), dct_type, norm).astype(np.float64).T
+    lw = T.lifter_weights(int(n_mfcc), float(lifter))
+    if lw is not None:
+        lw = 1.0 + (float(lifter) / 2.0) * np.sin(np.pi * np.arange(1, int(n_mfcc) + 1) / float(lifter))
+        if np.any(lw == 0.0):
+            raise ValueError(f"{who}: lifter={lifter} has a zero weight, which cannot be divided out")
+        W = W / lw[None, :]
+    return np.ascontiguousarray(W.astype(np.float32))
+
+
+def mel_pinv_table(sr: float, n_fft: int, n_mels: int, fmin: float = 0.0, fmax=None) -> np.ndarray:
+    """pinv(_tables.mel_filterbank(...)) [1 + n_fft / 2, n_mels], computed in float64, as float32."""
+    return np.ascontiguousarray(np.linalg.pinv(T.mel_filterbank(sr, n_fft, n_mels, fmin, fmax).astype(np.float64)).astype(np.float32))
+
+
+def mfcc_to_mel(mfcc: torch.Tensor, n_mels: int = 128, dct_type: int = 2, norm="ortho", ref: float = 1.0, lifter: float = 0,
+                as_db: bool = False) -> torch.Tensor:
+    """librosa.feature.inverse.mfcc_to_mel on MFCC rows [B, K, T] -> mel power [B, n_mels, T] float32 (mel-major, the
+    layout mel rows have here): the inverse DCT with the lifter divided out, then db_to_power(ref).  as_db: the log-mel
+    rows in dB, before db_to_power (mel_to_stft(db_ref=ref) converts them on its load)."""
+    who = "mfcc_to_mel"
+    _f32(mfcc, f"{who}: mfcc", 3, axes="[B, n_mfcc, T]")
+    K = int(mfcc.shape[1])
+    if not (np.isfinite(ref) and ref > 0):
+        raise ValueError(f"{who}: ref must be positive and finite (got {ref!r})")
+    if K < 1 or K > n_mels:
+        raise ValueError(f"{who}: n_mfcc={K} must be in [1, n_mels={n_mels}]")
+    W = idct_lifter_table(K, n_mels, dct_type, norm, lifter)         # (checked before any device work)
+    _on_device(mfcc, f"{who}: mfcc")
+    Wd = _cached(("idct", K, int(n_mels), dct_type, float(lifter)), lambda: _dev(W), limit=8)
+    return _inv_dense(who, mfcc, Wd, None, None if as_db else "db", ref=ref, mel_major_out=True)
+
+
+def mel_to_stft(mel: torch.Tensor, sr: float = 22050, n_fft: int = 2048, power: float = 2.0, fmin: float = 0.0, fmax=None,
+                db_ref: Optional[float] = None) -> torch.Tensor:
+    """Mel power rows [B, M, T] -> magnitudes S [B, T, 1025] float32: max(pinv(mel_filterbank) mel, 0)^(1 / power).
+
+    This is the minimum-norm least-squares inverse, clipped at zero: torchaudio's InverseMelScale, NOT librosa's
+    mel_to_stft.  librosa solves a non-negative least-squares problem by L-BFGS; with 128 equations and 1025 unknowns it
+    is underdetermined, and its answer depends on the solver's path, so there is nothing to pin.  db_ref: mel holds dB
+    relative to it (mfcc_to_mel(as_db=True)) and is converted on load."""
+    who = "mel_to_stft"
+    _gl_stft_args(who, n_fft)
+    _f32(mel, f"{who}: mel", 3, axes="[B, n_mels, T]")
+    M = int(mel.shape[1])
+    if M < 1 or M > 1025:
+        raise ValueError(f"{who}: n_mels={M} must be in [1, 1025]")
+    for v, name in ((power, "power"), (db_ref, "db_ref")):
+        if v is not None and not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{who}: {name} must be positive and finite (got {v!r})")
+    _on_device(mel, f"{who}: mel")
+    Wd = _cached(("melpinv", float(sr), M, float(fmin), None if fmax is None else float(fmax)),
+                 lambda: _dev(mel_pinv_table(sr, 2048, M, fmin, fmax)), limit=8)
+    return _inv_dense(who, mel, Wd, db_ref, "root", power=power)
+
+
+def mel_to_audio(mel: torch.Tensor, sr: float = 22050, n_fft: int = 2048, power: float = 2.0, fmin: float = 0.0, fmax=None,
+                 n_iter: int = 32, momentum: float = 0.99, seed: int = 0, first_row: int = 0, length: Optional[int] = None,
+                 db_ref: Optional[float] = None) -> torch.Tensor:
+    """griffinlim(mel_to_stft(mel)): mel power rows [B, M, T] -> clips [B, length]."""
+    return griffinlim(mel_to_stft(mel, sr, n_fft, power, fmin, fmax, db_ref), n_iter, momentum, "random", seed, first_row, length)
+
+
+def mfcc_to_audio(mfcc: torch.Tensor, n_mels: int = 128, dct_type: int = 2, norm="ortho", ref: float = 1.0, lifter: float = 0,
+                  sr: float = 22050, fmin: float = 0.0, fmax=None, n_iter: int = 32, momentum: float = 0.99, seed: int = 0,
+                  first_row: int = 0, length: Optional[int] = None) -> torch.Tensor:
+    """mel_to_audio(mfcc_to_mel(mfcc)): the log-mel rows stay in dB between the two and become power on the second's load."""
+    logmel = mfcc_to_mel(mfcc, n_mels, dct_type, norm, ref, lifter, as_db=True)
+    return mel_to_audio(logmel, sr, 2048, 2.0, fmin, fmax, n_iter, momentum, seed, first_row, length, db_ref=ref)
