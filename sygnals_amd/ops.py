@@ -2212,6 +2212,7 @@ def idwt(packed: torch.Tensor, lens, wavelet="db4", mode: str = "symmetric") -> 
 
 # ------------------------------------------------------------------ audio effects
 LFO_SHAPES = {"sine": 0, "triangle": 1, "square": 2}          # SYG_LFO_* of include/sygnals_hip.h
+TREMOLO_MAX_ROWS = 8 * 65535                                  # syg_fx_tremolo_f32: eight rows a workgroup, no row loop
 
 
 def fx_delay_chunk() -> int:
@@ -2273,6 +2274,8 @@ def fx_tremolo(x: torch.Tensor, sr: float, rate: float = 5.0, depth: float = 0.5
         raise ValueError("fx_tremolo: rate and sr must be positive")
     if x.shape[0] < 1 or x.shape[1] < 1:
         raise ValueError("fx_tremolo: empty input")
+    if x.shape[0] > TREMOLO_MAX_ROWS:
+        raise ValueError(f"fx_tremolo: too many rows ({x.shape[0]}; one call takes at most {TREMOLO_MAX_ROWS})")
     out = _out(out, x.shape, x)
     _call("syg_fx_tremolo_f32", _ptr(x), x.shape[0], x.shape[1], _ld(x), float(sr), float(rate), float(depth),
           LFO_SHAPES[shape], int(n0), _ptr(out), _ld(out))
