@@ -76,6 +76,18 @@ const char* syg_last_error(void);
 int syg_set_option(int key, int value);
 int syg_get_option(int key);
 
+/* The launch caps every family shares, -1 for an unknown key.  More rows than SYG_LAUNCH_MAX_GRID_Y are looped over, split
+ * into launches or refused, as each entry states; a persistent grid has at most the stated workgroups per CU and its
+ * kernel loops over the rest. */
+enum {
+  SYG_LAUNCH_MAX_GRID_Y = 0,               /* rows of a grid's y dimension */
+  SYG_LAUNCH_LPC_FRAMES_WGS_PER_CU = 1,    /* syg_lpc_frames_f32 */
+  SYG_LAUNCH_LPC_ENVELOPE_WGS_PER_CU = 2,  /* syg_lpc_envelope_f32 */
+  SYG_LAUNCH_PITCH_FRAMES_WGS_PER_CU = 3,  /* syg_pitch_frames_f32 */
+  SYG_LAUNCH_NOISE_WGS_PER_CU = 4          /* syg_fx_add_noise_f32, syg_fx_add_noise_gen_f32 */
+};
+int64_t syg_launch_constants(int which);
+
 /* ---------------------------------------------------------------------------------
  * Fused headline path: framed STFT (n_fft = 2048) -> |X|^2 -> mel filterbank.
  * Replaces, per clip, librosa.stft + np.abs + **2 + librosa.feature.melspectrogram as

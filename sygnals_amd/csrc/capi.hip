@@ -1,5 +1,5 @@
-// Error string + version entry points of the C ABI.
-#include "common.h"
+// Error string, version and launch-cap entry points of the C ABI.
+#include "host.h"
 #include <string.h>
 #include <atomic>
 
@@ -47,3 +47,14 @@ extern "C" int syg_build_variant(void) { return 200; }                     // pc
 extern "C" int syg_build_variant(void) { return 0; }
 #endif
 extern "C" const char* syg_last_error(void) { return syg::g_err; }
+
+extern "C" int64_t syg_launch_constants(int which) {
+  switch (which) {
+    case SYG_LAUNCH_MAX_GRID_Y: return syg::MAX_GRID_Y;
+    case SYG_LAUNCH_LPC_FRAMES_WGS_PER_CU: return syg::LPC_FRAMES_WGS_PER_CU;
+    case SYG_LAUNCH_LPC_ENVELOPE_WGS_PER_CU: return syg::LPC_ENVELOPE_WGS_PER_CU;
+    case SYG_LAUNCH_PITCH_FRAMES_WGS_PER_CU: return syg::PITCH_FRAMES_WGS_PER_CU;
+    case SYG_LAUNCH_NOISE_WGS_PER_CU: return syg::NOISE_WGS_PER_CU;
+    default: syg::set_error("launch_constants: unknown key %d", which); return -1;
+  }
+}

@@ -377,10 +377,7 @@ int check_rows(const char* who, int64_t rows, int64_t n, int64_t n_min) {
               "%s: bad rows / n (rows >= 1, n in [%lld, 2^26], rows n <= 2^31)", who, (long long)n_min);
   return SYG_OK;
 }
-unsigned pointwise_grid(int64_t total) {
-  const int64_t want = ceil_div(total, 256), cap = (int64_t)device_cu_count() * 32;
-  return (unsigned)(want < cap ? want : cap);
-}
+unsigned pointwise_grid(int64_t total) { return capped_grid(ceil_div(total, 256), CEPS_POINTWISE_WGS_PER_CU); }
 int stage_pitch(int Q) { return (Q + 63) / 64 * 64 + 64 / CP_TILE; }
 
 }  // namespace
@@ -421,10 +418,7 @@ extern "C" int syg_cepstrogram2048_f32(const float* y, int64_t B, int64_t L, int
   CepArgs A{y, L, ldy, hop, center, T, tpc, B * tpc, window, n_ceps, Qp, (float)amin, out};
   const size_t lds = sizeof(CepLds) + sizeof(float) * (size_t)CP_TILE * (size_t)Qp;
   if (const int rc = reserve_dynamic_lds("cepstrogram2048", (const void*)cepstrogram2048_kernel, lds)) return rc;
-  int64_t blocks = A.tiles;
-  const int64_t cap = (int64_t)device_cu_count() * CP_BLOCKS_PER_CU;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(cepstrogram2048_kernel, dim3((unsigned)blocks), dim3(CP_WAVES * 64), lds, (hipStream_t)stream, A,
+  hipLaunchKernelGGL(cepstrogram2048_kernel, dim3(capped_grid(A.tiles, CP_BLOCKS_PER_CU)), dim3(CP_WAVES * 64), lds, (hipStream_t)stream, A,
                      (const float2*)twiddle);
   SYG_CHECK_LAUNCH("cepstrogram2048");
   return SYG_OK;

@@ -494,7 +494,7 @@ extern "C" int syg_chroma_fold_bins_f32(const float* x, int64_t B, int64_t K, in
               (long long)sxk, (long long)w);
   SYG_REQUIRE(P >= 0 && P <= CH_P_MAX && (P == 0 || phi), "%s: the output transform must have 0 .. %d rows and a table (got P = %d)",
               who, CH_P_MAX, P);
-  SYG_REQUIRE(B <= 65535, "%s: at most 65535 clips a call (got %lld)", who, (long long)B);
+  SYG_REQUIRE(B <= MAX_GRID_Y, "%s: at most 65535 clips a call (got %lld)", who, (long long)B);
   BinsArgs A;
   A.x = x; A.wt = wt; A.phi = phi; A.out = out; A.B = B; A.K = K; A.T = T; A.sxb = sxb; A.sxk = sxk; A.nc = n_chroma; A.cplx = cplx;
   A.power = power; A.has_thr = has_threshold ? 1 : 0; A.thr = threshold; A.norm = norm; A.P = P;

@@ -834,7 +834,7 @@ using namespace syg;
 extern "C" int syg_decimate2_f32(const float* x, int64_t B, int64_t L, int64_t ldx, const float* taps, int ntaps,
                                  float scale, float* y, int64_t ldy, void* stream) {
   SYG_REQUIRE(x && taps && y, "decimate2: null pointer argument");
-  SYG_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && ldx >= L, "decimate2: bad B/L/ldx");
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && L >= 1 && ldx >= L, "decimate2: bad B/L/ldx");
   SYG_REQUIRE(ntaps >= 1 && (ntaps & 1) == 1 && ntaps <= 1025, "decimate2: ntaps must be odd and <= 1025");
   const int64_t Lout = (L + 1) / 2;
   SYG_REQUIRE(ldy >= Lout, "decimate2: ldy too small");
@@ -855,7 +855,7 @@ extern "C" int syg_decimate2_f32(const float* x, int64_t B, int64_t L, int64_t l
 extern "C" int syg_decimate2_chain_f32(const float* x, int64_t B, int64_t L, int64_t ldx, const float* taps, int ntaps,
                                        float scale, int levels, float* const* y, const int64_t* ldy, void* stream) {
   SYG_REQUIRE(x && taps && y && ldy, "decimate2_chain: null pointer argument");
-  SYG_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && ldx >= L, "decimate2_chain: bad B/L/ldx");
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && L >= 1 && ldx >= L, "decimate2_chain: bad B/L/ldx");
   SYG_REQUIRE(levels >= 1 && levels <= 4, "decimate2_chain: levels must be 1 ... 4 (got %d)", levels);
   SYG_REQUIRE(ntaps >= 1 && (ntaps & 1) == 1 && ntaps <= 1025, "decimate2_chain: ntaps must be odd and <= 1025");
   SYG_REQUIRE(y[levels - 1], "decimate2_chain: the last level needs an output buffer");
@@ -905,7 +905,7 @@ extern "C" int syg_cqt_octave_f32(const float* y, int64_t B, int64_t L, int64_t 
   //  take 192 KiB)
   SYG_REQUIRE(is_pow2(n_fft) && n_fft >= 8 && n_fft <= 1024, "cqt_octave: n_fft must be a power of two in [8, 1024] (got %d)",
               n_fft);
-  SYG_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && ldy >= L && hop >= 1, "cqt_octave: bad B/L/ldy/hop");
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && L >= 1 && ldy >= L && hop >= 1, "cqt_octave: bad B/L/ldy/hop");
   SYG_REQUIRE(T >= 1 && T <= 1 + L / hop, "cqt_octave: T=%lld exceeds the centred frame count %lld", (long long)T,
               (long long)(1 + L / hop));
   SYG_REQUIRE(n_filt >= 1 && n_filt <= MAXFILT, "cqt_octave: n_filt must be in [1, %d]", MAXFILT);
@@ -941,7 +941,7 @@ extern "C" int syg_cqt_octave_gemm_f32(const float* y, int64_t B, int64_t L, int
                                        void* stream) {
   SYG_REQUIRE(y && gpacked && out, "cqt_octave_gemm: null pointer argument");
   SYG_REQUIRE(n_fft == 128 || n_fft == 256 || n_fft == 512, "cqt_octave_gemm: n_fft must be 128, 256 or 512 (got %d)", n_fft);
-  SYG_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && ldy >= L && hop >= 1, "cqt_octave_gemm: bad B/L/ldy/hop");
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && L >= 1 && ldy >= L && hop >= 1, "cqt_octave_gemm: bad B/L/ldy/hop");
   SYG_REQUIRE(T >= 1 && T <= 1 + L / hop, "cqt_octave_gemm: T=%lld exceeds the centred frame count %lld", (long long)T,
               (long long)(1 + L / hop));
   SYG_REQUIRE(n_filt >= 1 && n_filt <= 64, "cqt_octave_gemm: n_filt must be in [1, 64]");
@@ -975,7 +975,7 @@ extern "C" int syg_cqt_octave_bf16x3_f32(const float* y, int64_t B, int64_t L, i
                                          void* stream) {
   SYG_REQUIRE(y && gsplit && out, "cqt_octave_bf16x3: null pointer argument");
   SYG_REQUIRE(n_fft == 128 || n_fft == 256, "cqt_octave_bf16x3: n_fft must be 128 or 256 (got %d)", n_fft);
-  SYG_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && ldy >= L && hop >= 1, "cqt_octave_bf16x3: bad B/L/ldy/hop");
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && L >= 1 && ldy >= L && hop >= 1, "cqt_octave_bf16x3: bad B/L/ldy/hop");
   SYG_REQUIRE(T >= 1 && T <= 1 + L / hop, "cqt_octave_bf16x3: T=%lld exceeds the centred frame count %lld", (long long)T,
               (long long)(1 + L / hop));
   SYG_REQUIRE(n_filt >= 1 && n_filt <= 16, "cqt_octave_bf16x3: n_filt must be in [1, 16] (two 16-row tiles)");

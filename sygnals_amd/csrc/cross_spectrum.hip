@@ -349,7 +349,7 @@ extern "C" int syg_csd_f32(const float* x, const float* y, int64_t B, int64_t By
   SYG_REQUIRE(is_pow2(nfft) && nfft >= 8 && nfft <= CSD_MAX_N, "csd: nfft must be a power of two in [8, %d] (got %d)",
               CSD_MAX_N, nfft);
   SYG_REQUIRE(nperseg >= 1 && nperseg <= nfft && step >= 1 && step <= nperseg, "csd: bad nperseg/step");
-  SYG_REQUIRE(B >= 1 && B <= 65535 && L >= nperseg && ldx >= L, "csd: bad B/L/ldx");
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && L >= nperseg && ldx >= L, "csd: bad B/L/ldx");
   SYG_REQUIRE(By == 1 || By == B, "csd: y must have one row or B = %lld rows (got %lld)", (long long)B, (long long)By);
   SYG_REQUIRE(By == 1 || ldy >= L, "csd: bad ldy");
   SYG_REQUIRE(detrend >= 0 && detrend <= 2, "csd: detrend must be 0 (none), 1 (constant) or 2 (linear)");
@@ -383,7 +383,7 @@ extern "C" int syg_csd_rows_f32(const float* X, const float* Y, int64_t rows, in
                                 int last, int64_t nseg, double scale, float* pxy_out, float* pxx_out, float* pyy_out,
                                 float* coh_out, void* stream) {
   SYG_REQUIRE(X && Y && acc, "csd_rows: null pointer argument");
-  SYG_REQUIRE(rows >= 1 && rows <= 65535 && n >= 1 && n <= ((int64_t)1 << 26), "csd_rows: bad rows / n");
+  SYG_REQUIRE(rows >= 1 && rows <= MAX_GRID_Y && n >= 1 && n <= ((int64_t)1 << 26), "csd_rows: bad rows / n");
   SYG_REQUIRE(nseg >= rows, "csd_rows: nseg = %lld is below the rows of this call (%lld)", (long long)nseg, (long long)rows);
   if (last) {
     int rc = csd_check_outputs("csd_rows", pxy_out, pxx_out, pyy_out, coh_out);
@@ -400,7 +400,7 @@ extern "C" int syg_csd_rows_f32(const float* X, const float* Y, int64_t rows, in
 extern "C" int syg_gcc_weight_c64(const float* X, const float* Y, int64_t rows, int64_t rows_y, int64_t n, int phat,
                                   float* out, void* stream) {
   SYG_REQUIRE(X && Y && out, "gcc_weight: null pointer argument");
-  SYG_REQUIRE(rows >= 1 && rows <= 65535 && (rows_y == 1 || rows_y == rows), "gcc_weight: bad row counts");
+  SYG_REQUIRE(rows >= 1 && rows <= MAX_GRID_Y && (rows_y == 1 || rows_y == rows), "gcc_weight: bad row counts");
   SYG_REQUIRE(n >= 1 && n <= ((int64_t)1 << 27), "gcc_weight: bad n");
   SYG_REQUIRE(phat == 0 || phat == 1, "gcc_weight: weighting must be 0 (none) or 1 (phat)");
   hipLaunchKernelGGL(gcc_weight_kernel, dim3(gcc_grid_x(n, rows), (unsigned)rows), dim3(256), 0, (hipStream_t)stream,
@@ -411,7 +411,7 @@ extern "C" int syg_gcc_weight_c64(const float* X, const float* Y, int64_t rows, 
 
 extern "C" int syg_gcc_crop_f32(const float* c, int64_t rows, int64_t n, int64_t max_lag, float* out, void* stream) {
   SYG_REQUIRE(c && out, "gcc_crop: null pointer argument");
-  SYG_REQUIRE(rows >= 1 && rows <= 65535 && n >= 1, "gcc_crop: bad rows / n");
+  SYG_REQUIRE(rows >= 1 && rows <= MAX_GRID_Y && n >= 1, "gcc_crop: bad rows / n");
   SYG_REQUIRE(max_lag >= 0 && 2 * max_lag + 1 <= n, "gcc_crop: the window of 2 max_lag + 1 = %lld lags does not fit n = %lld",
               (long long)(2 * max_lag + 1), (long long)n);
   hipLaunchKernelGGL(gcc_crop_kernel, dim3(gcc_grid_x(2 * max_lag + 1, rows), (unsigned)rows), dim3(256), 0,

@@ -227,8 +227,8 @@ __global__ __launch_bounds__(256) void cwt_crop_kernel(CropArgs A) {
 }
 
 int cw_check_out(const char* who, int64_t B, int64_t L, int64_t S_out, int cplx, int output, int64_t stride, int64_t n_out) {
-  SYG_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && L < ((int64_t)1 << 40), "%s: bad B / L (B in [1, 65535], L in [1, 2^40))", who);
-  SYG_REQUIRE(S_out >= 1 && S_out <= 65535, "%s: bad S (the scales of y, in [1, 65535])", who);
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && L >= 1 && L < ((int64_t)1 << 40), "%s: bad B / L (B in [1, 65535], L in [1, 2^40))", who);
+  SYG_REQUIRE(S_out >= 1 && S_out <= MAX_GRID_Y, "%s: bad S (the scales of y, in [1, 65535])", who);
   SYG_REQUIRE(cplx == 0 || cplx == 1, "%s: cplx must be 0 (real wavelet) or 1 (re and im planes)", who);
   SYG_REQUIRE(output >= 0 && output < CW_OUT_COUNT, "%s: unknown output code %d (0 coef, 1 magnitude, 2 power)", who, output);
   SYG_REQUIRE(stride >= 1 && stride < ((int64_t)1 << 40), "%s: stride must be at least 1", who);
@@ -249,7 +249,7 @@ extern "C" int syg_cwt_span_max(void) { return CW_SPAN_MAX; }
 extern "C" int syg_cwt_taps_lds_max(void) { return CW_TAPS_LDS_MAX; }
 
 extern "C" int64_t syg_cwt_work_bytes(int64_t B, int64_t R, int64_t M) {
-  if (B < 1 || R < 1 || M < 2 || B > 65535 || R > 65535 || M > ((int64_t)1 << 27)) {
+  if (B < 1 || R < 1 || M < 2 || B > MAX_GRID_Y || R > MAX_GRID_Y || M > ((int64_t)1 << 27)) {
     set_error("cwt_work_bytes: bad B / R / M (B, R in [1, 65535], M in [2, 2^27])");
     return -1;
   }
@@ -286,7 +286,7 @@ extern "C" int syg_cwt_f32(const float* x, int64_t B, int64_t L, int64_t ldx, co
 
 extern "C" int syg_cwt_spectrum_c64(const float* X, const float* H, int64_t B, int64_t R, int64_t M, float* Z, void* stream) {
   SYG_REQUIRE(X && H && Z, "cwt_spectrum: null pointer argument (X / H / Z)");
-  SYG_REQUIRE(B >= 1 && B <= 65535 && R >= 1 && R <= 65535 && M >= 2 && M <= ((int64_t)1 << 27),
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && R >= 1 && R <= MAX_GRID_Y && M >= 2 && M <= ((int64_t)1 << 27),
               "cwt_spectrum: bad B / R / M (B, R in [1, 65535], M in [2, 2^27])");
   SYG_REQUIRE(Z != X && Z != H, "cwt_spectrum: in-place operation is not supported");
   hipLaunchKernelGGL(cwt_spectrum_kernel, dim3((unsigned)ceil_div(M, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,

@@ -12,7 +12,7 @@
 // inverse transform of the result IS the real output row -- half the FFT work and no separate real/complex
 // conversion passes.  The even/odd split keeps each transform's rounding relative to its own signal, which pairing
 // two different signals in one complex transform would not.
-#include "common.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -194,7 +194,7 @@ extern "C" int syg_pack_frames_f32(const float* x, int64_t rows, int64_t len, in
                                    float* out, int64_t n, void* work, void* stream) {
   SYG_REQUIRE(x && out, "pack_rows: null pointer argument");
   // ldx < len is allowed: overlapping rows (frames of one signal, row stride = hop)
-  SYG_REQUIRE(rows >= 1 && rows <= 65535 && len >= 1 && n >= 1 && ldx >= 1, "pack_rows: bad sizes");
+  SYG_REQUIRE(rows >= 1 && rows <= MAX_GRID_Y && len >= 1 && n >= 1 && ldx >= 1, "pack_rows: bad sizes");
   SYG_REQUIRE(rows_per_group >= 0 && (rows_per_group == 0 || group_stride >= 1), "pack_rows: bad row grouping");
   SYG_REQUIRE(detrend >= 0 && detrend <= 2, "pack_rows: detrend must be 0 (none), 1 (constant) or 2 (linear)");
   SYG_REQUIRE(!detrend || work, "pack_rows: detrend needs the work buffer (syg_pack_rows_work_bytes)");
@@ -226,7 +226,7 @@ extern "C" int syg_pack_rows_f32(const float* x, int64_t rows, int64_t len, int6
 extern "C" int syg_rconv_spectrum_c64(const float* za, const float* zb, int64_t rows, int64_t rows_b, int64_t H,
                                       float* out, void* stream) {
   SYG_REQUIRE(za && zb && out, "rconv_spectrum: null pointer argument");
-  SYG_REQUIRE(rows >= 1 && rows <= 65535 && (rows_b == 1 || rows_b == rows), "rconv_spectrum: bad row counts");
+  SYG_REQUIRE(rows >= 1 && rows <= MAX_GRID_Y && (rows_b == 1 || rows_b == rows), "rconv_spectrum: bad row counts");
   SYG_REQUIRE(H >= 2, "rconv_spectrum: H must be >= 2");
   hipLaunchKernelGGL(rconv_spectrum_kernel, dim3(grid_x(H / 2 + 1, rows), (unsigned)rows), dim3(256), 0,
                      (hipStream_t)stream, (const float2*)za, (const float2*)zb, rows_b, H, (float2*)out);
@@ -236,7 +236,7 @@ extern "C" int syg_rconv_spectrum_c64(const float* za, const float* zb, int64_t 
 
 extern "C" int syg_analytic_mask_c64(float* X, int64_t rows, int64_t n, void* stream) {
   SYG_REQUIRE(X, "analytic_mask: null pointer argument");
-  SYG_REQUIRE(rows >= 1 && rows <= 65535 && n >= 1, "analytic_mask: bad sizes");
+  SYG_REQUIRE(rows >= 1 && rows <= MAX_GRID_Y && n >= 1, "analytic_mask: bad sizes");
   hipLaunchKernelGGL(analytic_mask_kernel, dim3(grid_x(n, rows), (unsigned)rows), dim3(256), 0, (hipStream_t)stream,
                      (float2*)X, n);
   SYG_CHECK_LAUNCH("analytic_mask");
@@ -245,7 +245,7 @@ extern "C" int syg_analytic_mask_c64(float* X, int64_t rows, int64_t n, void* st
 
 extern "C" int syg_psd_onesided_f32(const float* X, int64_t rows, int64_t n, double scale, float* out, void* stream) {
   SYG_REQUIRE(X && out, "psd_onesided: null pointer argument");
-  SYG_REQUIRE(rows >= 1 && rows <= 65535 && n >= 1, "psd_onesided: bad sizes");
+  SYG_REQUIRE(rows >= 1 && rows <= MAX_GRID_Y && n >= 1, "psd_onesided: bad sizes");
   hipLaunchKernelGGL(psd_onesided_kernel, dim3(grid_x(n / 2 + 1, rows), (unsigned)rows), dim3(256), 0,
                      (hipStream_t)stream, (const float2*)X, n, (float)scale, out);
   SYG_CHECK_LAUNCH("psd_onesided");

@@ -354,7 +354,7 @@ __global__ __launch_bounds__(64) void dtw_backtrack_kernel(BtArgs A) {
 int dtw_check_shape(int64_t B, int64_t N, int64_t M) {
   SYG_REQUIRE(N >= 1 && M >= 1 && N <= DW_DIM_MAX && M <= DW_DIM_MAX, "dtw: N=%lld and M=%lld must be in [1, 2^30]",
               (long long)N, (long long)M);
-  SYG_REQUIRE(B >= 1 && B <= 65535, "dtw: B=%lld must be in [1, 65535] a call", (long long)B);
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y, "dtw: B=%lld must be in [1, 65535] a call", (long long)B);
   SYG_REQUIRE(N * M <= ((int64_t)1 << 56) / B, "dtw: B N M is too large");
   return SYG_OK;
 }
@@ -445,7 +445,7 @@ extern "C" int syg_dtw_cost_f32(const float* X, const float* Y, int64_t B, int64
   if (const int rc = dtw_check_lens("dtw_cost", x_len, x_len_host, B, N, "x_len")) return rc;
   if (const int rc = dtw_check_lens("dtw_cost", y_len, y_len_host, B, M, "y_len")) return rc;
   const int64_t gx = ceil_div(M, DC_T), gy = ceil_div(N, DC_T);
-  SYG_REQUIRE(gy <= 65535 && gx < 0x7fffffff, "dtw_cost: N=%lld is above %d rows a call", (long long)N, 65535 * DC_T);
+  SYG_REQUIRE(gy <= MAX_GRID_Y && gx < 0x7fffffff, "dtw_cost: N=%lld is above %d rows a call", (long long)N, (int)(MAX_GRID_Y * DC_T));
   DcArgs A{X, Y, K, N, M, ldx, ldy, bsx, bsy, x_len, y_len, C};
   const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)B), block(256);
   hipStream_t st = (hipStream_t)stream;

@@ -460,7 +460,7 @@ extern "C" int syg_stack_memory_f32(const float* x, int64_t B, int64_t K, int64_
   if (const int rc = check_out_size(who, B, n_steps * K, T)) return rc;
   SYG_REQUIRE(!overlaps(x, span(B, K, T, sxb, sxk), out, B * n_steps * K * T), "%s: out overlaps x", who);
   const int64_t rows = B * n_steps * K;
-  hipLaunchKernelGGL(stack_memory_kernel, dim3((unsigned)ceil_div(T, 256), (unsigned)(rows < 65535 ? rows : 65535)), dim3(256), 0,
+  hipLaunchKernelGGL(stack_memory_kernel, dim3((unsigned)ceil_div(T, 256), grid_rows(rows)), dim3(256), 0,
                      (hipStream_t)stream, x, sxb, sxk, B, K, T, n_steps, delay, out);
   SYG_CHECK_LAUNCH(who);
   return SYG_OK;

@@ -41,7 +41,6 @@ constexpr int NB = 1025;
 #endif                               // tools/effects_bench.py --delay-only times (DESIGN.md 4.10 has the figures)
 constexpr int FX_CHUNK = SYG_FX_CHUNK;
 constexpr int FX_THREADS = 256;
-constexpr int64_t FX_MAX_ROWS_Y = 65535;
 
 // ------------------------------------------------------------------ delay
 struct DelayArgs {
@@ -175,7 +174,7 @@ __global__ __launch_bounds__(FX_THREADS) void gate_mask_kernel(const float2* __r
 }
 
 // ------------------------------------------------------------------ pointwise effects
-// grid: x over the samples of a row, y over the rows (a row loop past 65535 rows)
+// grid: x over the samples of a row, y over the rows (a row loop past MAX_GRID_Y rows)
 __global__ __launch_bounds__(FX_THREADS) void mix_kernel(const float* __restrict__ x, int64_t Lx, int64_t ldx,
                                                           const float* __restrict__ y, int64_t Ly, int64_t ldy, int64_t B,
                                                           int64_t L, float a, float bcoef, float* out, int64_t ldo) {
@@ -537,9 +536,7 @@ int check_noise_gen_shape(int64_t B, int64_t L, int64_t first_row) {
   return SYG_OK;
 }
 
-inline dim3 rows_grid(int64_t L, int64_t rows) {
-  return dim3((unsigned)ceil_div(L, FX_THREADS), (unsigned)(rows < FX_MAX_ROWS_Y ? rows : FX_MAX_ROWS_Y));
-}
+inline dim3 rows_grid(int64_t L, int64_t rows) { return dim3((unsigned)ceil_div(L, FX_THREADS), grid_rows(rows)); }
 
 // rows [B, L] with strides: the checks every pointwise entry shares
 int check_rows(const char* who, const void* x, const void* out, int64_t B, int64_t L, int64_t ldx, int64_t ldo) {
@@ -663,7 +660,7 @@ extern "C" int syg_fx_tremolo_f32(const float* x, int64_t B, int64_t L, int64_t 
   SYG_REQUIRE(shape >= SYG_LFO_SINE && shape <= SYG_LFO_SQUARE, "fx_tremolo: unknown LFO shape %d", shape);
   SYG_REQUIRE(n0 >= 0 && n0 < ((int64_t)1 << 52), "fx_tremolo: bad first sample index");
   const int64_t gy = ceil_div(B, TREM_ROWS);
-  SYG_REQUIRE(gy <= FX_MAX_ROWS_Y, "fx_tremolo: too many rows");
+  SYG_REQUIRE(gy <= MAX_GRID_Y, "fx_tremolo: too many rows");
   constexpr double PI = 3.141592653589793238462643383279502884;
   hipLaunchKernelGGL(tremolo_kernel, dim3((unsigned)ceil_div(L, FX_THREADS), (unsigned)gy), dim3(FX_THREADS), 0,
                      (hipStream_t)stream, x, B, L, ldx, sr, (2.0 * PI) * rate, depth, shape, n0, out, ldo);
@@ -712,8 +709,7 @@ extern "C" int syg_fx_add_noise_f32(const float* y, int64_t B, int64_t L, int64_
   if (L <= AN_RESIDENT) {
     const size_t lds = 2 * (size_t)L * sizeof(float);
     if (const int rc = reserve_dynamic_lds("fx_add_noise", (const void*)noise_resident_kernel, lds)) return rc;
-    const int64_t cap = (int64_t)device_cu_count() * 8;
-    hipLaunchKernelGGL(noise_resident_kernel, dim3((unsigned)(B < cap ? B : cap)), dim3(AN_THREADS), lds, st, A);
+    hipLaunchKernelGGL(noise_resident_kernel, dim3(capped_grid(B, NOISE_WGS_PER_CU)), dim3(AN_THREADS), lds, st, A);
     SYG_CHECK_LAUNCH("fx_add_noise");
     return SYG_OK;
   }
@@ -723,7 +719,7 @@ extern "C" int syg_fx_add_noise_f32(const float* y, int64_t B, int64_t L, int64_
   A.S = noise_slices(B, L);
   A.slen = ceil_div(L, A.S);
   A.part = (double2*)work;
-  const unsigned gy = (unsigned)(B < FX_MAX_ROWS_Y ? B : FX_MAX_ROWS_Y);
+  const unsigned gy = grid_rows(B);
   hipLaunchKernelGGL(noise_power_kernel, dim3((unsigned)A.S, gy), dim3(FX_THREADS), 0, st, A);
   SYG_CHECK_LAUNCH("fx_add_noise");
   hipLaunchKernelGGL(noise_mix_kernel, dim3((unsigned)ceil_div(L, AN_SEG), gy), dim3(FX_THREADS), 0, st, A);
@@ -747,11 +743,11 @@ extern "C" int syg_fx_add_noise_gen_f32(const float* y, int64_t B, int64_t L, in
   hipStream_t st = (hipStream_t)stream;
   const int vy = ((uintptr_t)y & 15) == 0 && (ldy & 3) == 0, vo = ((uintptr_t)out & 15) == 0 && (ldo & 3) == 0;
   NoiseGenArgs A{y, snr_db, out, B, L, ldy, ldo, 1, L, nullptr, nullptr, rng_key(seed), (uint32_t)first_row, vy, vo};
-  const int64_t cap = (int64_t)device_cu_count() * 8;
+  const unsigned gb = capped_grid(B, NOISE_WGS_PER_CU);
   if (L <= AN_RESIDENT) {
     const size_t lds = (size_t)ceil_div(L, 4) * sizeof(float4);
     if (const int rc = reserve_dynamic_lds("fx_add_noise_gen", (const void*)noise_gen_resident_kernel, lds)) return rc;
-    hipLaunchKernelGGL(noise_gen_resident_kernel, dim3((unsigned)(B < cap ? B : cap)), dim3(ANG_THREADS), lds, st, A);
+    hipLaunchKernelGGL(noise_gen_resident_kernel, dim3(gb), dim3(ANG_THREADS), lds, st, A);
     SYG_CHECK_LAUNCH("fx_add_noise_gen");
     return SYG_OK;
   }
@@ -761,10 +757,10 @@ extern "C" int syg_fx_add_noise_gen_f32(const float* y, int64_t B, int64_t L, in
   noise_gen_slices(B, L, A.S, A.slen);
   A.part = (double2*)work;
   A.scale = A.part + B * A.S;
-  const unsigned gy = (unsigned)(B < FX_MAX_ROWS_Y ? B : FX_MAX_ROWS_Y);
+  const unsigned gy = grid_rows(B);
   hipLaunchKernelGGL(noise_gen_power_kernel, dim3((unsigned)A.S, gy), dim3(FX_THREADS), 0, st, A);
   SYG_CHECK_LAUNCH("fx_add_noise_gen");
-  hipLaunchKernelGGL(noise_gen_scale_kernel, dim3((unsigned)(B < cap ? B : cap)), dim3(64), 0, st, A);
+  hipLaunchKernelGGL(noise_gen_scale_kernel, dim3(gb), dim3(64), 0, st, A);
   SYG_CHECK_LAUNCH("fx_add_noise_gen");
   hipLaunchKernelGGL(noise_gen_mix_kernel, dim3((unsigned)ceil_div(L, AN_SEG), gy), dim3(FX_THREADS), 0, st, A);
   SYG_CHECK_LAUNCH("fx_add_noise_gen");

@@ -425,7 +425,7 @@ extern "C" int syg_mel_dense_f32(const float* P, int64_t B, int64_t T, int F, co
   SYG_REQUIRE(B >= 1 && T >= 1 && F >= 1 && F <= 16385 && M >= 1, "mel_dense: bad shape");
   const int64_t tiles_per_clip = (T + 15) / 16;
   const int64_t waves = B * tiles_per_clip;
-  SYG_REQUIRE((waves + 3) / 4 < (int64_t)0x7fffffff && M <= 16 * MELT_PER_WAVE * 65535, "mel_dense: grid too large");
+  SYG_REQUIRE((waves + 3) / 4 < (int64_t)0x7fffffff && M <= 16 * MELT_PER_WAVE * MAX_GRID_Y, "mel_dense: grid too large");
   const dim3 grid((unsigned)((waves + 3) / 4), (unsigned)((M + 16 * MELT_PER_WAVE - 1) / (16 * MELT_PER_WAVE)));
   hipLaunchKernelGGL(mel_dense_mfma_kernel, grid, dim3(256), 0, (hipStream_t)stream, P, B, T, F, basis, M, mel_out,
                      tiles_per_clip);
@@ -466,7 +466,7 @@ extern "C" int syg_welch_f32(const float* x, int64_t B, int64_t L, int64_t ldx, 
   SYG_REQUIRE(is_pow2(nfft) && nfft >= 8 && nfft <= 2 * MAX_N, "welch: nfft must be a power of two in [8, %d]",
               2 * MAX_N);
   SYG_REQUIRE(nperseg >= 1 && nperseg <= nfft && step >= 1 && step <= nperseg, "welch: bad nperseg/step");
-  SYG_REQUIRE(B >= 1 && B <= 65535 && L >= nperseg && ldx >= L, "welch: bad B/L/ldx");
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && L >= nperseg && ldx >= L, "welch: bad B/L/ldx");
   SYG_REQUIRE(detrend >= 0 && detrend <= 2, "welch: detrend must be 0 (none), 1 (constant) or 2 (linear)");
   const int64_t nseg = (L - (nperseg - step)) / step;
   SYG_REQUIRE(nseg >= 1, "welch: no complete segment");
@@ -523,7 +523,7 @@ extern "C" int syg_cmul_c64(const float* a, const float* b, float* out, int64_t 
 extern "C" int syg_pack_real_c64(const float* x, int64_t rows, int64_t len, int64_t ldx, const float* window,
                                  float* out, int64_t n, void* stream) {
   SYG_REQUIRE(x && out, "pack_real: null pointer argument");
-  SYG_REQUIRE(rows >= 1 && rows <= 65535 && len >= 0 && n >= 1 && ldx >= len, "pack_real: bad sizes");
+  SYG_REQUIRE(rows >= 1 && rows <= MAX_GRID_Y && len >= 0 && n >= 1 && ldx >= len, "pack_real: bad sizes");
   int64_t blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(pack_real_kernel, dim3((unsigned)blocks, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, x,

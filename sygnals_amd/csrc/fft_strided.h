@@ -155,7 +155,7 @@ int fft_strided_launch(const char* who, int maxn, int (*row_threads)(int), bool 
   SYG_REQUIRE(in && out && twiddle, "%s: null pointer argument", who);
   SYG_REQUIRE((Engine::POW2 ? is_pow2(n) : n >= 2) && n <= maxn, "%s: n must be %sin [2, %d] (got %d)", who,
               Engine::POW2 ? "a power of two " : "", maxn, n);
-  SYG_REQUIRE(batch >= 1 && batch < (int64_t)0x7fffffff && outer >= 1 && outer <= 65535, "%s: bad batch/outer", who);
+  SYG_REQUIRE(batch >= 1 && batch < (int64_t)0x7fffffff && outer >= 1 && outer <= MAX_GRID_Y, "%s: bad batch/outer", who);
   SYG_REQUIRE(in != out, "%s: in-place operation is not supported", who);
   SYG_REQUIRE(flags >= 0 && flags <= 7 && (flags & 5) != 5 && mask_n >= 0 && in_valid >= 0, "%s: bad flags / mask length", who);
   Engine eng;                                                  // (only the mixed engine refuses a length inside the range)

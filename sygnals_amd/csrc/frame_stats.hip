@@ -345,7 +345,7 @@ extern "C" int syg_frame_stats_f32(const float* y, int64_t B, int64_t L, int64_t
               SYG_NFSTAT);
   SYG_REQUIRE(num_bins >= 1 && num_bins <= FS_MAXBINS, "frame_stats: num_bins must be in [1, %d] (got %d)", FS_MAXBINS,
               num_bins);
-  SYG_REQUIRE(B <= 65535, "frame_stats: at most 65535 clips per call");
+  SYG_REQUIRE(B <= MAX_GRID_Y, "frame_stats: at most 65535 clips per call");
   const int64_t gx = (T + FS_WAVES - 1) / FS_WAVES;
   SYG_REQUIRE(gx < (int64_t)0x7fffffff, "frame_stats: too many frames");
   const size_t span_bytes = ((size_t)(FS_WAVES - 1) * hop + frame_length) * sizeof(float);

@@ -1,5 +1,5 @@
-// Host side of every entry point: the two device queries in front of a launch, the frame-count rules and the small
-// integer helpers.  No device code.  `who` names the entry point in the message; a check returns SYG_OK or sets the
+// Host side of every entry point: the two device queries in front of a launch, the launch caps, the frame-count rules and
+// the small integer helpers.  No device code.  `who` names the entry point in the message; a check returns SYG_OK or sets the
 // last error and returns the code to pass on.  (What only the fused STFT front ends share is in stft_host.h.)
 #pragma once
 #include "common.h"
@@ -19,6 +19,25 @@ inline int device_cu_count() {
     cus = 256;
   return cus;
 }
+
+constexpr int64_t MAX_GRID_Y = 65535;  // rows of a grid's y dimension: an entry loops or splits past it, or refuses more
+// y dimension of a grid over `rows` rows
+inline unsigned grid_rows(int64_t rows) { return (unsigned)(rows < MAX_GRID_Y ? rows : MAX_GRID_Y); }
+// Rows of the piece [b0, b0 + per) of a batch of B rows that is launched `per` rows at a time
+inline int64_t piece_rows(int64_t b0, int64_t B, int64_t per) { return B - b0 < per ? B - b0 : per; }
+// Persistent grid: a workgroup for each of `want` pieces of work, at most wgs_per_cu a CU; the kernel loops over the rest
+inline unsigned capped_grid(int64_t want, int wgs_per_cu) {
+  const int64_t cap = (int64_t)device_cu_count() * wgs_per_cu;
+  return (unsigned)(want < cap ? want : cap);
+}
+
+// workgroups a CU of the persistent grids (a figure that an LDS budget decides stays with its kernel)
+constexpr int LPC_FRAMES_WGS_PER_CU = 8;       // lpc_frames_kernel
+constexpr int LPC_ENVELOPE_WGS_PER_CU = 32;    // lpc_envelope_kernel
+constexpr int PITCH_FRAMES_WGS_PER_CU = 16;    // pitch_frames_kernel
+constexpr int ISTFT_WGS_PER_CU = 64;           // istft2048_kernel
+constexpr int CEPS_POINTWISE_WGS_PER_CU = 32;  // the pointwise cepstrum kernels
+constexpr int NOISE_WGS_PER_CU = 8;            // noise_resident_kernel, noise_gen_resident_kernel, noise_gen_scale_kernel
 
 // Dynamic LDS of a launch.  Up to 64 KiB needs no attribute (and no runtime call).  Above it the attribute is set at
 // every launch: it belongs to the (function, device) pair, and a per-process "already set" flag would leave a second

@@ -400,11 +400,8 @@ extern "C" int syg_istft2048_f32(const float* D, int64_t B, int64_t T, int hop, 
   const int ncomp = y_b ? 2 : 1;
   IstftArgs A{(const float2*)D, T, nframes, length, ldy, nseg, B * nseg * ncomp, window, {mask_a, mask_b}, {y_a, y_b},
               ncomp};
-  int64_t blocks = (A.nwaves + IPW - 1) / IPW;
-  const int64_t cap = (int64_t)device_cu_count() * 64;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(istft2048_kernel, dim3((unsigned)blocks), dim3(IPW * 64), 0, (hipStream_t)stream, A,
-                     (const float2*)twiddle);
+  hipLaunchKernelGGL(istft2048_kernel, dim3(capped_grid(ceil_div(A.nwaves, IPW), ISTFT_WGS_PER_CU)), dim3(IPW * 64), 0,
+                     (hipStream_t)stream, A, (const float2*)twiddle);
   SYG_CHECK_LAUNCH("istft2048");
   return SYG_OK;
 }

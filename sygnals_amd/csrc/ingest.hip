@@ -5,7 +5,7 @@
 // sygnals/cli/features_cmd.py:66-68 (np.mean over channels).  Moving the conversion behind the host-to-device copy
 // halves the PCIe bytes for 16-bit audio (the copy, not the kernels, bounds the end-to-end rate: DESIGN.md section 5).
 // Pure streaming: each thread converts four consecutive frames (a 16-byte float4 store).
-#include "common.h"
+#include "host.h"
 
 namespace syg {
 namespace {
@@ -76,7 +76,7 @@ extern "C" int syg_pcm_to_f32(const void* pcm, int bits, int64_t rows, int64_t f
                               float* out, int64_t ldo, void* stream) {
   SYG_REQUIRE(pcm && out, "pcm_to_f32: null pointer argument");
   SYG_REQUIRE(bits == 8 || bits == 16 || bits == 32, "pcm_to_f32: bits must be 8 (unsigned), 16 or 32 (got %d)", bits);
-  SYG_REQUIRE(rows >= 1 && rows <= 65535 && frames >= 1 && channels >= 1 && channels <= 256,
+  SYG_REQUIRE(rows >= 1 && rows <= MAX_GRID_Y && frames >= 1 && channels >= 1 && channels <= 256,
               "pcm_to_f32: need 1 <= rows <= 65535, frames >= 1, 1 <= channels <= 256");
   SYG_REQUIRE(ld >= frames * channels && ldo >= frames, "pcm_to_f32: row strides shorter than a row");
   SYG_REQUIRE(((uintptr_t)out & 15) == 0, "pcm_to_f32: out must be 16-byte aligned");

@@ -38,7 +38,6 @@ namespace {
 
 using namespace sos;
 
-constexpr int64_t MAX_GRID_Y = 65535;
 constexpr int LD_FS_MIN = 8000, LD_FS_MAX = 384000;
 constexpr int LD_MOMENTARY = 4, LD_SHORT_TERM = 30;    // segments of a block
 constexpr int TP_TILE = 1024, TP_THREADS = 256;        // input positions a true-peak workgroup stages at a time
@@ -349,10 +348,7 @@ __global__ __launch_bounds__(GAIN_THREADS) void gain_rows_kernel(const float* x,
 int64_t whole_segments(int64_t L, int fs) { return L * 10 / fs; }
 int64_t chunks(int64_t n) { return (n + CS - 1) / CS; }
 // clips of one launch: the grid's second dimension holds their rows
-int64_t clips_per_launch(int64_t B, int64_t C) {
-  const int64_t n = MAX_GRID_Y / C;
-  return B < n ? B : n;
-}
+int64_t clips_per_launch(int64_t B, int64_t C) { return piece_rows(0, B, MAX_GRID_Y / C); }
 // bad B / C / L / strides of a [B, C, L] input; `who` names the entry point
 int check_clips(const char* who, int64_t B, int64_t C, int64_t L, int64_t sb, int64_t sc) {
   SYG_REQUIRE(B >= 1 && C >= 1 && C <= MAX_GRID_Y && L >= 1 && L < ((int64_t)1 << 40),
@@ -425,7 +421,7 @@ extern "C" int syg_loudness_segments_f32(const float* x, int64_t B, int64_t C, i
   hipStream_t st = (hipStream_t)stream;
   const int64_t per = clips_per_launch(B, C);
   for (int64_t b0 = 0; b0 < B; b0 += per) {
-    const int64_t nb = B - b0 < per ? B - b0 : per, rows = nb * C;
+    const int64_t nb = piece_rows(b0, B, per), rows = nb * C;
     const float* xb = x + b0 * sb;
     double* zs = (double*)work;                        // [rows, nch, 4]
     double* init = zs + rows * nch * 4;                // [rows, nch, 4]
@@ -492,7 +488,7 @@ extern "C" int syg_true_peak_f32(const float* x, int64_t B, int64_t C, int64_t L
   void (*k)(const float*, int64_t, int64_t, int, int64_t, int64_t, int, const float*, unsigned*) =
       up == 1 ? true_peak_kernel<1> : up == 2 ? true_peak_kernel<2> : up == 3 ? true_peak_kernel<3> : true_peak_kernel<4>;
   for (int64_t b0 = 0; b0 < B; b0 += per) {
-    const int64_t nb = B - b0 < per ? B - b0 : per;
+    const int64_t nb = piece_rows(b0, B, per);
     hipLaunchKernelGGL(k, dim3((unsigned)gx, (unsigned)(nb * C)), dim3(TP_THREADS), 0, st, x + b0 * sb, sb, sc, (int)C, L,
                        up == 1 ? (int64_t)0 : n_pre_remove, Kp, table, (unsigned*)peak + b0);
     SYG_CHECK_LAUNCH("true_peak");
@@ -520,7 +516,7 @@ extern "C" int syg_gain_rows_f32(const float* x, int64_t B, int64_t C, int64_t L
   const int64_t gx = ceil_div(L, (int64_t)GAIN_THREADS * GAIN_PER), per = clips_per_launch(B, C);
   SYG_REQUIRE(gx < 0x7fffffff, "gain_rows: too many tiles");
   for (int64_t b0 = 0; b0 < B; b0 += per) {
-    const int64_t nb = B - b0 < per ? B - b0 : per;
+    const int64_t nb = piece_rows(b0, B, per);
     hipLaunchKernelGGL(gain_rows_kernel, dim3((unsigned)gx, (unsigned)(nb * C)), dim3(GAIN_THREADS), 0, (hipStream_t)stream,
                        x + b0 * sb, sb, sc, (int)C, L, gain + b0, y + b0 * yb, yb, yc);
     SYG_CHECK_LAUNCH("gain_rows");

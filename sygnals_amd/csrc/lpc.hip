@@ -518,12 +518,9 @@ extern "C" int syg_lpc_frames_f32(const float* y, int64_t B, int64_t L, int64_t 
   const int64_t tpc = ceil_div(T, LPC_TILE);
   LpcArgs A{y, L, ldy, N, hop, center ? N / 2 : 0, staged, span_floats, T, tpc, B * tpc, window, order, method, a, k, err};
   const size_t lds = sizeof(float) * ((size_t)span_floats + (size_t)LPC_TILE * (size_t)(2 * order + 3));
-  int64_t blocks = A.tiles;
-  const int64_t cap = (int64_t)device_cu_count() * 8;
-  if (blocks > cap) blocks = cap;
   hipStream_t s = (hipStream_t)stream;
   switch ((N + 63) / 64) {                                   // registers a lane holds of each of f and b
-#define SYG_LPC_CASE(E) case E: launch_frames<E>(A, (unsigned)blocks, lds, s); break;
+#define SYG_LPC_CASE(E) case E: launch_frames<E>(A, capped_grid(A.tiles, LPC_FRAMES_WGS_PER_CU), lds, s); break;
     SYG_LPC_CASE(1) SYG_LPC_CASE(2) SYG_LPC_CASE(3) SYG_LPC_CASE(4) SYG_LPC_CASE(5) SYG_LPC_CASE(6) SYG_LPC_CASE(7) SYG_LPC_CASE(8)
     SYG_LPC_CASE(9) SYG_LPC_CASE(10) SYG_LPC_CASE(11) SYG_LPC_CASE(12) SYG_LPC_CASE(13) SYG_LPC_CASE(14) SYG_LPC_CASE(15) SYG_LPC_CASE(16)
     SYG_LPC_CASE(17) SYG_LPC_CASE(18) SYG_LPC_CASE(19) SYG_LPC_CASE(20) SYG_LPC_CASE(21) SYG_LPC_CASE(22) SYG_LPC_CASE(23) SYG_LPC_CASE(24)
@@ -588,9 +585,8 @@ extern "C" int syg_lpc_envelope_f32(const float* a, const float* err, int64_t B,
   SYG_REQUIRE(amin >= 0.0 && amin <= (double)FLT_MAX, "lpc_envelope: amin must be finite and >= 0 (got %g)", amin);
   const int64_t K = n_fft / 2 + 1;
   SYG_REQUIRE(B >= 1 && T >= 1 && T <= ((int64_t)1 << 31) / K / B, "lpc_envelope: bad B / T (each >= 1, B (n_fft / 2 + 1) T <= 2^31)");
-  const int64_t want = ceil_div(B * K * T, 256), cap = (int64_t)device_cu_count() * 32;
-  hipLaunchKernelGGL(lpc_envelope_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, (hipStream_t)stream, a, err, B, order, T, K,
-                     phasor, db, (float)amin, out);
+  hipLaunchKernelGGL(lpc_envelope_kernel, dim3(capped_grid(ceil_div(B * K * T, 256), LPC_ENVELOPE_WGS_PER_CU)), dim3(256), 0,
+                     (hipStream_t)stream, a, err, B, order, T, K, phasor, db, (float)amin, out);
   SYG_CHECK_LAUNCH("lpc_envelope");
   return SYG_OK;
 }

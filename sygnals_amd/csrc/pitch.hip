@@ -481,11 +481,8 @@ extern "C" int syg_pitch_frames_f32(const float* y, int64_t B, int64_t L, int64_
   SYG_REQUIRE(sr > 0.0, "pitch_frames: bad sr");
   FrameArgs A{y, L, ldy, win_length, hop, center, T, B * T, sr, min_period, max_period, n_lag, mode, trough_threshold,
               fmin, n_bins, ptab, K, f0_out, cand_bin, cand_prob, cand_count, voiced_prob, cmndf_out};
-  int64_t blocks = (A.nframes + PW - 1) / PW;
-  const int64_t cap = (int64_t)device_cu_count() * 16;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(pitch_frames_kernel, dim3((unsigned)blocks), dim3(PW * 64), 0, (hipStream_t)stream, A,
-                     (const float2*)twiddle);
+  hipLaunchKernelGGL(pitch_frames_kernel, dim3(capped_grid(ceil_div(A.nframes, PW), PITCH_FRAMES_WGS_PER_CU)), dim3(PW * 64), 0,
+                     (hipStream_t)stream, A, (const float2*)twiddle);
   SYG_CHECK_LAUNCH("pitch_frames");
   return SYG_OK;
 }

@@ -161,7 +161,7 @@ extern "C" int syg_resample_poly_f32(const float* x, int64_t B, int64_t L, int64
   SYG_REQUIRE(x && table && y, "resample_poly: null pointer argument (x / table / y)");
   SYG_REQUIRE(up >= 1 && down >= 1 && up <= RS_RATE_MAX && down <= RS_RATE_MAX,
               "resample_poly: up=%d and down=%d must be in [1, %d]", up, down, RS_RATE_MAX);
-  SYG_REQUIRE(B >= 1 && B <= 65535 && L >= 1 && L < ((int64_t)1 << 40), "resample_poly: bad B / L (B in [1, 65535], L in [1, 2^40))");
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && L >= 1 && L < ((int64_t)1 << 40), "resample_poly: bad B / L (B in [1, 65535], L in [1, 2^40))");
   SYG_REQUIRE(n_out == ceil_div(L * up, down), "resample_poly: n_out=%lld is not ceil(L up / down) = %lld", (long long)n_out,
               (long long)ceil_div(L * up, down));
   SYG_REQUIRE(ldx >= L, "resample_poly: ldx=%lld is less than L=%lld", (long long)ldx, (long long)L);

@@ -12,7 +12,6 @@ namespace syg {
 namespace {
 
 constexpr int RNG_THREADS = 256;
-constexpr int64_t RNG_MAX_ROWS_Y = 65535;
 constexpr int64_t RNG_COLORED_MAX = (int64_t)1 << 26;     // longest transform of the strided FFT
 
 __global__ __launch_bounds__(RNG_THREADS) void philox_words_kernel(const uint4* __restrict__ ctr, const uint2* __restrict__ key,
@@ -92,8 +91,6 @@ int check_rows_rng(const char* who, const void* out, int64_t B, int64_t L, int64
   return SYG_OK;
 }
 
-inline unsigned rows_y(int64_t B) { return (unsigned)(B < RNG_MAX_ROWS_Y ? B : RNG_MAX_ROWS_Y); }
-
 }  // namespace
 }  // namespace syg
 
@@ -128,7 +125,7 @@ extern "C" int syg_rng_normal_f32(float* out, int64_t B, int64_t L, int64_t ldo,
   const int vec = (offset & 3) == 0 && (ldo & 3) == 0 && ((uintptr_t)out & 15) == 0;
   NormalArgs A{out, B, L, ldo, offset, rng_key(seed), (uint32_t)first_row, 0, vec};
   const int64_t calls = ((offset + L - 1) >> 2) - (offset >> 2) + 1;
-  hipLaunchKernelGGL(rng_normal_kernel, dim3((unsigned)ceil_div(calls, RNG_THREADS), rows_y(B)), dim3(RNG_THREADS), 0,
+  hipLaunchKernelGGL(rng_normal_kernel, dim3((unsigned)ceil_div(calls, RNG_THREADS), grid_rows(B)), dim3(RNG_THREADS), 0,
                      (hipStream_t)stream, A);
   SYG_CHECK_LAUNCH("rng_normal");
   return SYG_OK;
@@ -141,7 +138,7 @@ extern "C" int syg_rng_normal_pairs_c64(float* Z, int64_t P, int64_t M, uint64_t
               "rng_normal_pairs: first_row must be even with rows first_row .. first_row + 2 P - 1 in [0, 2^31) (got %lld, P = %lld)",
               (long long)first_row, (long long)P);
   NormalArgs A{Z, 2 * P, M, 2 * M, 0, rng_key(seed), (uint32_t)first_row, 1, 0};
-  hipLaunchKernelGGL(rng_normal_kernel, dim3((unsigned)ceil_div(ceil_div(M, 4), RNG_THREADS), rows_y(2 * P)), dim3(RNG_THREADS), 0,
+  hipLaunchKernelGGL(rng_normal_kernel, dim3((unsigned)ceil_div(ceil_div(M, 4), RNG_THREADS), grid_rows(2 * P)), dim3(RNG_THREADS), 0,
                      (hipStream_t)stream, A);
   SYG_CHECK_LAUNCH("rng_normal_pairs");
   return SYG_OK;
@@ -164,7 +161,7 @@ extern "C" int syg_rng_unpack_pairs_f32(const float* Z, int64_t M, int64_t first
   SYG_REQUIRE(Z, "rng_unpack_pairs: null pointer argument (Z)");
   if (const int rc = check_rows_rng("rng_unpack_pairs", out, B, L, ldo, first_row)) return rc;
   SYG_REQUIRE(M >= L && M <= RNG_COLORED_MAX, "rng_unpack_pairs: bad M (L <= M <= 2^26)");
-  hipLaunchKernelGGL(unpack_pairs_kernel, dim3((unsigned)ceil_div(L, RNG_THREADS), rows_y(B)), dim3(RNG_THREADS), 0,
+  hipLaunchKernelGGL(unpack_pairs_kernel, dim3((unsigned)ceil_div(L, RNG_THREADS), grid_rows(B)), dim3(RNG_THREADS), 0,
                      (hipStream_t)stream, Z, M, first_row, out, B, L, ldo);
   SYG_CHECK_LAUNCH("rng_unpack_pairs");
   return SYG_OK;

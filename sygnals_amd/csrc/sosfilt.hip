@@ -29,7 +29,7 @@
 // tiles through LDS (lane-major rows of 36 floats: 128-bit, conflict-free LDS accesses on both sides) so that
 // global accesses stay coalesced while each lane walks its own chunk; the next tile's loads are issued before the
 // recurrence over the current one.  One wave per workgroup: ordering inside the wave replaces barriers.
-#include "common.h"
+#include "host.h"
 #include "sosfilt_clip.h"
 #include "sosfilt_scan.h"
 #include <string.h>
@@ -323,7 +323,7 @@ extern "C" int syg_sosfiltfilt_f32(const float* x, int64_t B, int64_t L, int64_t
   SYG_REQUIRE(x && y && sos_host && zi_host, "sosfiltfilt: null pointer argument");
   SYG_REQUIRE(n_sections >= 1 && n_sections <= MAXS, "sosfiltfilt: n_sections must be in [1, %d] (got %d)", MAXS,
               n_sections);
-  SYG_REQUIRE(B >= 1 && B <= 65535 && L >= 2 && ldx >= L && ldy >= L, "sosfiltfilt: bad B/L/ld");
+  SYG_REQUIRE(B >= 1 && B <= MAX_GRID_Y && L >= 2 && ldx >= L && ldy >= L, "sosfiltfilt: bad B/L/ld");
   SYG_REQUIRE(padlen >= 0 && padlen < L, "The length of the input vector x must be greater than padlen, which is %d.",
               padlen);
   const int S = n_sections, D = 2 * S;

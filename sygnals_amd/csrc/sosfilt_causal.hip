@@ -26,7 +26,7 @@
 // More than MAXS = 8 sections run as consecutive groups of at most 8 (a causal cascade composes exactly): group 0 reads
 // x and writes y, every later group filters y in place, each with its own slice of zi / zf.  y may alias x: a wave
 // reads a tile of its own chunks before it writes it, and no other wave touches those chunks in that launch.
-#include "common.h"
+#include "host.h"
 #include "sosfilt_scan.h"
 #include <string.h>
 
@@ -36,7 +36,6 @@ namespace {
 using namespace sos;
 
 constexpr int MAX_SECTIONS = 32;     // sections per call: four groups of MAXS
-constexpr int64_t MAX_GRID_Y = 65535;
 
 struct CausalCoef {
   double b0[MAXS], b1[MAXS], b2[MAXS], a1[MAXS], a2[MAXS];   // a0 = 1
@@ -175,7 +174,7 @@ int launch_group(const float* in, int64_t B, int64_t L, int64_t ldin, const Caus
   const int G = scan_segment(nch), nseg = (nch + G - 1) / G;
   const unsigned gx = (unsigned)((nch + 63) / 64);
   for (int64_t b0 = 0; b0 < B; b0 += MAX_GRID_Y) {                 // one grid dimension's worth of rows per launch
-    const int64_t nb = (B - b0 < MAX_GRID_Y) ? (B - b0) : MAX_GRID_Y;
+    const int64_t nb = piece_rows(b0, B, MAX_GRID_Y);
     const float* inb = in + b0 * ldin;
     float* yb = y + b0 * ldy;
     const double* zib = zi ? zi + b0 * ldz : nullptr;
@@ -219,7 +218,7 @@ extern "C" int64_t syg_sosfilt_constants(int which) {
 
 extern "C" int64_t syg_sosfilt_work_bytes(int64_t B, int64_t L, int n_sections) {
   if (B < 1 || L < 1 || n_sections < 1 || n_sections > MAX_SECTIONS) return -1;
-  const int64_t rows = B < MAX_GRID_Y ? B : MAX_GRID_Y;            // rows of one launch; groups and launches reuse it
+  const int64_t rows = grid_rows(B);                               // rows of one launch; groups and launches reuse it
   const int S = n_sections < MAXS ? n_sections : MAXS;
   const int64_t nch = chunks(L);
   // zero-state end states + true initial states per chunk, and the same two per segment of the long rows' scan (a

@@ -103,14 +103,11 @@ inline int check_segtab(const char* who, const float* segtab, int n_segtab, int 
 template <class Rows, class Kern, class... Args>
 int launch_front(const char* who, Kern kern, int64_t wgs, int wgs_per_cu, int threads, size_t lds_bytes, hipStream_t st,
                  const Rows* rows, Args... args) {
-  const int64_t cap = (int64_t)device_cu_count() * wgs_per_cu;
-  if (wgs > cap) wgs = cap;
   Rows rw;
   memset(&rw, 0, sizeof(rw));
   if (rows) rw = *rows;
-  const int rc = reserve_dynamic_lds(who, (const void*)kern, lds_bytes);
-  if (rc) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(threads), lds_bytes, st, args..., rw);
+  if (const int rc = reserve_dynamic_lds(who, (const void*)kern, lds_bytes)) return rc;
+  hipLaunchKernelGGL(kern, dim3(capped_grid(wgs, wgs_per_cu)), dim3(threads), lds_bytes, st, args..., rw);
   SYG_CHECK_LAUNCH(who);
   return SYG_OK;
 }

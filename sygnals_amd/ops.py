@@ -182,6 +182,16 @@ def _constants(entry: str, names) -> dict:
     return {name: int(fn(i)) for i, name in enumerate(names)}
 
 
+_LAUNCH_KEYS = ("max_grid_y", "lpc_frames_wgs_per_cu", "lpc_envelope_wgs_per_cu", "pitch_frames_wgs_per_cu",
+                "noise_wgs_per_cu")                                                                  # SYG_LAUNCH_*
+
+
+def launch_constants() -> dict:
+    """The launch caps of the library (it owns them): rows of a grid's y dimension (MAX_ROWS restates it) and the workgroups
+    a CU of the persistent grids of the LPC frame and envelope kernels, the pitch frame kernel and the noise mixes."""
+    return _constants("syg_launch_constants", _LAUNCH_KEYS)
+
+
 def _row_blocks(n: int):
     """(first row, row count) of the launches that take n rows MAX_ROWS (the grid's 65535) at a time."""
     for lo in range(0, n, MAX_ROWS):
@@ -2212,7 +2222,7 @@ def idwt(packed: torch.Tensor, lens, wavelet="db4", mode: str = "symmetric") -> 
 
 # ------------------------------------------------------------------ audio effects
 LFO_SHAPES = {"sine": 0, "triangle": 1, "square": 2}          # SYG_LFO_* of include/sygnals_hip.h
-TREMOLO_MAX_ROWS = 8 * 65535                                  # syg_fx_tremolo_f32: eight rows a workgroup, no row loop
+TREMOLO_MAX_ROWS = 8 * MAX_ROWS                               # syg_fx_tremolo_f32: eight rows a workgroup, no row loop
 
 
 def fx_delay_chunk() -> int:
