@@ -1557,6 +1557,45 @@ int syg_gl_project_f32(const float* R, const float* P, const float* S, int64_t B
 int syg_inv_dense_f32(const float* X, int64_t B, int64_t M, int64_t T, const float* W, int64_t F, int pre, float pre_ref,
                       int post, float post_arg, float* out, int out_mel_major, void* stream);
 
+/* -------------------------------------------------------------------------------
+ * Non-negative matrix factorisation by multiplicative updates (csrc/nmf.hip): scikit-learn's solver="mu" at tol = 0,
+ * which is what librosa.decompose.decompose runs when handed NMF(solver="mu").  tests/nmf_ref.py is the contract.
+ * Frame-major and contiguous: V [B, T, F] float32, non-negative and finite; activations A [B, T, K] (sklearn's W);
+ * components C [B, K, F] (sklearn's H), or one dictionary [1, K, F] for every clip with c_shared = 1.  eps is FLT_EPSILON.
+ * Served: F in [1, 2049], K in [1, 64], T >= 1, B >= 1 (B T F <= 2^40, T <= 2^30).
+ *   syg_nmf_f32             n_iter iterations in place on A and C, each the A-step, then the C-step with the new A:
+ *       Frobenius  A <- A (V C^T) / (A (C C^T)),  C <- C (A^T V) / ((A^T A) C);
+ *       KL         A <- A ((V / AC) C^T) / sum_f C,  C <- C (A^T (V / AC)) / sum_t A, AC raised to eps where below it;
+ *       a denominator equal to 0 becomes eps; under KL an entry of the new C below 2^-52 (float64's epsilon) becomes 0, as
+ *       sklearn has it.  update_A = 0 or update_C = 0 leaves that factor untouched (update_C = 0
+ *       is librosa's fit=False).  Only V, A, C and K K + K floats of scratch a clip pass through memory.  No stopping
+ *       rule, no regularisation.  form: how the contractions over F and T run -- SYG_NMF_FORM_FMA, plain fp32 FMA;
+ *       SYG_NMF_FORM_MFMA, v_mfma_f32_16x16x4_f32 (exact fp32, another summation order); SYG_NMF_FORM_AUTO, the faster of
+ *       the two as measured: MFMA from K = syg_nmf_constants(8) up.  work: syg_nmf_work_bytes(B, T, F, K) bytes on the device, 8-byte aligned.
+ *   syg_nmf_divergence_f32  out [B] float64: sklearn's _beta_divergence of each clip, AC and the sum formed in float64
+ *       from the float32 factors.  Frobenius: sum (V - AC)^2 / 2.  KL: sum over V > eps of V log(V / max(AC, eps)) - V,
+ *       plus sum AC.  Sums are added in an order that depends on (T, F) alone.  work as above.
+ *   syg_nmf_masks_f32       out [B, n_groups, T, F, 2] = D [B, T, F, 2] times the soft mask of each group,
+ *       (sum_k G[g, k] A[t, k] C[k, f]) / max(sum_k A[t, k] C[k, f], eps), G [n_groups, K] row-major, n_groups <= 64.
+ *   syg_nmf_constants(i)    0: largest K, 1: largest F, 2: largest n_groups, 3 / 4: frames of an A-step tile and bins of
+ *       its chunk, 5 / 6: bins of a C-step tile and frames of its chunk, 7: chunk of the per-clip sums, 8: the smallest K that SYG_NMF_FORM_AUTO gives to the MFMA form; -1 past them.
+ * Rejected before any device work: null pointers, sizes outside the served ranges, an unknown loss (Itakura-Saito and
+ * other beta are not served), a negative n_iter, update_C with c_shared.
+ * ------------------------------------------------------------------------------- */
+#define SYG_NMF_FROBENIUS 0
+#define SYG_NMF_KL 1
+#define SYG_NMF_FORM_AUTO (-1)
+#define SYG_NMF_FORM_FMA 0
+#define SYG_NMF_FORM_MFMA 1
+int syg_nmf_constants(int which);
+int64_t syg_nmf_work_bytes(int64_t B, int64_t T, int64_t F, int64_t K);
+int syg_nmf_f32(const float* V, int64_t B, int64_t T, int64_t F, int64_t K, float* A, float* C, int c_shared, int64_t n_iter,
+                int loss, int update_A, int update_C, int form, void* work, void* stream);
+int syg_nmf_divergence_f32(const float* V, const float* A, const float* C, int c_shared, int64_t B, int64_t T, int64_t F,
+                           int64_t K, int loss, double* out, void* work, void* stream);
+int syg_nmf_masks_f32(const float* D, const float* A, const float* C, int c_shared, const float* G, int64_t B, int64_t T,
+                      int64_t F, int64_t K, int64_t n_groups, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,11 @@ SIGNATURES = {
     "syg_gl_project_work_bytes": (_l, [_l, _l]),
     "syg_gl_project_f32": (_i, [_p, _p, _p, _l, _l, _f, _p, _p, _p, _p]),
     "syg_inv_dense_f32": (_i, [_p, _l, _l, _l, _p, _l, _i, _f, _i, _f, _p, _i, _p]),
+    "syg_nmf_constants": (_i, [_i]),
+    "syg_nmf_work_bytes": (_l, [_l, _l, _l, _l]),
+    "syg_nmf_f32": (_i, [_p, _l, _l, _l, _l, _p, _p, _i, _l, _i, _i, _i, _i, _p, _p]),
+    "syg_nmf_divergence_f32": (_i, [_p, _p, _p, _i, _l, _l, _l, _l, _i, _p, _p, _p]),
+    "syg_nmf_masks_f32": (_i, [_p, _p, _p, _i, _p, _l, _l, _l, _l, _l, _p, _p]),
 }
 
 _lib = None

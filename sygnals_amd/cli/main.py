@@ -930,6 +930,44 @@ def dsp_griffinlim(input_file, output, n_iter, momentum, seed, source, n_mels, n
                f"saved to '{Path(output).name}'.")
 
 
+@dsp_cmd.command("decompose")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", default=None, type=click.Path(), help="Where components and activations are written (.npz).")
+@click.option("--components", "n_components", type=int, default=8, show_default=True)
+@click.option("--iterations", "n_iter", type=int, default=200, show_default=True)
+@click.option("--loss", type=click.Choice(["frobenius", "kullback-leibler"]), default="frobenius", show_default=True)
+@click.option("--seed", type=int, default=0, show_default=True, help="Seed of the random starting factors.")
+def dsp_decompose(input_file, output, n_components, n_iter, loss, seed):
+    """Factor the STFT magnitudes of INPUT (n_fft 2048, hop 512) into spectral components [1025, K] and their activations
+    [K, T] by multiplicative-update NMF, and print the divergence before and after."""
+    if output is None:
+        raise click.UsageError("-o / --output is required: where to write components and activations (.npz).")
+    if Path(output).suffix.lower() != ".npz":
+        raise click.UsageError(f"-o / --output must be an .npz file: two matrices are written (got '{Path(output).name}').")
+    if not 1 <= n_components <= 64:
+        raise click.UsageError(f"--components must be in [1, 64] (got {n_components}).")
+    if n_iter < 0:
+        raise click.UsageError(f"--iterations must be non-negative (got {n_iter}).")
+    if seed < 0:
+        raise click.UsageError(f"--seed must be non-negative (got {seed}).")
+    x, sr = _load_signal(input_file, None)
+    if np.size(x) < 1:
+        raise click.UsageError("The input is empty.")
+    from .. import ops
+    try:
+        y = ops.to_device_f32(np.asarray(x, dtype=np.float32)[None])
+        S = ops.cabs_pow(ops.stft2048_c2c(y), 1)
+        A0, C0 = ops.nmf(S, n_components, n_iter=0, seed=seed)
+        A, C = ops.nmf(S, A0=A0, C0=C0, n_iter=n_iter, beta_loss=loss)
+        d0, d1 = (float(ops.nmf_divergence(S, a, c, loss)[0].item()) for a, c in ((A0, C0), (A, C)))
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    sio.save_data({"components": C[0].T.contiguous().cpu().numpy(), "activations": A[0].T.contiguous().cpu().numpy(),
+                   "divergence": np.array([d0, d1]), "loss": np.array(loss)}, output)
+    click.echo(f"Decomposed {S.shape[1]} frames x 1025 bins into {n_components} components in {n_iter} iterations ({loss}), "
+               f"divergence {d0:.6g} -> {d1:.6g}, saved to '{Path(output).name}'.")
+
+
 @dsp_cmd.command("stft")
 @click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
 @click.option("-o", "--output", required=True, type=click.Path())

@@ -4290,3 +4290,169 @@ def mfcc_to_audio(mfcc: torch.Tensor, n_mels: int = 128, dct_type: int = 2, norm
     """mel_to_audio(mfcc_to_mel(mfcc)): the log-mel rows stay in dB between the two and become power on the second's load."""
     logmel = mfcc_to_mel(mfcc, n_mels, dct_type, norm, ref, lifter, as_db=True)
     return mel_to_audio(logmel, sr, 2048, 2.0, fmin, fmax, n_iter, momentum, seed, first_row, length, db_ref=ref)
+
+
+# ------------------------------------------------------------------ non-negative matrix factorisation
+# Frame-major: V [B, T, F] = A [B, T, K] C [B, K, F]; A is sklearn's W (activations), C its H (components).
+
+_NMF_LOSSES = {"frobenius": 0, 2: 0, 2.0: 0, "kullback-leibler": 1, 1: 1, 1.0: 1}
+_NMF_SERVED = ("served: beta_loss 'frobenius' (2) or 'kullback-leibler' (1), the multiplicative-update solver, "
+               "init 'random' or given factors")
+
+
+def nmf_constants() -> dict:
+    """eps (float32's machine epsilon, sklearn's EPSILON) and the served ranges and tiles of csrc/nmf.hip."""
+    d = _constants("syg_nmf_constants", ("max_components", "max_bins", "max_groups", "a_tile_frames", "a_chunk_bins",
+                                         "c_tile_bins", "c_chunk_frames", "sums_chunk", "mfma_min_components"))
+    d["eps"] = float(np.finfo(np.float32).eps)
+    return d
+
+
+def _nmf_loss(who, beta_loss) -> int:
+    if isinstance(beta_loss, bool) or not isinstance(beta_loss, (str, int, float)) or beta_loss not in _NMF_LOSSES:
+        raise ValueError(f"{who}: beta_loss={beta_loss!r} is not served (Itakura-Saito and other beta need powers of AC "
+                         f"per entry); {_NMF_SERVED}")
+    return _NMF_LOSSES[beta_loss]
+
+
+def _nmf_factors(who, V, A, C, K=None):
+    """The shape checks of (V, A, C), without a device: V [B, T, F], A [B, T, K], C [B, K, F] or [1, K, F].  Returns
+    (B, T, F, K, c_shared)."""
+    _f32(V, f"{who}: V", 3, (), "[B, T, F]")
+    B, Tn, F = (int(n) for n in V.shape)
+    if B < 1 or Tn < 1 or F < 1:
+        raise ValueError(f"{who}: empty input (V has shape {list(V.shape)})")
+    if F > 2049:
+        raise ValueError(f"{who}: F={F} bins must be in [1, 2049]")
+    if K is None:
+        K = int(A.shape[-1]) if isinstance(A, torch.Tensor) and A.dim() == 3 else \
+            int(C.shape[1]) if isinstance(C, torch.Tensor) and C.dim() == 3 else None
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= 64:
+        raise ValueError(f"{who}: n_components={K!r} must be an integer in [1, 64]")
+    K = int(K)
+    if A is not None:
+        _f32(A, f"{who}: A", 3, (Tn, K), f"[{B}, {Tn}, {K}]")
+        if A.shape[0] != B:
+            raise ValueError(f"{who}: A must be a float32 tensor [{B}, {Tn}, {K}]")
+    shared = False
+    if C is not None:
+        _f32(C, f"{who}: C", 3, (K, F), f"[{B}, {K}, {F}] or [1, {K}, {F}]")
+        if C.shape[0] != B and C.shape[0] != 1:
+            raise ValueError(f"{who}: C must be a float32 tensor [{B}, {K}, {F}] or [1, {K}, {F}]")
+        shared = C.shape[0] == 1 and B > 1
+    return B, Tn, F, K, shared
+
+
+_NMF_FORMS = {None: -1, "fma": 0, "mfma": 1}
+
+
+def _nmf_on_device(who, V, **others):
+    """V and every other tensor argument are on V's device (a host factor would hand the kernel a host pointer)."""
+    _on_device(V, f"{who}: V")
+    for name, t in others.items():
+        if isinstance(t, torch.Tensor) and t.device != V.device:
+            raise ValueError(f"{who}: {name} must be on the device of V ({V.device}; got {t.device})")
+
+
+def nmf_divergence(V: torch.Tensor, A: torch.Tensor, C: torch.Tensor, beta_loss="frobenius") -> torch.Tensor:
+    """sklearn's _beta_divergence of each clip (syg_nmf_divergence_f32): [B] float64, AC and the sums formed in float64 from
+    the float32 factors.  Frobenius: sum (V - AC)^2 / 2; KL: sum over V > eps of V log(V / max(AC, eps)) - V, plus sum AC."""
+    who = "nmf_divergence"
+    loss = _nmf_loss(who, beta_loss)
+    if A is None or C is None:
+        raise ValueError(f"{who}: A and C must be float32 tensors")
+    B, Tn, F, K, shared = _nmf_factors(who, V, A, C)
+    _nmf_on_device(who, V, A=A, C=C)
+    V, A, C = V.contiguous(), A.contiguous(), C.contiguous()
+    out = torch.empty((B,), dtype=torch.float64, device=V.device)
+    work = _workspace("syg_nmf_work_bytes", B, Tn, F, K, dtype=torch.float64, device=V.device)
+    _call("syg_nmf_divergence_f32", _ptr(V), _ptr(A), _ptr(C), int(shared), B, Tn, F, K, loss, _ptr(out), _ptr(work))
+    return out
+
+
+def nmf(V: torch.Tensor, n_components: Optional[int] = None, *, A0: Optional[torch.Tensor] = None,
+        C0: Optional[torch.Tensor] = None, n_iter: int = 200, beta_loss="frobenius", update_A: bool = True,
+        update_C: bool = True, seed: int = 0, first_row: int = 0, return_trace: bool = False, solver: str = "mu",
+        init: Optional[str] = None, form: Optional[str] = None):
+    """Non-negative matrix factorisation V [B, T, F] ~ A [B, T, K] C [B, K, F] by multiplicative updates (syg_nmf_f32):
+    scikit-learn's NMF(solver="mu", tol=0) in frame-major layout, A its W (activations), C its H (components).  Exactly
+    n_iter iterations run, each the A-step, then the C-step with the new A; returns (A, C), new tensors (copies of A0 and
+    C0 also where a factor is not updated).
+
+    A0 / C0 start the factors; a missing one is drawn by sklearn's init="random" rule, sqrt(mean(V_b) / K) |randn|, from
+    row first_row + b of `seed` (ops.randn; the components take the row's first K F normals, the activations the next
+    T K), so clip b of a batch equals the single clip first_row + b.  C0 may be [1, K, F], one dictionary for every clip,
+    with update_C=False (librosa's fit=False); to learn one dictionary from many clips, reshape them to one clip of B T
+    frames.  return_trace adds [B, n_iter + 1] float64, nmf_divergence before the first and after every iteration; the
+    factors are the same bit for bit with or without it.  form: how the contractions run, "fma" or "mfma" (the exact
+    f32-input MFMA: the same products in another summation order); None takes the measured choice, MFMA from
+    nmf_constants()["mfma_min_components"] components up."""
+    who = "nmf"
+    loss = _nmf_loss(who, beta_loss)
+    if not (form is None or isinstance(form, str)) or form not in _NMF_FORMS:
+        raise ValueError(f"{who}: form must be None, 'fma' or 'mfma' (got {form!r})")
+    if not (isinstance(solver, str) and solver == "mu"):
+        raise ValueError(f"{who}: solver={solver!r} is not served (coordinate descent is sequential per coordinate); {_NMF_SERVED}")
+    if not (init is None or (isinstance(init, str) and init in ("random", "custom"))):
+        raise ValueError(f"{who}: init={init!r} is not served (nndsvd, nndsvda and nndsvdar need an SVD); {_NMF_SERVED}")
+    if isinstance(n_iter, bool) or not isinstance(n_iter, (int, np.integer)) or n_iter < 0:
+        raise ValueError(f"{who}: n_iter must be a non-negative integer (got {n_iter!r})")
+    n_iter = int(n_iter)
+    if n_components is None and A0 is None and C0 is None:
+        raise ValueError(f"{who}: n_components is needed when neither A0 nor C0 is given")
+    B, Tn, F, K, shared = _nmf_factors(who, V, A0, C0, n_components)
+    update_A, update_C = bool(update_A), bool(update_C)
+    if C0 is not None and C0.shape[0] == 1 and B > 1 and update_C:
+        raise ValueError(f"{who}: a shared dictionary C0 [1, {K}, {F}] cannot be updated: pass update_C=False, or reshape "
+                         f"the batch to one clip of B T frames to learn one dictionary")
+    if A0 is None or C0 is None:
+        seed, first_row = RNG.check_seed(seed), RNG.check_rows(first_row, B)
+    _nmf_on_device(who, V, A0=A0, C0=C0)
+    V = V.contiguous()
+    A = A0.contiguous().clone() if A0 is not None else None
+    C = C0.contiguous().clone() if C0 is not None else None
+    if A is None or C is None:
+        scale = torch.sqrt(torch.mean(V, dim=(1, 2), dtype=torch.float64) / K).to(torch.float32)
+        if C is None:
+            C = (randn(B, K * F, seed, first_row).abs_() * scale[:, None]).view(B, K, F)
+        if A is None:
+            A = (randn(B, Tn * K, seed, first_row, offset=K * F).abs_() * scale[:, None]).view(B, Tn, K)
+    work = _workspace("syg_nmf_work_bytes", B, Tn, F, K, dtype=torch.float64, device=V.device)
+
+    def run(n):
+        _call("syg_nmf_f32", _ptr(V), B, Tn, F, K, _ptr(A), _ptr(C), int(shared), n, loss, int(update_A), int(update_C),
+              _NMF_FORMS[form], _ptr(work))
+    if not return_trace:
+        run(n_iter)
+        return A, C
+    trace = torch.empty((B, n_iter + 1), dtype=torch.float64, device=V.device)
+    trace[:, 0] = nmf_divergence(V, A, C, beta_loss)
+    for it in range(n_iter):
+        run(1)
+        trace[:, it + 1] = nmf_divergence(V, A, C, beta_loss)
+    return A, C, trace
+
+
+def nmf_masks(D: torch.Tensor, A: torch.Tensor, C: torch.Tensor, G: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The complex spectra D [B, T, F, 2] split by the soft masks of the factorisation (syg_nmf_masks_f32):
+    out[b, g] = D[b] (sum_k G[g, k] A[t, k] C[k, f]) / max(sum_k A[t, k] C[k, f], eps), [B, n_groups, T, F, 2].
+    G [n_groups, K] weights the components of each group (default: the identity, a group per component); the groups of a
+    partition (columns of G summing to 1) add up to D.  The masks themselves are never written."""
+    who = "nmf_masks"
+    _f32(D, f"{who}: D", 4, (2,), "[B, T, F, 2]")
+    if A is None or C is None:
+        raise ValueError(f"{who}: A and C must be float32 tensors")
+    B, Tn, F, K, shared = _nmf_factors(who, D[..., 0], A, C)
+    if G is not None:
+        _f32(G, f"{who}: G", 2, (K,), f"[n_groups, {K}]")
+        if not 1 <= G.shape[0] <= 64:
+            raise ValueError(f"{who}: n_groups={G.shape[0]} must be in [1, 64]")
+    _nmf_on_device(who, D, A=A, C=C, G=G, out=out)
+    if G is None:
+        G = torch.eye(K, dtype=torch.float32, device=D.device)
+    NG = int(G.shape[0])
+    D, A, C, G = D.contiguous(), A.contiguous(), C.contiguous(), G.contiguous()
+    o = _out(out, (B, NG, Tn, F, 2), D, contiguous=True)
+    _call("syg_nmf_masks_f32", _ptr(D), _ptr(A), _ptr(C), int(shared), _ptr(G), B, Tn, F, K, NG, _ptr(o))
+    return o

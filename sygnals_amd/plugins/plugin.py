@@ -118,6 +118,9 @@ class SygnalsAmdPlugin(_Base):
         from ..core.features import inverse
         for fn in (inverse.griffinlim, inverse.mel_to_stft, inverse.mel_to_audio, inverse.mfcc_to_mel, inverse.mfcc_to_audio):
             registry.add_feature(fn.__name__, fn)
+        from ..core import decompose as dc
+        for fn in (dc.decompose, dc.separate_components):
+            registry.add_feature(fn.__name__, fn)
         registry.add_feature("extract_features", manager.extract_features)
         registry.add_feature("extract_features_batch", manager.extract_features_batch)
 
