@@ -1596,6 +1596,54 @@ int syg_nmf_divergence_f32(const float* V, const float* A, const float* C, int c
 int syg_nmf_masks_f32(const float* D, const float* A, const float* C, int c_shared, const float* G, int64_t B, int64_t T,
                       int64_t F, int64_t K, int64_t n_groups, float* out, void* stream);
 
+/* -------------------------------------------------------------------------------
+ * Self-similarity (csrc/similarity.hip): the k nearest frames of every frame, the dense recurrence matrix of those lists,
+ * librosa.decompose.nn_filter over them and the soft masks of REPET-SIM.  tests/similarity_ref.py is the contract.
+ * Frame-major float32: X [B, T, D] the query frames (row stride ldx >= D, batch stride bsx), Y [B, T', D] the frames
+ * searched (ldy, bsy; bsy = 0 shares one Y), or Y = NULL for self-similarity, where the candidates of row i are the j with
+ * |i - j| >= width.  x_len / y_len [B] int32 on the device, or NULL: frames past a length are neither queries nor candidates.
+ *   syg_sim_knn_f32   row i keeps its min(k, candidates) nearest candidates, ordered by distance, then by index: idx
+ *       [B, T, k] int32 (-1 past the count), dist [B, T, k] (+inf past it), count [B, T] int32.  metric:
+ *       SYG_SIM_SQEUCLIDEAN sum (x - y)^2, SYG_SIM_EUCLIDEAN its root, SYG_SIM_COSINE 1 - x.y / max(|x| |y|, FLT_MIN).
+ *       The selection runs on v_mfma_f32_16x16x4_f32 dot products and the squared norms; the kept distances are formed
+ *       again from the frames themselves and the list put in their order.  Equal frames give bit-equal distances.  Nothing
+ *       of size T T' passes through memory.  work: syg_sim_knn_work_bytes(B, T, T', Y != NULL) bytes on the device (the
+ *       squared norms), 8-byte aligned.  k <= syg_sim_k_max() = 256.
+ *   syg_sim_dense_f32 out [B, T, T'] from the lists: SYG_SIM_CONNECTIVITY 1, SYG_SIM_DISTANCE the distance,
+ *       SYG_SIM_AFFINITY exp(-distance / bandwidth[b]) (bandwidth [B] float64 on the device); 0 elsewhere.  sym keeps
+ *       (i, j) only if i is in j's list too; self sets the diagonal to 1 (0 under SYG_SIM_DISTANCE).  rowmax [B, T], or
+ *       NULL: the largest kept distance of each row, -1 where none is kept; out may be NULL where rowmax is wanted alone.
+ *   syg_nn_filter_f32 out [B, T, F] (contiguous): out[b, i] aggregates S[b, j] (row stride lds, batch stride bss) over row
+ *       i's list.  SYG_NN_MEAN; SYG_NN_AVERAGE sum w S / sum w with w = weights [B, T, k], or exp(-weights / bandwidth[b])
+ *       where bandwidth is given (the weights are then distances); SYG_NN_MEDIAN numpy's median, an input value bit for
+ *       bit at odd counts.  A frame with an empty list (or a zero sum of weights) keeps S[b, i].
+ *   syg_repet_masks_f32  with Sf = min(S, R), R the filtered magnitudes: mask_b = softmask(Sf, margin_b (S - Sf), power),
+ *       mask_f = softmask(S - Sf, margin_f Sf, power), librosa.util.softmask without split_zeros; n cells.
+ * Rejected before any device work: null pointers, sizes outside the served ranges, k outside [1, 256], width < 1, a width
+ * other than 1 with Y, an unknown metric (cityblock has no contraction form), mode or aggregate, a row stride below the
+ * row's length, sym or self on a matrix that is not square, non-positive margins or power.
+ * ------------------------------------------------------------------------------- */
+#define SYG_SIM_EUCLIDEAN 0
+#define SYG_SIM_SQEUCLIDEAN 1
+#define SYG_SIM_COSINE 2
+#define SYG_SIM_CONNECTIVITY 0
+#define SYG_SIM_DISTANCE 1
+#define SYG_SIM_AFFINITY 2
+#define SYG_NN_MEAN 0
+#define SYG_NN_AVERAGE 1
+#define SYG_NN_MEDIAN 2
+int syg_sim_k_max(void);
+int64_t syg_sim_knn_work_bytes(int64_t B, int64_t T, int64_t Ty, int has_y);
+int syg_sim_knn_f32(const float* X, const float* Y, int64_t B, int64_t T, int64_t Ty, int64_t D, int64_t ldx, int64_t ldy,
+                    int64_t bsx, int64_t bsy, const int* x_len, const int* y_len, int64_t k, int64_t width, int metric, int* idx,
+                    float* dist, int* count, void* work, void* stream);
+int syg_sim_dense_f32(const int* idx, const float* dist, const int* count, int64_t B, int64_t T, int64_t Ty, int64_t k, int mode,
+                      int sym, int self, const double* bandwidth, float* out, float* rowmax, void* stream);
+int syg_nn_filter_f32(const float* S, int64_t B, int64_t T, int64_t F, int64_t lds, int64_t bss, const int* idx, const int* count,
+                      int64_t k, const float* weights, const double* bandwidth, int aggregate, float* out, void* stream);
+int syg_repet_masks_f32(const float* S, const float* Sf, int64_t n, double margin_b, double margin_f, double power, float* mask_f,
+                        float* mask_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

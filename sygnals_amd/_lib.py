@@ -227,6 +227,12 @@ SIGNATURES = {
     "syg_nmf_f32": (_i, [_p, _l, _l, _l, _l, _p, _p, _i, _l, _i, _i, _i, _i, _p, _p]),
     "syg_nmf_divergence_f32": (_i, [_p, _p, _p, _i, _l, _l, _l, _l, _i, _p, _p, _p]),
     "syg_nmf_masks_f32": (_i, [_p, _p, _p, _i, _p, _l, _l, _l, _l, _l, _p, _p]),
+    "syg_sim_k_max": (_i, []),
+    "syg_sim_knn_work_bytes": (_l, [_l, _l, _l, _i]),
+    "syg_sim_knn_f32": (_i, [_p, _p, _l, _l, _l, _l, _l, _l, _l, _l, _p, _p, _l, _l, _i, _p, _p, _p, _p, _p]),
+    "syg_sim_dense_f32": (_i, [_p, _p, _p, _l, _l, _l, _l, _i, _i, _i, _p, _p, _p, _p]),
+    "syg_nn_filter_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _l, _p, _p, _i, _p, _p]),
+    "syg_repet_masks_f32": (_i, [_p, _p, _l, _d, _d, _d, _p, _p, _p]),
 }
 
 _lib = None

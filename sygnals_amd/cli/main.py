@@ -968,6 +968,46 @@ def dsp_decompose(input_file, output, n_components, n_iter, loss, seed):
                f"divergence {d0:.6g} -> {d1:.6g}, saved to '{Path(output).name}'.")
 
 
+@dsp_cmd.command("separate-repeating")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", default=None, type=click.Path(), help="Where the background (the repeating part) is written.")
+@click.option("--foreground", default=None, type=click.Path(), help="Where the foreground (what does not repeat) is written.")
+@click.option("--width-seconds", "width_seconds", type=float, default=2.0, show_default=True,
+              help="Frames closer than this are not compared with each other.")
+@click.option("--metric", type=click.Choice(["cosine", "euclidean", "sqeuclidean"]), default="cosine", show_default=True)
+@click.option("--margin-background", "margin_b", type=float, default=2.0, show_default=True)
+@click.option("--margin-foreground", "margin_f", type=float, default=10.0, show_default=True)
+@click.option("--power", type=float, default=2.0, show_default=True, help="Exponent of the soft masks.")
+@click.option("--fs", type=int, default=None, help="Sampling rate of the input (Hz) if the file carries none.")
+def dsp_separate_repeating(input_file, output, foreground, width_seconds, metric, margin_b, margin_f, power, fs):
+    """Split INPUT into a repeating background and a foreground by similarity (REPET-SIM): every STFT frame (n_fft 2048,
+    hop 512) is replaced by the median of its nearest frames at least --width-seconds away, and two soft masks divide the
+    clip between what that median explains and the rest."""
+    if output is None:
+        raise click.UsageError("-o / --output is required: where to write the background.")
+    for name, v in (("--width-seconds", width_seconds), ("--margin-background", margin_b), ("--margin-foreground", margin_f),
+                    ("--power", power)):
+        if not (v > 0 and np.isfinite(v)):
+            raise click.UsageError(f"{name} must be positive (got {v:g}).")
+    x, sr = _load_signal(input_file, fs)
+    if not sr:
+        raise click.UsageError("--fs is required: the input file carries no sampling rate.")
+    if np.size(x) < 1:
+        raise click.UsageError("The input is empty.")
+    from ..core.decompose import separate_repeating
+    try:
+        fg, bg = separate_repeating(np.asarray(x, dtype=np.float32), float(sr), width_seconds=width_seconds, metric=metric,
+                                    margin_background=margin_b, margin_foreground=margin_f, power=power)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    _save_series(bg, sr, output)
+    if foreground is not None:
+        _save_series(fg, sr, foreground)
+    width = max(1, int(round(width_seconds * float(sr) / 512)))
+    click.echo(f"Separated {np.size(x)} samples ({metric}, frames at least {width} apart), background saved to "
+               f"'{Path(output).name}'" + (f", foreground to '{Path(foreground).name}'." if foreground is not None else "."))
+
+
 @dsp_cmd.command("stft")
 @click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
 @click.option("-o", "--output", required=True, type=click.Path())

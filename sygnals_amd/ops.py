@@ -4456,3 +4456,279 @@ def nmf_masks(D: torch.Tensor, A: torch.Tensor, C: torch.Tensor, G: Optional[tor
     o = _out(out, (B, NG, Tn, F, 2), D, contiguous=True)
     _call("syg_nmf_masks_f32", _ptr(D), _ptr(A), _ptr(C), int(shared), _ptr(G), B, Tn, F, K, NG, _ptr(o))
     return o
+
+
+# ------------------------------------------------------------------ self-similarity: k-NN lists, recurrence, nn_filter
+# Frame-major: X [B, T, D] the query frames, Y [B, T', D] the frames searched (X itself by default).  The float64
+# restatement tests/similarity_ref.py is the contract.
+
+SIM_METRICS = {"euclidean": 0, "sqeuclidean": 1, "cosine": 2}
+SIM_MODES = {"connectivity": 0, "distance": 1, "affinity": 2}
+NN_AGGREGATES = {"mean": 0, "average": 1, "median": 2}
+K_MAX = 256                                   # neighbours a row keeps at most (the library's syg_sim_k_max)
+
+
+def similarity_constants() -> dict:
+    """k_max (the longest neighbour list, read from the library) and the names served."""
+    return dict(k_max=int(lib().syg_sim_k_max()), metrics=tuple(SIM_METRICS), modes=tuple(SIM_MODES),
+                aggregates=tuple(NN_AGGREGATES))
+
+
+def _sim_name(who, what, value, table, note=""):
+    if not isinstance(value, str) or value not in table:
+        raise ValueError(f"{who}: {what}={value!r} is not served{note}; served: {', '.join(repr(n) for n in table)}")
+    return table[value]
+
+
+def _sim_metric(who, metric) -> int:
+    return _sim_name(who, "metric", metric, SIM_METRICS, " (cityblock and the other metrics have no dot-product form)")
+
+
+def _sim_int(who, name, v, lo, hi=None):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{who}: {name}={v!r} must be an integer " + (f"in [{lo}, {hi}]" if hi is not None else f">= {lo}"))
+    return int(v)
+
+
+def sim_default_k(T: int, width: int = 1) -> int:
+    """librosa's default neighbour count, min(K_MAX, max(1, 2 ceil(sqrt(max(1, T - 2 width + 1)))))."""
+    return int(min(K_MAX, max(1, 2 * int(np.ceil(np.sqrt(max(1, T - 2 * width + 1)))))))
+
+
+def _sim_frames(who, t, name):
+    """t [B, T, D] checked without a device: the tensor's sizes."""
+    _f32(t, f"{who}: {name}", 3, (), "[B, T, D]")
+    if min(t.shape) < 1:
+        raise ValueError(f"{who}: empty input ({name} has shape {list(t.shape)})")
+    return tuple(int(n) for n in t.shape)
+
+
+def _sim_strided(t):
+    """t [B, T, D] with unit stride along D, its row and batch strides (a copy where rows overlap or a stride is negative)."""
+    t = _unit_stride(t)
+    B, Tn, D = t.shape
+    ld = int(t.stride(1)) if Tn > 1 else D
+    bs = int(t.stride(0)) if B > 1 else 0
+    if ld < D or bs < 0:
+        t = t.contiguous()
+        ld, bs = D, (Tn * D if B > 1 else 0)
+    return t, ld, bs
+
+
+def _sim_lens(who, v, B, Tn, device, name):
+    """A per-clip length list as a device int32 [B] (values in [0, T]), or None."""
+    if v is None:
+        return None
+    host = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+    if host.shape != (B,) or host.dtype.kind not in "iu" or host.min() < 0 or host.max() > Tn:
+        raise ValueError(f"{who}: {name} must hold one integer length in [0, {Tn}] per clip ([{B}])")
+    return torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(device)
+
+
+def sim_knn(X: torch.Tensor, Y: Optional[torch.Tensor] = None, k: Optional[int] = None, width: int = 1,
+            metric: str = "euclidean", x_len=None, y_len=None):
+    """The k nearest frames of every frame (syg_sim_knn_f32): X [B, T, D] float32 on the device (rows may be strided) ->
+    (idx [B, T, k] int32, dist [B, T, k] float32, count [B, T] int32).  Row i keeps its min(k, candidates) nearest
+    candidates ordered by distance, then by index; entries past count are idx = -1, dist = +inf.  Y [B, T', D] (or
+    [1, T', D], one for every clip) are the frames searched, every one a candidate; without it X searches itself and
+    the candidates of row i are the j with |i - j| >= width.  metric: euclidean | sqeuclidean | cosine
+    (1 - x.y / max(|x| |y|, FLT_MIN): a zero frame is at distance 1 from everything).  k=None: sim_default_k(T, width),
+    librosa's rule; k <= K_MAX.  x_len / y_len [B]: ragged batches; frames past a length are neither queries nor
+    candidates.  The dense distance matrix is never written."""
+    who = "sim_knn"
+    code = _sim_metric(who, metric)
+    # (_f32_in would copy a tensor whose last stride is not 1 and knows nothing of rows: the frames keep their row and
+    # batch strides here, so the two stages of the input check are taken apart: _sim_frames, _on_device, _sim_strided)
+    B, Tn, D = _sim_frames(who, X, "X")
+    width = _sim_int(who, "width", width, 1, 1 << 30)
+    Ty = Tn
+    if Y is not None:
+        By, Ty, Dy = _sim_frames(who, Y, "Y")
+        if Dy != D or By not in (1, B):
+            raise ValueError(f"{who}: Y {list(Y.shape)} must be [{B}, T', {D}] or [1, T', {D}] (X is {list(X.shape)})")
+        if width != 1:
+            raise ValueError(f"{who}: width applies to self-similarity; with Y every frame is a candidate (got width={width})")
+    elif y_len is not None:
+        raise ValueError(f"{who}: y_len needs Y (self-similarity takes x_len for both)")
+    k = sim_default_k(Tn, width) if k is None else _sim_int(who, "k", k, 1, K_MAX)
+    _on_device(X, f"{who}: X")
+    if Y is not None and Y.device != X.device:
+        raise ValueError(f"{who}: Y must be on the device of X ({X.device}; got {Y.device})")
+    X, ldx, bsx = _sim_strided(X)
+    ldy = bsy = 0
+    if Y is not None:
+        Y, ldy, bsy = _sim_strided(Y)
+        if Y.shape[0] == 1:
+            bsy = 0
+    xl = _sim_lens(who, x_len, B, Tn, X.device, "x_len")
+    yl = _sim_lens(who, y_len, B, Ty, X.device, "y_len")
+    idx = torch.empty((B, Tn, k), dtype=torch.int32, device=X.device)
+    dist = torch.empty((B, Tn, k), dtype=torch.float32, device=X.device)
+    count = torch.empty((B, Tn), dtype=torch.int32, device=X.device)
+    work = _workspace("syg_sim_knn_work_bytes", B, Tn, Ty, int(Y is not None), dtype=torch.float64, device=X.device)
+    _call("syg_sim_knn_f32", _ptr(X), _ptr(Y), B, Tn, Ty, D, ldx, ldy, bsx, bsy, _ptr(xl), _ptr(yl), k, width, code, _ptr(idx),
+          _ptr(dist), _ptr(count), _ptr(work))
+    idx._syg_cols = count._syg_cols = Ty           # the library's own lists: _sim_check_lists has nothing to find in them
+    return idx, dist, count
+
+
+def _sim_lists(who, idx, dist, count):
+    """The shape checks of a set of lists, without a device: (B, T, k)."""
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 3 or idx.dtype != torch.int32:
+        raise ValueError(f"{who}: idx must be an int32 tensor [B, T, k]")
+    B, Tn, k = (int(n) for n in idx.shape)
+    if B < 1 or Tn < 1 or not 1 <= k <= K_MAX:
+        raise ValueError(f"{who}: idx {list(idx.shape)} must be [B, T, k] with B, T >= 1 and k in [1, {K_MAX}]")
+    if not isinstance(count, torch.Tensor) or count.dtype != torch.int32 or tuple(count.shape) != (B, Tn):
+        raise ValueError(f"{who}: count must be an int32 tensor [{B}, {Tn}]")
+    if dist is not None and (not isinstance(dist, torch.Tensor) or dist.dtype != torch.float32 or tuple(dist.shape) != (B, Tn, k)):
+        raise ValueError(f"{who}: the distances / weights must be a float32 tensor [{B}, {Tn}, {k}]")
+    return B, Tn, k
+
+
+def _sim_check_lists(who, idx, count, n_cols):
+    """The caller's lists hold what the kernels index with: counts in [0, k], the entries below a count in [0, n_cols).
+    Lists that sim_knn made for n_cols columns are marked and pass without the two reductions and their host syncs (the
+    kernels clamp what they index with in any case)."""
+    if getattr(idx, "_syg_cols", None) == n_cols and getattr(count, "_syg_cols", None) == n_cols:
+        return
+    k = idx.shape[2]
+    live = torch.arange(k, device=idx.device)[None, None, :] < count[:, :, None]
+    bad = (count < 0) | (count > k)
+    if bool(bad.any()) or bool((live & ((idx < 0) | (idx >= n_cols))).any()):
+        raise ValueError(f"{who}: count must be in [0, {k}] and the entries of idx below it in [0, {n_cols})")
+
+
+def sim_bandwidth(rowmax: torch.Tensor, who: str = "recurrence_matrix") -> torch.Tensor:
+    """The default bandwidth of the affinities, per clip [B] float64: numpy's median, over the rows that kept a link, of
+    the row's largest kept distance (rowmax [B, T], negative where a row kept nothing).  A clip without a link gets 1
+    (it has no affinity to scale); a clip whose bandwidth comes out 0 raises ValueError."""
+    r = rowmax.to(torch.float64)
+    has = r >= 0
+    n = has.sum(dim=1)
+    s = torch.sort(torch.where(has, r, torch.full_like(r, float("inf"))), dim=1).values
+    lo = torch.clamp((n - 1) // 2, min=0)[:, None]
+    hi = torch.clamp(n // 2, max=r.shape[1] - 1)[:, None]
+    bw = 0.5 * (torch.gather(s, 1, lo) + torch.gather(s, 1, hi))[:, 0]
+    bw = torch.where(n > 0, bw, torch.ones_like(bw))
+    if bool((bw == 0).any()):
+        raise ValueError(f"{who}: the default bandwidth of a clip is 0 (its median nearest-neighbour distance); "
+                         "pass bandwidth, or use mode='connectivity'")
+    return bw
+
+
+def _sim_bandwidth_arg(who, bandwidth, B, device):
+    """A caller's bandwidth (a positive number, or one per clip) as a float64 device tensor [B]."""
+    a = np.asarray(bandwidth.detach().cpu().numpy() if isinstance(bandwidth, torch.Tensor) else bandwidth, dtype=np.float64)
+    if a.ndim == 0:
+        a = np.full((B,), float(a))
+    if a.shape != (B,) or not np.all(np.isfinite(a)) or np.any(a <= 0):
+        raise ValueError(f"{who}: bandwidth must be a positive finite number, or one per clip ([{B}])")
+    return torch.from_numpy(a).to(device)
+
+
+def sim_dense(idx: torch.Tensor, dist: torch.Tensor, count: torch.Tensor, n_cols: Optional[int] = None, *,
+              mode: str = "connectivity", sym: bool = False, bandwidth=None, self: bool = False, return_bandwidth: bool = False):
+    """The dense recurrence matrix [B, T, n_cols] float32 of a set of lists (syg_sim_dense_f32): connectivity 1, distance
+    the distance, affinity exp(-distance / bandwidth); 0 elsewhere.  sym keeps (i, j) only if each is in the other's
+    list; self sets the diagonal to 1 (0 under distance).  bandwidth=None: sim_bandwidth of the rows' largest kept
+    distances, taken after the sym pruning."""
+    who = "recurrence_matrix"
+    code = _sim_name(who, "mode", mode, SIM_MODES)
+    B, Tn, k = _sim_lists(who, idx, dist, count)
+    if dist is None:
+        raise ValueError(f"{who}: the distances must be a float32 tensor [{B}, {Tn}, {k}]")
+    n_cols = Tn if n_cols is None else _sim_int(who, "n_cols", n_cols, 1, 1 << 30)
+    sym, self = bool(sym), bool(self)
+    if (sym or self) and n_cols != Tn:
+        raise ValueError(f"{who}: sym and self need a square matrix (T={Tn}, T'={n_cols})")
+    if bandwidth is not None and code != 2:
+        raise ValueError(f"{who}: bandwidth applies to mode='affinity' (got mode={mode!r})")
+    _on_device(idx, f"{who}: idx")
+    if dist.device != idx.device or count.device != idx.device:
+        raise ValueError(f"{who}: idx, dist and count must be on one device")
+    idx, dist, count = idx.contiguous(), dist.contiguous(), count.contiguous()
+    _sim_check_lists(who, idx, count, n_cols)
+    bw = None
+    if code == 2:
+        if bandwidth is None:
+            rowmax = torch.empty((B, Tn), dtype=torch.float32, device=idx.device)
+            _call("syg_sim_dense_f32", _ptr(idx), _ptr(dist), _ptr(count), B, Tn, n_cols, k, 1, int(sym), 0, None, None, _ptr(rowmax))
+            bw = sim_bandwidth(rowmax)
+        else:
+            bw = _sim_bandwidth_arg(who, bandwidth, B, idx.device)
+    out = torch.empty((B, Tn, n_cols), dtype=torch.float32, device=idx.device)
+    _call("syg_sim_dense_f32", _ptr(idx), _ptr(dist), _ptr(count), B, Tn, n_cols, k, code, int(sym), int(self), _ptr(bw), _ptr(out), None)
+    return (out, bw) if return_bandwidth else out
+
+
+def recurrence_matrix(X: torch.Tensor, Y: Optional[torch.Tensor] = None, *, k: Optional[int] = None, width: int = 1,
+                      metric: str = "euclidean", sym: bool = False, mode: str = "connectivity", bandwidth=None,
+                      self: bool = False, x_len=None, y_len=None) -> torch.Tensor:
+    """librosa.segment.recurrence_matrix (Y=None) / cross_similarity (Y given) of frame-major features X [B, T, D] ->
+    [B, T, T'] float32, dense: sim_knn, then sim_dense.  Row i holds the links of frame i.  sym and self apply to
+    self-similarity."""
+    who = "recurrence_matrix"
+    _sim_name(who, "mode", mode, SIM_MODES)
+    if Y is not None and (sym or self):
+        raise ValueError(f"{who}: sym and self apply to self-similarity, not to a cross-similarity with Y")
+    if bandwidth is not None and mode != "affinity":
+        raise ValueError(f"{who}: bandwidth applies to mode='affinity' (got mode={mode!r})")
+    idx, dist, count = sim_knn(X, Y, k, width, metric, x_len, y_len)
+    return sim_dense(idx, dist, count, int(Y.shape[1]) if Y is not None else None, mode=mode, sym=sym, bandwidth=bandwidth, self=self)
+
+
+def nn_filter(S: torch.Tensor, idx: torch.Tensor, count: torch.Tensor, weights: Optional[torch.Tensor] = None,
+              aggregate: str = "mean", bandwidth=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """librosa.decompose.nn_filter on frame-major S [B, T, F] (syg_nn_filter_f32): out[b, i] aggregates S[b, j] over row
+    i's list (idx [B, T, k], count [B, T]; sim_knn's, or the caller's).  aggregate: mean | average (sum w S / sum w with
+    w = weights [B, T, k]; with bandwidth the weights are distances and w = exp(-weights / bandwidth)) | median (numpy's:
+    the mean of the two middle values at an even count, an input value bit for bit at an odd one).  A frame with an
+    empty list keeps S[b, i]."""
+    who = "nn_filter"
+    code = _sim_name(who, "aggregate", aggregate, NN_AGGREGATES)
+    B, Tn, F = _sim_frames(who, S, "S")
+    lb, lt, k = _sim_lists(who, idx, weights, count)
+    if (lb, lt) != (B, Tn):
+        raise ValueError(f"{who}: idx {list(idx.shape)} must be [{B}, {Tn}, k] (S is {list(S.shape)})")
+    if code == 1 and weights is None:
+        raise ValueError(f"{who}: aggregate='average' needs weights [{B}, {Tn}, {k}] (the lists' affinities, or distances with bandwidth)")
+    if code != 1 and (weights is not None or bandwidth is not None):
+        raise ValueError(f"{who}: weights and bandwidth apply to aggregate='average' (got {aggregate!r})")
+    _on_device(S, f"{who}: S")
+    for name, t in (("idx", idx), ("count", count), ("weights", weights)):
+        if t is not None and t.device != S.device:
+            raise ValueError(f"{who}: {name} must be on the device of S ({S.device}; got {t.device})")
+    S, lds, bss = _sim_strided(S)
+    idx, count = idx.contiguous(), count.contiguous()
+    weights = weights.contiguous() if weights is not None else None
+    _sim_check_lists(who, idx, count, Tn)
+    bw = _sim_bandwidth_arg(who, bandwidth, B, S.device) if bandwidth is not None else None
+    o = _out(out, (B, Tn, F), S, contiguous=True)
+    _call("syg_nn_filter_f32", _ptr(S), B, Tn, F, lds, bss, _ptr(idx), _ptr(count), k, _ptr(weights), _ptr(bw), code, _ptr(o))
+    return o
+
+
+def _repet_number(who, name, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v <= 0:
+        raise ValueError(f"{who}: {name}={v!r} must be a positive finite number")
+    return float(v)
+
+
+def repet_masks(S: torch.Tensor, Sf: torch.Tensor, margin_b: float = 2.0, margin_f: float = 10.0, power: float = 2.0):
+    """The two soft masks of REPET-SIM (syg_repet_masks_f32) from magnitudes S and their nn_filter Sf, same shape: with
+    R = min(S, Sf), mask_b = softmask(R, margin_b (S - R), power) and mask_f = softmask(S - R, margin_f R, power)
+    (librosa.util.softmask).  Returns (mask_f, mask_b)."""
+    who = "repet_masks"
+    mb, mf, pw = (_repet_number(who, n, v) for n, v in (("margin_b", margin_b), ("margin_f", margin_f), ("power", power)))
+    if not isinstance(S, torch.Tensor) or S.dtype != torch.float32 or S.numel() < 1:
+        raise ValueError(f"{who}: S must be a non-empty float32 tensor")
+    if not isinstance(Sf, torch.Tensor) or Sf.dtype != torch.float32 or Sf.shape != S.shape:
+        raise ValueError(f"{who}: Sf must be a float32 tensor {list(S.shape)}")
+    _on_device(S, f"{who}: S")
+    if Sf.device != S.device:
+        raise ValueError(f"{who}: Sf must be on the device of S ({S.device}; got {Sf.device})")
+    S, Sf = S.contiguous(), Sf.contiguous()
+    Mf, Mb = torch.empty_like(S), torch.empty_like(S)
+    _call("syg_repet_masks_f32", _ptr(S), _ptr(Sf), S.numel(), mb, mf, pw, _ptr(Mf), _ptr(Mb))
+    return Mf, Mb

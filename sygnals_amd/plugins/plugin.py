@@ -119,8 +119,10 @@ class SygnalsAmdPlugin(_Base):
         for fn in (inverse.griffinlim, inverse.mel_to_stft, inverse.mel_to_audio, inverse.mfcc_to_mel, inverse.mfcc_to_audio):
             registry.add_feature(fn.__name__, fn)
         from ..core import decompose as dc
-        for fn in (dc.decompose, dc.separate_components):
+        for fn in (dc.decompose, dc.separate_components, dc.nn_filter, dc.separate_repeating):
             registry.add_feature(fn.__name__, fn)
+        from ..core import similarity
+        registry.add_feature("recurrence_matrix", similarity.recurrence_matrix)
         registry.add_feature("extract_features", manager.extract_features)
         registry.add_feature("extract_features_batch", manager.extract_features_batch)
 
