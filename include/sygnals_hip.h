@@ -1644,6 +1644,49 @@ int syg_nn_filter_f32(const float* S, int64_t B, int64_t T, int64_t F, int64_t l
 int syg_repet_masks_f32(const float* S, const float* Sf, int64_t n, double margin_b, double margin_f, double power, float* mask_f,
                         float* mask_b, void* stream);
 
+/* -------------------------------------------------------------------------------
+ * Viterbi decoding (csrc/sequence.hip): the most likely state path of a hidden Markov chain, the recurrence of
+ * librosa.sequence.viterbi, viterbi_discriminative and viterbi_binary.  tests/sequence_ref.py is the contract.
+ *   emission   [B, S, T] float32 (SYG_VITERBI_F32) or float64 (SYG_VITERBI_F64) on the device, addressed as
+ *              emission[b stride_b + j stride_s + t stride_t] (element strides, none negative): [B, S, T] and [B, T, S]
+ *              blocks are both read in whole lines.  log_domain: the values are log-probabilities and are used as given;
+ *              otherwise lp = log(emission + eps), taken in float64.
+ *   lengths    [B] int32 on the device, each in 1 .. T, or NULL (every sequence has T frames): states past a length
+ *              are -1.  (The kernels clamp a length into 1 .. T; the caller checks it.)
+ *   log_trans  float64 [S, S] (row = source state), batch stride trans_bs = 0 (shared) or S S; log_init float64 [S],
+ *              init_bs = 0 or S; log_marginal float64 [S] (marginal_bs = 0 or S), or NULL: lp[t, j] -= log_marginal[j],
+ *              the discriminative form.  These logs are made on the host.
+ *   value[0, j] = lp[0, j] + log_init[j];  ptr[t, j] = the FIRST i that maximises value[t-1, i] + log_trans[i, j];
+ *   value[t, j] = lp[t, j] + (value[t-1, ptr] + log_trans[ptr, j]);  states[len-1] = the first argmax of value[len-1],
+ *   states[t] = ptr[t+1, states[t+1]];  logp = value[len-1, states[len-1]].  Scores, additions and comparisons are
+ *   float64 in this order and there are no atomics: the same call gives the same bits, a batch equals its rows.
+ *   states [B, T] int32, logp [B] float64.  work: syg_viterbi_work_bytes(B, S, T) bytes on the device, 8-byte aligned
+ *   (the back pointers: one byte each up to 256 states, two beyond).
+ *   form: SYG_VITERBI_AUTO takes syg_viterbi_form(B, S); SYG_VITERBI_WIDE one workgroup a sequence and one thread a
+ *   state (any S); SYG_VITERBI_NARROW one lane a sequence, S <= SYG_VITERBI_S_NARROW.  Both forms give the same bits.
+ * Rejected before any device work: null pointers, an unknown dtype or form, S outside 1 .. SYG_VITERBI_S_MAX, B or T
+ * below 1, more than 2^40 back pointers, a workspace that is too small, a negative stride, a batch stride of a table that
+ * is neither 0 nor the table's size, an eps that is negative or not finite, the narrow form above its S.
+ * ------------------------------------------------------------------------------- */
+#define SYG_VITERBI_F32 0
+#define SYG_VITERBI_F64 1
+#define SYG_VITERBI_AUTO 0
+#define SYG_VITERBI_WIDE 1
+#define SYG_VITERBI_NARROW 2
+enum {
+  SYG_VITERBI_S_MAX = 0,     /* largest S */
+  SYG_VITERBI_S_LDS = 1,     /* largest S whose log_trans lives in LDS (beyond it is read from global memory) */
+  SYG_VITERBI_S_NARROW = 2,  /* largest S of the narrow form */
+  SYG_VITERBI_TILE = 3       /* frames of an emission tile staged through LDS */
+};
+int64_t syg_viterbi_constants(int key);
+int syg_viterbi_form(int64_t B, int64_t S);
+int64_t syg_viterbi_work_bytes(int64_t B, int64_t S, int64_t T);
+int syg_viterbi_f32(const void* emission, int dtype, int log_domain, int64_t stride_b, int64_t stride_s, int64_t stride_t,
+                    int64_t B, int64_t S, int64_t T, const int* lengths, const double* log_trans, int64_t trans_bs,
+                    const double* log_init, int64_t init_bs, const double* log_marginal, int64_t marginal_bs, double eps,
+                    void* work, int64_t work_bytes, int* states, double* logp, int form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -233,6 +233,10 @@ SIGNATURES = {
     "syg_sim_dense_f32": (_i, [_p, _p, _p, _l, _l, _l, _l, _i, _i, _i, _p, _p, _p, _p]),
     "syg_nn_filter_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _l, _p, _p, _i, _p, _p]),
     "syg_repet_masks_f32": (_i, [_p, _p, _l, _d, _d, _d, _p, _p, _p]),
+    "syg_viterbi_constants": (_l, [_i]),
+    "syg_viterbi_form": (_i, [_l, _l]),
+    "syg_viterbi_work_bytes": (_l, [_l, _l, _l]),
+    "syg_viterbi_f32": (_i, [_p, _i, _i, _l, _l, _l, _l, _l, _l, _p, _p, _l, _p, _l, _p, _l, _d, _p, _l, _p, _p, _i, _p]),
 }
 
 _lib = None

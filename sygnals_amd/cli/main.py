@@ -455,6 +455,62 @@ def dsp_dtw(input_file_1, input_file_2, output, metric, subseq, on):
     click.echo(f"DTW path ({len(wp)} steps) saved to '{Path(output).name}'.")
 
 
+@dsp_cmd.command("viterbi")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output", required=True, type=click.Path())
+@click.option("--key", default="prob", show_default=True, help="The array of the NPZ file that holds the probabilities.")
+@click.option("--kind", type=click.Choice(["plain", "discriminative", "binary"]), default="plain", show_default=True,
+              help="plain: [S, T] likelihoods; discriminative: [S, T] posteriors, each frame summing to 1; binary: [n_labels, T] "
+                   "probabilities that each label is active.")
+@click.option("--transition", type=click.Choice(["uniform", "loop", "cycle", "local"]), default="loop", show_default=True)
+@click.option("--self-prob", "self_prob", type=float, default=0.9, show_default=True,
+              help="Probability of staying in a state (loop, cycle).")
+@click.option("--width", type=int, default=3, show_default=True, help="Width of the band in states (local).")
+def dsp_viterbi(input_file, output, key, kind, transition, self_prob, width):
+    """Decode the most likely state sequence of PROB.npz (librosa.sequence.viterbi and its variants).  An NPZ output holds
+    `states` and `logp`; any other suffix a table frame, state (one state column per label for --kind binary)."""
+    from ..core import sequence as SQ
+    if not 0.0 <= self_prob <= 1.0:
+        raise click.UsageError(f"--self-prob must lie in [0, 1] (got {self_prob:g}).")
+    if width < 1:
+        raise click.UsageError(f"--width must be at least 1 (got {width}).")
+    res = sio.read_data(input_file)
+    if not isinstance(res, dict):
+        raise click.UsageError("The input must be an NPZ file that holds the probabilities ([S, T], or [n_labels, T] for --kind binary).")
+    if key not in res:
+        raise click.UsageError(f"The input holds no array '{key}' (it holds: {', '.join(sorted(res))}); name it with --key.")
+    prob = np.asarray(res[key])
+    if prob.ndim != 2 or prob.dtype.kind != "f":
+        raise click.UsageError(f"'{key}' must be a 2-D array of floating-point probabilities, got shape {prob.shape} of {prob.dtype}.")
+    n = 2 if kind == "binary" else prob.shape[0]
+    try:
+        if transition == "uniform":
+            tr = SQ.transition_uniform(n)
+        elif transition == "loop":
+            tr = SQ.transition_loop(n, self_prob)
+        elif transition == "cycle":
+            tr = SQ.transition_cycle(n, self_prob)
+        else:
+            tr = SQ.transition_local(n, width)
+        decode = {"plain": SQ.viterbi, "discriminative": SQ.viterbi_discriminative, "binary": SQ.viterbi_binary}[kind]
+        states, logp = decode(prob, tr, return_logp=True)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    if Path(output).suffix.lower() == ".npz":
+        sio.save_data({"states": states, "logp": np.asarray(logp, dtype=np.float64)}, output)
+    else:
+        cols = {"frame": np.arange(prob.shape[1])}
+        if kind == "binary":
+            cols.update({f"state_{l}": states[l] for l in range(states.shape[0])})
+        else:
+            cols["state"] = states
+        try:
+            sio.save_data(pd.DataFrame(cols), output)
+        except ValueError as e:
+            raise click.UsageError(str(e))
+    click.echo(f"Viterbi path ({kind}, {n} states, {prob.shape[1]} frames) saved to '{Path(output).name}'.")
+
+
 def _load_pair(input_file_1, input_file_2, fs):
     """Two signals of ONE sampling rate: --fs when given, else the rate the files carry (both, and equal) or none."""
     x, sr_x = _load_signal(input_file_1, None)

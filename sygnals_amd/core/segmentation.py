@@ -135,6 +135,50 @@ def segment_by_silence(y, sr: int, threshold_db: float = -40.0, min_silence_dura
                               padding_sec)
 
 
+def detect_activity_batch(y, sr: int, *, frame_length: int = 2048, hop_length: int = 512, threshold: float = 0.02,
+                          self_prob=(0.5, 0.6)):
+    """A smoothed activity mask of every clip: y [B, L] float32 on the device -> [B, T] int32 of 0 (inactive) / 1 (active).
+    librosa's documented Viterbi recipe on the device's own RMS (our definition; nothing here is pinned to librosa):
+        r = (rms - threshold) / std(rms);  p = 1 / (1 + exp(-r));
+        viterbi_discriminative([1 - p, p], transition_loop(2, self_prob))
+    with rms the centred frame RMS of syg_frame_stats_f32, the population standard deviation over the clip's frames and
+    r, p in float64.  A clip of constant RMS (std = 0) reads as inactive in every frame, never as NaN.  sr is not used by
+    the recipe; it is taken for the signature the segmenters share."""
+    import torch
+    from .._sequence import transition_loop
+    if not isinstance(y, torch.Tensor) or y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError("detect_activity_batch: y must be a float32 tensor [B, L]")
+    if frame_length < 1 or hop_length < 1:
+        raise ValueError("detect_activity_batch: frame_length and hop_length must be positive")
+    if not np.isfinite(threshold):
+        raise ValueError("detect_activity_batch: threshold must be finite")
+    trans = transition_loop(2, self_prob)
+    st = ops.frame_stats(y, frame_length, hop_length, True, mask=1 << _ROW_RMS)
+    rms = st[:, _ROW_RMS].to(torch.float64)
+    std = rms.std(dim=1, unbiased=False, keepdim=True)
+    flat = std == 0
+    r = (rms - float(threshold)) / torch.where(flat, torch.ones_like(std), std)
+    p = torch.where(flat, torch.zeros_like(r), 1.0 / (1.0 + torch.exp(-r)))
+    return ops.viterbi(torch.stack([1.0 - p, p], dim=1), trans, p_state=np.array([0.5, 0.5]))
+
+
+def segment_by_activity(y, sr: int, frame_length: int = 2048, hop_length: int = 512, threshold: float = 0.02,
+                        self_prob=(0.5, 0.6)) -> List[Tuple[int, int]]:
+    """(start, end) sample pairs of the active stretches of a 1-D signal, in the shape segment_by_silence returns: the
+    runs of 1 in detect_activity_batch's mask, frame a starting at sample a * hop_length."""
+    y = np.asarray(y)
+    if y.ndim != 1:
+        raise ValueError("Input signal y must be 1D.")
+    ops.require_gpu()
+    if y.size == 0:
+        return []
+    mask = detect_activity_batch(ops.to_device_f32(y[None, :]), sr, frame_length=frame_length, hop_length=hop_length,
+                                 threshold=threshold, self_prob=self_prob)[0].cpu().numpy()
+    edges = np.flatnonzero(np.diff(np.concatenate(([0], (mask == 1).astype(np.int8), [0]))))
+    return [(int(a) * hop_length, min(len(y), int(b) * hop_length)) for a, b in zip(edges[0::2], edges[1::2])
+            if int(a) * hop_length < len(y)]
+
+
 def segment_by_event(y, sr: int, event_times_sec, segment_duration_sec: Optional[float] = None,
                      pre_event_sec: float = 0.05, post_event_sec: float = 0.2) -> List[Tuple[int, int]]:
     y = np.asarray(y)

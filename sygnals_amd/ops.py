@@ -24,6 +24,7 @@ from . import _pcen as PC
 from . import _resample as RS
 from . import _rhythm as RH
 from . import _rng as RNG
+from . import _sequence as SQ
 from . import _specaug as SA
 from . import _tables as T
 from ._fftplan import (MAX_LDS_FFT, MAX_MIXED_FFT, MAX_ROWS, conv_fft_len, fft_plan, is_pow2,      # noqa: F401 (re-exported)
@@ -146,7 +147,7 @@ def _out(out, shape, x: torch.Tensor, what: str = "out", dtype=torch.float32, co
 _SILENT_SIZERS = frozenset(("syg_pack_rows_work_bytes", "syg_welch_work_bytes", "syg_csd_work_bytes",
                             "syg_onset_strength_work_bytes", "syg_dwt_work_bytes", "syg_dynamics_work_bytes",
                             "syg_spec_augment_work_bytes", "syg_tempogram_work_bytes", "syg_tempo_pick_work_bytes",
-                            "syg_beat_local_score_work_bytes", "syg_tuning_hist_work_bytes"))
+                            "syg_beat_local_score_work_bytes", "syg_tuning_hist_work_bytes", "syg_viterbi_work_bytes"))
 
 
 def _work_bytes(entry: str, *args, error: Optional[Exception] = None) -> int:
@@ -4732,3 +4733,120 @@ def repet_masks(S: torch.Tensor, Sf: torch.Tensor, margin_b: float = 2.0, margin
     Mf, Mb = torch.empty_like(S), torch.empty_like(S)
     _call("syg_repet_masks_f32", _ptr(S), _ptr(Sf), S.numel(), mb, mf, pw, _ptr(Mf), _ptr(Mb))
     return Mf, Mb
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Viterbi decoding (csrc/sequence.hip; the host side -- builders, checks, log tables -- is _sequence.py)
+
+VITERBI_FORMS = {None: 0, "wide": 1, "narrow": 2}
+VITERBI_WORK_MAX = 256 << 20                      # bytes of back pointers a launch takes at most: the batch goes in pieces
+_VITERBI_KEYS = ("s_max", "s_lds", "s_narrow", "tile")                                    # SYG_VITERBI_* of include/sygnals_hip.h
+_VITERBI_DTYPES = {torch.float32: 0, torch.float64: 1}
+
+
+def viterbi_constants() -> dict:
+    """The figures syg_viterbi_f32 rests on (the library owns them): s_max the largest S, s_lds the largest S whose
+    transition table lives in LDS, s_narrow the largest S of the narrow form, tile the frames of an emission tile; and
+    work_max, the bytes of back pointers above which viterbi() decodes the batch in pieces."""
+    return dict(_constants("syg_viterbi_constants", _VITERBI_KEYS), work_max=VITERBI_WORK_MAX)
+
+
+def viterbi_work_bytes(B: int, S: int, T: int) -> int:
+    """Bytes of the back-pointer workspace of B sequences of T frames over S states (syg_viterbi_work_bytes)."""
+    return _work_bytes("syg_viterbi_work_bytes", int(B), int(S), int(T))
+
+
+def viterbi_form(B: int, S: int) -> str:
+    """The form the library's rule takes for B sequences over S states: 'wide' or 'narrow'."""
+    f = int(lib().syg_viterbi_form(int(B), int(S)))
+    if f < 0:
+        raise ValueError(f"viterbi: B = {B}, S = {S} is not served ({SQ.SERVED})")
+    return {1: "wide", 2: "narrow"}[f]
+
+
+def _viterbi_host(v) -> np.ndarray:
+    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+
+def _viterbi_table_dev(a: np.ndarray) -> torch.Tensor:
+    """A float64 table on the device; the small ones (shared transition matrices, initial rows) are kept."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.size <= 4096:
+        return _cached(("viterbi", a.shape, a.tobytes()), lambda: _dev(a), limit=64)
+    return _dev(a)
+
+
+def viterbi(prob: Optional[torch.Tensor] = None, transition=None, *, log_prob: Optional[torch.Tensor] = None, p_init=None,
+            p_state=None, lengths=None, eps: Optional[float] = None, form: Optional[str] = None, return_logp: bool = False,
+            out: Optional[torch.Tensor] = None, chunk: Optional[int] = None):
+    """The most likely state path of every clip (syg_viterbi_f32; tests/sequence_ref.py is the definition).
+    prob [B, S, T] float32 or float64 on the device, any strides (a [B, T, S] block is passed as its transpose(1, 2)
+    view) -> states [B, T] int32, and logp [B] float64 with return_logp.
+    transition [S, S] or one per clip [B, S, S], p_init [S] or [B, S] (default 1 / S) and p_state (None: the plain
+    decoder; given: the discriminative one, log(prob + eps) - log(p_state + eps)) are host arrays or tensors of
+    probabilities; their logs are taken on the host in float64 with eps, which defaults to the smallest normal number of
+    prob's dtype.  Only log(prob + eps) is taken on the device, in float64.
+    log_prob= instead of prob: the emissions are log-probabilities and so are transition, p_init (default log(1 / S)) and
+    p_state: every table is used as given, no log is taken, eps plays no part.
+    lengths [B] integers in 1 .. T: states past a clip's length are -1.  form: None (the library's rule), 'wide' or
+    'narrow' (S <= s_narrow); both give the same bits.  out: an int32 [B, T] tensor for the states.  The batch is decoded
+    in pieces of `chunk` clips (default: as many as keep the back pointers under work_max bytes), which changes no bit.
+    Values outside [0, 1] or NaN in prob are not looked for (that would be a device reduction and a sync)."""
+    who = "viterbi"
+    if (prob is None) == (log_prob is None):
+        raise ValueError(f"{who}: give either prob or log_prob=, not both and not neither")
+    log_dom = log_prob is not None
+    x = log_prob if log_dom else prob
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype not in _VITERBI_DTYPES or min(x.shape) < 1:
+        raise ValueError(f"{who}: {'log_prob' if log_dom else 'prob'} must be a non-empty float32 or float64 tensor [B, S, T]")
+    B, S, Tn = (int(n) for n in x.shape)
+    K = viterbi_constants()
+    if S > K["s_max"]:
+        raise ValueError(f"{who}: S = {S} states is above the cap of {K['s_max']} ({SQ.SERVED})")
+    if transition is None:
+        raise ValueError(f"{who}: transition is required ({SQ.SERVED})")
+    if form not in VITERBI_FORMS:
+        raise ValueError(f"{who}: form={form!r} is not served; served: None, 'wide', 'narrow'")
+    if form == "narrow" and S > K["s_narrow"]:
+        raise ValueError(f"{who}: the narrow form serves S <= {K['s_narrow']}, not S = {S}")
+    if log_dom:
+        e = 0.0
+    else:
+        e = SQ.tiny(np.float32 if x.dtype == torch.float32 else np.float64) if eps is None else float(eps)
+        if not np.isfinite(e) or e < 0:
+            raise ValueError(f"{who}: eps={eps!r} must be finite and not negative")
+    tr = SQ.check_transition(who, _viterbi_host(transition), S, B, stochastic=not log_dom)
+    if p_init is None:
+        pi = np.full(S, np.log(1.0 / S) if log_dom else 1.0 / S)
+    else:
+        pi = SQ.check_distribution(who, "p_init", _viterbi_host(p_init), S, B, stochastic=not log_dom)
+    ps = None if p_state is None else SQ.check_distribution(who, "p_state", _viterbi_host(p_state), S, B, stochastic=not log_dom)
+    lens = None
+    if lengths is not None:
+        lens = np.asarray(_viterbi_host(lengths))
+        if lens.shape != (B,) or lens.dtype.kind not in "iu" or lens.min() < 1 or lens.max() > Tn:
+            raise ValueError(f"{who}: lengths must hold one integer in [1, {Tn}] per clip ([{B}])")
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or chunk < 1):
+        raise ValueError(f"{who}: chunk={chunk!r} must be a positive integer")
+    states = _out(out, (B, Tn), x, dtype=torch.int32, contiguous=True)
+    _on_device(x, f"{who}: {'log_prob' if log_dom else 'prob'}")
+
+    def table(a):
+        return None if a is None else _viterbi_table_dev(a if log_dom else SQ.log_table(a, e))
+    lt, li, lm = table(tr), table(pi), table(ps)
+    ld = None if lens is None else torch.from_numpy(np.ascontiguousarray(lens.astype(np.int32))).to(x.device)
+    logp = torch.empty(B, dtype=torch.float64, device=x.device)
+    per = viterbi_work_bytes(1, S, Tn)
+    Bc = min(B, int(chunk) if chunk is not None else max(1, VITERBI_WORK_MAX // per))
+    work = _workspace("syg_viterbi_work_bytes", Bc, S, Tn, dtype=torch.float64, device=x.device)
+    sb, ss, st = (int(v) for v in x.stride())
+    for b0 in range(0, B, Bc):
+        n = min(Bc, B - b0)
+
+        def piece(t, per_clip):
+            return None if t is None else _ptr(t[b0:b0 + n] if per_clip else t)
+        _call("syg_viterbi_f32", _ptr(x[b0:b0 + n]), _VITERBI_DTYPES[x.dtype], int(log_dom), sb, ss, st, n, S, Tn,
+              piece(ld, True), piece(lt, tr.ndim == 3), S * S if tr.ndim == 3 else 0, piece(li, pi.ndim == 2),
+              S if pi.ndim == 2 else 0, piece(lm, ps is not None and ps.ndim == 2), S if ps is not None and ps.ndim == 2 else 0,
+              e, _ptr(work), _nbytes(work), _ptr(states[b0:b0 + n]), _ptr(logp[b0:b0 + n]), VITERBI_FORMS[form])
+    return (states, logp) if return_logp else states
