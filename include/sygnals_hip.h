@@ -1687,6 +1687,72 @@ int syg_viterbi_f32(const void* emission, int dtype, int log_domain, int64_t str
                     const double* log_init, int64_t init_bs, const double* log_marginal, int64_t marginal_bs, double eps,
                     void* work, int64_t work_bytes, int* states, double* logp, int form, void* stream);
 
+/* -------------------------------------------------------------------------------
+ * Structure analysis (csrc/structure.hip): what librosa.segment does with a recurrence matrix and the feature sequence
+ * behind it.  tests/structure_ref.py is the contract.  Matrices are float32 [B, rows, cols] on the device with a row stride
+ * (ld*) and a batch stride (bs*, 0 shares one matrix); outputs are contiguous.
+ *   syg_lag_shear_f32   recurrence_to_lag (inverse = 0) and lag_to_recurrence (inverse = 1) of square matrices [t, t].
+ *       n = 2 t (pad = 1) or t.  axis 1 (librosa's -1): lag [n, t], lag[l, i] = R~[(l + i) mod n, i], R~ being R with zero
+ *       rows appended; rec[r, i] = lag[(r - i) mod n, i], r < t.  axis 0: the transpose of all of it, lag [t, n].  A read
+ *       and a write an element.
+ *   syg_path_enhance_f32   out[b, r, c] = max over filters f of sum over the taps e in [fstart[f], fstart[f + 1]) of
+ *       w_e R~[b, r + dr_e, c + dc_e], clipped at 0 with clip = 1.  R [B, T, T'] may be rectangular; R~ extends it by the
+ *       boundary rule `mode` (scipy.ndimage's: SYG_BOUNDARY_*; cval fills under SYG_BOUNDARY_CONSTANT), folded as often
+ *       as the offsets need.  taps: int32 [n_taps, 4] on the device, (dr, dc, the weight's float32 bits, 0); fstart int32
+ *       [n_filters + 1] on the device.  dr_min .. dc_max: the extent of the offsets; each spans at most
+ *       SYG_STRUCT_PATH_SPAN_MAX.  (The kernel clamps a tap's offsets into that extent and fstart into [0, n_taps].)  The
+ *       taps of a filter are summed in list order into four float32 partial sums (tap e into sum e mod 4, counted from
+ *       the filter's first tap) combined as (s0 + s1) + (s2 + s3): the same call gives the same bits, a batch equals its rows.
+ *   syg_diag_median_f32   timelag_filter(median_filter, size = (1, w)) of square R [B, t, t] without the lag matrix:
+ *       out[r, i] = median over j < w of R~[(r - i + c_j) mod n, c_j], c_j = m(i + j - w / 2), m the boundary rule along
+ *       time (cval where the constant fills), R~ zero in rows t .. n - 1, n = 2 t (pad = 1) or t.  axis 0: the transpose.
+ *       w odd, 1 .. SYG_STRUCT_MEDIAN_W_MAX; the result is an input value bit for bit (-0 orders below +0).
+ *   syg_agglomerative_f32   Ward clustering of chains of frames.  X [B, T, D] frame-major (frame stride ldx, batch stride
+ *       bsx).  Span s covers length[s] frames from frame offset[s] of the flattened [B T] frame index and stays inside its
+ *       clip; spans must not overlap.  Start from singletons, merge the neighbouring pair with the least
+ *       n_a n_b / (n_a + n_b) |S_a / n_a - S_b / n_b|^2 (float64; the leftmost on ties) until k[s] segments remain.  bounds
+ *       [n_spans, k_max] int32: the segment starts relative to the span, ascending, -1 past k[s]; count [n_spans].  offset,
+ *       length, k: int32 [n_spans] on the device (the kernel clamps them into the clip, max_len and k_max).  max_len: the
+ *       longest span, at most SYG_STRUCT_AGG_T_MAX.  work: syg_agglomerative_work_bytes(B, T, D) bytes on the device
+ *       (the float64 segment sums), 8-byte aligned.
+ *   syg_segment_sync_f32   out [B, n_seg, D]: SYG_SYNC_MEAN (summed in float64, ascending), SYG_SYNC_MAX or SYG_SYNC_MIN of
+ *       the frames [edges[j], edges[j + 1]) of X [B, T, D]; edges int32 [n_seg + 1] on the device, batch stride edge_bs = 0
+ *       (shared) or n_seg + 1.  An empty segment gives 0.  The median is not served.
+ * Rejected before any device work: null pointers, sizes outside the served ranges, flags other than 0 or 1, an unknown
+ * boundary rule or aggregate, an even w or one above the cap, offsets that span more than the cap, a span or k_max above
+ * its cap, a stride below the row's length, a workspace that is too small.
+ * ------------------------------------------------------------------------------- */
+#define SYG_BOUNDARY_REFLECT 0
+#define SYG_BOUNDARY_MIRROR 1
+#define SYG_BOUNDARY_NEAREST 2
+#define SYG_BOUNDARY_WRAP 3
+#define SYG_BOUNDARY_CONSTANT 4
+#define SYG_SYNC_MEAN 0
+#define SYG_SYNC_MAX 1
+#define SYG_SYNC_MIN 2
+enum {
+  SYG_STRUCT_AGG_T_MAX = 0,       /* frames of the longest span syg_agglomerative_f32 serves */
+  SYG_STRUCT_MEDIAN_W_MAX = 1,    /* widest window of syg_diag_median_f32 */
+  SYG_STRUCT_PATH_TILE_ROWS = 2,  /* outputs of a path_enhance tile */
+  SYG_STRUCT_PATH_TILE_COLS = 3,
+  SYG_STRUCT_PATH_SPAN_MAX = 4,   /* widest extent (max - min) of the tap offsets along an axis */
+  SYG_STRUCT_SHEAR_T_MAX = 5      /* largest t of syg_lag_shear_f32 and syg_diag_median_f32 */
+};
+int64_t syg_structure_constants(int key);
+int syg_lag_shear_f32(const float* in, int64_t B, int64_t t, int64_t ldi, int64_t bsi, int inverse, int axis, int pad, float* out,
+                      void* stream);
+int syg_path_enhance_f32(const float* R, int64_t B, int64_t T, int64_t Tc, int64_t ldr, int64_t bsr, const int* taps, int64_t n_taps,
+                         const int* fstart, int n_filters, int dr_min, int dr_max, int dc_min, int dc_max, int mode, float cval,
+                         int clip, float* out, void* stream);
+int syg_diag_median_f32(const float* R, int64_t B, int64_t t, int64_t ldr, int64_t bsr, int w, int axis, int pad, int mode, float cval,
+                        float* out, void* stream);
+int64_t syg_agglomerative_work_bytes(int64_t B, int64_t T, int64_t D);
+int syg_agglomerative_f32(const float* X, int64_t B, int64_t T, int64_t D, int64_t ldx, int64_t bsx, const int* offset,
+                          const int* length, const int* k, int64_t n_spans, int64_t max_len, int64_t k_max, int* bounds, int* count,
+                          void* work, int64_t work_bytes, void* stream);
+int syg_segment_sync_f32(const float* X, int64_t B, int64_t T, int64_t D, int64_t ldx, int64_t bsx, const int* edges, int64_t n_seg,
+                         int64_t edge_bs, int aggregate, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,13 @@ SIGNATURES = {
     "syg_viterbi_form": (_i, [_l, _l]),
     "syg_viterbi_work_bytes": (_l, [_l, _l, _l]),
     "syg_viterbi_f32": (_i, [_p, _i, _i, _l, _l, _l, _l, _l, _l, _p, _p, _l, _p, _l, _p, _l, _d, _p, _l, _p, _p, _i, _p]),
+    "syg_structure_constants": (_l, [_i]),
+    "syg_lag_shear_f32": (_i, [_p, _l, _l, _l, _l, _i, _i, _i, _p, _p]),
+    "syg_path_enhance_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p, _p]),
+    "syg_diag_median_f32": (_i, [_p, _l, _l, _l, _l, _i, _i, _i, _i, _f, _p, _p]),
+    "syg_agglomerative_work_bytes": (_l, [_l, _l, _l]),
+    "syg_agglomerative_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _l, _l, _l, _p, _p, _p, _l, _p]),
+    "syg_segment_sync_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _l, _i, _p, _p]),
 }
 
 _lib = None

@@ -1064,6 +1064,44 @@ def dsp_separate_repeating(input_file, output, foreground, width_seconds, metric
                f"'{Path(output).name}'" + (f", foreground to '{Path(foreground).name}'." if foreground is not None else "."))
 
 
+@dsp_cmd.command("structure")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
+@click.option("-k", "--segments", "k", type=int, required=True, help="Number of segments to cut the clip into.")
+@click.option("--feature", type=click.Choice(["mfcc", "chroma"]), default="mfcc", show_default=True)
+@click.option("--enhance", type=int, default=None, help="Enhance the diagonal paths of the recurrence matrix with filters of N frames.")
+@click.option("--median", type=int, default=None, help="Median-filter the recurrence matrix along its diagonals over W frames (odd).")
+@click.option("-o", "--output", default=None, type=click.Path(), help="Where the segment table is written (CSV).")
+@click.option("--fs", type=int, default=None, help="Sampling rate of the input (Hz) if the file carries none.")
+def dsp_structure(input_file, k, feature, enhance, median, output, fs):
+    """Cut INPUT into -k segments: features (n_fft 2048, hop 512), their affinity recurrence matrix, optionally its diagonal
+    paths enhanced (--enhance) and median-filtered (--median), the matrix's rows appended to the features, and a Ward
+    clustering of neighbouring frames.  Writes segment, start_frame, start_time."""
+    if k < 1:
+        raise click.UsageError(f"-k / --segments must be at least 1 (got {k}).")
+    if enhance is not None and enhance < 1:
+        raise click.UsageError(f"--enhance must be at least 1 (got {enhance}).")
+    if median is not None and (median < 1 or median > 63 or median % 2 == 0):
+        raise click.UsageError(f"--median must be odd and in [1, 63] (got {median}).")
+    x, sr = _load_signal(input_file, fs)
+    if not sr:
+        raise click.UsageError("--fs is required: the input file carries no sampling rate.")
+    if np.size(x) < 1:
+        raise click.UsageError("The input is empty.")
+    from ..core.structure import structure_segments
+    try:
+        bounds = structure_segments(np.asarray(x, dtype=np.float32), float(sr), k, feature=feature, enhance=enhance, median=median)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    import pandas as pd
+    table = pd.DataFrame({"segment": np.arange(len(bounds)), "start_frame": bounds, "start_time": bounds * 512.0 / float(sr)})
+    if output is not None:
+        table.to_csv(output, index=False)
+    click.echo(f"Cut {np.size(x)} samples into {len(bounds)} segments ({feature}"
+               + (f", paths enhanced over {enhance} frames" if enhance else "") + (f", diagonal median over {median} frames" if median else "")
+               + "), starts at frames " + " ".join(str(int(b)) for b in bounds)
+               + (f", saved to '{Path(output).name}'." if output is not None else "."))
+
+
 @dsp_cmd.command("stft")
 @click.argument("input_file", type=click.Path(exists=True, dir_okay=False))
 @click.option("-o", "--output", required=True, type=click.Path())

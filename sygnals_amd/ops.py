@@ -26,6 +26,7 @@ from . import _rhythm as RH
 from . import _rng as RNG
 from . import _sequence as SQ
 from . import _specaug as SA
+from . import _structure as ST
 from . import _tables as T
 from ._fftplan import (MAX_LDS_FFT, MAX_MIXED_FFT, MAX_ROWS, conv_fft_len, fft_plan, is_pow2,      # noqa: F401 (re-exported)
                        next_direct_len, smooth_split)
@@ -4850,3 +4851,238 @@ def viterbi(prob: Optional[torch.Tensor] = None, transition=None, *, log_prob: O
               S if pi.ndim == 2 else 0, piece(lm, ps is not None and ps.ndim == 2), S if ps is not None and ps.ndim == 2 else 0,
               e, _ptr(work), _nbytes(work), _ptr(states[b0:b0 + n]), _ptr(logp[b0:b0 + n]), VITERBI_FORMS[form])
     return (states, logp) if return_logp else states
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Structure analysis (csrc/structure.hip; the filter bank and the frame fixing are _structure.py): what librosa.segment
+# does with a recurrence matrix [B, T, T'] and the frame-major features [B, T, D] behind it.  tests/structure_ref.py is
+# the contract.
+
+_STRUCT_KEYS = ("agg_t_max", "median_w_max", "path_tile_rows", "path_tile_cols", "path_span_max", "shear_t_max")   # SYG_STRUCT_*
+
+
+def structure_constants() -> dict:
+    """The figures the structure kernels rest on (the library owns them): agg_t_max the frames of the longest span
+    agglomerative serves, median_w_max the widest diagonal median, the path_enhance tile and the widest extent of its
+    filters' offsets, shear_t_max the largest square matrix of the shear and the diagonal median; and the names served."""
+    return dict(_constants("syg_structure_constants", _STRUCT_KEYS), modes=tuple(ST.BOUNDARY_MODES),
+                aggregates=tuple(ST.SYNC_AGGREGATES))
+
+
+def _struct_mats(who, R, name="R", square=False):
+    """R [B, T, T'] checked without a device: its sizes."""
+    _f32(R, f"{who}: {name}", 3, (), "[B, T, T']")
+    if min(R.shape) < 1:
+        raise ValueError(f"{who}: empty input ({name} has shape {list(R.shape)})")
+    B, Tn, Tc = (int(n) for n in R.shape)
+    if square and Tn != Tc:
+        raise ValueError(f"{who}: {name} must be square [B, t, t] (got {list(R.shape)})")
+    return B, Tn, Tc
+
+
+def _struct_axis(who, axis) -> int:
+    """librosa's axis of a matrix (-1 / 1: time along the columns, 0: along the rows) as the library's flag."""
+    if isinstance(axis, bool) or axis not in (-1, 0, 1):
+        raise ValueError(f"{who}: axis={axis!r} must be -1 (or 1) or 0")
+    return 0 if axis == 0 else 1
+
+
+def _struct_cval(who, cval) -> float:
+    if isinstance(cval, bool) or not isinstance(cval, (int, float, np.integer, np.floating)) or not np.isfinite(cval):
+        raise ValueError(f"{who}: cval={cval!r} must be a finite number")
+    return float(cval)
+
+
+def recurrence_to_lag(R: torch.Tensor, pad: bool = True, axis: int = -1) -> torch.Tensor:
+    """librosa.segment.recurrence_to_lag of square matrices R [B, t, t] float32 on the device (rows may be strided) ->
+    [B, 2 t, t] (pad) or [B, t, t]; axis=0: [B, t, 2 t].  lag[l, i] = R~[(l + i) mod n, i], R~ zero past row t."""
+    who = "recurrence_to_lag"
+    B, t, _ = _struct_mats(who, R, "rec", square=True)
+    ax = _struct_axis(who, axis)
+    if t > structure_constants()["shear_t_max"]:
+        raise ValueError(f"{who}: t = {t} is above the served {structure_constants()['shear_t_max']}")
+    _on_device(R, f"{who}: rec")
+    R, ld, bs = _sim_strided(R)
+    n = 2 * t if pad else t
+    out = torch.empty((B, n, t) if ax == 1 else (B, t, n), dtype=torch.float32, device=R.device)
+    _call("syg_lag_shear_f32", _ptr(R), B, t, ld, bs, 0, ax, int(bool(pad)), _ptr(out))
+    return out
+
+
+def lag_to_recurrence(lag: torch.Tensor, axis: int = -1) -> torch.Tensor:
+    """librosa.segment.lag_to_recurrence: lag [B, 2 t, t] or [B, t, t] (axis=0: [B, t, 2 t]) -> [B, t, t]."""
+    who = "lag_to_recurrence"
+    B, rows, cols = _struct_mats(who, lag, "lag")
+    ax = _struct_axis(who, axis)
+    n, t = (rows, cols) if ax == 1 else (cols, rows)
+    if n not in (t, 2 * t):
+        raise ValueError(f"{who}: lag must be [t, t] or padded along axis={axis} to 2 t (got {[rows, cols]})")
+    if t > structure_constants()["shear_t_max"]:
+        raise ValueError(f"{who}: t = {t} is above the served {structure_constants()['shear_t_max']}")
+    _on_device(lag, f"{who}: lag")
+    lag, ld, bs = _sim_strided(lag)
+    out = torch.empty((B, t, t), dtype=torch.float32, device=lag.device)
+    _call("syg_lag_shear_f32", _ptr(lag), B, t, ld, bs, 1, ax, int(n == 2 * t), _ptr(out))
+    return out
+
+
+def _path_tables_dev(F: "ST.PathFilters"):
+    return _cached(("path_filters", F.taps.shape, F.taps.tobytes()), lambda: (_dev(F.taps), _dev(F.fstart)), limit=16)
+
+
+def path_enhance(R: torch.Tensor, n: int, window="hann", max_ratio: float = 2.0, min_ratio=None, n_filters: int = 7,
+                 zero_mean: bool = False, clip: bool = True, mode: str = "reflect", cval: float = 0.0) -> torch.Tensor:
+    """librosa.segment.path_enhance of R [B, T, T'] float32 on the device (rows may be strided) -> [B, T, T']: the maximum
+    over a bank of n_filters diagonal smoothing filters of slopes min_ratio .. max_ratio (syg_path_enhance_f32 over the
+    tap lists of _structure.path_filters), clipped at 0 with clip.  mode / cval: scipy.ndimage's boundary rule."""
+    who = "path_enhance"
+    B, Tn, Tc = _struct_mats(who, R)
+    code = ST.boundary_code(who, mode)
+    cv = _struct_cval(who, cval)
+    F = ST.path_filters(n, window, max_ratio, min_ratio, n_filters, zero_mean)
+    K = structure_constants()
+    r0, r1, c0, c1 = F.span
+    if max(r1 - r0, c1 - c0) > K["path_span_max"]:
+        raise ValueError(f"{who}: the filters of n = {n} span {max(r1 - r0, c1 - c0) + 1} cells; served are up to "
+                         f"{K['path_span_max'] + 1}")
+    _on_device(R, f"{who}: R")
+    R, ld, bs = _sim_strided(R)
+    taps, fstart = _path_tables_dev(F)
+    out = torch.empty((B, Tn, Tc), dtype=torch.float32, device=R.device)
+    _call("syg_path_enhance_f32", _ptr(R), B, Tn, Tc, ld, bs, _ptr(taps), int(F.taps.shape[0]), _ptr(fstart), len(F.fstart) - 1, r0, r1,
+          c0, c1, code, cv, int(bool(clip)), _ptr(out))
+    return out
+
+
+def diag_median(R: torch.Tensor, w: int, mode: str = "reflect", cval: float = 0.0, pad: bool = True, axis: int = -1) -> torch.Tensor:
+    """timelag_filter(scipy.ndimage.median_filter, pad)(R, size=(1, w), mode, cval) of square R [B, t, t] float32 on the
+    device, without the lag matrix (syg_diag_median_f32): the median along every diagonal, cyclic over 2 t (pad) or t rows.
+    w odd, up to median_w_max; the result is an input value bit for bit."""
+    who = "diag_median"
+    B, t, _ = _struct_mats(who, R, square=True)
+    K = structure_constants()
+    if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or w < 1 or w > K["median_w_max"] or w % 2 == 0:
+        raise ValueError(f"{who}: w={w!r} must be an odd integer in [1, {K['median_w_max']}]")
+    ax = _struct_axis(who, axis)
+    code = ST.boundary_code(who, mode)
+    cv = _struct_cval(who, cval)
+    if t > K["shear_t_max"]:
+        raise ValueError(f"{who}: t = {t} is above the served {K['shear_t_max']}")
+    _on_device(R, f"{who}: R")
+    R, ld, bs = _sim_strided(R)
+    out = torch.empty((B, t, t), dtype=torch.float32, device=R.device)
+    _call("syg_diag_median_f32", _ptr(R), B, t, ld, bs, int(w), ax, int(bool(pad)), code, cv, _ptr(out))
+    return out
+
+
+def _struct_ints(who, name, v, n=None) -> np.ndarray:
+    a = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+    if a.ndim == 0 and n is not None:
+        a = np.full((n,), a)
+    if a.ndim != 1 or a.dtype.kind not in "iu" or a.size < 1 or (n is not None and a.size != n):
+        raise ValueError(f"{who}: {name} must be " + ("an integer or " if n is not None else "")
+                         + f"a one-dimensional array of integers{'' if n is None else f' [{n}]'}")
+    return a.astype(np.int64)
+
+
+def agglomerative(X: torch.Tensor, k, offset=None, length=None):
+    """Temporally constrained Ward clustering (librosa.segment.agglomerative) of frame-major X [B, T, D] float32 on the
+    device (frames may be strided): from singletons, the neighbouring pair with the least Ward cost (float64; the leftmost
+    on ties) is merged until k segments remain.  Without offset / length every clip is one span and k is an integer or one
+    per clip; with them span s covers length[s] frames from offset[s] of the flattened [B T] frame index (inside one clip,
+    not overlapping) and k one per span.  A span holds up to agg_t_max frames and 1 <= k <= its length.
+    -> (bounds [n_spans, max k] int32 on the device: the segment starts relative to the span, ascending, -1 past k;
+    count [n_spans] int32)."""
+    who = "agglomerative"
+    B, Tn, D = _sim_frames(who, X, "X")
+    if (offset is None) != (length is None):
+        raise ValueError(f"{who}: offset and length come together")
+    if offset is None:
+        off, ln = np.arange(B, dtype=np.int64) * Tn, np.full((B,), Tn, dtype=np.int64)
+    else:
+        off = _struct_ints(who, "offset", offset)
+        ln = _struct_ints(who, "length", length, off.size)
+        if off.min() < 0 or ln.min() < 1 or np.any(off % Tn + ln > Tn) or off.max() >= B * Tn:
+            raise ValueError(f"{who}: a span must hold at least one frame and lie inside one clip of {Tn} frames")
+        o = np.argsort(off, kind="stable")
+        if np.any(off[o][1:] < (off[o] + ln[o])[:-1]):
+            raise ValueError(f"{who}: spans must not overlap")
+    ks = _struct_ints(who, "k", k, off.size)
+    if ks.min() < 1 or np.any(ks > ln):
+        raise ValueError(f"{who}: k must be in [1, frames of the span] (got k in [{ks.min()}, {ks.max()}], spans of {ln.min()} to "
+                         f"{ln.max()} frames)")
+    cap = structure_constants()["agg_t_max"]
+    if ln.max() > cap:
+        raise ValueError(f"{who}: a span of {ln.max()} frames is above the served {cap} frames (the boundary costs and links of a "
+                         "span live in LDS)")
+    _on_device(X, f"{who}: X")
+    X, ldx, bsx = _sim_strided(X)
+    if B > 1 and bsx == 0:
+        X, ldx, bsx = X.contiguous(), D, Tn * D
+    n, kmax = int(off.size), int(ks.max())
+    tab = torch.from_numpy(np.stack([off, ln, ks]).astype(np.int32)).to(X.device)
+    bounds = torch.empty((n, kmax), dtype=torch.int32, device=X.device)
+    count = torch.empty((n,), dtype=torch.int32, device=X.device)
+    work = _workspace("syg_agglomerative_work_bytes", B, Tn, D, dtype=torch.float64, device=X.device)
+    _call("syg_agglomerative_f32", _ptr(X), B, Tn, D, ldx, bsx, _ptr(tab[0]), _ptr(tab[1]), _ptr(tab[2]), n, int(ln.max()), kmax,
+          _ptr(bounds), _ptr(count), _ptr(work), _nbytes(work))
+    return bounds, count
+
+
+def subsegment(X: torch.Tensor, frames, n_segments: int = 4):
+    """librosa.segment.subsegment of frame-major X [B, T, D]: every clip is cut at `frames` (host integers, shared by the
+    clips; unsorted, repeated or past T as librosa.util.fix_frames takes them) and each piece into min(n_segments, its
+    frames) agglomerative segments.  -> (bounds [B, n] int32 on the device, frames of the clip, ascending, -1 past count;
+    count [B])."""
+    who = "subsegment"
+    B, Tn, D = _sim_frames(who, X, "X")
+    n_segments = _sim_int(who, "n_segments", n_segments, 1)
+    edges = ST.fix_frames(_struct_ints(who, "frames", frames), Tn)
+    starts, lens = edges[:-1], np.diff(edges)
+    ks = np.minimum(lens, n_segments)
+    P = starts.size
+    off = (np.arange(B, dtype=np.int64)[:, None] * Tn + starts[None, :]).ravel()
+    b, _ = agglomerative(X, np.tile(ks, B), off, np.tile(lens, B))
+    b = b.reshape(B, P, -1)
+    live = b >= 0
+    b = torch.where(live, b + torch.from_numpy(starts.astype(np.int32)).to(b.device)[None, :, None], b)
+    # the pieces are in ascending order and so are the starts inside one: the live entries, kept in place order
+    n = int(ks.sum())
+    keep = torch.from_numpy((np.arange(b.shape[2])[None, :] < ks[:, None]).ravel()).to(b.device)
+    out = b.reshape(B, -1)[:, keep].contiguous()
+    return out, torch.full((B,), n, dtype=torch.int32, device=out.device)
+
+
+def segment_sync(X: torch.Tensor, edges, aggregate: str = "mean", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """librosa.util.sync of frame-major X [B, T, D] float32 on the device -> [B, n_seg, D]: the mean (summed in float64), max
+    or min of the frames [edges[j], edges[j + 1]).  edges: integers [n_seg + 1] shared by the clips, or [B, n_seg + 1], not
+    descending, in [0, T] (a host array, or an int32 device tensor that is used as it is); an empty segment gives 0.
+    The median is not served."""
+    who = "segment_sync"
+    if aggregate == "median" or aggregate is np.median:
+        raise ValueError(f"{who}: aggregate='median' is not served; served: 'mean', 'max', 'min'")
+    code = _sim_name(who, "aggregate", aggregate, ST.SYNC_AGGREGATES)
+    B, Tn, D = _sim_frames(who, X, "X")
+    on_dev = isinstance(edges, torch.Tensor) and edges.is_cuda
+    if on_dev:
+        if edges.dtype != torch.int32 or edges.dim() not in (1, 2):
+            raise ValueError(f"{who}: edges on the device must be an int32 tensor [n_seg + 1] or [{B}, n_seg + 1]")
+        e = edges.contiguous()
+        shape = tuple(e.shape)
+    else:
+        a = np.asarray(edges.numpy() if isinstance(edges, torch.Tensor) else edges)
+        if a.dtype.kind not in "iu" or a.ndim not in (1, 2) or a.size < 1:
+            raise ValueError(f"{who}: edges must be integers [n_seg + 1] or [{B}, n_seg + 1]")
+        if a.min() < 0 or a.max() > Tn or np.any(np.diff(a, axis=-1) < 0):
+            raise ValueError(f"{who}: edges must not descend and lie in [0, {Tn}]")
+        shape = a.shape
+    if shape[-1] < 2 or shape[-1] - 1 > Tn or (len(shape) == 2 and shape[0] != B):
+        raise ValueError(f"{who}: edges {list(shape)} must be [n_seg + 1] or [{B}, n_seg + 1] with 1 <= n_seg <= {Tn}")
+    n_seg = shape[-1] - 1
+    _on_device(X, f"{who}: X")
+    X, ldx, bsx = _sim_strided(X)
+    if not on_dev:
+        e = torch.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(X.device)
+    o = _out(out, (B, n_seg, D), X, contiguous=True)
+    _call("syg_segment_sync_f32", _ptr(X), B, Tn, D, ldx, bsx, _ptr(e), n_seg, n_seg + 1 if len(shape) == 2 else 0, code, _ptr(o))
+    return o

@@ -123,6 +123,9 @@ class SygnalsAmdPlugin(_Base):
             registry.add_feature(fn.__name__, fn)
         from ..core import similarity
         registry.add_feature("recurrence_matrix", similarity.recurrence_matrix)
+        from ..core import structure
+        for fn in (structure.path_enhance, structure.agglomerative, structure.subsegment):
+            registry.add_feature(fn.__name__, fn)
         from ..core import segmentation, sequence
         registry.add_feature("viterbi", sequence.viterbi)
         registry.add_feature("segment_by_activity", segmentation.segment_by_activity)
