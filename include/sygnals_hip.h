@@ -1753,6 +1753,50 @@ int syg_agglomerative_f32(const float* X, int64_t B, int64_t T, int64_t D, int64
 int syg_segment_sync_f32(const float* X, int64_t B, int64_t T, int64_t D, int64_t ldx, int64_t bsx, const int* edges, int64_t n_seg,
                          int64_t edge_bs, int aggregate, float* out, void* stream);
 
+/* -------------------------------------------------------------------------------
+ * Kaldi-compatible front end (csrc/kaldi_front.hip): torchaudio.compliance.kaldi.fbank / mfcc on y [B, L] float32 clips
+ * (row stride ldy), samples in, features out, one launch.  tests/kaldi_ref.py is the contract; the host tables are made
+ * in sygnals_amd/_kaldi.py (float64, rounded to float32 once).
+ *   Frames of wl samples, zero-padded on the right to n_fft for the transform.  snip_edges = 1: T = 1 + (L - wl) / hop
+ *   (0 if L < wl), frame t starts at t hop.  snip_edges = 0: T = (L + hop / 2) / hop, frame t starts at
+ *   t hop + hop / 2 - wl / 2, an index s outside [0, L) reflected (s <- -s - 1 or 2 L - 1 - s until inside).  Per frame:
+ *   dither N(0, 1) (Philox, keyed by seed, clip, frame, sample), the frame mean removed (remove_dc; float64 sum, rounded
+ *   once), pre-emphasis x[i] -= preemph x[i - 1] with x[-1] := x[0], the window.  The log-energy log(max(sum x^2, eps)) is
+ *   taken before the pre-emphasis (raw_energy = 1) or behind the window, and floored at log(energy_floor) if that is > 0.
+ *   |rfft|^2 (use_power = 1) or |rfft| of the bins [0, n_fft / 2) goes onto the filterbank; use_log = 1 writes
+ *   E > eps ? logf(E) : log_eps, with eps = 1.1920929e-07 and log_eps the float32 nearest to log(eps).
+ * Tables, float32 on the device:
+ *   window   [wl]
+ *   twiddle  [n_fft + n_fft / 2][2]: W_n_fft^k, k < n_fft, then W_(n_fft/2)^k, k < n_fft / 2 (cos, sin of -2 pi k / n)
+ *   basis_p  [16 ceil(n_mels / 16), n_fft / 2], rows past n_mels zero, 16-byte aligned (the Nyquist bin carries no weight)
+ *   dct      [num_ceps, n_mels]: the orthonormal DCT-II rows times the lifter, or null for the filterbank output
+ * Output out[b sob + t sot + c soc], one of sot and soc being 1: [B, C, T] and [B, T, C] are both one launch.
+ *   dct null: C = n_mels + use_energy; the energy column is first, or last under htk_compat.
+ *   dct set:  C = num_ceps; use_energy replaces coefficient 0 by the log-energy, htk_compat moves coefficient 0 to the end;
+ *             fb (or null) receives the log filterbank [B, T, n_mels] through its own strides.
+ * Served: n_fft 256, 512, 1024 or 2048, 2 <= wl <= n_fft, hop >= 1, 3 <= n_mels <= 256, 1 <= num_ceps <= n_mels,
+ * 0 <= preemph <= 1, dither >= 0, energy_floor >= 0.  Everything else is rejected before any device work, as are null
+ * pointers, a T that does not follow the framing rule and strides below the row's length.  No atomics: a call repeats its
+ * bits and a batch equals its rows.  A workgroup takes SYG_KALDI_TILE frames of a clip; the grid is capped at
+ * SYG_KALDI_WGS_PER_CU workgroups a CU and loops over the rest.
+ * ------------------------------------------------------------------------------- */
+enum {
+  SYG_KALDI_TILE = 0,         /* frames of a workgroup's tile */
+  SYG_KALDI_N_MIN = 1,        /* smallest and */
+  SYG_KALDI_N_MAX = 2,        /* largest padded frame length (powers of two between them) */
+  SYG_KALDI_MEL_MIN = 3,
+  SYG_KALDI_MEL_MAX = 4,
+  SYG_KALDI_LDS_MAX = 5,      /* LDS bytes of a workgroup, at most */
+  SYG_KALDI_WGS_PER_CU = 6,   /* workgroups a CU of the capped grid */
+  SYG_KALDI_LDS_WORST = 7     /* LDS bytes of the largest served shape */
+};
+int64_t syg_kaldi_constants(int key);
+int syg_kaldi_fbank_f32(const float* y, int64_t B, int64_t L, int64_t ldy, int wl, int hop, int n_fft, int snip_edges, int64_t T,
+                        const float* window, const float* twiddle, const float* basis_p, int n_mels, float preemph,
+                        int remove_dc, int raw_energy, int use_power, int use_log, float log_eps, float energy_floor,
+                        float dither, uint64_t seed, int use_energy, int htk_compat, const float* dct, int num_ceps, float* out,
+                        int64_t sob, int64_t sot, int64_t soc, float* fb, int64_t sfb, int64_t sft, int64_t sfc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

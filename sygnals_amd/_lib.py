@@ -244,6 +244,9 @@ SIGNATURES = {
     "syg_agglomerative_work_bytes": (_l, [_l, _l, _l]),
     "syg_agglomerative_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _l, _l, _l, _p, _p, _p, _l, _p]),
     "syg_segment_sync_f32": (_i, [_p, _l, _l, _l, _l, _l, _p, _l, _l, _i, _p, _p]),
+    "syg_kaldi_constants": (_l, [_i]),
+    "syg_kaldi_fbank_f32": (_i, [_p, _l, _l, _l, _i, _i, _i, _i, _l, _p, _p, _p, _i, _f, _i, _i, _i, _i, _f, _f, _f, _u, _i, _i, _p, _i, _p,
+                                 _l, _l, _l, _p, _l, _l, _l, _p]),
 }
 
 _lib = None

@@ -247,6 +247,59 @@ def features_pcen(input_file, output, n_mels, n_fft, hop_length, gain, bias, pow
     click.echo(f"pcen ({m.shape[0]} bands x {m.shape[1]} frames) saved to '{Path(output).name}'.")
 
 
+@features_cmd.command("fbank")
+@click.argument("input_file", type=click.Path(exists=True, dir_okay=False, resolve_path=True))
+@click.option("-o", "--output", type=click.Path(resolve_path=True), required=True,
+              help="Output file path (.npz: time and the matrix; any other suffix: a table time, fbank_0 ... or mfcc_0 ...).")
+@click.option("--num-mel-bins", type=int, default=23, show_default=True, help="Mel bands (3 ... 256).")
+@click.option("--frame-length", type=float, default=25.0, show_default=True, help="Window length (milliseconds).")
+@click.option("--frame-shift", type=float, default=10.0, show_default=True, help="Shift between frames (milliseconds).")
+@click.option("--window-type", default="povey", show_default=True, help="hamming, hanning, povey, rectangular or blackman.")
+@click.option("--dither", type=float, default=0.0, show_default=True, help="Dither (standard deviations of added noise).")
+@click.option("--seed", type=int, default=0, show_default=True, help="Seed of the dither.")
+@click.option("--no-snip-edges", is_flag=True, help="Frames centred on multiples of the shift, the clip reflected at its ends.")
+@click.option("--use-energy", is_flag=True, help="Add the log-energy column (fbank) or put it in place of coefficient 0 (MFCC).")
+@click.option("--htk-compat", is_flag=True, help="HTK's column order: the energy / coefficient 0 last.")
+@click.option("--subtract-mean", is_flag=True, help="Subtract each column's mean over the frames.")
+@click.option("--mfcc", "as_mfcc", is_flag=True, help="Write MFCCs instead of the log filterbank.")
+@click.option("--num-ceps", type=int, default=13, show_default=True, help="Cepstral coefficients (with --mfcc).")
+@click.option("--cepstral-lifter", type=float, default=22.0, show_default=True, help="Kaldi's lifter (with --mfcc; 0: none).")
+def features_fbank(input_file, output, num_mel_bins, frame_length, frame_shift, window_type, dither, seed, no_snip_edges,
+                   use_energy, htk_compat, subtract_mean, as_mfcc, num_ceps, cepstral_lifter):
+    """Kaldi-compatible log mel filterbank energies (or MFCCs) of an audio signal."""
+    from .. import _kaldi as KD
+    from ..core.features import kaldi as KF
+    res = sio.read_data(Path(input_file))
+    if not isinstance(res, tuple) or len(res) != 2 or not res[1]:
+        raise click.UsageError(f"Input file '{Path(input_file).name}' is not recognized as audio.")
+    signal, sr = res
+    if signal.ndim != 1:
+        signal = np.mean(signal, axis=0)
+    kw = dict(num_mel_bins=num_mel_bins, frame_length=frame_length, frame_shift=frame_shift, window_type=window_type,
+              dither=dither, snip_edges=not no_snip_edges, use_energy=use_energy, htk_compat=htk_compat,
+              subtract_mean=subtract_mean)
+    if as_mfcc:
+        kw.update(num_ceps=num_ceps, cepstral_lifter=cepstral_lifter)
+    who = "features fbank"
+    try:
+        spec = KD.check(who, as_mfcc, float(sr), kw)
+        KD.check_seed(who, seed)
+        if KD.frames_of(spec, signal.shape[0]) < 1:
+            raise ValueError(f"{who}: the input ({signal.shape[0]} samples) is shorter than one frame of {spec.wl} samples.")
+        m = (KF.mfcc if as_mfcc else KF.fbank)(signal, sample_frequency=float(sr), seed=seed, **kw)
+    except ValueError as e:
+        raise click.UsageError(str(e))
+    name = "mfcc" if as_mfcc else "fbank"
+    time = np.arange(m.shape[0]) * spec.hop / float(sr)
+    if Path(output).suffix.lower() == ".npz":
+        sio.save_data({"time": time, name: m}, Path(output))
+    else:
+        table = {"time": time}
+        table.update({f"{name}_{i}": m[:, i] for i in range(m.shape[1])})
+        sio.save_data(pd.DataFrame(table), Path(output))
+    click.echo(f"{name} ({m.shape[0]} frames x {m.shape[1]} columns) saved to '{Path(output).name}'.")
+
+
 # ---------------------------------------------------------------- dsp
 @click.group("dsp")
 def dsp_cmd():

@@ -17,6 +17,7 @@ from . import _cepstrum as CP
 from . import _chroma as CH
 from . import _cwt as CW
 from . import _dynamics as DY
+from . import _kaldi as KD
 from . import _laplace as LP
 from . import _loudness as LD
 from . import _lpc
@@ -5086,3 +5087,87 @@ def segment_sync(X: torch.Tensor, edges, aggregate: str = "mean", out: Optional[
     o = _out(out, (B, n_seg, D), X, contiguous=True)
     _call("syg_segment_sync_f32", _ptr(X), B, Tn, D, ldx, bsx, _ptr(e), n_seg, n_seg + 1 if len(shape) == 2 else 0, code, _ptr(o))
     return o
+
+
+# ------------------------------------------------------------------ Kaldi-compatible front end: fbank and MFCC
+_KALDI_KEYS = ("tile", "n_fft_min", "n_fft_max", "mel_min", "mel_max", "lds_max", "wgs_per_cu", "lds_worst")       # SYG_KALDI_*
+
+
+def kaldi_constants() -> dict:
+    """The figures the Kaldi front end rests on (the library owns them): the frames of a workgroup's tile, the smallest and
+    largest padded frame length, the band counts served, the LDS a workgroup may take, the workgroups a CU of the capped
+    grid, the LDS of the largest served shape."""
+    return _constants("syg_kaldi_constants", _KALDI_KEYS)
+
+
+def _kaldi_tables(s: "KD.Spec"):
+    """(window, twiddle, padded mel banks, DCT x lifter | None) on the device."""
+    win = _cached(("kaldi_win", s.window_type, s.wl, s.blackman_coeff),
+                  lambda: _dev(KD.window(s.window_type, s.wl, s.blackman_coeff).astype(np.float32)))
+    tw = _cached(("kaldi_tw", s.N), lambda: _dev(KD.twiddle_f32(s.N)))
+    bp = _cached(("kaldi_mel", s.M, s.N, s.sr, s.low, s.high), lambda: _dev(KD.mel_padded_f32(s.M, s.N, s.sr, s.low, s.high)))
+    dct = None
+    if s.mfcc:
+        dct = _cached(("kaldi_dct", s.num_ceps, s.M, s.lifter),
+                      lambda: _dev(KD.dct_lifter(s.num_ceps, s.M, s.lifter).astype(np.float32)))
+    return win, tw, bp, dct
+
+
+def _kaldi_front(who, mfcc, y, sr, layout, seed, out, return_fbank, kw):
+    s = KD.check(who, mfcc, sr, kw)
+    layout = KD.check_layout(who, layout)
+    seed = KD.check_seed(who, seed)
+    _f32(y, f"{who}: y", 2, axes="[B, L]")
+    B, L = y.shape
+    if B < 1 or L < 1:
+        raise ValueError(f"{who}: empty input (shape [{B}, {L}])")
+    Tn = KD.frames_of(s, L)
+    shape = lambda C: (B, C, Tn) if layout == "ct" else (B, Tn, C)            # noqa: E731
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != shape(s.C) or out.dtype != torch.float32
+                            or out.device != y.device or not out.is_contiguous()):
+        raise ValueError(f"{who}: out must be a contiguous float32 tensor {list(shape(s.C))} on the input's device")
+    _on_device(y, f"{who}: y")
+    y = _unit_stride(y)
+    if Tn == 0:                                                              # too short a clip: torchaudio's empty result
+        o = torch.empty(shape(s.C), dtype=torch.float32, device=y.device) if out is None else out
+        return (o, torch.empty(shape(s.M), dtype=torch.float32, device=y.device)) if return_fbank else o
+    win, tw, bp, dct = _kaldi_tables(s)
+    # subtract_mean is a second launch of cmvn, which takes [B, C, T]: the first launch writes that layout
+    direct = not (s.subtract_mean and layout == "tc")
+    o = out if (out is not None and direct) else torch.empty(shape(s.C) if direct else (B, s.C, Tn), dtype=torch.float32,
+                                                             device=y.device)
+    ct = layout == "ct" or not direct
+    so = (s.C * Tn, 1, Tn) if ct else (s.C * Tn, s.C, 1)
+    fb, sf = None, (0, 0, 0)
+    if return_fbank:
+        fb = torch.empty(shape(s.M), dtype=torch.float32, device=y.device)
+        sf = (s.M * Tn, 1, Tn) if layout == "ct" else (s.M * Tn, s.M, 1)
+    _call("syg_kaldi_fbank_f32", _ptr(y), B, L, _ld(y), s.wl, s.hop, s.N, int(s.snip_edges), Tn, _ptr(win), _ptr(tw), _ptr(bp), s.M,
+          s.preemph, int(s.remove_dc), int(s.raw_energy), int(s.use_power), int(s.use_log), KD.LOG_EPS, s.energy_floor, s.dither,
+          seed, int(s.use_energy), int(s.htk_compat), _ptr(dct), s.num_ceps, _ptr(o), *so, _ptr(fb), *sf)
+    if s.subtract_mean:
+        cmvn(o, variance=False, out=o)
+        if not direct:
+            t = o.transpose(1, 2)
+            o = out.copy_(t) if out is not None else t.contiguous()
+    return (o, fb) if return_fbank else o
+
+
+def kaldi_fbank(y: torch.Tensor, sr: float = 16000.0, layout: str = "ct", seed: int = 0, out: Optional[torch.Tensor] = None,
+                **kw) -> torch.Tensor:
+    """torchaudio.compliance.kaldi.fbank of y [B, L] float32 clips on the device, one launch: [B, C, T] (layout "ct", what
+    cmvn / delta / spec_augment take) or [B, T, C] ("tc", Kaldi's own), C = num_mel_bins + use_energy.  **kw: torchaudio's
+    keywords with its defaults (_kaldi.FBANK_DEFAULTS); the definition is tests/kaldi_ref.py.  Served: padded frame lengths
+    256 ... 2048, 3 <= num_mel_bins <= 256; vtln_warp != 1 and round_to_power_of_two=False are refused.  seed keys the dither
+    (Philox; used only with dither != 0).  subtract_mean is a second launch of cmvn(variance=False).  A clip shorter than
+    a frame, or than min_duration, gives T = 0."""
+    return _kaldi_front("kaldi_fbank", False, y, sr, layout, seed, out, False, kw)
+
+
+def kaldi_mfcc(y: torch.Tensor, sr: float = 16000.0, layout: str = "ct", seed: int = 0, out: Optional[torch.Tensor] = None,
+               return_fbank: bool = False, **kw):
+    """torchaudio.compliance.kaldi.mfcc of y [B, L] in the same launch as the filterbank: the orthonormal DCT-II of the log
+    mel energies, the first num_ceps coefficients, Kaldi's lifter; use_energy replaces coefficient 0 by the log-energy,
+    htk_compat moves coefficient 0 to the end.  return_fbank=True returns (mfcc, log fbank [B, M, T] / [B, T, M]) from the one
+    launch (the filterbank without subtract_mean).  **kw: _kaldi.MFCC_DEFAULTS."""
+    return _kaldi_front("kaldi_mfcc", True, y, sr, layout, seed, out, bool(return_fbank), kw)

@@ -126,6 +126,9 @@ class SygnalsAmdPlugin(_Base):
         from ..core import structure
         for fn in (structure.path_enhance, structure.agglomerative, structure.subsegment):
             registry.add_feature(fn.__name__, fn)
+        from ..core.features import kaldi
+        registry.add_feature("kaldi_fbank", kaldi.kaldi_fbank)
+        registry.add_feature("kaldi_mfcc", kaldi.kaldi_mfcc)
         from ..core import segmentation, sequence
         registry.add_feature("viterbi", sequence.viterbi)
         registry.add_feature("segment_by_activity", segmentation.segment_by_activity)
